@@ -8,21 +8,27 @@ encoder -> decoder loop -> post-net -> mel->linear -> Griffin-Lim -> audio.  The
 submitted as ONE xdtts_synthesize_sequence call (each decoded alone, batch 1; the vocoder of one runs beside the
 encoder of the next); extra.headline_one_call_per_utterance times K separate synchronous calls.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (W utterances), times the K utterances, and prints the headline line (`value`,
+`ms_per_step` = one timed utterance, the phase times and the roofline derived from the timed region).  With
+--dump-outputs DIR, rank 0 then writes the last timed utterance's mel (80 x frames) and audio as DIR/mel.npy and
+DIR/audio.npy (float32); the inputs are seeded, so two builds can be compared output for output.
 
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL).  Utterances
 are independent (src/tacotron2/mod.rs:422-434), so the N*K utterances of the
 timed region are assigned to ranks by xd-tts_amd/shard.py with no data-path collective
 ("scaling": "weak": K utterances per GPU whatever N is).  Rank 0 prints ONE JSON line.
 
-Besides the headline the line carries `extra` blocks for the other BASELINE.json configs, measured
-after the timed region (each a few tens of ms of GPU time):
+With --full, the line also carries the live latency floor of the roofline, and `extra` blocks for the other
+BASELINE.json configs, measured after the timed region (each a few tens of ms of GPU time):
   extra.config3  configs[2]: 32 variable-length utterances (40-200 ids) -> <=100-id chunks decoded as one
                  padded/masked lock-step batch (decoder-only figures + roofline of the batched LSTM kernels)
   extra.config4  configs[3]: 32 utterances per GPU (256 at N = 8), length-sorted round-robin over the ranks,
                  end to end (batched mel-gen + per-utterance vocoder); counters all-gathered over RCCL
   extra.config5  configs[4]: Griffin-Lim only, 1000 frames, 30/60/120 iterations, with its HBM roofline
-and `cpu_baseline` (N = 1 only): the CPU port of the same algorithm on the host cores.
+and `cpu_baseline` with `parity` (N = 1 only): the CPU port of the same algorithm on the host cores, and
+the first timed utterance against the oracle.  --no-extras / --no-cpu-baseline drop those parts of a --full run.
 """
 import argparse
 import importlib
@@ -146,10 +152,14 @@ _T0 = time.perf_counter()
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (utterances per GPU)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the live latency floor, the extras, the CPU baselines and the parity leg (default: headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's mel and audio (rank 0) as DIR/mel.npy and DIR/audio.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline and parity")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the extra blocks (profiling runs)")
     ap.add_argument("--check-shared-utterance", action="store_true",
                     help="every rank also synthesizes utterance 0 (outside the timed region) and the line carries the sha256 of "
                          "its mel and audio per rank: identical bits on every rank and in a single-process run")
@@ -160,6 +170,10 @@ def main():
                     help="every rank loads through Tacotron2::load(DIR) (mod.rs:242) -- the path a deployment uses -- from a "
                          "tacotron2.xdtw that rank 0 writes there first (synthetic weights); default: each rank generates them")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras = args.full and not args.no_extras
+    cpu_base = args.full and not args.no_cpu_baseline
 
     import torch   # before the product library: see tests/conftest.py on the load order of the HIP runtime
 
@@ -262,6 +276,11 @@ def main():
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     mel, audio = mels[-1], audios[-1]
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives for its last step: the mel (80 x frames) and the audio, float32
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "mel.npy"), np.ascontiguousarray(mel, dtype=np.float32))
+        np.save(os.path.join(args.dump_outputs, "audio.npy"), np.ascontiguousarray(audio, dtype=np.float32))
     tt, tg = model.last_timings(), vocoder.last_timings()      # HIP-event sums over the K utterances of the timed region
     enc_ms, dec_ms, post_ms, dec_steps = tt["encoder_ms"], tt["decoder_ms"], tt["postnet_ms"], tt["steps"]
     m2l_ms, gl_ms = tg["mel_to_linear_ms"], tg["iterations_ms"]
@@ -279,7 +298,10 @@ def main():
     bytes_per_utt = steps_per_utt * DECODER_PARAM_BYTES + active * per_item_bytes(T_ENC)
     achieved = bytes_per_utt / (dec_ms / K * 1e-3) / 1e9
     traffic, traffic_src = pmc_traffic()
-    floor_us, floor_src = edge_floor(pkg, local_rank)
+    if args.full:
+        floor_us, floor_src = edge_floor(pkg, local_rank)
+    else:
+        floor_us, floor_src = None, {"measured": "not in a plain run (bench.py --full measures it live)"}
     flops_per_step = active * per_item_flops(T_ENC) / steps_per_utt           # 37.7 MFLOP per active chunk
     us_per_step = dec_ms / dec_steps * 1e3
     out = {
@@ -359,7 +381,7 @@ def main():
     # GPU's mel -> linear of it and the un-normalised 30- / 60-iteration audio from that S and the oracle's seeded phase table (the audio
     # of the timed call itself is the 60-iteration one from the in-kernel stream behind the output normalisation: compared with that below)
     parity_dir = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and np.array_equal(seq[0], _ids0):
+    if rank == 0 and world == 1 and cpu_base and np.array_equal(seq[0], _ids0):
         import tempfile
 
         parity_dir = tempfile.mkdtemp(prefix="xdtts_parity_")
@@ -388,7 +410,7 @@ def main():
         else:
             every = [mine_sha]
         extra["shared_utterance"] = {"what": "utterance 0 of the headline set synthesized by every rank", "per_rank": every}
-    if not args.no_extras:
+    if extras:
         # ---- the same utterances with the REFERENCE's vocoder setting: 30 iterations (GriffinLim::new(.., 30, 0.99),
         # src/tacotron2/mod.rs:456; SURVEY 8(d) "reference default 30 also reported"), outside the timed region above
         try:
@@ -409,7 +431,7 @@ def main():
             voc30.close()
         except Exception as e:  # noqa: BLE001  (the headline line must still be printed)
             extra["headline_30_iterations"] = {"error": repr(e)}
-    if not args.no_extras:
+    if extras:
         # ---- the same K utterances as K synchronous xdtts_synthesize_ids calls, one after the other (the headline of rounds 1-4: nothing
         # of utterance u + 1 starts before utterance u's audio is on the host)
         try:
@@ -428,7 +450,7 @@ def main():
                 "same_bits_as_the_sequence_call": bool(np.array_equal(a1, audio) and np.array_equal(m1, mel))}
         except Exception as e:  # noqa: BLE001
             extra["headline_one_call_per_utterance"] = {"error": repr(e)}
-    if not args.no_extras:
+    if extras:
         # ---- the same utterance with the gate ON (the reference's real mode, mod.rs:319-324): gate_layer rigged so that
         # sigmoid(gate) > 0.6 fires exactly at 633 / 167 frames (xd-tts_amd/gate_rig.py; every frame is unchanged), so the
         # device-side stop rule, the survivor hand-over of the pair and the frame-count round trip are TIMED, not only tested
@@ -458,7 +480,7 @@ def main():
             log("gate-on variant done")
         except Exception as e:  # noqa: BLE001
             extra["headline_gate_on"] = {"error": repr(e)}
-    if not args.no_extras:
+    if extras:
         # ---- configs[2] / configs[3]: this rank's share of 32*N utterances as one lock-step batch -------
         all_utts = wl.config4(pkg, n_batches=world)
         share, chunks, steps, owner = shard.plan_share(lambda ids: wl.chunk_utterance(pkg, ids), all_utts, rank, world, wl.FRAMES_PER_ID_BATCH)
@@ -499,9 +521,9 @@ def main():
         counters = res_f if res_f is not None else {"frames": 0, "samples": 0, "seconds": -1.0}
         totals, max_s, per_rank = shard.gather_counters(counters, dist, device=red_dev if dist else "cpu")
         share_ok = all(r["seconds"] >= 0 for r in per_rank)
-    if not args.no_extras and not share_ok:
+    if extras and not share_ok:
         extra["config3"] = extra["config4"] = {"error": "a rank's share failed", "this_rank": share_err, "per_rank": per_rank}
-    if not args.no_extras and share_ok:
+    if extras and share_ok:
         fr, t_mel, tm, voc_ms = res["frames"], res["mel_gen_seconds"], res["timings"], res["vocoder_seconds"] * 1e3
         it = tm["steps"]
         act = float(sum(steps))                                                    # active chunk-steps of this rank
@@ -539,7 +561,7 @@ def main():
                               "note": "xdtts_tacotron2_infer_batch then xdtts_griffinlim_infer_batch, the mel crossing the host (the reference's own call sequence per utterance, src/lib.rs:123,141)"},
             "per_rank": per_rank,
         }
-    if not args.no_extras:
+    if extras:
         # ---- configs[4]: Griffin-Lim only, 1000 frames ------------------------------------------------
         if rank == 0:
           try:
@@ -603,7 +625,7 @@ def main():
         out["extra"] = extra
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_base:
             try:
                 out["cpu_baseline"] = cpu_baseline(parity_dir)
             except Exception as e:  # noqa: BLE001

@@ -34,7 +34,7 @@ def test_bench_two_ranks_on_one_gpu(pkg, tmp_path):
     env = dict(os.environ, XDTTS_BENCH_DEVICE="0", XDTTS_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--check-shared-utterance", "--load-from-dir", str(tmp_path / "model")]
+           "--full", "--no-cpu-baseline", "--check-shared-utterance", "--load-from-dir", str(tmp_path / "model")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

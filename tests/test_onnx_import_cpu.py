@@ -1,6 +1,7 @@
 """tools/onnx_to_xdtw.py (the reference's on-disk weight format): synthetic
 ONNX graphs laid out the two ways torch.onnx.export writes this model must convert to the exact
 canonical tensors -- LSTM gate re-order, MatMul/Gemm orientation, conv order, BN statistics."""
+import json
 import os
 import struct
 import sys
@@ -73,12 +74,18 @@ def test_lfs_pointer_and_missing_pieces_are_reported(tmp_path):
         conv.collect(str(tmp_path))
 
 
-def test_reference_checkout_holds_pointers_only():
-    """Why the converter is unverified against the real graphs (documented in its header)."""
-    ref = "/root/reference/models/tacotron2/encoder.onnx"
-    if not os.path.exists(ref):
-        pytest.skip("reference checkout not present on this box")
+def test_reference_checkout_holds_pointers_only(tmp_path):
+    """Why the converter is unverified against the real graphs (documented in its header).  The reference's
+    models/tacotron2/*.onnx are recorded in tests/golden/reference_model_pointers.json."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_model_pointers.json")) as fh:
+        files = json.load(fh)["files"]
+    assert sorted(files) == ["decoder_iter.onnx", "encoder.onnx", "postnet.onnx"]
+    for name, text in files.items():
+        (tmp_path / name).write_bytes(text.encode())
+    ref = str(tmp_path / "encoder.onnx")
     assert os.path.getsize(ref) < 1024 and open(ref, "rb").read(24).startswith(b"version https://git-lfs")
+    with pytest.raises(ValueError, match="git-LFS pointer"):     # that model directory is refused with a message
+        conv.collect(str(tmp_path))
 
 
 # ---- the same import inside the library: Tacotron2::load(dir) on the reference's model directory ----
