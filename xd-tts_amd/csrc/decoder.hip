@@ -716,25 +716,6 @@ __global__ __launch_bounds__(256) void k_lstm(DecoderBufs d, int i, int cur, con
 // tagged 8-byte granules {tag = step + 1, value}: the in-launch exchanges of the batched kernels (comments at k_attention_b)
 typedef unsigned long long u64;
 constexpr unsigned AB_SPIN_LIMIT = 1u << 20;
-
-// One agent-scope fetch-and-add per WAVE, its result in a scalar: lane 0 alone issues it (the exec mask is narrowed and restored inside
-// the statement).  Written as one opaque statement because the compiler threads `if (lane == 0) t = atomic...; t = readfirstlane(t)`
-// through a surrounding loop into one loop for lane 0 and another for the other 63 lanes, whose readfirstlane then reads a lane that
-// never held the result (seen: round 6, the relay's ticket loop never ended).  The wave must be whole (all 64 lanes active) here.
-__device__ __forceinline__ unsigned wave_fetch_add(unsigned *p, unsigned v) {
-  unsigned r;
-  unsigned long long keep;
-  asm volatile(
-      "s_mov_b64 %1, exec\n\t"
-      "s_mov_b64 exec, 1\n\t"
-      "global_atomic_add %0, %2, %3, %4 sc0\n\t"
-      "s_waitcnt vmcnt(0)\n\t"
-      "s_mov_b64 exec, %1"
-      : "=&v"(r), "=&s"(keep)
-      : "v"(0u), "v"(v), "s"(p)
-      : "memory");
-  return (unsigned)__builtin_amdgcn_readfirstlane((int)r);
-}
 __device__ __forceinline__ void granule_store(u64 *slot, unsigned tag, float v) {
   __hip_atomic_store(slot, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -781,25 +762,19 @@ struct NoHook {
 // PART, adds the early partial of the remaining columns (DecoderBufs::att_part) in the cell-update waves.
 // TAIL (decoder LSTM, two-launch form): h_dec leaves as granules d.hdg for the chunk's projection / prenet blocks of the same
 // launch (dec_tail_chunk) instead of the partial-mel rows the prenet launch would sum.
-// C1 / CN1 (round 6): a FIRST range [C1, C1 + CN1) multiplied ahead of [C0, C0 + CN) -- the attention launch runs its h_att(s-1)
-// columns (data two launches old) before the prenet columns x(s), whose first loads take ~4 us to arrive from the other XCDs' tail
-// blocks; wsrc is then the BLOCK's first k-step (k-step 0 of its rows), not the wave's.
-template <int NCOLS, int KIND, int NTA, class Hook = NoHook, int C0 = 0, int CN = NCOLS, bool PART = false, bool TAIL = false, int C1 = 0, int CN1 = 0>
+template <int NCOLS, int KIND, int NTA, class Hook = NoHook, int C0 = 0, int CN = NCOLS, bool PART = false, bool TAIL = false>
 __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int cur, int step, int blk, const float4 *__restrict__ wsrc,
                                                const float4 bz, const float (&wa)[6], float *s_acc, unsigned long long active,
                                                unsigned long long d_probe_entry = 0, Hook after_loop = Hook()) {  // active: bit j = chunk n0 + j still runs at this step
-  constexpr int NW = MFMA_WAVES, KW = CN / NW, JJ0 = KW / 16, JJ1 = CN1 / NW / 16, JJ = JJ0 + JJ1;
-  static_assert(CN % (16 * NW) == 0 && C0 % 16 == 0 && CN1 % (16 * NW) == 0 && C1 % 16 == 0, "whole k-steps per wave");
+  constexpr int NW = MFMA_WAVES, KW = CN / NW, JJ = KW / 16;
+  static_assert(CN % (16 * NW) == 0 && C0 % 16 == 0, "whole k-steps per wave");
   constexpr int N0 = KIND == 0 ? PRENET : ATT_RNN, N1 = EMB;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fi = lane & 15, fg = lane >> 4;  // (wave index as a scalar: the segment choice in src() below is then scalar code, not exec-masked branches)
   const float4 *seg0 = reinterpret_cast<const float4 *>(KIND == 0 ? d.xf : d.att_hf[cur ^ 1]);
   const float4 *seg1 = reinterpret_cast<const float4 *>(d.ctxf);
   const float4 *seg2 = reinterpret_cast<const float4 *>(KIND == 0 ? d.att_hf[cur] : d.dec_hf[cur]);
-  // k-step of the weight rows / first column that loop step jj multiplies (wave-uniform)
-  auto kstep = [&](int jj) { return CN1 == 0 ? C0 / 16 + wave * JJ0 + jj : (jj < JJ1 ? C1 / 16 + wave * JJ1 + jj : C0 / 16 + wave * JJ0 + (jj - JJ1)); };
-  auto w_at = [&](int jj) { return CN1 == 0 ? wsrc + (size_t)jj * 64 : wsrc + (size_t)kstep(jj) * 64; };
   auto src = [&](int jj) {  // first 16-byte vector of this lane for k-step jj (wave-uniform segment choice)
-    const int col = 16 * kstep(jj);
+    const int col = C0 + wave * KW + 16 * jj;
     const float4 *sb = col < N0 ? seg0 + (size_t)(col >> 2) * d.Bpad
                                 : (col < N0 + N1 ? seg1 + (size_t)((col - N0) >> 2) * d.Bpad : seg2 + (size_t)((col - N0 - N1) >> 2) * d.Bpad);
     return sb + (size_t)fg * d.Bpad + n0 + fi;
@@ -847,7 +822,7 @@ __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int
   float4 ring[RX][NTA], wring[8];
 #pragma unroll
   for (int p = 0; p < (DW > DX ? DW : DX) && p < JJ; ++p) {
-    if (p < DW) wring[p] = *w_at(p);  // plain loads: with the non-temporal hint of the GEMV kernels the 52-chunk iteration took 2.3 us longer
+    if (p < DW) wring[p] = wsrc[(size_t)p * 64];  // plain loads: with the non-temporal hint of the GEMV kernels the 52-chunk iteration took 2.3 us longer
                                       // (the 71 MB of weights fit the 256 MB Infinity Cache and are read again 50 us later)
     if (p < DX) {
       const float4 *sp = src(p);
@@ -874,7 +849,7 @@ __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int
       for (int t = 0; t < NTA; ++t) ring[(jj + DX) % RX][t] = sp[16 * t];  // (non-temporal: 38.5 -> 45 us per iteration, the 32 CUs of an XCD share these lines in L2)
     }
     asm volatile("" ::: "memory");
-    if (jj + DW < JJ) wring[(jj + DW) % 8] = *w_at(jj + DW);
+    if (jj + DW < JJ) wring[(jj + DW) % 8] = wsrc[(size_t)(jj + DW) * 64];
     asm volatile("" ::: "memory");
     // (the asm fences order memory operations only: the MFMAs of the NEXT k-step, whose operands are in flight already, are free
     // to be hoisted above this k-step's loads, and then every load is waited for right behind its issue -- seen in the ISA after an
@@ -930,11 +905,6 @@ __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int
             h_out[(size_t)n * ATT_RNN + unit] = hn;
         }
         hf_out[((size_t)blk * d.Bpad + n) * 4 + fg] = hn;
-        if (KIND == 0 && d.hring) {  // ... and into this step's slab of the write-once ring (the same launch's extra blocks poll it)
-          const unsigned hb = __float_as_uint(hn);
-          __hip_atomic_store(d.hring + ((size_t)step * (ATT_RNN / 4) + blk) * d.Bpad * 4 + (size_t)n * 4 + fg, hb == 0xffffffffu ? 0x7fc00000u : hb, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-        }
         if (TAIL && !(d.tail_fault && blk == d.tail_fault - 1)) granule_store(d.hdg + (size_t)n * DEC_RNN + unit, (unsigned)step + 1u, hn);
       }
     }
@@ -991,13 +961,10 @@ __device__ __forceinline__ unsigned hw_place() {  // (xcc << 16) | HW_ID: which 
 // blocks are a latency chain; the decoder-LSTM launch of step s then multiplies [h_att(s) ; ctx(s)] only.  hcur: half of dec_hf.
 constexpr int EARLY_K0 = PRENET / 16, EARLY_KS = (ATT_COLS - PRENET) / 16;  // k-steps 16 .. 111 of the 112
 constexpr int EARLY_K0_D = (ATT_RNN + EMB) / 16, EARLY_KS_D = DEC_RNN / 16;  // decoder LSTM: k-steps 96 .. 159 of the 160
-#ifndef XDTTS_HRING_AUX
-#define XDTTS_HRING_AUX 16  // cache policy of the first poll of a ring quad (16 = sc1; retries: sc0 sc1)
-#endif
-template <int NTA, int KIND = 0, bool HIN = false, bool SHORT = false>
+template <int NTA, int KIND = 0>
 __device__ __forceinline__ void att_early_partial(const DecoderBufs &d, int hcur, int blk, const float4 *__restrict__ Wm, float *lds,
-                                                  unsigned long long t_entry = 0, int step = 0, unsigned long long active = ~0ull) {
-  constexpr int NWV = MFMA_WAVES, K0 = KIND ? EARLY_K0_D : EARLY_K0, KS = KIND ? EARLY_KS_D : (SHORT ? EMB / 16 : EARLY_KS), JJ = KS / NWV;  // SHORT: the 512 context columns only (DecoderBufs::att_hfirst)
+                                                  unsigned long long t_entry = 0, int step = 0) {
+  constexpr int NWV = MFMA_WAVES, K0 = KIND ? EARLY_K0_D : EARLY_K0, KS = KIND ? EARLY_KS_D : EARLY_KS, JJ = KS / NWV;
   constexpr int KSTEPS = (KIND ? DEC_COLS : ATT_COLS) / 16;
   static_assert(KS % NWV == 0, "whole k-steps per wave");
 #ifdef XDTTS_LSTM_PROBE
@@ -1006,19 +973,6 @@ __device__ __forceinline__ void att_early_partial(const DecoderBufs &d, int hcur
 #endif
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fi = lane & 15, fg = lane >> 4;
   const float4 *wsrc = Wm + ((size_t)blk * KSTEPS + K0 + wave * JJ) * 64 + lane;
-  unsigned xcc = 0;
-  unsigned *rcnt = nullptr;  // per-XCD relay of the h_att ring (below): this XCD's counters of the step, [0] octets of rows drawn, [1] rows in the copy
-  if constexpr (HIN) {
-    if (d.hstage) {  // the block draws its octet now, the answer is needed after the first K-loop
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      xcc &= 7u;
-      rcnt = d.hcnt + ((size_t)xcc * d.hring_steps + step) * 64;  // (256 bytes per counter pair, the XCDs' counters far apart: not one line, not one channel)
-      if (wave == 0) {
-        const unsigned t = wave_fetch_add(rcnt, 1u);
-        if (lane == 0) reinterpret_cast<volatile unsigned *>(lds)[0] = t;
-      }
-    }
-  }
   const float4 *seg1 = reinterpret_cast<const float4 *>(d.ctxf), *seg2 = reinterpret_cast<const float4 *>(KIND ? d.dec_hf[hcur] : d.att_hf[hcur]);
   auto src = [&](int jj) {  // (wave-uniform segment choice: scalar code)
     const int col = 16 * (wave * JJ + jj);  // column behind the prenet columns (KIND 1: of h_dec)
@@ -1065,118 +1019,6 @@ __device__ __forceinline__ void att_early_partial(const DecoderBufs &d, int hcur
 #pragma unroll
     for (int t = 0; t < NTA; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.w, xv[t].w, acc[t], 0, 0, 0);
   }
-  if constexpr (HIN) {
-    // KIND 1, two-launch form with d.hring: the decoder LSTM's h_att(s) columns too -- k-steps 0 .. 63 of its weights against the vector
-    // the attention-LSTM blocks of THIS launch are publishing into the step's ring slab.  Every 16-byte operand quad (k-quad 4 j + fg,
-    // chunk) has one producer block; it is polled (sc1, retries sc0 sc1) until none of its words is the fill pattern, one k-step
-    // ahead of the MFMAs.  Lanes of chunks that do not run this step take zeros and wait for nobody.
-    constexpr int JH = (ATT_RNN / 16) / NWV;  // 8 k-steps per wave
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs_ring = __builtin_amdgcn_make_buffer_rsrc((void *)(d.hring + (size_t)step * ATT_RNN * d.Bpad), 0, 0x7fffffff, 0x00020000);
-    const float4 *wh = Wm + ((size_t)blk * KSTEPS + wave * JH) * 64 + lane;
-    const unsigned spin_limit = d.att_spins > 0 ? (unsigned)d.att_spins : AB_SPIN_LIMIT;
-    bool on[NTA];
-#pragma unroll
-    for (int t = 0; t < NTA; ++t) on[t] = (active >> (16 * t + fi)) & 1ull;
-    // Per-XCD relay (d.hstage): 256 blocks each pulling the whole slab from the other XCDs get ~24 GB/s per CU (6 TB/s over the chip: the
-    // rate of every in-launch bulk edge on this part).  Instead the blocks that find themselves on XCD x (HW_REG_XCC_ID: a fact, not an
-    // assumption about placement) share the pull: every block draws an octet of the slab's 256 k-quad rows of [chunks][4] from the XCD's
-    // ticket counter (at entry, one atomic per block), each of its waves polls one row of it out of the ring (one quad per lane) and
-    // writes it into the XCD's own copy with plain stores (they stay in that XCD's L2); everybody polls its operands out of that copy,
-    // with L1-bypassing loads that hit the shared L2, under the ring's own rule (a quad with a fill word is not there yet).  The XCD has
-    // two copies, by step parity: whoever fills a row of this step's copy puts the fill pattern back into the same row of the other,
-    // which the previous launch is done with and the next one will poll (the host fills both at the start of a request).  Any number
-    // of blocks per XCD completes the copy: a wave whose poll stays pending looks at the ticket counter and takes an undrawn octet whole.
-    const bool relay = d.hstage != nullptr;
-    __amdgpu_buffer_rsrc_t rs = rs_ring, rs_stage = rs_ring, rs_other = rs_ring;
-    constexpr unsigned ROWS = ATT_RNN / 4, OCTETS = ROWS / NWV;
-    const bool mine = lane < 16 * NTA, wanted = mine && ((active >> lane) & 1ull);
-    auto move_row = [&](unsigned row) {  // ring -> this XCD's copy of the step, one quad per lane; the same row of the other copy back to "unwritten"
-      const int off = (int)((row * (unsigned)d.Bpad + (unsigned)lane) * 16u);
-      u32x4 v = (u32x4){0u, 0u, 0u, 0u};
-      if (wanted) {
-        unsigned spins = 0;
-        v = __builtin_amdgcn_raw_buffer_load_b128(rs_ring, off, 0, 16);
-        while (v.x == 0xffffffffu || v.y == 0xffffffffu || v.z == 0xffffffffu || v.w == 0xffffffffu) {
-          if (++spins > spin_limit || ((spins & 127u) == 0 && __hip_atomic_load(d.att_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-            atomicExch(d.att_err, 1);
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-          v = __builtin_amdgcn_raw_buffer_load_b128(rs_ring, off, 0, 17);
-        }
-      }
-      if (mine) {
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs_stage, off, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128((u32x4){0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, rs_other, off, 0, 0);
-      }
-    };
-    auto rescue = [&]() {  // octets no block has drawn (fewer than 32 of these blocks on this XCD): whoever waits long enough takes one whole
-      if ((unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(rcnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) >= OCTETS) return;
-      const unsigned t2 = wave_fetch_add(rcnt, 1u);
-      if (t2 < OCTETS)
-        for (unsigned r = 0; r < (unsigned)NWV; ++r) move_row(t2 * NWV + r);
-    };
-    if (relay) {
-      const size_t copy = (size_t)ATT_RNN * d.Bpad;
-      rs_stage = __builtin_amdgcn_make_buffer_rsrc((void *)(d.hstage + (2 * xcc + (step & 1)) * copy), 0, 0x7fffffff, 0x00020000);
-      rs_other = __builtin_amdgcn_make_buffer_rsrc((void *)(d.hstage + (2 * xcc + ((step & 1) ^ 1)) * copy), 0, 0x7fffffff, 0x00020000);
-      __syncthreads();  // the block's octet (ticket drawn at entry): one row per wave
-      const unsigned tk = (unsigned)__builtin_amdgcn_readfirstlane((int)reinterpret_cast<volatile unsigned *>(lds)[0]);
-      if (tk < OCTETS) move_row(tk * NWV + (unsigned)wave);
-      rs = rs_stage;
-    }
-    auto voff = [&](int jj, int t) { return (int)((((unsigned)(4 * (wave * JH + jj) + fg) * (unsigned)d.Bpad) + 16u * t + fi) * 16u); };
-    // (operand quads DH k-steps ahead: a poll of another XCD's fresh data takes ~1.3 us whatever it finds, a k-step's MFMAs 0.2 us)
-    constexpr int DH = NTA <= 2 ? 6 : (NTA == 3 ? 4 : 3);
-    u32x4 hb[DH][NTA];
-    float4 wv2[DH];
-#pragma unroll
-    for (int p = 0; p < DH; ++p) {
-#pragma unroll
-      for (int t = 0; t < NTA; ++t) hb[p][t] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff(p, t), 0, 16);
-      wv2[p] = wh[(size_t)p * 64];
-    }
-#pragma unroll
-    for (int jj = 0; jj < JH; ++jj) {
-      u32x4(&v)[NTA] = hb[jj % DH];
-      unsigned pending = 0u, spins = 0;
-#pragma unroll
-      for (int t = 0; t < NTA; ++t) {
-        pending |= (on[t] && (v[t].x == 0xffffffffu || v[t].y == 0xffffffffu || v[t].z == 0xffffffffu || v[t].w == 0xffffffffu)) ? 1u << t : 0u;
-        if (!on[t]) v[t] = (u32x4){0u, 0u, 0u, 0u};
-      }
-      while (pending) {
-        if (++spins > spin_limit || ((spins & 127u) == 0 && __hip_atomic_load(d.att_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-          atomicExch(d.att_err, 1);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        if (relay && (spins & 63u) == 32u) rescue();
-#pragma unroll
-        for (int t = 0; t < NTA; ++t)
-          if ((pending >> t) & 1u) v[t] = relay ? __builtin_amdgcn_raw_buffer_load_b128(rs, voff(jj, t), 0, 16) : __builtin_amdgcn_raw_buffer_load_b128(rs, voff(jj, t), 0, 17);  // (the XCD's copy lives in this L2: sc1 is enough)
-#pragma unroll
-        for (int t = 0; t < NTA; ++t)
-          if (((pending >> t) & 1u) && v[t].x != 0xffffffffu && v[t].y != 0xffffffffu && v[t].z != 0xffffffffu && v[t].w != 0xffffffffu) pending &= ~(1u << t);
-        asm volatile("" ::: "memory");
-      }
-      const float4 wv = wv2[jj % DH];
-#pragma unroll
-      for (int t = 0; t < NTA; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.x, __uint_as_float(v[t].x), acc[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < NTA; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.y, __uint_as_float(v[t].y), acc[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < NTA; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.z, __uint_as_float(v[t].z), acc[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < NTA; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.w, __uint_as_float(v[t].w), acc[t], 0, 0, 0);
-      if (jj + DH < JH) {  // the slot just consumed: the operands DH k-steps on
-#pragma unroll
-        for (int t = 0; t < NTA; ++t) v[t] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff(jj + DH, t), 0, 16);
-        wv2[jj % DH] = wh[(size_t)(jj + DH) * 64];
-      }
-    }
-  }
 #ifdef XDTTS_LSTM_PROBE
   ep[1] = wall_clock64();
 #endif
@@ -1199,32 +1041,11 @@ __device__ __forceinline__ void att_early_partial(const DecoderBufs &d, int hcur
 }
 // the role as a whole: tiles by the chunks still active at step `next`
 template <int KIND = 0>
-__device__ __forceinline__ void att_early_role(const DecoderBufs &d, int next, int hcur, int blk, const float4 *__restrict__ Wm, float *lds, unsigned long long t_entry,
-                                               bool hin = false) {
+__device__ __forceinline__ void att_early_role(const DecoderBufs &d, int next, int hcur, int blk, const float4 *__restrict__ Wm, float *lds, unsigned long long t_entry) {
   const int lane = threadIdx.x & 63;
   const bool a = lane < d.B && next < d.nframes[min(lane, d.B - 1)];  // (a chunk the next prenet launch stops still counts: its tile's partial is not read then)
   const unsigned long long m = __ballot(a);
   const int nta = m ? (63 - __clzll((long long)m)) / 16 + 1 : 0;
-  if (KIND == 1 && hin) {  // (the attention launch's extra blocks, with the ring: + the h_att(s) columns, polled inside the launch)
-    switch (nta) {
-      case 1: att_early_partial<1, KIND, KIND == 1>(d, hcur, blk, Wm, lds, t_entry, next, m); break;
-      case 2: att_early_partial<2, KIND, KIND == 1>(d, hcur, blk, Wm, lds, t_entry, next, m); break;
-      case 3: att_early_partial<3, KIND, KIND == 1>(d, hcur, blk, Wm, lds, t_entry, next, m); break;
-      case 4: att_early_partial<4, KIND, KIND == 1>(d, hcur, blk, Wm, lds, t_entry, next, m); break;
-      default: break;
-    }
-    return;
-  }
-  if (KIND == 0 && d.att_hfirst) {  // (the attention launch multiplies its h_att columns itself: the context columns only here)
-    switch (nta) {
-      case 1: att_early_partial<1, KIND, false, KIND == 0>(d, hcur, blk, Wm, lds, t_entry, next); break;
-      case 2: att_early_partial<2, KIND, false, KIND == 0>(d, hcur, blk, Wm, lds, t_entry, next); break;
-      case 3: att_early_partial<3, KIND, false, KIND == 0>(d, hcur, blk, Wm, lds, t_entry, next); break;
-      case 4: att_early_partial<4, KIND, false, KIND == 0>(d, hcur, blk, Wm, lds, t_entry, next); break;
-      default: break;
-    }
-    return;
-  }
   switch (nta) {
     case 1: att_early_partial<1, KIND>(d, hcur, blk, Wm, lds, t_entry, next); break;
     case 2: att_early_partial<2, KIND>(d, hcur, blk, Wm, lds, t_entry, next); break;
@@ -1447,17 +1268,7 @@ __global__ __launch_bounds__(64 * MFMA_WAVES) void k_lstm_mfma(DecoderBufs d, in
     wa[rt] = (KIND == 1 && wave < 4 && mrow < MEL_LD) ? reinterpret_cast<const float *>(Wepi)[((size_t)blk * MEL_LD + mrow) * 4 + fg] : 0.f;
   }
   if (KIND == 1 && d.hdg) {  // two-launch form: h_dec as granules, then the chunk's projection / prenet tail
-    if (d.dec_part && d.hring) {  // ... and so were the h_att(s) columns (polled from the ring inside that launch): the 512 context columns only
-      constexpr int C0S = KIND == 1 ? ATT_RNN : 0, CNS = KIND == 1 ? EMB : NCOLS;
-      const float4 *ws = Wm + ((size_t)blk * (NCOLS / 16) + C0S / 16 + wave * (CNS / NW / 16)) * 64 + lane;
-      switch (nta) {
-        case 1: lstm_mfma_pass<NCOLS, KIND, 1, NoHook, C0S, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m, t_entry); break;
-        case 2: lstm_mfma_pass<NCOLS, KIND, 2, NoHook, C0S, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m, t_entry); break;
-        case 3: lstm_mfma_pass<NCOLS, KIND, 3, NoHook, C0S, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m, t_entry); break;
-        case 4: lstm_mfma_pass<NCOLS, KIND, 4, NoHook, C0S, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m, t_entry); break;
-        default: return;
-      }
-    } else if (d.dec_part) {  // ... and the h_dec(s-1) columns were multiplied by the attention launch's extra blocks: [h_att ; ctx] only
+    if (d.dec_part) {  // ... and the h_dec(s-1) columns were multiplied by the attention launch's extra blocks: [h_att ; ctx] only
       constexpr int CNS = KIND == 1 ? ATT_RNN + EMB : NCOLS;
       const float4 *ws = Wm + ((size_t)blk * (NCOLS / 16) + wave * (CNS / NW / 16)) * 64 + lane;
       switch (nta) {
@@ -1977,7 +1788,7 @@ __global__ __launch_bounds__(64 * MFMA_WAVES, TWO ? 4 : 2) void k_att_lstm_atten
   const float wa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   __shared__ __attribute__((aligned(16))) float s_acc[NW * 4 * 64 * 4];
   if (TWO && (int)blockIdx.x >= NBLK) {  // blocks 256..511 (with d.dec_part): the early partial of THIS step's decoder-LSTM pass over h_dec(s-1)
-    att_early_role<1>(d, d.ctl[0] + i, cur, (int)blockIdx.x - NBLK, dec_wm, s_acc, 0, d.hring != nullptr);
+    att_early_role<1>(d, d.ctl[0] + i, cur, (int)blockIdx.x - NBLK, dec_wm, s_acc, 0);
     return;
   }
   // blocks 4 b .. 4 b + 3 are the attention blocks of chunk b; their loads for that phase go out as soon as the wave has
@@ -1988,17 +1799,6 @@ __global__ __launch_bounds__(64 * MFMA_WAVES, TWO ? 4 : 2) void k_att_lstm_atten
   auto hook = [&]() {
     if (attn) attention_loads<512, true>(L, d, i, cur, b, part, Wq, v_w);  // (the late group follows the publish of h: attention_chunk)
   };
-  if (EARLY && TWO && d.att_hfirst) {  // + its own h_att(s-1) columns, ahead of the prenet columns (att_part then holds the context columns only)
-    constexpr int HC = EARLY && TWO ? ATT_RNN : 0;
-    const float4 *wblk = Wm + (size_t)blk * (ATT_COLS / 16) * 64 + lane;
-    switch (nta) {
-      case 1: lstm_mfma_pass<ATT_COLS, 0, 1, decltype(hook), 0, CN, EARLY, false, ATT_IN, HC>(d, 0, cur, step, blk, wblk, bz, wa, s_acc, m, 0, hook); break;
-      case 2: lstm_mfma_pass<ATT_COLS, 0, 2, decltype(hook), 0, CN, EARLY, false, ATT_IN, HC>(d, 0, cur, step, blk, wblk, bz, wa, s_acc, m, 0, hook); break;
-      case 3: lstm_mfma_pass<ATT_COLS, 0, 3, decltype(hook), 0, CN, EARLY, false, ATT_IN, HC>(d, 0, cur, step, blk, wblk, bz, wa, s_acc, m, 0, hook); break;
-      case 4: lstm_mfma_pass<ATT_COLS, 0, 4, decltype(hook), 0, CN, EARLY, false, ATT_IN, HC>(d, 0, cur, step, blk, wblk, bz, wa, s_acc, m, 0, hook); break;
-      default: return;
-    }
-  } else
   switch (nta) {
     case 1: lstm_mfma_pass<ATT_COLS, 0, 1, decltype(hook), 0, CN, EARLY>(d, 0, cur, step, blk, wsrc, bz, wa, s_acc, m, 0, hook); break;
     case 2: lstm_mfma_pass<ATT_COLS, 0, 2, decltype(hook), 0, CN, EARLY>(d, 0, cur, step, blk, wsrc, bz, wa, s_acc, m, 0, hook); break;
@@ -2099,9 +1899,6 @@ static void enqueue_steps(const DecoderBufs &d, const DeviceWeights &w, int i0, 
   DecoderBufs dd = d;                                    // what the decoder-LSTM launch sees
   if (!two) dd.hdg = dd.melg = nullptr;
   if (!two) dd.dec_part = nullptr;
-  if (!two) dd.hring = nullptr;
-  if (!two) dd.hstage = dd.hcnt = nullptr;
-  if (!two) dd.att_hfirst = 0;
   const TailWeights tw{reinterpret_cast<const float4 *>(w.proj_w.p), w.proj_b.p, w.pre0T.p, w.pre1T.p, w.loc_conv.p, w.loc_denseT.p};
   for (int i = i0; i < i0 + nsteps; ++i) {
     const int cur = i & 1;

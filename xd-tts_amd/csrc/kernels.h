@@ -78,21 +78,6 @@ struct DecoderBufs {
   int att_spins, att_fault;  // test hooks: poll limit (0 = default) and a block (index + 1) that never publishes its energies
   int tail_fault;            // test hook, two-launch form: a decoder-LSTM block (index + 1) that never publishes its h_dec granules
   int att_slow;              // test hook: a block (index + 1) of both batched launches that stalls ~7 us at a different point of every step
-  // Two-launch form, round 6: h_att(s) ALSO as a write-once ring of plain values in B-operand order [step][1024 / 4][Bpad][4]
-  // (0xFFFFFFFF = not yet written; a value is its own arrival flag, decoder_persistent16.hip), so that the extra blocks of the
-  // attention launch multiply the decoder LSTM's h_att columns INSIDE that launch, behind its h_dec columns, while the attention
-  // chain runs -- the decoder-LSTM launch's critical pass then covers the 512 context columns only.  null = that pass covers
-  // [h_att ; ctx] (1536 columns) as before.  hring_steps: steps the ring is laid out for.
-  unsigned *hring;
-  int hring_steps;
-  // ... and the per-XCD relay of that ring (decoder.hip, att_early_partial): hstage [8 XCDs][2 step parities][1024 / 4][Bpad][4], copies of
-  // the step's slab per XCD; hcnt [8][steps][64] = {octets of rows drawn, ..} per XCD and step (zero at the start of a request).
-  // null = every block polls the ring itself.
-  unsigned *hstage, *hcnt;
-  // Two-launch form, round 6: the attention launch multiplies its OWN h_att(s-1) columns (1024 of the 1792) ahead of the prenet
-  // columns -- old data, in the ~4 us its first loads of x(s) take to arrive -- and att_part, written by the decoder-LSTM launch's
-  // extra blocks, covers the 512 context columns only: 1024 columns x chunks of matrix work leave the launch that is bound by it.
-  int att_hfirst;
 };
 constexpr int ATT_EXCHANGE_BLOCKS = 8;  // granule rows per chunk (CTX_BLOCKS in decoder.hip)
 // [B][T][128] -> [B][32][T][4]
