@@ -117,7 +117,7 @@ def test_batch_of_variable_length_chunks(pkg, model, orc, blob):
 
 
 def test_batch_mels_are_pieces_of_one_slab_released_one_by_one(pkg, model):
-    """xdtts_tacotron2_infer_batch hands out pieces of ONE pinned slab (xd-tts_amd/csrc/api.cpp: PinnedSlab): the slab
+    """xdtts_tacotron2_infer_batch hands out pieces of ONE pinned slab (xd-tts_amd/csrc/runtime.h: PinnedSlab): the slab
     returns to the pool only with the last piece, so a later call never writes into memory a live mel still refers to; a
     piece released twice is a no-op."""
     import ctypes as C

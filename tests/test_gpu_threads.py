@@ -1,7 +1,7 @@
 """The `&self` / `Send + Sync` surface (SURVEY 8(b) "Threading"; src/lib.rs:110-159 takes &self, the Rust shim declares
 `unsafe impl Sync`): one handle called from two threads, and two mel-gen handles plus one
 vocoder handle on one GPU with interleaved calls.  Every launch that needs the whole chip co-resident (persistent decoder,
-cooperative encoder BiLSTM, persistent Griffin-Lim) is serialised by the per-GPU lock in api.cpp: results must be bit-equal
+cooperative encoder BiLSTM, persistent Griffin-Lim) is serialised by the per-GPU lock in runtime.cpp: results must be bit-equal
 to the serial run, nothing may deadlock, and the handles must still be on their fast engines afterwards.
 (ctypes releases the GIL around every foreign call, so the calls really overlap.)"""
 import threading

@@ -12,7 +12,6 @@ run gate_rig_check.py         python tools/gate_rig_check.py
 run gemm_bench.py             python tools/gemm_bench.py 200 2
 run gl_check.py               python tools/gl_check.py
 run gl_hash.py                python tools/gl_hash.py
-run gl_poll_sweep.py          python tools/gl_poll_sweep.py 1000 6
 run gl_tf_sweep.py            python tools/gl_tf_sweep.py
 run headline_call.py          python tools/headline_call.py 3
 run p8_check.py               python tools/p8_check.py

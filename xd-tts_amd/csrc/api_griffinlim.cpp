@@ -1,0 +1,262 @@
+// api_griffinlim.cpp -- the extern "C" boundary, vocoder half: argument checks and locking; the work is in griffinlim_handle.cpp.
+#include <algorithm>
+#include <cmath>
+#include <memory>
+
+#include "griffinlim_handle.h"
+
+using namespace xdtts;
+
+extern "C" {
+
+xdtts_status xdtts_mel_filter_bank(float sample_rate, size_t n_fft, size_t n_mels, float fmin, float fmax_or_nan,
+                                   float *out) {
+  return guard([&] {
+    if (!out || n_fft < 2 || n_mels == 0 || !(sample_rate > 0)) fail(XDTTS_ERR_BAD_ARG, "bad filter bank request");
+    const double sr = sample_rate;
+    const double fmax = std::isnan(fmax_or_nan) ? sr / 2.0 : (double)fmax_or_nan;  // Option<f32>::None
+    xdtts::mel_filter_bank(sr, (int)n_fft, (int)n_mels, fmin, fmax, out);
+  });
+}
+
+xdtts_status xdtts_griffinlim_new(const float *mel_basis, size_t n_mels, size_t n_bins, size_t noverlap, float power,
+                                  size_t iters, float momentum, int32_t device_id, xdtts_griffinlim **out) {
+  return guard([&] {
+    if (!out) fail(XDTTS_ERR_BAD_ARG, "out handle pointer is null");
+    *out = nullptr;
+    if (!mel_basis || n_mels == 0 || n_bins < 2) fail(XDTTS_ERR_BAD_ARG, "bad mel basis");
+    const size_t n_fft = 2 * (n_bins - 1);
+    if (n_fft != 1024) fail(XDTTS_ERR_BAD_ARG, "n_fft %zu unsupported: the framed-FFT kernel is built for 1024", n_fft);
+    if (noverlap >= n_fft) fail(XDTTS_ERR_BAD_ARG, "noverlap %zu must be < n_fft %zu", noverlap, n_fft);
+    if (n_fft - noverlap != n_fft / 4)
+      fail(XDTTS_ERR_BAD_ARG, "hop %zu unsupported: the framed-FFT kernels are built for hop = n_fft/4 = 256 (mod.rs:456)", n_fft - noverlap);
+    if (n_mels % 16 != 0) fail(XDTTS_ERR_BAD_ARG, "n_mels %zu must be a multiple of 16", n_mels);
+    if (!(power > 0) || momentum < 0) fail(XDTTS_ERR_BAD_ARG, "bad power/momentum");
+    device_id = select_device(device_id);
+    auto g = std::make_unique<xdtts_griffinlim>();
+    g->device = device_id;
+    g->n_mels = (int)n_mels;
+    g->nb = (int)n_bins;
+    g->n_fft = (int)n_fft;
+    g->hop = (int)(n_fft - noverlap);
+    g->iters = (int)iters;
+    g->power = power;
+    g->momentum = momentum;
+    HIP_CHECK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    g->ev.create();
+    std::vector<float> pinv;
+    host_pinv(mel_basis, (int)n_mels, (int)n_bins, pinv);
+    g->pinv.upload(pinv.data(), pinv.size(), g->stream);
+    {  // NNLS refinement operands: the basis and its transpose, bins zero-padded to NBP, and the step 1/L
+      const int NBP = xdtts_griffinlim::NBP, nm = (int)n_mels, nbi = (int)n_bins;
+      std::vector<float> bp((size_t)nm * NBP, 0.f), bt((size_t)NBP * nm, 0.f);
+      for (int i = 0; i < nm; ++i)
+        for (int b = 0; b < nbi; ++b) bp[(size_t)i * NBP + b] = bt[(size_t)b * nm + i] = mel_basis[(size_t)i * nbi + b];
+      g->basis_p.upload(bp.data(), bp.size(), g->stream);
+      g->basisT_p.upload(bt.data(), bt.size(), g->stream);
+      g->nnls_step = (float)(1.0 / host_lipschitz(mel_basis, nm, nbi));
+      g->norm_parts.alloc(GLN_SCRATCH);
+    }
+    std::vector<float2> tw(n_fft);
+    std::vector<float> win(n_fft);
+    const double PI = 3.14159265358979323846;
+    for (size_t k = 0; k < n_fft; ++k) {
+      tw[k] = make_float2((float)std::cos(2.0 * PI * k / n_fft), (float)(-std::sin(2.0 * PI * k / n_fft)));
+      win[k] = (float)(0.5 - 0.5 * std::cos(2.0 * PI * k / n_fft));  // periodic hann
+    }
+    g->tw.upload(tw.data(), tw.size(), g->stream);
+    g->win.upload(win.data(), win.size(), g->stream);
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+    *out = g.release();
+  });
+}
+
+void xdtts_griffinlim_opts_default(xdtts_griffinlim_opts *o) {
+  if (!o) return;
+  o->nnls_iters = 0;
+  o->power_mode = 0;
+  o->mel_decompress = 0;
+  o->output_normalise = 3;  // rms, never past +-1: the level of the reference's own WAV_SPEC files
+  o->batch_shape = 0;
+  o->rms_target = 0.1f;
+}
+
+xdtts_status xdtts_griffinlim_set_opts(xdtts_griffinlim *g, const xdtts_griffinlim_opts *o) {
+  return guard([&] {
+    if (!g || !o) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (o->nnls_iters < 0 || o->nnls_iters > 100000 || o->power_mode < 0 || o->power_mode > 2 || o->mel_decompress < 0 ||
+        o->mel_decompress > 2 || o->output_normalise < 0 || o->output_normalise > 3 || !(o->rms_target > 0.f) || !(o->rms_target <= 1e6f) || (o->batch_shape != 0 && o->batch_shape != 4))
+      fail(XDTTS_ERR_BAD_ARG, "griffin-lim option out of range");
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->gopts = *o;
+  });
+}
+
+xdtts_status xdtts_griffinlim_get_opts(const xdtts_griffinlim *g, xdtts_griffinlim_opts *o) {
+  return guard([&] {
+    if (!g || !o) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    *o = g->gopts;
+  });
+}
+
+xdtts_status xdtts_griffinlim_set_seed(xdtts_griffinlim *g, uint32_t seed) {
+  return guard([&] {
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->seed = seed;
+  });
+}
+
+xdtts_status xdtts_griffinlim_infer(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
+                                    float **audio, size_t *n_samples) {
+  return guard([&] {
+    if (!g || !mel || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    *audio = nullptr;
+    *n_samples = 0;
+    if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
+    if (n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "need at least 2 frames, got %zu", n_frames);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    g->mel_in.upload(mel, n_mels * n_frames, g->stream);
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+    gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, audio, n_samples);
+  });
+}
+
+// GriffinLim::infer for several utterances at once (the vocoder half of a batch, BASELINE.json configs[3]):
+// the utterances' frames are concatenated, mel -> linear is one GEMM over all of them, and the persistent
+// kernel takes as many utterances per launch as fit one workgroup per CU.  Every utterance's audio is bit-identical to what
+// xdtts_griffinlim_infer returns for it alone.
+xdtts_status xdtts_griffinlim_infer_batch(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames,
+                                          int32_t n_utt, float **audios, size_t *n_samples) {
+  return guard([&] {
+    if (!g || !mels || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "bad argument");
+    if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
+    std::vector<int> fbase(n_utt), Fu(n_utt);
+    size_t Ftot = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      audios[u] = nullptr;
+      n_samples[u] = 0;
+      if (!mels[u] || n_frames[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 2 frames", u);
+      fbase[u] = (int)Ftot;
+      Fu[u] = (int)n_frames[u];
+      Ftot += n_frames[u];
+      if (Ftot > (1u << 24)) fail(XDTTS_ERR_BAD_ARG, "batch too large");
+    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    // mel of all utterances side by side: [n_mels][Ftot], staged in pinned memory (one fast upload)
+    PinnedGuard mel_all((size_t)n_mels * Ftot);
+    for (int u = 0; u < n_utt; ++u)
+      for (size_t m = 0; m < n_mels; ++m)
+        std::memcpy(mel_all.p + m * Ftot + fbase[u], mels[u] + m * n_frames[u], sizeof(float) * n_frames[u]);
+    g->mel_in.upload(mel_all.p, (size_t)n_mels * Ftot, g->stream);
+    HIP_CHECK(hipStreamSynchronize(g->stream));  // the staging buffer goes back to the pool
+    gl_batch_from_device(g, g->mel_in.p, Fu, audios, n_samples);
+  });
+}
+
+xdtts_status xdtts_griffinlim_mel_to_linear(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
+                                            float *S_out) {
+  return guard([&] {
+    if (!g || !mel || !S_out || n_frames == 0) fail(XDTTS_ERR_BAD_ARG, "bad argument");
+    if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    const int F = (int)n_frames;
+    g->mel_in.upload(mel, n_mels * n_frames, g->stream);
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+    g->bufs(F);
+    g->mel_to_linear(g->mel_in.p, F);
+    // S is [F][nb] on the device; the boundary layout is the crate's (nb x F)
+    g->frames.alloc((size_t)F * g->n_fft);
+    launch_transpose(g->S.p, g->frames.p, F, g->nb, g->stream);
+    HIP_CHECK(hipMemcpyAsync(S_out, g->frames.p, (size_t)F * g->nb * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+  });
+}
+
+xdtts_status xdtts_griffinlim_infer_linear(xdtts_griffinlim *g, const float *S, const float *phase0, size_t n_frames,
+                                           size_t iters, float **audio, size_t *n_samples) {
+  return guard([&] {
+    if (!g || !S || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    *audio = nullptr;
+    *n_samples = 0;
+    if (n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "need at least 2 frames, got %zu", n_frames);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    const int F = (int)n_frames;
+    GlBufs b = g->bufs(F);
+    // boundary layout (nb x F) -> device layout [F][nb]
+    g->frames.upload(S, (size_t)F * g->nb, g->stream);
+    launch_transpose(g->frames.p, g->S.p, g->nb, F, g->stream);
+    const float *p0 = nullptr;
+    if (phase0) {
+      g->phase0.upload(phase0, (size_t)F * g->nb * 2, g->stream);
+      p0 = g->phase0.p;
+    }
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
+    gl_iterate_and_fetch(g, b, p0, iters ? (int)iters : g->iters, audio, n_samples, false);  // G2..G5 + final ISTFT only
+  });
+}
+
+// Parity hook: `n_iter` Griffin-Lim iterations (no final ISTFT) from a caller-held state.
+xdtts_status xdtts_griffinlim_step(xdtts_griffinlim *g, const float *S, float *angles, float *rebuilt, size_t n_frames,
+                                   size_t n_iter) {
+  return guard([&] {
+    if (!g || !S || !angles || !rebuilt) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "need at least 2 frames, got %zu", n_frames);
+    if (n_iter == 0) n_iter = 1;
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    const int F = (int)n_frames;
+    const size_t ne = (size_t)F * g->nb;
+    GlBufs b = g->bufs(F);
+    g->frames.upload(S, ne, g->stream);
+    launch_transpose(g->frames.p, g->S.p, g->nb, F, g->stream);
+    g->phase0.alloc(ne * 4);  // staging: angles then rebuilt, (nb x F x 2) each
+    HIP_CHECK(hipMemcpyAsync(g->phase0.p, angles, ne * 2 * sizeof(float), hipMemcpyHostToDevice, g->stream));
+    HIP_CHECK(hipMemcpyAsync(g->phase0.p + ne * 2, rebuilt, ne * 2 * sizeof(float), hipMemcpyHostToDevice, g->stream));
+    launch_gl_state_import(b, g->phase0.p, g->phase0.p + ne * 2, g->stream);
+    launch_gl_prepare(b, g->stream);
+    const float alpha = g->momentum / (1.0f + g->momentum);
+    std::lock_guard<ChipLock> chip(chip_mutex(g->device));
+    g->probe_tick();
+    for (int attempt = 0;; ++attempt) {
+      const float2 *tp = nullptr;
+      const float2 *fin = g->run_iterations(b, (int)n_iter, alpha, nullptr, true, &tp);
+      if (!g->last_persistent) {  // the launch engine updates the state in place
+        launch_gl_state_export(b, fin, b.tprev, g->phase0.p, g->phase0.p + ne * 2, g->stream);
+        break;
+      }
+      HIP_CHECK(hipStreamSynchronize(g->stream));
+      if (!g->persistent_failed()) {
+        launch_gl_state_export(b, fin, tp, g->phase0.p, g->phase0.p + ne * 2, g->stream);
+        break;
+      }
+      if (attempt) fail(XDTTS_ERR_HIP, "Griffin-Lim step: exchange failure");
+    }
+    HIP_CHECK(hipMemcpyAsync(angles, g->phase0.p, ne * 2 * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    HIP_CHECK(hipMemcpyAsync(rebuilt, g->phase0.p + ne * 2, ne * 2 * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+  });
+}
+
+xdtts_status xdtts_griffinlim_last_timings(const xdtts_griffinlim *g, float ms[3]) {
+  return guard([&] {
+    if (!g || !ms) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    for (int i = 0; i < 3; ++i) ms[i] = g->last_ms[i];
+  });
+}
+
+void xdtts_griffinlim_free(xdtts_griffinlim *g) {
+  if (!g) return;
+  (void)hipSetDevice(g->device);
+  if (g->stream) (void)hipStreamSynchronize(g->stream);
+  delete g;
+}
+
+}  // extern "C"

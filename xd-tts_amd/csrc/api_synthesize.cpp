@@ -1,0 +1,231 @@
+// api_synthesize.cpp -- the extern "C" boundary, both halves in one call: XdTts::infer for one utterance, a sequence, a batch.
+#include <algorithm>
+#include <cmath>
+
+#include "griffinlim_handle.h"
+#include "tacotron2_handle.h"
+
+using namespace xdtts;
+
+extern "C" {
+
+// ---- XdTts::infer (src/lib.rs:110-159) --------------------------------------------------------------
+
+xdtts_status xdtts_synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
+                                  const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts, float **mel,
+                                  size_t *n_frames, float **audio, size_t *n_samples) {
+  return guard([&] {
+    if (!h || !g || !mel || !n_frames || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
+    *mel = nullptr;
+    *audio = nullptr;
+    *n_frames = *n_samples = 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::lock_guard<std::mutex> lk2(g->mu);
+    const xdtts_infer_opts o = resolve_opts(opts);
+    std::vector<int64_t> padded;
+    std::vector<int> lens;
+    chunks_from_splits(ids, n, splits, n_splits, o.max_chunk, padded, lens);
+    int total = 0;
+    h->infer_batch_device(padded.data(), lens.data(), (int)lens.size(), o.max_chunk, o, nullptr, &total);
+    if (total < 2) fail(XDTTS_ERR_BAD_ARG, "mel has %d frame(s); the vocoder needs at least 2", total);
+    PinnedGuard mel_host((size_t)N_MEL * total);
+    // the vocoder stream reads the mel behind the post-net (event 3 of infer_batch_device); the mel's copy to the host
+    // follows on the mel-gen stream and overlaps the vocoder
+    HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));
+    HIP_CHECK(hipMemcpyAsync(mel_host.p, h->mel_dev.p, (size_t)N_MEL * total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    Drain drain(h->stream);  // the pinned buffer does not go back to the pool with the copy in flight
+    gl_run_from_device_mel(g, h->mel_dev.p, total, audio, n_samples);
+    h->finish_timings();  // (stream sync: the mel has landed)
+    *mel = mel_host.release();
+    *n_frames = (size_t)total;
+  });
+}
+
+// XdTts::infer for a SEQUENCE of utterances, one after the other as the reference runs them (src/lib.rs:110-159: each utterance
+// decoded alone, batch 1) -- but software-pipelined across the two halves: the frame loop owns every CU (weights in the register
+// files), so nothing can run beside it; what can overlap is utterance u's vocoder (mel -> linear, Griffin-Lim, normalise: its own
+// stream) with utterance u + 1's ENCODER (embedding, three convolutions, BiLSTM on 16 CUs, memory layer).  The frame loop of
+// u + 1 is ordered behind the vocoder of u by an event (two grids that each want the chip co-resident never meet), and the host
+// collects u's audio while u + 1 decodes.  Same bits as xdtts_synthesize_ids called once per utterance.
+xdtts_status xdtts_synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
+                                       const size_t *const *splits, const size_t *n_splits, int32_t n_utt, const xdtts_infer_opts *opts,
+                                       float **mels, size_t *n_frames, float **audios, size_t *n_samples) {
+  return guard([&] {
+    if (!h || !g || !ids || !n_ids || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "null argument / no utterance");
+    if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
+    for (int u = 0; u < n_utt; ++u) {
+      audios[u] = nullptr;
+      n_frames[u] = n_samples[u] = 0;
+      if (mels) mels[u] = nullptr;
+      if (!ids[u] || n_ids[u] == 0) fail(XDTTS_ERR_BAD_ARG, "utterance %d is empty", u);
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::lock_guard<std::mutex> lk2(g->mu);
+    std::lock_guard<ChipLock> chip(chip_mutex(h->device));  // the whole sequence: co-resident launches of two streams are in flight
+    const xdtts_infer_opts o = resolve_opts(opts);
+    struct Hook {  // (the hook never outlives this call, whatever throws)
+      xdtts_tacotron2 *h;
+      ~Hook() {
+        h->before_decoder = nullptr;
+        h->while_decoding = nullptr;
+      }
+    } unhook{h};
+    std::vector<PinnedGuard> mel_host(n_utt), audio_host(n_utt);
+    std::vector<int> total(n_utt, 0);
+    std::vector<float *> audio_out(n_utt, nullptr);
+    // timing events per utterance (the post-net of u ends while the host is already enqueuing u + 1): utterance u records into a
+    // fresh set, read when everything has drained; xdtts_*_last_timings then report the SUMS over the sequence
+    std::vector<Events> per(n_utt);
+    for (Events &e : per) e.create();
+    // Declared BEHIND the pinned buffers and the event sets, i.e. destroyed BEFORE them: whatever throws (utterance u's chunking
+    // fails while utterance u - 1's mel copy, vocoder and audio copy are still in flight), both streams drain first and only then
+    // do the buffers go back to the shared pool and the events get destroyed.
+    Drain drain(h->stream, g->stream);
+    float gsum[3] = {0.f, 0.f, 0.f};
+    int steps_sum = 0;
+    auto add_gl = [&]() {
+      for (int i = 0; i < 3; ++i) gsum[i] += g->last_ms[i];
+    };
+    auto release_all = [&]() {
+      for (int u = 0; u < n_utt; ++u)
+        if (audio_out[u]) pinned_release(audio_out[u]);
+    };
+    try {
+      for (int u = 0; u < n_utt; ++u) {
+        std::vector<int64_t> padded;
+        std::vector<int> lens;
+        chunks_from_splits(ids[u], n_ids[u], splits ? splits[u] : nullptr, (splits && n_splits) ? n_splits[u] : 0, o.max_chunk, padded, lens);
+        if (u > 0) h->before_decoder = [&] { HIP_CHECK(hipStreamWaitEvent(h->stream, g->ev.e[2], 0)); };  // vocoder of u - 1 done (its audio copy is behind it on g->stream)
+        // The pinned output buffers of utterance u are taken from the pool WHILE its frame loop runs (the host has 5.6 ms to wait there), not
+        // between the vocoder's enqueue and the next encoder's: a pool miss is a hipHostMalloc of 0.8 MB -- 0.2-0.4 ms on some boxes -- and in
+        // that place it made the next encoder start when the vocoder had finished instead of beside it (round 6: the sequence headline's two
+        // modes, 6.15-6.25 / 6.5-6.6 ms per utterance; the kernel timeline of tools/sequence_timeline.sh shows k_embed behind k_gl_persistent
+        // in the slow utterances).  Gate-less decodes only: the frame count is then known beforehand.
+        long predicted = 0;
+        if (o.fixed_steps > 0 || o.fixed_frames_per_id > 0.f)
+          for (int len : lens) {
+            const long l = o.fixed_steps > 0 ? o.fixed_steps : std::lround((double)o.fixed_frames_per_id * len);
+            predicted += std::min<long>(std::max<long>(l, 1), o.max_steps);
+          }
+        h->while_decoding = nullptr;
+        if (predicted >= 2)
+          h->while_decoding = [&, u, predicted] {
+            if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * predicted);
+            if (!audio_host[u].p) audio_host[u] = PinnedGuard((size_t)g->hop * (size_t)(predicted - 1));
+          };
+        for (int i = 0; i < 4; ++i) std::swap(h->ev.e[i], per[u].e[i]);  // (per[u] now holds what the handle had: utterance u - 1's set, or its own)
+        h->infer_batch_device(padded.data(), lens.data(), (int)lens.size(), o.max_chunk, o, nullptr, &total[u]);
+        h->before_decoder = nullptr;
+        h->while_decoding = nullptr;
+        if (predicted != total[u]) mel_host[u] = PinnedGuard(), audio_host[u] = PinnedGuard();  // (the stop rule decided otherwise: sized below)
+        steps_sum += h->last_steps;
+        if (total[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: mel has %d frame(s); the vocoder needs at least 2", u, total[u]);
+        // the frame loop of u has drained, and it waited for the vocoder of u - 1: collect that audio now
+        if (u > 0) {
+          gl_collect(g, total[u - 1], audio_host[u - 1], &audio_out[u - 1], &n_samples[u - 1]);
+          add_gl();
+        }
+        if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * total[u]);
+        HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));  // the vocoder reads the mel behind the post-net
+        HIP_CHECK(hipMemcpyAsync(mel_host[u].p, h->mel_dev.p, (size_t)N_MEL * total[u] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        gl_enqueue_from_device_mel(g, h->mel_dev.p, total[u], audio_host[u]);
+      }
+      gl_collect(g, total[n_utt - 1], audio_host[n_utt - 1], &audio_out[n_utt - 1], &n_samples[n_utt - 1]);
+      add_gl();
+      h->finish_timings();  // (stream sync: every mel has landed; last_ms = the last utterance's phases)
+      float hsum[4] = {h->last_ms[0], h->last_ms[1], h->last_ms[2], h->last_ms[3]};
+      for (int u = 1; u < n_utt; ++u) {  // utterance u - 1's events sit in per[u]
+        float ms = 0.f;
+        for (int i = 0; i < 3; ++i) {
+          HIP_CHECK(hipEventElapsedTime(&ms, per[u].e[i], per[u].e[i + 1]));
+          hsum[i] += ms;
+        }
+        HIP_CHECK(hipEventElapsedTime(&ms, per[u].e[0], per[u].e[3]));
+        hsum[3] += ms;
+      }
+      for (int i = 0; i < 4; ++i) h->last_ms[i] = hsum[i];
+      for (int i = 0; i < 3; ++i) g->last_ms[i] = gsum[i];
+      h->last_steps = steps_sum;
+    } catch (...) {
+      (void)hipStreamSynchronize(h->stream);  // (nothing in flight writes into a buffer that is handed back below)
+      (void)hipStreamSynchronize(g->stream);
+      release_all();
+      throw;
+    }
+    for (int u = 0; u < n_utt; ++u) {
+      audios[u] = audio_out[u];
+      n_frames[u] = (size_t)total[u];
+      if (mels) mels[u] = mel_host[u].release();
+    }
+  });
+}
+
+// XdTts::infer for several utterances in one call (BASELINE.json configs[3]; the author's "batched / parallel
+// sentences" note, src/phonemes.rs:677-680): all chunks through one lock-step mel-gen batch (chunks are independent,
+// src/tacotron2/mod.rs:422-434), the post-net writes every utterance's chunks side by side on the time axis
+// (mod.rs:430), and the vocoder batch reads that mel where it lies in HBM -- no copy to the host and back, no
+// re-staging between the two halves.  The per-utterance mels leave for the host while the vocoder runs.
+xdtts_status xdtts_synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
+                                    int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
+                                    const int32_t *fixed_steps_per_item, float **mels, size_t *n_frames, float **audios,
+                                    size_t *n_samples) {
+  return guard([&] {
+    if (!h || !g || !ids || !lens || !utt_chunks || !n_frames || !audios || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
+    if (B <= 0 || n_utt <= 0 || t_stride <= 0) fail(XDTTS_ERR_BAD_ARG, "batch %d / utterances %d / stride %d out of range", B, n_utt, t_stride);
+    long nchunks = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      if (utt_chunks[u] <= 0) fail(XDTTS_ERR_BAD_ARG, "utterance %d has no chunk", u);
+      nchunks += utt_chunks[u];
+      audios[u] = nullptr;
+      n_frames[u] = n_samples[u] = 0;
+      if (mels) mels[u] = nullptr;
+    }
+    if (nchunks != B) fail(XDTTS_ERR_BAD_ARG, "utt_chunks sum to %ld, the batch has %d chunks", nchunks, B);
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::lock_guard<std::mutex> lk2(g->mu);
+    const xdtts_infer_opts o = resolve_opts(opts);
+    const int T = o.max_chunk;
+    const std::vector<int64_t> padded = pad_batch_ids(ids, lens, B, t_stride, T);
+    int total = 0;
+    const std::vector<int> F = h->infer_batch_device(padded.data(), lens, B, T, o, fixed_steps_per_item, &total);
+    std::vector<int> Fu(n_utt, 0), col0(n_utt, 0);
+    for (int u = 0, b = 0, off = 0; u < n_utt; ++u) {
+      col0[u] = off;
+      for (int k = 0; k < utt_chunks[u]; ++k) Fu[u] += F[b++];
+      off += Fu[u];
+      if (Fu[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d has %d mel frame(s); the vocoder needs at least 2", u, Fu[u]);
+    }
+    // the vocoder stream reads the mel behind the post-net (event 3 of infer_batch_device); the host copies of the
+    // mel follow on the mel-gen stream and overlap the vocoder
+    HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));
+    std::vector<PinnedGuard> mel_out;
+    Drain drain(h->stream);  // no mel buffer goes back to the pool while a copy into it may be in flight
+    if (mels) {
+      mel_out.reserve((size_t)n_utt);
+      for (int u = 0; u < n_utt; ++u) {
+        mel_out.emplace_back((size_t)N_MEL * Fu[u]);
+        HIP_CHECK(hipMemcpy2DAsync(mel_out[(size_t)u].p, sizeof(float) * (size_t)Fu[u], h->mel_dev.p + col0[u], sizeof(float) * (size_t)total,
+                                   sizeof(float) * (size_t)Fu[u], N_MEL, hipMemcpyDeviceToHost, h->stream));
+      }
+    }
+    gl_batch_from_device(g, h->mel_dev.p, Fu, audios, n_samples);
+    try {
+      h->finish_timings();  // (stream sync: the mel copies have landed)
+    } catch (...) {  // the caller gets either every buffer of the call or none
+      for (int u = 0; u < n_utt; ++u) {
+        if (audios[u]) pinned_release(audios[u]);
+        audios[u] = nullptr;
+        n_samples[u] = 0;
+      }
+      throw;
+    }
+    for (int u = 0; u < n_utt; ++u) {
+      n_frames[u] = (size_t)Fu[u];
+      if (mels) mels[u] = mel_out[(size_t)u].release();
+    }
+  });
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/xdtts.h"
+#include "env.h"
 
 namespace xdtts {
 
@@ -97,10 +98,7 @@ inline bool coop_validated(const void *fn, unsigned threads, size_t lds, unsigne
 template <class... Args>
 inline hipError_t launch_coresident(bool coop_default, const void *fn, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
   void *argv[] = {(void *)&args...};
-  static const int forced = [] {
-    const char *e = getenv("XDTTS_COOP");
-    return !e ? -1 : (e[0] == '0' ? 0 : 1);
-  }();
+  const int forced = env::coop_forced();
   const unsigned blocks = grid.x * grid.y * grid.z, threads = block.x * block.y * block.z;
   bool coop = forced < 0 ? coop_default : forced == 1;
   if (coop && forced < 0 && coop_validated(fn, threads, lds, blocks, false)) coop = false;  // this grid has been accepted before

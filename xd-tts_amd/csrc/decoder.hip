@@ -1,6 +1,6 @@
 // decoder.hip -- the Tacotron2 autoregressive decoder step as a chain of HIP kernels for gfx950:
 // the launch-per-stage engine.  Small lock-step batches (1-4 chunks, T <= 128) run the persistent
-// weight-stationary kernel of decoder_persistent.hip instead (api.cpp: run_decoder); this file serves
+// weight-stationary kernel of decoder_persistent.hip instead (tacotron2_decode.cpp: run_decoder); this file serves
 // the batched MFMA form for >= 5 chunks (three launches per step: k_prenet_b, k_att_lstm_attention,
 // k_lstm_mfma<DEC>, see the comments at those kernels), longer encoder memories, and is the second
 // implementation the parity tests compare the persistent kernel with.
@@ -1528,7 +1528,7 @@ __global__ __launch_bounds__(256) void k_softmax_ctx(DecoderBufs d, int i, const
 // the persistent engine's edges do: 8-byte {tag = step + 1, value} granules, stored and polled with relaxed
 // agent-scope (sc1) accesses, no fence, no counter.  Every block publishes before it polls, the blocks of a chunk are
 // neighbours in dispatch order, so the wait is short; a bounded spin sets d.att_err instead of hanging (the host
-// then decodes the request again with the two-kernel form, api.cpp).  Chunks that have stopped are skipped.
+// then decodes the request again with the two-kernel form, tacotron2_decode.cpp).  Chunks that have stopped are skipped.
 // Every global load of the attention phase that does not depend on this step's attention-LSTM output, issued in the
 // order the values are needed (vmcnt retires in issue order).
 struct AttentionLoads {
@@ -1886,10 +1886,6 @@ static void enqueue_steps(const DecoderBufs &d, const DeviceWeights &w, int i0, 
   const float4 *att_w = reinterpret_cast<const float4 *>(w.att_w.p);
   const float4 *dec_w = reinterpret_cast<const float4 *>(w.dec_w.p);
   const float4 *q4 = reinterpret_cast<const float4 *>(w.q_w4.p), *wh4 = reinterpret_cast<const float4 *>(w.proj_wh4.p);
-  // XDTTS_DEBUG_MIX (developer timing aid only; results are garbage when set): string over the
-  // letters p,a,q,s,d selecting which kernels a step launches, e.g. "ppppp".
-  const char *mix = getenv("XDTTS_DEBUG_MIX");
-  const std::string order = mix ? mix : "paqsd";
   // LSTMs as MFMA GEMMs: the caller chose the batched layout (decoder_bufs: from BATCH_MFMA_MIN chunks, or the parity hook's engine 2 at any B)
   const bool batched = d.xf && w.att_wm.p && w.dec_wm.p;
   const float4 *att_wm = reinterpret_cast<const float4 *>(w.att_wm.p), *dec_wm = reinterpret_cast<const float4 *>(w.dec_wm.p);
@@ -1902,59 +1898,47 @@ static void enqueue_steps(const DecoderBufs &d, const DeviceWeights &w, int i0, 
   const TailWeights tw{reinterpret_cast<const float4 *>(w.proj_w.p), w.proj_b.p, w.pre0T.p, w.pre1T.p, w.loc_conv.p, w.loc_denseT.p};
   for (int i = i0; i < i0 + nsteps; ++i) {
     const int cur = i & 1;
-    for (char k : order) {
-      switch (k) {
-        case 'p':
-          if (two) break;  // (launch_decoder_prologue ran the first step's prenet; every later one is the previous decoder-LSTM launch's tail)
-          if (batched)
-            hipLaunchKernelGGL(k_prenet_b, dim3(PRENET_SPLIT * d.B + d.B * (d.T <= LOC_MFMA_T ? 2 : ((d.T + LOC_TT - 1) / LOC_TT + 7) / 8)), dim3(PRENET_BT), 0, s, d, i, 0, w.pre0T.p, w.pre1T.p,
-                               w.proj_b.p, w.loc_conv.p, w.loc_denseT.p);
-          else
-            hipLaunchKernelGGL(k_prenet, dim3(PRENET_BLOCKS * d.B), dim3(256), 0, s, d, i, 0, w.pre0T.p, w.pre1T.p,
-                               w.proj_b.p);
-          break;
-        case 'a':
-          if (two)  // ... and no partial-mel rows: the decoder-LSTM launch's tail projects h_dec and the context itself
-            hipLaunchKernelGGL((k_att_lstm_attention<true, true>), dim3(dd.dec_part ? 2 * NBLK : NBLK), dim3(64 * MFMA_WAVES), 0, s, dd, i, cur, att_wm, w.att_b.p,
-                               reinterpret_cast<const float4 *>(w.q_w.p), w.v_w.p, w.proj_wc.p, dec_wm);  // (+ 256 blocks: the decoder LSTM's h_dec(s-1) columns)
-          else if (early)  // attention LSTM (its 256 prenet columns + the early partial) + energies + softmax + context
-            hipLaunchKernelGGL(k_att_lstm_attention<true>, dim3(NBLK), dim3(64 * MFMA_WAVES), 0, s, d, i, cur, att_wm, w.att_b.p,
-                               reinterpret_cast<const float4 *>(w.q_w.p), w.v_w.p, w.proj_wc.p, dec_wm);
-          else if (fuse_aq)  // attention LSTM + energies + softmax + context ('q' and 's' are then no-ops)
-            hipLaunchKernelGGL(k_att_lstm_attention<false>, dim3(NBLK), dim3(64 * MFMA_WAVES), 0, s, d, i, cur, att_wm, w.att_b.p,
-                               reinterpret_cast<const float4 *>(w.q_w.p), w.v_w.p, w.proj_wc.p, dec_wm);
-          else if (batched)
-            hipLaunchKernelGGL((k_lstm_mfma<ATT_COLS, 0>), dim3(NBLK, (d.B + 63) / 64), dim3(64 * MFMA_WAVES), 0, s, d, i, cur, att_wm, w.att_b.p, q4, att_wm, tw);
-          else
-            hipLaunchKernelGGL((k_lstm<ATT_COLS, 0>), dim3(NBLK), dim3(256), 0, s, d, i, cur, att_w, w.att_b.p, q4,
-                               w.loc_conv.p, w.loc_denseT.p);
-          break;
-        case 'q':
-          if (fuse_aq) break;
-          if (batched && d.ep_g) {  // energies + softmax + context in one launch ('s' is then a no-op)
-            hipLaunchKernelGGL(k_attention_b, dim3(CTX_BLOCKS * d.B), dim3(256), 0, s, d, i, cur, reinterpret_cast<const float4 *>(w.q_w.p),
-                               w.v_w.p, w.proj_wc.p);
-            break;
-          }
-          hipLaunchKernelGGL(k_qenergy, dim3(ATT_DIM / 4, batched ? std::max(2, (d.B + QE_GROUP - 1) / QE_GROUP) : 1), dim3(256), 0, s, d, i, cur,
-                             reinterpret_cast<const float4 *>(w.q_w.p), w.v_w.p);
-          break;
-        case 's':
-          if (batched && d.ep_g) break;
-          hipLaunchKernelGGL(k_softmax_ctx, dim3(CTX_BLOCKS * d.B), dim3(256), 0, s, d, i, w.proj_wc.p);
-          break;
-        case 'd':
-          if (batched) {  // (early: 256 more blocks multiply the next attention-LSTM pass's 1536 known columns)
-            hipLaunchKernelGGL((k_lstm_mfma<DEC_COLS, 1>), dim3(early ? 2 * NBLK : NBLK, (d.B + 63) / 64), dim3(64 * MFMA_WAVES), 0, s, dd, i, cur, dec_wm, w.dec_b.p, wh4,
-                               att_wm, tw);
-          } else
-            hipLaunchKernelGGL((k_lstm<DEC_COLS, 1>), dim3(loc_tiles * d.B + NBLK), dim3(256), 0, s, d, i, cur, dec_w,
-                               w.dec_b.p, wh4, w.loc_conv.p, w.loc_denseT.p);
-          break;
-        default:
-          break;
-      }
+    // prenet (two-launch form: launch_decoder_prologue ran the first step's; every later one is the previous decoder-LSTM launch's tail)
+    if (!two) {
+      if (batched)
+        hipLaunchKernelGGL(k_prenet_b, dim3(PRENET_SPLIT * d.B + d.B * (d.T <= LOC_MFMA_T ? 2 : ((d.T + LOC_TT - 1) / LOC_TT + 7) / 8)), dim3(PRENET_BT), 0, s, d, i, 0, w.pre0T.p, w.pre1T.p,
+                           w.proj_b.p, w.loc_conv.p, w.loc_denseT.p);
+      else
+        hipLaunchKernelGGL(k_prenet, dim3(PRENET_BLOCKS * d.B), dim3(256), 0, s, d, i, 0, w.pre0T.p, w.pre1T.p,
+                           w.proj_b.p);
     }
+    // attention LSTM
+    if (two)  // ... and no partial-mel rows: the decoder-LSTM launch's tail projects h_dec and the context itself
+      hipLaunchKernelGGL((k_att_lstm_attention<true, true>), dim3(dd.dec_part ? 2 * NBLK : NBLK), dim3(64 * MFMA_WAVES), 0, s, dd, i, cur, att_wm, w.att_b.p,
+                         reinterpret_cast<const float4 *>(w.q_w.p), w.v_w.p, w.proj_wc.p, dec_wm);  // (+ 256 blocks: the decoder LSTM's h_dec(s-1) columns)
+    else if (early)  // attention LSTM (its 256 prenet columns + the early partial) + energies + softmax + context
+      hipLaunchKernelGGL(k_att_lstm_attention<true>, dim3(NBLK), dim3(64 * MFMA_WAVES), 0, s, d, i, cur, att_wm, w.att_b.p,
+                         reinterpret_cast<const float4 *>(w.q_w.p), w.v_w.p, w.proj_wc.p, dec_wm);
+    else if (fuse_aq)  // attention LSTM + energies + softmax + context in one launch
+      hipLaunchKernelGGL(k_att_lstm_attention<false>, dim3(NBLK), dim3(64 * MFMA_WAVES), 0, s, d, i, cur, att_wm, w.att_b.p,
+                         reinterpret_cast<const float4 *>(w.q_w.p), w.v_w.p, w.proj_wc.p, dec_wm);
+    else if (batched)
+      hipLaunchKernelGGL((k_lstm_mfma<ATT_COLS, 0>), dim3(NBLK, (d.B + 63) / 64), dim3(64 * MFMA_WAVES), 0, s, d, i, cur, att_wm, w.att_b.p, q4, att_wm, tw);
+    else
+      hipLaunchKernelGGL((k_lstm<ATT_COLS, 0>), dim3(NBLK), dim3(256), 0, s, d, i, cur, att_w, w.att_b.p, q4,
+                         w.loc_conv.p, w.loc_denseT.p);
+    // energies, softmax and context (nothing left to do when they rode in the attention-LSTM launch)
+    if (batched && d.ep_g) {
+      if (!fuse_aq)  // one launch for the three
+        hipLaunchKernelGGL(k_attention_b, dim3(CTX_BLOCKS * d.B), dim3(256), 0, s, d, i, cur, reinterpret_cast<const float4 *>(w.q_w.p),
+                           w.v_w.p, w.proj_wc.p);
+    } else {
+      hipLaunchKernelGGL(k_qenergy, dim3(ATT_DIM / 4, batched ? std::max(2, (d.B + QE_GROUP - 1) / QE_GROUP) : 1), dim3(256), 0, s, d, i, cur,
+                         reinterpret_cast<const float4 *>(w.q_w.p), w.v_w.p);
+      hipLaunchKernelGGL(k_softmax_ctx, dim3(CTX_BLOCKS * d.B), dim3(256), 0, s, d, i, w.proj_wc.p);
+    }
+    // decoder LSTM
+    if (batched) {  // (early: 256 more blocks multiply the next attention-LSTM pass's 1536 known columns)
+      hipLaunchKernelGGL((k_lstm_mfma<DEC_COLS, 1>), dim3(early ? 2 * NBLK : NBLK, (d.B + 63) / 64), dim3(64 * MFMA_WAVES), 0, s, dd, i, cur, dec_wm, w.dec_b.p, wh4,
+                         att_wm, tw);
+    } else
+      hipLaunchKernelGGL((k_lstm<DEC_COLS, 1>), dim3(loc_tiles * d.B + NBLK), dim3(256), 0, s, d, i, cur, dec_w,
+                         w.dec_b.p, wh4, w.loc_conv.p, w.loc_denseT.p);
   }
 }
 

@@ -383,7 +383,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
   // wd (k = 1, 2 and k = 4, 5) are dead after this loop: 32 weight registers make room for 8 PB + 2 of these.
   float pma[PB][2][2], pmd[PB][2][2], pmp[2] = {0.f, 0.f};
   if (d.ctx_fold) {
-    // ... or read from the table one GEMM per request has made of them (api.cpp): 33 us of set-up less per chunk and launch
+    // ... or read from the table one GEMM per request has made of them (tacotron2_decode.cpp): 33 us of set-up less per chunk and launch
 #pragma unroll
     for (int b = 0; b < PB; ++b)
 #pragma unroll

@@ -26,7 +26,7 @@
 // Per step:  x -> [attention LSTM] -> h_att -> [query, energies] -> e -> [softmax, context] -> ctx -> [decoder LSTM] -> h_dec
 //            -> [projection rows] -> mel -> [stop rule, prenet] -> x(s+1)
 // Every spin is bounded and watches a global error word; a timed-out exchange ends the launch and the request is decoded again
-// by the other engines (api.cpp), exactly as for the 8-slot kernel.
+// by the other engines (tacotron2_decode.cpp), exactly as for the 8-slot kernel.
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>

@@ -721,7 +721,6 @@ P8Bufs p8_bufs(unsigned long long *base, int *err, int B, int nsteps) {
     g.delay[1] = 80;
     g.delay[4] = g.delay[5] = 0;
   }
-  if (const char *e = getenv("XDTTS_P8_DELAY")) sscanf(e, "%d,%d,%d,%d,%d,%d", &g.delay[0], &g.delay[1], &g.delay[2], &g.delay[3], &g.delay[4], &g.delay[5]);  // developer sweep
   return g;
 }
 

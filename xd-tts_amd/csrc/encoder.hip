@@ -140,10 +140,9 @@ void launch_bilstm_coop(const float *xproj, const float *whhT_fwd, const float *
                         unsigned long long *exchange, int *err, int B, int T, int group, hipStream_t s) {
   unsigned spins = SPIN_LIMIT;
   int fault = 0;
-  if (const char *e = getenv("XDTTS_ENC_SPINS")) spins = (unsigned)atoi(e);  // test hooks for the lost-workgroup path
-  if (const char *e = getenv("XDTTS_ENC_FAULT")) fault = atoi(e);
-  int first = ENC_FIRST_POLL;
-  if (const char *e = getenv("XDTTS_ENC_FIRST")) first = atoi(e);  // developer tuning knob
+  env::override_int(env::ENC_SPINS, &spins);  // test hooks for the lost-workgroup path
+  env::override_int(env::ENC_FAULT, &fault);
+  const int first = ENC_FIRST_POLL;
   // 8 workgroups per group of chunks must be co-resident, so a large batch runs as launches of at most `group` groups each
   // (sized to the CU count by the caller); a batch of more than `group` chunks puts two chunks on a group.  The exchange
   // buffer (bilstm_coop_exchange_words(2 * group) then) is reused between launches.

@@ -467,8 +467,8 @@ void launch_copy_rows(const float *src, size_t src_stride, float *dst, size_t ds
 int gemm_splitk_plan(const GemmArgs &g, size_t *ws_floats, size_t *tiles, int *tile) {
   *ws_floats = *tiles = 0;
   *tile = 0;
-  static const int forced = getenv("XDTTS_GEMM_SPLITK") ? atoi(getenv("XDTTS_GEMM_SPLITK")) : -1;  // developer comparison aids (0 / 1: off)
-  static const int forced_t = getenv("XDTTS_GEMM_SPLIT_TILE") ? atoi(getenv("XDTTS_GEMM_SPLIT_TILE")) : 0;
+  static const int forced = env::int_or(env::GEMM_SPLITK, -1);  // developer comparison aids (0 / 1: off)
+  static const int forced_t = env::int_or(env::GEMM_SPLIT_TILE, 0);
   if (forced == 0 || forced == 1) return 1;
   long rows = 0, t32 = 0, t64 = 0;
   for (int z = 0; z < g.batch; ++z) {
@@ -502,17 +502,16 @@ void launch_gemm_nt(const GemmArgs &g, hipStream_t s) {
   if (g.ragged && g.batch > GEMM_RAGGED_MAX) fail(XDTTS_ERR_BAD_ARG, "gemm: ragged batch of %d", g.batch);
   if (g.K % 16 != 0 || g.lda % 4 != 0) fail(XDTTS_ERR_BAD_ARG, "gemm: K=%d lda=%ld not supported", g.K, g.lda);
   // 64x64 tiles once they fill the chip at least twice over (XDTTS_GEMM_TILE=32|64: developer comparison aid)
-  static const int forced = getenv("XDTTS_GEMM_TILE") ? atoi(getenv("XDTTS_GEMM_TILE")) : 0;
+  static const int forced = env::int_or(env::GEMM_TILE, 0);
   const long tiles64 = (long)((g.N + 63) / 64) * ((g.M + 63) / 64) * g.batch;
   // (short and very wide -- the context fold of the persistent decoder, M = T = 100 rows x 8273 columns x K = 512 per chunk: its second
   // 64-row tile is 36 % full; measured 33.4 us with 32x32 tiles, 39.5 with 64x64, 44.4 with 32x64)
   const bool big = g.tile ? g.tile == 64 : (forced ? forced == 64 : (g.N >= 64 && tiles64 >= 512 && !(g.M <= 128 && g.N >= 4096)));
-  // row tiles per XCD when A (unique bytes: rows x lda) outweighs W -- the batches; XDTTS_GEMM_XCD=0|1 forces it (comparison aid)
-  static const int forced_x = getenv("XDTTS_GEMM_XCD") ? atoi(getenv("XDTTS_GEMM_XCD")) : -1;
+  // row tiles per XCD when A (unique bytes: rows x lda) outweighs W -- the batches
   long rows = 0;
   for (int z = 0; z < g.batch; ++z) rows += g.ragged ? g.Mz[z] : g.M;
   GemmArgs a = g;
-  a.xcd_rows = forced_x >= 0 ? forced_x : (rows * g.lda > (long)g.N * g.K ? 1 : 0);
+  a.xcd_rows = rows * g.lda > (long)g.N * g.K ? 1 : 0;
   const int tb = big ? 64 : 32;
   const int nx = (g.N + tb - 1) / tb;
   int ny = (g.M + tb - 1) / tb, nz = g.batch;

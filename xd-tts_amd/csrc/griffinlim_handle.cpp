@@ -1,0 +1,609 @@
+// griffinlim_handle.cpp -- the vocoder handle (GriffinLim::infer, mod.rs:441-520): mel -> linear, the iteration engines and
+// their fallback, the single-utterance and the batch request paths.
+#include "griffinlim_handle.h"
+
+#include <algorithm>
+#include <cmath>
+
+using namespace xdtts;
+
+xdtts_griffinlim::~xdtts_griffinlim() {
+  for (hipEvent_t e : copy_ev) (void)hipEventDestroy(e);
+  if (copy_stream) (void)hipStreamDestroy(copy_stream);
+  if (host_err) (void)hipHostFree(host_err);
+  if (stream) (void)hipStreamDestroy(stream);
+}
+
+GlBufs xdtts_griffinlim::bufs(int F) {
+  S.alloc((size_t)F * nb);
+  ang.alloc((size_t)F * nb);
+  ang2.alloc((size_t)F * nb);
+  tprev.alloc((size_t)F * nb);
+  frames.alloc((size_t)F * n_fft);
+  wss_inv.alloc((size_t)std::max(1, hop * (F - 1)));
+  audio.alloc((size_t)std::max(1, hop * (F - 1)));
+  GlBufs g{};
+  g.F = F;
+  g.n_fft = n_fft;
+  g.hop = hop;
+  g.nb = nb;
+  g.S = S.p;
+  g.ang = ang.p;
+  g.ang2 = ang2.p;
+  g.tprev = tprev.p;
+  g.frames = frames.p;
+  g.wss_inv = wss_inv.p;
+  g.tw = tw.p;
+  g.win = win.p;
+  return g;
+}
+
+// step 1 of GriffinLim::infer: mel (device, n_mels x F) -> S [F][nb], with the convention switches of
+// xdtts_griffinlim_opts: de-compression, optional projected-gradient NNLS refinement, exponent.
+//   x0 = max(pinv m, 0);  x <- max(x - (1/L) A^T (A x - m), 0)  nnls_iters times, batched over the
+//   frames as two MFMA GEMMs per step (residual [F][80], then the update of X [F][NBP]).
+void xdtts_griffinlim::mel_to_linear(const float *mel_dev_ptr, int F) {
+  melT.alloc((size_t)F * n_mels);
+  launch_gl_exp_transpose(mel_dev_ptr, melT.p, n_mels, F, gopts.mel_decompress, stream);
+  const float ex = gopts.power_mode == 0 ? 1.0f / power : (gopts.power_mode == 1 ? power : 1.0f);
+  GemmArgs a{};
+  a.A = melT.p;
+  a.lda = n_mels;
+  a.W = pinv.p;
+  a.M = F;
+  a.N = nb;
+  a.K = n_mels;
+  a.batch = 1;
+  if (gopts.nnls_iters <= 0) {
+    a.C = S.p;
+    a.ldc = nb;
+    a.act = ex == 1.0f ? 1 : 3;
+    a.p = ex;
+    launch_gemm_nt(a, stream);
+    return;
+  }
+  nnls_x.alloc((size_t)F * NBP);
+  nnls_r.alloc((size_t)F * n_mels);
+  HIP_CHECK(hipMemsetAsync(nnls_x.p, 0, (size_t)F * NBP * sizeof(float), stream));  // padding columns stay 0
+  a.C = nnls_x.p;
+  a.ldc = NBP;
+  a.act = 1;
+  launch_gemm_nt(a, stream);
+  for (int it = 0; it < gopts.nnls_iters; ++it) {
+    GemmArgs r{};  // R = X A^T - m
+    r.A = nnls_x.p;
+    r.lda = NBP;
+    r.W = basis_p.p;  // [n_mels][NBP]
+    r.C = nnls_r.p;
+    r.ldc = n_mels;
+    r.M = F;
+    r.N = n_mels;
+    r.K = NBP;
+    r.batch = 1;
+    r.R = melT.p;
+    r.ldr = n_mels;
+    r.beta = -1.0f;
+    launch_gemm_nt(r, stream);
+    GemmArgs u{};  // X = max(X - (1/L) R A, 0)
+    u.A = nnls_r.p;
+    u.lda = n_mels;
+    u.W = basisT_p.p;  // [NBP][n_mels]
+    u.C = nnls_x.p;
+    u.ldc = NBP;
+    u.M = F;
+    u.N = NBP;
+    u.K = n_mels;
+    u.batch = 1;
+    u.alpha = -nnls_step;
+    u.R = nnls_x.p;
+    u.ldr = NBP;
+    u.r_before_act = 1;
+    u.act = 1;
+    launch_gemm_nt(u, stream);
+  }
+  launch_gl_pow_rows(nnls_x.p, NBP, S.p, nb, F, ex, stream);
+}
+
+bool xdtts_griffinlim::persistent_usable() {
+  if (env::equals(env::GL, "launch")) return false;  // developer comparison aid: launch-per-iteration engine
+  gate.ensure_probed([&] { return gl_persistent_supported(device, &n_cu, &per_cu4); });
+  return gate.usable();
+}
+
+void xdtts_griffinlim::persist_prepare(size_t xch_words, unsigned tags) {
+  if (xch_words > xch.n || epoch > 0x7fff0000u - tags) {  // fresh (or wrapped) tags: clear every granule
+    xch.alloc(xch_words);
+    HIP_CHECK(hipMemsetAsync(xch.p, 0, xch.n * sizeof(unsigned long long), stream));
+    epoch = 0;
+  }
+  if (!gl_err.p) {
+    gl_err.alloc(1);
+    HIP_CHECK(hipMemsetAsync(gl_err.p, 0, sizeof(int), stream));
+    HIP_CHECK(hipHostMalloc((void **)&host_err, sizeof(int), hipHostMallocDefault));
+  }
+}
+GlPersist xdtts_griffinlim::persist_args(int n_iter) {
+  GlPersist p{};
+  p.xch = xch.p;
+  p.err = gl_err.p;
+  p.epoch = epoch;
+  p.poll_delay = 6;  // first poll 6 x 128 clocks after the publish (F = 1000: 4.31-4.36 us per iteration at 5..7, 4.39 behind the overlap-add, 4.45-4.53 at 2 or 10..12)
+  epoch += (unsigned)n_iter + 2u;
+  return p;
+}
+
+// The iteration engine on the current state (ang, tprev, S in place): n_iter iterations and, when
+// audio_out is given, the final ISTFT into it.  Returns the buffer holding the final angles
+// (*tprev_fin: the final rebuilt spectrum).  Small-to-medium frame counts run as ONE persistent
+// launch; the caller holds the chip lock until the stream has drained and then asks
+// persistent_failed().
+const float2 *xdtts_griffinlim::run_iterations(const GlBufs &g, int n_iter, float alpha, float *audio_out, bool want_state,
+                                               const float2 **tprev_fin, bool gen_phase) {
+  int TF = 0, nblk = 0;
+  last_persistent = false;
+  err_fetched = false;
+  if (tprev_fin) *tprev_fin = g.tprev;
+  if (persistent_usable() && gl_persistent_plan(g.F, n_cu, &TF, &nblk)) {
+    persist_prepare(gl_persistent_xch_words(nblk), (unsigned)n_iter);
+    GlPersist p = persist_args(n_iter);
+    p.nblk = nblk;
+    p.TF = TF;
+    env::override_int(env::GL_SPINS, &p.spins);  // test hook
+    env::override_int(env::GL_SLOW, &p.slow);    // test hook: straggler workgroup
+    p.gen_phase = gen_phase ? 1 : 0;
+    p.seed = seed;
+    if (want_state) {
+      p.ang_out = g.ang2;
+      tprev2.alloc((size_t)g.F * g.nb);
+      p.tprev_out = tprev2.p;
+      if (tprev_fin) *tprev_fin = p.tprev_out;
+    }
+#ifdef XDTTS_GL_PROFILE
+    static DevBuf<unsigned long long> prof;
+    prof.alloc(256 * 12);
+    p.prof = prof.p;
+#endif
+    launch_gl_persistent(g, p, g.ang, g.tprev, n_iter, alpha, audio_out, stream);
+#ifdef XDTTS_GL_PROFILE
+    if (const char *path = env::raw(env::GL_PROFILE)) {
+      std::vector<unsigned long long> hp((size_t)nblk * 12);
+      HIP_CHECK(hipMemcpyAsync(hp.data(), prof.p, hp.size() * 8, hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipStreamSynchronize(stream));
+      if (FILE *f = fopen(path, "w")) {
+        fprintf(f, "%d %d\n", nblk, n_iter);
+        for (int c = 0; c < nblk; ++c) {
+          for (int i = 0; i < 12; ++i) fprintf(f, "%llu ", hp[(size_t)c * 12 + i]);
+          fprintf(f, "\n");
+        }
+        fclose(f);
+      }
+    }
+#endif
+    last_persistent = true;
+    return want_state ? g.ang2 : g.ang;
+  }
+  const float2 *fin = launch_gl_iterate(g, n_iter, alpha, stream);
+  if (audio_out) launch_gl_final(g, fin, audio_out, stream);
+  return fin;
+}
+
+// After the stream has drained: did a bounded spin of the persistent launch run out (grid not
+// co-resident)?  If so the handle is demoted to the launch-per-iteration engine (and probes the
+// persistent one again after PROBE_AFTER calls); the input state is intact, the caller re-runs.
+// (fetch_error_word() ahead of a sync the caller needs anyway saves persistent_failed() its own round trip)
+void xdtts_griffinlim::fetch_error_word() {
+  if (!last_persistent) return;
+  HIP_CHECK(hipMemcpyAsync(host_err, gl_err.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+  err_fetched = true;
+}
+bool xdtts_griffinlim::persistent_failed() {
+  if (!last_persistent) return false;
+  if (!err_fetched) {
+    HIP_CHECK(hipMemcpyAsync(host_err, gl_err.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  err_fetched = false;
+  if (!*host_err) return false;
+  HIP_CHECK(hipMemsetAsync(gl_err.p, 0, sizeof(int), stream));
+  HIP_CHECK(hipMemsetAsync(xch.p, 0, xch.n * sizeof(unsigned long long), stream));
+  epoch = 0;
+  gate.demote();
+  std::fprintf(stderr, "libxdtts_hip: persistent Griffin-Lim exchange timed out (grid not co-resident); "
+                       "this handle uses the launch-per-iteration engine for the next %d calls\n", EngineGate::PROBE_AFTER);
+  return true;
+}
+
+// phase init + iterations + final ISTFT; S already in place.  Result in audio (device).
+void xdtts_griffinlim::iterate(const GlBufs &g, const float *phase0_dev, int n_iter) {
+  const float alpha = momentum / (1.0f + momentum);
+  int TF = 0, nblk = 0;
+  if (persistent_usable() && gl_persistent_plan(g.F, n_cu, &TF, &nblk)) {
+    // one launch: nothing to capture; with the seeded stream the kernel draws the phase itself (no
+    // phase-init launch, no window-sum table: the kernel keeps its own)
+    if (phase0_dev) launch_gl_phase_init(g, seed, phase0_dev, stream);
+    run_iterations(g, n_iter, alpha, audio.p, false, nullptr, phase0_dev == nullptr);
+    return;
+  }
+  launch_gl_phase_init(g, seed, phase0_dev, stream);
+  launch_gl_prepare(g, stream);
+  last_persistent = false;
+  // the launch-per-iteration loop is launch-bound: replay it as one hipGraph
+  struct Key {
+    GlBufs g;
+    const float *audio;
+    int n_iter;
+    float alpha;
+  } key;
+  std::memset(&key, 0, sizeof key);
+  std::memcpy(&key.g, &g, sizeof g);
+  key.audio = audio.p;
+  key.n_iter = n_iter;
+  key.alpha = alpha;
+  graph.replay(&key, sizeof key, stream, [&] { launch_gl_iterations(g, n_iter, alpha, audio.p, stream); });
+}
+
+void xdtts_griffinlim::finish_timings() {
+  HIP_CHECK(hipStreamSynchronize(stream));
+  HIP_CHECK(hipEventElapsedTime(&last_ms[0], ev.e[0], ev.e[1]));
+  HIP_CHECK(hipEventElapsedTime(&last_ms[1], ev.e[1], ev.e[2]));
+  HIP_CHECK(hipEventElapsedTime(&last_ms[2], ev.e[0], ev.e[2]));
+}
+
+namespace xdtts {
+
+// Slaney-scale helpers for create_mel_filter_bank (librosa.filters.mel, htk=False, norm="slaney")
+static double hz_to_mel(double f) {
+  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp;
+  const double logstep = std::log(6.4) / 27.0;
+  return f >= min_log_hz ? min_log_mel + std::log(f / min_log_hz) / logstep : f / f_sp;
+}
+static double mel_to_hz(double m) {
+  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp;
+  const double logstep = std::log(6.4) / 27.0;
+  return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
+}
+
+// pinv(A) = A^T (A A^T)^-1 for the full-row-rank mel basis, fp64 Cholesky.  librosa's nnls starts
+// from lstsq(A, M) clipped at 0 and its L-BFGS-B refinement stops at iteration 0 for this
+// objective scaling, so clip(pinv M, 0) is the inversion the vocoder performs.
+void host_pinv(const float *basis, int n, int nbins, std::vector<float> &out) {
+  std::vector<double> G((size_t)n * n, 0.0), z(n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double s = 0;
+      for (int b = 0; b < nbins; ++b) s += (double)basis[(size_t)i * nbins + b] * basis[(size_t)j * nbins + b];
+      G[(size_t)i * n + j] = G[(size_t)j * n + i] = s;
+    }
+  for (int j = 0; j < n; ++j) {
+    double d = G[(size_t)j * n + j];
+    for (int k = 0; k < j; ++k) d -= G[(size_t)j * n + k] * G[(size_t)j * n + k];
+    if (!(d > 0)) fail(XDTTS_ERR_BAD_ARG, "mel basis is rank deficient (filter %d)", j);
+    d = std::sqrt(d);
+    G[(size_t)j * n + j] = d;
+    for (int i = j + 1; i < n; ++i) {
+      double s = G[(size_t)i * n + j];
+      for (int k = 0; k < j; ++k) s -= G[(size_t)i * n + k] * G[(size_t)j * n + k];
+      G[(size_t)i * n + j] = s / d;
+    }
+  }
+  out.resize((size_t)nbins * n);
+  for (int b = 0; b < nbins; ++b) {
+    for (int i = 0; i < n; ++i) {
+      double s = basis[(size_t)i * nbins + b];
+      for (int k = 0; k < i; ++k) s -= G[(size_t)i * n + k] * z[k];
+      z[i] = s / G[(size_t)i * n + i];
+    }
+    for (int i = n - 1; i >= 0; --i) {
+      double s = z[i];
+      for (int k = i + 1; k < n; ++k) s -= G[(size_t)k * n + i] * z[k];
+      z[i] = s / G[(size_t)i * n + i];
+    }
+    for (int i = 0; i < n; ++i) out[(size_t)b * n + i] = (float)z[i];
+  }
+}
+
+// lambda_max(A A^T) by power iteration (double): the Lipschitz constant of the NNLS gradient
+double host_lipschitz(const float *basis, int n, int nbins) {
+  std::vector<double> G((size_t)n * n, 0.0), v(n, 1.0 / std::sqrt((double)n)), w(n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double s = 0;
+      for (int b = 0; b < nbins; ++b) s += (double)basis[(size_t)i * nbins + b] * basis[(size_t)j * nbins + b];
+      G[(size_t)i * n + j] = G[(size_t)j * n + i] = s;
+    }
+  double lam = 0;
+  for (int it = 0; it < 1000; ++it) {
+    double nrm = 0;
+    for (int i = 0; i < n; ++i) {
+      double a = 0;
+      for (int j = 0; j < n; ++j) a += G[(size_t)i * n + j] * v[j];
+      w[i] = a;
+      nrm += a * a;
+    }
+    nrm = std::sqrt(nrm);
+    if (!(nrm > 0)) fail(XDTTS_ERR_BAD_ARG, "mel basis is all zero");
+    for (int i = 0; i < n; ++i) v[i] = w[i] / nrm;
+    const bool done = std::fabs(nrm - lam) <= 1e-13 * nrm;
+    lam = nrm;
+    if (done) break;
+  }
+  return lam;
+}
+
+void mel_filter_bank(double sr, int n_fft, int n_mels, double fmin, double fmax, float *out) {
+  const int nb = (int)(n_fft / 2 + 1), nm = (int)n_mels;
+  std::vector<double> mel_f(nm + 2);
+  const double m0 = hz_to_mel(fmin), m1 = hz_to_mel(fmax);
+  for (int i = 0; i < nm + 2; ++i) mel_f[i] = mel_to_hz(m0 + (m1 - m0) * i / (nm + 1));
+  for (int i = 0; i < nm; ++i) {
+    const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
+    for (int b = 0; b < nb; ++b) {
+      const double f = (sr / 2.0) * b / (nb - 1);
+      const double lower = (f - mel_f[i]) / (mel_f[i + 1] - mel_f[i]);
+      const double upper = (mel_f[i + 2] - f) / (mel_f[i + 2] - mel_f[i + 1]);
+      const double wv = std::min(lower, upper);
+      out[(size_t)i * nb + b] = (float)((wv > 0 ? wv : 0) * enorm);
+    }
+  }
+}
+
+// Phase init + iterations + final ISTFT on the S in place, then the audio to a pinned host buffer.
+// The persistent engine needs its grid co-resident: the chip lock is held from the launch until the
+// stream has drained; a timed-out exchange demotes the handle and the request runs again on the
+// launch-per-iteration engine (S and the phase seed are intact).
+void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, float **audio, size_t *n_samples,
+                          bool normalise) {
+  const size_t N = (size_t)g->hop * (size_t)(b.F - 1);
+  std::lock_guard<ChipLock> chip(chip_mutex(g->device));
+  g->probe_tick();
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    g->iterate(b, phase0_dev, iters);
+    if (normalise) launch_gl_output_normalise(g->audio.p, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
+    HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+    PinnedGuard host(N);
+    HIP_CHECK(hipMemcpyAsync(host.p, g->audio.p, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    g->fetch_error_word();
+    g->finish_timings();  // (drains the stream)
+    if (g->persistent_failed()) {
+      HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));  // time the run that counts
+      continue;
+    }
+    *audio = host.release();
+    *n_samples = N;
+    return;
+  }
+  fail(XDTTS_ERR_HIP, "Griffin-Lim: the fallback engine reported an exchange failure");
+}
+
+// The two halves of gl_run_from_device_mel for a caller that overlaps the vocoder with other work (xdtts_synthesize_sequence):
+// everything enqueued on g->stream, nothing waited for; then the wait, the engine's error word and -- after a timed-out
+// exchange -- the request again on the fallback engine (S is intact until the next enqueue).  Caller holds g->mu and the chip lock.
+void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host) {
+  GlBufs b = g->bufs(F);
+  const size_t N = (size_t)g->hop * (size_t)(F - 1);
+  HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+  g->mel_to_linear(mel_dev_ptr, F);
+  HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
+  g->probe_tick();
+  g->iterate(b, nullptr, g->iters);
+  launch_gl_output_normalise(g->audio.p, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
+  HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+  if (!host.p) host = PinnedGuard(N);  // (the sequence hands in one it took from the pool while the frame loop ran)
+  HIP_CHECK(hipMemcpyAsync(host.p, g->audio.p, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+  g->fetch_error_word();
+}
+void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples) {
+  g->finish_timings();  // (drains the stream)
+  if (g->persistent_failed()) {
+    host = PinnedGuard();
+    gl_iterate_and_fetch(g, g->bufs(F), nullptr, g->iters, audio, n_samples, true);
+    return;
+  }
+  *audio = host.release();
+  *n_samples = (size_t)g->hop * (size_t)(F - 1);
+}
+
+void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, float **audio, size_t *n_samples) {
+  GlBufs b = g->bufs(F);
+  HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+  g->mel_to_linear(mel_dev_ptr, F);
+  HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
+  gl_iterate_and_fetch(g, b, nullptr, g->iters, audio, n_samples, true);  // GriffinLim::infer: G1..G6
+}
+
+// The vocoder half of a batch from a mel that is already in HBM (on g's device): [n_mels][sum Fu], utterance u at columns
+// fbase[u] .. fbase[u] + Fu[u].  mel -> linear is one GEMM over all frames, and the persistent kernel takes as many
+// utterances per launch as fit one workgroup per CU (a workgroup never spans two utterances and exchanges overlaps only
+// inside its own).  Caller holds g->mu.  The reads of the mel are enqueued on g->stream: the caller orders them behind
+// the mel's producer (a stream sync or an event wait on g->stream).
+void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples) {
+  {
+    const int n_utt = (int)Fu.size();
+    std::vector<int> fbase(n_utt), abase(n_utt);
+    size_t Ftot = 0, Ntot = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      fbase[u] = (int)Ftot;
+      abase[u] = (int)Ntot;
+      Ftot += (size_t)Fu[u];
+      Ntot += (size_t)g->hop * (size_t)(Fu[u] - 1);
+      if (Ftot > (1u << 24)) fail(XDTTS_ERR_BAD_ARG, "batch too large");
+    }
+    HIP_CHECK(hipSetDevice(g->device));
+    hipStream_t st = g->stream;
+    std::vector<int> fl(Ftot);
+    for (int u = 0; u < n_utt; ++u)
+      for (int f = 0; f < Fu[u]; ++f) fl[(size_t)fbase[u] + f] = f;
+    g->frame_local.upload(fl.data(), fl.size(), st);
+    GlBufs all = g->bufs((int)Ftot);
+    g->audio.alloc(std::max<size_t>(Ntot, 1));
+    HIP_CHECK(hipStreamSynchronize(st));  // the host vector above
+    const float alpha = g->momentum / (1.0f + g->momentum);
+    std::lock_guard<ChipLock> chip(chip_mutex(g->device));
+    g->probe_tick();
+    for (int attempt = 0;; ++attempt) {
+      HIP_CHECK(hipEventRecord(g->ev.e[0], st));
+      g->mel_to_linear(mel_dev_all, (int)Ftot);
+      HIP_CHECK(hipEventRecord(g->ev.e[1], st));
+      launch_gl_phase_init_batch(all, g->seed, g->frame_local.p, st);
+      // pack consecutive utterances into persistent launches of <= one workgroup per CU.  A workgroup owns up to
+      // 4 frames (one wave each) or up to 8 (two waves per SIMD): an iteration of the 8-frame shape takes 6.8 us
+      // against 5.35 us (tools/gl_tf_sweep.py), so it wins as soon as it saves launches.  Two 4-frame workgroups
+      // per CU (k_gl_persistent<4, 2>: the state in LDS, 256 registers) take 7.1 us for the same eight frames
+      // (tools/vocoder_batch.py) and keep the 4-frame split, i.e. the single call's audio bit for bit.
+      const bool pers = g->persistent_usable();
+      std::vector<GlSeg> segs;
+      struct Launch { int seg0, nblk; std::vector<int> utts; };
+      std::vector<Launch> launches;
+      std::vector<char> batched(n_utt, 0);
+      auto pack = [&](int tf, int wg, bool build) {  // returns the relative cost: launches x time per iteration of the shape
+        // first-fit decreasing over launches of n_cu workgroups (which launch an utterance rides in does not
+        // change its audio: its own split into workgroups depends on its frame count alone)
+        std::vector<std::pair<int, int>> items;  // (workgroups, utterance)
+        int n_alone = 0;
+        for (int u = 0; u < n_utt; ++u) {
+          const int nb = (Fu[u] + tf - 1) / tf;
+          if (Fu[u] < 16 || nb > g->n_cu || Fu[u] / nb < 3) {  // on its own below
+            n_alone += Fu[u] >= 16;  // (a launch of the 5..8-frame shape; the tiny ones cost next to nothing)
+            continue;
+          }
+          items.emplace_back(nb, u);
+        }
+        std::stable_sort(items.begin(), items.end(), [](const std::pair<int, int> &a, const std::pair<int, int> &b) { return a.first > b.first; });
+        std::vector<int> room;                 // free workgroups of each launch
+        std::vector<std::vector<int>> riders;  // its utterances
+        for (const auto &it : items) {
+          size_t k = 0;
+          while (k < room.size() && room[k] < it.first) ++k;
+          if (k == room.size()) {
+            room.push_back(g->n_cu * wg);
+            riders.emplace_back();
+          }
+          room[k] -= it.first;
+          riders[k].push_back(it.second);
+        }
+        if (build)
+          for (size_t k = 0; k < riders.size(); ++k) {
+            const int seg0 = (int)segs.size();
+            for (int u : riders[k]) {
+              const int nb = (Fu[u] + tf - 1) / tf;
+              for (int b = 0; b < nb; ++b) {
+                GlSeg sg{};
+                sg.fbase = fbase[u];
+                sg.F = Fu[u];
+                sg.f0 = (int)(((long long)b * Fu[u]) / nb);
+                sg.n_own = (int)(((long long)(b + 1) * Fu[u]) / nb) - sg.f0;
+                sg.first = b == 0;
+                sg.last = b + 1 == nb;
+                sg.abase = abase[u];
+                segs.push_back(sg);
+              }
+              batched[u] = 1;
+            }
+            launches.push_back({seg0, (int)segs.size() - seg0, riders[k]});
+          }
+        // us per iteration of one launch of each shape (tools/vocoder_shapes.py, round 4 with the 16-byte exchange granules:
+        // 4.5-5.2 / 5.8-6.3 / 5.9-6.3; round 3: 5.35 / 7.1 / 6.8) -- at equal cost the 4-frame shape, whose audio is the single call's
+        return (tf <= 4 ? (wg > 1 ? 6.0 : 4.85) : 6.1) * (double)riders.size() + 6.1 * n_alone;
+      };
+      int TF = 4, WG = 1;
+      if (pers) {
+        // (the 4-frame shape splits an utterance the way its own call does, one or two workgroups per CU: batch_shape 4)
+        if (g->per_cu4 >= 2 && pack(4, 2, false) < pack(4, 1, false)) WG = 2;
+        if (g->gopts.batch_shape == 0 && pack(GLP_TF_MAX, 1, false) < pack(4, WG, false)) TF = GLP_TF_MAX, WG = 1;
+        if (env::is_set(env::GL_BATCH_FORCE)) {  // developer: "8" = 8-frame workgroups, "41" / "42" = 4-frame, one / two per CU
+          const int v = env::int_or(env::GL_BATCH_FORCE, 0);
+          if (v == 8) TF = GLP_TF_MAX, WG = 1;
+          if (v == 41) TF = 4, WG = 1;
+          if (v == 42 && g->per_cu4 >= 2) TF = 4, WG = 2;
+        }
+        pack(TF, WG, true);
+      }
+      bool used_persistent = false;
+      std::vector<PinnedGuard> out;  // each utterance straight into the buffer the caller receives
+      out.reserve((size_t)n_utt);
+      for (int u = 0; u < n_utt; ++u) out.emplace_back((size_t)g->hop * (size_t)(Fu[u] - 1));
+      Drain drain(g->copy_stream);  // no buffer of `out` goes back to the pool while a copy into it may be in flight
+      // Output normalisation (G6): the utterances of one fetch are consecutive rows of `tab` (launch by launch, then the
+      // ones that run alone), so each fetch is preceded by ONE two-launch normalisation of exactly its utterances.
+      const int norm_mode = g->gopts.output_normalise;
+      std::vector<int> tab_pos((size_t)n_utt, 0);
+      if (norm_mode) {
+        std::vector<int2> tab;
+        tab.reserve((size_t)n_utt);
+        auto add = [&](int u) {
+          tab_pos[(size_t)u] = (int)tab.size();
+          tab.push_back(make_int2(abase[u], g->hop * (Fu[u] - 1)));
+        };
+        for (const Launch &L : launches)
+          for (int u : L.utts) add(u);
+        for (int u = 0; u < n_utt; ++u)
+          if (!batched[u]) add(u);
+        g->norm_tab.upload(tab.data(), tab.size(), st);
+        g->norm_parts.alloc((size_t)GLN_SCRATCH * (size_t)n_utt);
+        HIP_CHECK(hipStreamSynchronize(st));
+      }
+      size_t n_ev = 0;
+      auto fetch_audio = [&](const std::vector<int> &utts) {  // after the work just enqueued on `st`
+        if (norm_mode && !utts.empty()) {
+          int n_max = 0;
+          for (int u : utts) n_max = std::max(n_max, g->hop * (Fu[u] - 1));
+          const int r0 = tab_pos[(size_t)utts[0]];
+          launch_gl_output_normalise(g->audio.p, g->norm_tab.p + r0, (int)utts.size(), 0, n_max, norm_mode, g->gopts.rms_target,
+                                     g->norm_parts.p + (size_t)r0 * GLN_SCRATCH, st);
+        }
+        hipEvent_t e = g->launch_done(n_ev++);
+        HIP_CHECK(hipEventRecord(e, st));
+        HIP_CHECK(hipStreamWaitEvent(g->copy_stream, e, 0));
+        for (int u : utts)
+          HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, g->audio.p + abase[u], sizeof(float) * (size_t)g->hop * (size_t)(Fu[u] - 1),
+                                   hipMemcpyDeviceToHost, g->copy_stream));
+      };
+      if (!segs.empty()) {
+        g->segs.upload(segs.data(), segs.size(), st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        g->persist_prepare(gl_persistent_xch_words(g->n_cu * std::max(1, std::min(g->per_cu4, 2))),
+                           (unsigned)launches.size() * ((unsigned)g->iters + 2u));
+        for (const Launch &L : launches) {
+          GlPersist p = g->persist_args(g->iters);
+          p.segs = g->segs.p + L.seg0;
+          p.nblk = L.nblk;
+          p.TF = TF;
+          p.per_cu = WG;
+          launch_gl_persistent(all, p, all.ang, all.tprev, g->iters, alpha, g->audio.p, st);
+          fetch_audio(L.utts);
+        }
+        used_persistent = true;
+      }
+      for (int u = 0; u < n_utt; ++u) {  // the rest one by one (tiny / very long utterances, or a demoted handle)
+        if (batched[u]) continue;
+        GlBufs v = all;
+        v.F = Fu[u];
+        v.S = all.S + (size_t)fbase[u] * g->nb;
+        v.ang = all.ang + (size_t)fbase[u] * g->nb;
+        v.ang2 = all.ang2 + (size_t)fbase[u] * g->nb;
+        v.tprev = all.tprev + (size_t)fbase[u] * g->nb;
+        v.frames = all.frames + (size_t)fbase[u] * g->n_fft;
+        v.wss_inv = all.wss_inv + abase[u];
+        launch_gl_prepare(v, st);
+        g->run_iterations(v, g->iters, alpha, g->audio.p + abase[u]);  // the engine the single-utterance call uses
+        used_persistent = used_persistent || g->last_persistent;
+        fetch_audio(std::vector<int>(1, u));
+      }
+      HIP_CHECK(hipEventRecord(g->ev.e[2], st));
+      g->finish_timings();
+      HIP_CHECK(hipStreamSynchronize(g->copy_stream));
+      g->last_persistent = used_persistent;
+      if (g->persistent_failed()) {
+        if (attempt) fail(XDTTS_ERR_HIP, "Griffin-Lim batch: exchange failure on the fallback engine");
+        continue;  // demoted: everything runs one by one on the launch-per-iteration kernels
+      }
+      for (int u = 0; u < n_utt; ++u) {
+        audios[u] = out[(size_t)u].release();
+        n_samples[u] = (size_t)g->hop * (size_t)(Fu[u] - 1);
+      }
+      return;
+    }
+  }
+}
+
+}  // namespace xdtts

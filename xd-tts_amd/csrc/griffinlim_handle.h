@@ -1,0 +1,84 @@
+// griffinlim_handle.h -- the vocoder handle, the host-side mel-bank algebra, and the gl_* request paths the extern "C"
+// functions of api_griffinlim.cpp and api_synthesize.cpp share.
+#pragma once
+#include "engine_gate.h"
+#include "kernels.h"
+#include "runtime.h"
+
+struct xdtts_griffinlim {
+  using GlBufs = xdtts::GlBufs;
+  using GlPersist = xdtts::GlPersist;
+  template <class T>
+  using DevBuf = xdtts::DevBuf<T>;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  mutable std::mutex mu;
+  int n_mels = 0, nb = 0, n_fft = 0, hop = 0, iters = 0;
+  float power = 1.f, momentum = 0.99f;
+  uint32_t seed = 0;
+  xdtts::Events ev;
+  float last_ms[3] = {0, 0, 0};
+  DevBuf<float> pinv, win, S, melT, mel_in, frames, wss_inv, audio, phase0;
+  // mel->linear options (xdtts_griffinlim_opts) and the NNLS refinement's operands
+  xdtts_griffinlim_opts gopts = [] { xdtts_griffinlim_opts o; xdtts_griffinlim_opts_default(&o); return o; }();  // one source for the defaults
+  static constexpr int NBP = 528;  // bins padded to the GEMM's K granule
+  DevBuf<float> basis_p, basisT_p, nnls_x, nnls_r, norm_parts;  // norm_parts: GLN_SCRATCH per utterance
+  DevBuf<int2> norm_tab;  // (first sample, samples) per utterance of a vocoder batch
+  float nnls_step = 0.f;   // 1 / lambda_max(A A^T)
+  xdtts::GraphCache graph;  // n_iter x (istft, stft) + final ISTFT for the cached (buffers, F, iterations, momentum, output)
+  DevBuf<float2> tw, ang, ang2, tprev, tprev2;  // tprev2: final rebuilt spectrum of the parity hook
+  // persistent engine (griffinlim.hip: k_gl_persistent)
+  DevBuf<unsigned long long> xch;  // neighbour-overlap granules
+  DevBuf<xdtts::GlSeg> segs;              // vocoder batch: per-workgroup segment table
+  DevBuf<int> frame_local;         // vocoder batch: row -> frame index inside its utterance
+  DevBuf<int> gl_err;
+  int *host_err = nullptr;         // pinned
+  unsigned epoch = 0;              // tag base; tags are never reused while xch lives
+  xdtts::EngineGate gate;          // the persistent engine (engine_gate.h)
+  int n_cu = 0;
+  int per_cu4 = 1;                 // co-resident workgroups of the 4-frame shape per CU (vocoder batch)
+  bool last_persistent = false;    // the last run_iterations used the persistent engine
+  // vocoder batch: the audio of a finished launch goes to the host while the next launches run
+  hipStream_t copy_stream = nullptr;
+  std::vector<hipEvent_t> copy_ev;
+  hipEvent_t launch_done(size_t k) {
+    if (!copy_stream) HIP_CHECK(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    while (copy_ev.size() <= k) {
+      hipEvent_t e = nullptr;
+      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      copy_ev.push_back(e);
+    }
+    return copy_ev[k];
+  }
+
+  ~xdtts_griffinlim();
+  GlBufs bufs(int F);
+  void mel_to_linear(const float *mel_dev_ptr, int F);
+  // Once per API call (never inside a retry attempt): a demoted handle counts the call and, after PROBE_AFTER of them,
+  // gives the persistent engine another try -- the cause of a timed-out exchange may have been transient.
+  void probe_tick() { gate.tick(); }
+  bool persistent_usable();
+  // exchange granules and error word of the persistent kernel, ready for launches that consume `tags` epoch tags in all
+  void persist_prepare(size_t xch_words, unsigned tags);
+  GlPersist persist_args(int n_iter);  // of the next launch: exchange, error word, its epoch (advanced), the first-poll delay
+  const float2 *run_iterations(const GlBufs &g, int n_iter, float alpha, float *audio_out, bool want_state = false,
+                               const float2 **tprev_fin = nullptr, bool gen_phase = false);
+  bool err_fetched = false;
+  void fetch_error_word();
+  bool persistent_failed();
+  void iterate(const GlBufs &g, const float *phase0_dev, int n_iter);
+  void finish_timings();
+};
+
+namespace xdtts {
+void host_pinv(const float *basis, int n, int nbins, std::vector<float> &out);
+double host_lipschitz(const float *basis, int n, int nbins);
+void mel_filter_bank(double sr, int n_fft, int n_mels, double fmin, double fmax, float *out);
+
+void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, float **audio, size_t *n_samples,
+                          bool normalise);
+void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host);
+void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples);
+void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, float **audio, size_t *n_samples);
+void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples);
+}  // namespace xdtts

@@ -48,7 +48,7 @@ struct DecoderBufs {
   // Persistent engine: the context columns of its LSTM / projection rows folded into the encoder memory,
   // ctx_fold [B][CTXF_ROWS][CTXF_LD]: row n of chunk b holds W_n[ctx cols] . memory_b[t] for t < T (rows: 4096 attention-LSTM
   // rows in packed order, 4096 decoder-LSTM rows, 81 projection rows; DeviceWeights::ctx_w) -- one GEMM per request
-  // (api.cpp) instead of a fold loop in every launch.  null = the kernel folds for itself.
+  // (tacotron2_decode.cpp) instead of a fold loop in every launch.  null = the kernel folds for itself.
   const float *ctx_fold;
   const float *dec_in;   // parity hook (xdtts_tacotron2_decoder_step): decoder_input [B][80] of this step, or null
   // Batched mode: processed_memory a second time as [B][32 dim groups][T][4] -- the energies kernel reads 4 dims of
