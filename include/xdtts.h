@@ -316,6 +316,31 @@ xdtts_status xdtts_griffinlim_step(xdtts_griffinlim *g, const float *S, float *a
 /* ms[0] mel->linear, ms[1] iterations, ms[2] total of the last call (HIP events). */
 xdtts_status xdtts_griffinlim_last_timings(const xdtts_griffinlim *g, float ms[3]);
 
+/* The inverse direction of GriffinLim::infer's conventions: librosa.stft(y, 1024, hop 256, periodic hann, center, reflect)
+ * -> magnitude -> mel basis -> compression, under the handle's power / power_mode / mel_decompress.
+ * n_frames = n_samples / hop + 1 (so the audio of an F-frame mel analyses to F frames).  S_out (n_bins x F) and
+ * mel_out (n_mels x F) are caller buffers, either may be NULL; mel_floor <= 0 means 1e-5 (Tacotron2's clamp).
+ * The exponent is the handle's, inverted: power_mode 0: mel = basis . S^power, 1: S^(1/power), 2: S; the compression inverts
+ * mel_decompress: 0: ln(max(m, mel_floor)), 1: m, 2: log10(max(m, mel_floor)).  n_frames may be NULL.
+ * _analysis_frames needs no device (g may be NULL: every handle's hop is 256).
+ * _analyze_batch: n_utt audios in one magnitude launch and one projection (then one small layout launch per wanted output and
+ * utterance); S_outs / mel_outs (either may be NULL, and so may single entries) and n_frames are per utterance; every result
+ * equals the single call's bit for bit, whatever the mix and order.  At most 2^20 frames per call. */
+size_t       xdtts_griffinlim_analysis_frames(const xdtts_griffinlim *g, size_t n_samples);
+xdtts_status xdtts_griffinlim_analyze(xdtts_griffinlim *g, const float *audio, size_t n_samples, float mel_floor,
+                                      float *S_out, float *mel_out, size_t *n_frames);
+xdtts_status xdtts_griffinlim_analyze_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n_samples,
+                                            int32_t n_utt, float mel_floor, float **S_outs, float **mel_outs,
+                                            size_t *n_frames);
+/* Spectral convergence of `audio` against a target magnitude S (n_bins x F, F == analysis_frames(n_samples)):
+ * out[0] = || a |STFT(audio)| - S ||_F / || S ||_F, out[1] = a.  fit_gain 0: a = 1; 1: the least-squares gain
+ * a = <|X|,S> / <|X|,|X|> (for audio that went through output_normalise).  S all zero -> XDTTS_ERR_BAD_ARG.
+ * The sums are taken in fp64 in a fixed order: the same input gives the same bits on every call. */
+xdtts_status xdtts_griffinlim_spectral_convergence(xdtts_griffinlim *g, const float *audio, size_t n_samples,
+                                                   const float *S, size_t n_frames, int32_t fit_gain, float out[2]);
+/* ms[0] transform + magnitude, ms[1] mel projection / distance, ms[2] total of the last analysis call. */
+xdtts_status xdtts_griffinlim_analysis_timings(const xdtts_griffinlim *g, float ms[3]);
+
 void xdtts_griffinlim_free(xdtts_griffinlim *g);
 
 /* ---- XdTts::infer pipeline (src/lib.rs:110-159): mel-gen then vocoder with the mel kept in

@@ -10,6 +10,7 @@
 //   xdtts::create_griffin_lim()             -- src/tacotron2/mod.rs:441-458
 // Errors become xdtts::Error (the shim's anyhow::Error); nothing here computes on the CPU.
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -108,11 +109,12 @@ inline Array2 create_mel_filter_bank(float sample_rate, size_t n_fft, size_t n_m
 
 class GriffinLim {
  public:
-  GriffinLim(const Array2 &mel_basis, size_t noverlap, float power, size_t iter, float momentum, int device_id = XDTTS_DEVICE_DEFAULT) {
+  GriffinLim(const Array2 &mel_basis, size_t noverlap, float power, size_t iter, float momentum, int device_id = XDTTS_DEVICE_DEFAULT)
+      : n_mels_(mel_basis.rows), n_bins_(mel_basis.cols) {
     check(xdtts_griffinlim_new(mel_basis.data.data(), mel_basis.rows, mel_basis.cols, noverlap, power, iter, momentum,
                                device_id, &g_));
   }
-  GriffinLim(GriffinLim &&o) noexcept : g_(std::exchange(o.g_, nullptr)) {}
+  GriffinLim(GriffinLim &&o) noexcept : g_(std::exchange(o.g_, nullptr)), n_mels_(o.n_mels_), n_bins_(o.n_bins_) {}
   GriffinLim(const GriffinLim &) = delete;
   GriffinLim &operator=(const GriffinLim &) = delete;
   ~GriffinLim() { xdtts_griffinlim_free(g_); }
@@ -132,10 +134,49 @@ class GriffinLim {
     check(xdtts_griffinlim_get_opts(g_, &o));
     return o;
   }
+  // The inverse direction (xdtts_griffinlim_analyze): audio -> (S (n_bins x F), mel (n_mels x F)) under the handle's conventions,
+  // F = audio.size() / 256 + 1
+  std::pair<Array2, Array2> analyze(const std::vector<float> &audio, float mel_floor = 1e-5f) const {
+    const size_t F = xdtts_griffinlim_analysis_frames(g_, audio.size());
+    Array2 S{n_bins_, F, std::vector<float>(n_bins_ * F)}, mel{n_mels_, F, std::vector<float>(n_mels_ * F)};
+    check(xdtts_griffinlim_analyze(g_, audio.data(), audio.size(), mel_floor, S.data.data(), mel.data.data(), nullptr));
+    return {std::move(S), std::move(mel)};
+  }
+  // ... for several audios in one call (xdtts_griffinlim_analyze_batch): the single call's bits per utterance
+  std::vector<std::pair<Array2, Array2>> analyze_batch(const std::vector<std::vector<float>> &audios, float mel_floor = 1e-5f) const {
+    const size_t n = audios.size();
+    std::vector<std::pair<Array2, Array2>> out(n);
+    std::vector<const float *> ys(n);
+    std::vector<size_t> ns(n), nf(n);
+    std::vector<float *> Sp(n), Mp(n);
+    for (size_t u = 0; u < n; ++u) {
+      const size_t F = xdtts_griffinlim_analysis_frames(g_, audios[u].size());
+      out[u].first = Array2{n_bins_, F, std::vector<float>(n_bins_ * F)};
+      out[u].second = Array2{n_mels_, F, std::vector<float>(n_mels_ * F)};
+      ys[u] = audios[u].data();
+      ns[u] = audios[u].size();
+      Sp[u] = out[u].first.data.data();
+      Mp[u] = out[u].second.data.data();
+    }
+    check(xdtts_griffinlim_analyze_batch(g_, ys.data(), ns.data(), (int32_t)n, mel_floor, Sp.data(), Mp.data(), nf.data()));
+    return out;
+  }
+  // (|| a |STFT(audio)| - S || / || S ||, a): how far `audio` is from the target magnitude S (n_bins x F)
+  std::pair<float, float> spectral_convergence(const std::vector<float> &audio, const Array2 &S, bool fit_gain = false) const {
+    float out[2] = {0.f, 0.f};
+    check(xdtts_griffinlim_spectral_convergence(g_, audio.data(), audio.size(), S.data.data(), S.cols, fit_gain ? 1 : 0, out));
+    return {out[0], out[1]};
+  }
+  std::array<float, 3> analysis_timings() const {  // ms: transform + magnitude, projection / distance, total
+    std::array<float, 3> ms{};
+    check(xdtts_griffinlim_analysis_timings(g_, ms.data()));
+    return ms;
+  }
   xdtts_griffinlim *raw() const { return g_; }
 
  private:
   xdtts_griffinlim *g_ = nullptr;
+  size_t n_mels_ = 0, n_bins_ = 0;  // the basis' shape: the sizes of the analysis outputs
 };
 
 // src/tacotron2/mod.rs:441-458

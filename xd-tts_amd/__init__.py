@@ -102,6 +102,11 @@ SYMBOLS = {
     "xdtts_griffinlim_mel_to_linear": (_I32, [_VP, _VP, _SZ, _SZ, _VP]),
     "xdtts_griffinlim_step": (_I32, [_VP, _VP, _VP, _VP, _SZ, _SZ]),
     "xdtts_griffinlim_last_timings": (_I32, [_VP, C.POINTER(C.c_float * 3)]),
+    "xdtts_griffinlim_analysis_frames": (_SZ, [_VP, _SZ]),
+    "xdtts_griffinlim_analyze": (_I32, [_VP, _VP, _SZ, _F, _VP, _VP, C.POINTER(_SZ)]),
+    "xdtts_griffinlim_analyze_batch": (_I32, [_VP, _VP, _VP, _I32, _F, _VP, _VP, _VP]),
+    "xdtts_griffinlim_spectral_convergence": (_I32, [_VP, _VP, _SZ, _VP, _SZ, _I32, C.POINTER(C.c_float * 2)]),
+    "xdtts_griffinlim_analysis_timings": (_I32, [_VP, C.POINTER(C.c_float * 3)]),
     "xdtts_griffinlim_free": (None, [_VP]),
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_batch": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP]),
@@ -543,7 +548,7 @@ class GriffinLim:
         basis = np.ascontiguousarray(mel_basis, dtype=np.float32)
         self._h = C.c_void_p()
         _check(lib.xdtts_griffinlim_new(_ptr(basis), basis.shape[0], basis.shape[1], noverlap, power, iters, momentum, device_id, C.byref(self._h)))
-        self.n_bins = basis.shape[1]
+        self.n_mels, self.n_bins = basis.shape
         self.set_seed(seed)
 
     def set_seed(self, seed):
@@ -617,6 +622,47 @@ class GriffinLim:
         ms = (C.c_float * 3)()
         _check(lib.xdtts_griffinlim_last_timings(self._h, C.byref(ms)))
         return {"mel_to_linear_ms": ms[0], "iterations_ms": ms[1], "total_ms": ms[2]}
+
+    # -- analysis: audio -> magnitude -> mel under the handle's conventions, spectral convergence ----
+    def analysis_frames(self, n_samples):
+        return int(lib.xdtts_griffinlim_analysis_frames(self._h, int(n_samples)))
+
+    def analyze(self, audio, mel_floor=1e-5, want_S=True, want_mel=True):
+        """librosa.stft(audio, 1024, hop 256) -> |.| -> mel basis -> compression, the inverse of infer's conventions (power,
+        power_mode, mel_decompress).  Returns (S (n_bins, F), mel (n_mels, F)), F = len(audio) // 256 + 1; None where not wanted."""
+        S, mel = self.analyze_batch([audio], mel_floor, want_S, want_mel)
+        return (S[0] if want_S else None), (mel[0] if want_mel else None)
+
+    def analyze_batch(self, audios, mel_floor=1e-5, want_S=True, want_mel=True):
+        """analyze() for a list of audios in one call (one magnitude launch, one projection); every result is the single
+        call's bit for bit.  Returns (list of S or None, list of mel or None)."""
+        ys = [np.ascontiguousarray(a, dtype=np.float32).ravel() for a in audios]
+        n = len(ys)
+        Fs = [self.analysis_frames(max(y.size, 1)) for y in ys]
+        S = [np.empty((self.n_bins, F), dtype=np.float32) for F in Fs] if want_S else None
+        mel = [np.empty((self.n_mels, F), dtype=np.float32) for F in Fs] if want_mel else None
+        ptrs = (C.c_void_p * n)(*[y.ctypes.data for y in ys])
+        ns = (C.c_size_t * n)(*[y.size for y in ys])
+        Sp = (C.c_void_p * n)(*[a.ctypes.data for a in S]) if want_S else None
+        Mp = (C.c_void_p * n)(*[a.ctypes.data for a in mel]) if want_mel else None
+        nf = (C.c_size_t * n)()
+        _check(lib.xdtts_griffinlim_analyze_batch(self._h, ptrs, ns, n, mel_floor, Sp, Mp, nf))
+        assert list(nf) == Fs
+        return S, mel
+
+    def spectral_convergence(self, audio, S, fit_gain=False):
+        """(|| a |STFT(audio)| - S || / || S ||, a) against the target magnitude S (n_bins, F); a = 1, or with fit_gain the
+        least-squares gain (for audio that went through output_normalise)."""
+        y = np.ascontiguousarray(audio, dtype=np.float32).ravel()
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        out = (C.c_float * 2)()
+        _check(lib.xdtts_griffinlim_spectral_convergence(self._h, _ptr(y), y.size, _ptr(S), S.shape[1], 1 if fit_gain else 0, C.byref(out)))
+        return float(out[0]), float(out[1])
+
+    def analysis_timings(self):
+        ms = (C.c_float * 3)()
+        _check(lib.xdtts_griffinlim_analysis_timings(self._h, C.byref(ms)))
+        return {"magnitude_ms": ms[0], "projection_ms": ms[1], "total_ms": ms[2]}
 
 
 def create_griffin_lim(device_id=0, iters=30, seed=0):

@@ -44,6 +44,7 @@ xdtts_status xdtts_griffinlim_new(const float *mel_basis, size_t n_mels, size_t 
     g->momentum = momentum;
     HIP_CHECK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     g->ev.create();
+    g->an_ev.create();
     std::vector<float> pinv;
     host_pinv(mel_basis, (int)n_mels, (int)n_bins, pinv);
     g->pinv.upload(pinv.data(), pinv.size(), g->stream);
@@ -249,6 +250,101 @@ xdtts_status xdtts_griffinlim_last_timings(const xdtts_griffinlim *g, float ms[3
   return guard([&] {
     if (!g || !ms) fail(XDTTS_ERR_BAD_ARG, "null argument");
     for (int i = 0; i < 3; ++i) ms[i] = g->last_ms[i];
+  });
+}
+
+// ---- analysis: the inverse direction of GriffinLim::infer's conventions (analysis.hip).  No co-resident grid: no chip lock. ----
+
+// What one call takes: the row tiles of the mel GEMM and of the boundary transposes go into a grid dimension of at most 65535
+// (32 rows each), so 2^20 frames in all (3.4 hours of audio) leave a factor two; 2^28 samples are 2^20 frames.
+static constexpr size_t AN_MAX_FRAMES = (size_t)1 << 20, AN_MAX_SAMPLES = (size_t)1 << 28;
+
+size_t xdtts_griffinlim_analysis_frames(const xdtts_griffinlim *g, size_t n_samples) {
+  return n_samples / (size_t)(g ? g->hop : 256) + 1;  // (every handle's hop is 256: xdtts_griffinlim_new)
+}
+
+xdtts_status xdtts_griffinlim_analyze_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n_samples, int32_t n_utt,
+                                            float mel_floor, float **S_outs, float **mel_outs, size_t *n_frames) {
+  return guard([&] {
+    if (!g || !audios || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (n_utt < 1) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    size_t Ftot = 0;
+    bool want_S = false, want_mel = false;
+    for (int u = 0; u < n_utt; ++u) {
+      if (!audios[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null audio", u);
+      if (n_samples[u] == 0 || n_samples[u] >= AN_MAX_SAMPLES) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need 1 .. 2^28 - 1 samples, got %zu", u, n_samples[u]);
+      Ftot += n_samples[u] / (size_t)g->hop + 1;
+      if (Ftot > AN_MAX_FRAMES) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^20 frames");
+      want_S = want_S || (S_outs && S_outs[u]);
+      want_mel = want_mel || (mel_outs && mel_outs[u]);
+    }
+    const float floor = mel_floor > 0.f ? mel_floor : 1e-5f;  // Tacotron2's clamp
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    const AnRows rows = gl_analysis_enqueue(g, audios, n_samples, n_utt, want_mel);
+    // boundary layouts, utterance by utterance: mel (n_mels x F) compressed, S (n_bins x F)
+    const size_t mel_at = (size_t)rows.Ftot * g->nb;
+    g->an_out.alloc((size_t)rows.Ftot * (size_t)(g->nb + g->n_mels));
+    for (int u = 0; u < n_utt; ++u) {
+      const size_t r0 = (size_t)rows.row0[(size_t)u];
+      const int F = rows.F[(size_t)u];
+      if (mel_outs && mel_outs[u])
+        launch_mel_compress(g->an_melT.p + r0 * g->n_mels, g->an_out.p + mel_at + r0 * g->n_mels, g->n_mels, F, g->gopts.mel_decompress, floor, g->stream);
+      if (S_outs && S_outs[u]) launch_transpose(g->an_S.p + r0 * g->nb, g->an_out.p + r0 * g->nb, F, g->nb, g->stream);
+    }
+    HIP_CHECK(hipEventRecord(g->an_ev.e[2], g->stream));
+    for (int u = 0; u < n_utt; ++u) {
+      const size_t r0 = (size_t)rows.row0[(size_t)u], F = (size_t)rows.F[(size_t)u];
+      if (mel_outs && mel_outs[u])
+        HIP_CHECK(hipMemcpyAsync(mel_outs[u], g->an_out.p + mel_at + r0 * g->n_mels, F * g->n_mels * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+      if (S_outs && S_outs[u])
+        HIP_CHECK(hipMemcpyAsync(S_outs[u], g->an_out.p + r0 * g->nb, F * g->nb * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+      if (n_frames) n_frames[u] = F;
+    }
+    gl_analysis_finish_timings(g);
+  });
+}
+
+xdtts_status xdtts_griffinlim_analyze(xdtts_griffinlim *g, const float *audio, size_t n_samples, float mel_floor, float *S_out,
+                                      float *mel_out, size_t *n_frames) {
+  return xdtts_griffinlim_analyze_batch(g, &audio, &n_samples, 1, mel_floor, &S_out, &mel_out, n_frames);
+}
+
+xdtts_status xdtts_griffinlim_spectral_convergence(xdtts_griffinlim *g, const float *audio, size_t n_samples, const float *S,
+                                                   size_t n_frames, int32_t fit_gain, float out[2]) {
+  return guard([&] {
+    if (!g || !audio || !S || !out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (n_samples == 0 || n_samples >= AN_MAX_SAMPLES) fail(XDTTS_ERR_BAD_ARG, "need 1 .. 2^28 - 1 samples, got %zu", n_samples);
+    const size_t F = n_samples / (size_t)g->hop + 1;
+    if (n_frames != F) fail(XDTTS_ERR_BAD_ARG, "the target has %zu frames, %zu samples analyse to %zu", n_frames, n_samples, F);
+    if (fit_gain != 0 && fit_gain != 1) fail(XDTTS_ERR_BAD_ARG, "fit_gain must be 0 or 1, got %d", fit_gain);
+    const size_t ne = F * (size_t)g->nb;
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    // the target in the device layout [F][nb] first, so that the timed span holds kernels only
+    g->an_out.upload(S, ne, g->stream);
+    g->an_St.alloc(ne);
+    launch_transpose(g->an_out.p, g->an_St.p, g->nb, (int)F, g->stream);
+    g->an_sums.alloc(3 * SPD_PARTS + 3);
+    gl_analysis_enqueue(g, &audio, &n_samples, 1, false);
+    double *sums = g->an_sums.p + 3 * SPD_PARTS;
+    launch_spec_distance(g->an_S.p, g->an_St.p, ne, g->an_sums.p, sums, g->stream);
+    HIP_CHECK(hipEventRecord(g->an_ev.e[2], g->stream));
+    double h[3] = {0, 0, 0};  // sum x s, sum x x, sum s s  (x = analysed magnitude, s = target)
+    HIP_CHECK(hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, g->stream));
+    gl_analysis_finish_timings(g);
+    if (!(h[2] > 0.0)) fail(XDTTS_ERR_BAD_ARG, "the target magnitude is all zero");
+    const double a = fit_gain ? (h[1] > 0.0 ? h[0] / h[1] : 0.0) : 1.0;
+    const double d2 = (a * a * h[1] - 2.0 * a * h[0]) + h[2];  // || a x - s ||^2
+    out[0] = (float)std::sqrt(std::max(d2, 0.0) / h[2]);
+    out[1] = (float)a;
+  });
+}
+
+xdtts_status xdtts_griffinlim_analysis_timings(const xdtts_griffinlim *g, float ms[3]) {
+  return guard([&] {
+    if (!g || !ms) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    for (int i = 0; i < 3; ++i) ms[i] = g->an_ms[i];
   });
 }
 

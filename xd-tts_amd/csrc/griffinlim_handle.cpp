@@ -606,4 +606,70 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
   }
 }
 
+AnRows gl_analysis_enqueue(xdtts_griffinlim *g, const float *const *audios, const size_t *n_samples, int n_utt, bool want_mel) {
+  AnRows rows;
+  rows.row0.resize((size_t)n_utt);
+  rows.F.resize((size_t)n_utt);
+  std::vector<long long> abase((size_t)n_utt);
+  std::vector<AnSeg> segs;
+  size_t Ftot = 0, Ntot = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    const size_t n = n_samples[u], F = n / (size_t)g->hop + 1;
+    rows.row0[(size_t)u] = (int)Ftot;
+    rows.F[(size_t)u] = (int)F;
+    abase[(size_t)u] = (long long)Ntot;
+    for (size_t f0 = 0; f0 < F; f0 += 4) {  // a workgroup: four consecutive frames of one utterance
+      AnSeg sg{};
+      sg.abase = (long long)Ntot;
+      sg.n = (int)n;
+      sg.F = (int)F;
+      sg.f0 = (int)f0;
+      sg.row0 = (int)Ftot;
+      segs.push_back(sg);
+    }
+    Ftot += F;
+    Ntot += n;
+  }
+  rows.Ftot = (int)Ftot;
+  hipStream_t st = g->stream;
+  g->an_audio.alloc(Ntot);
+  for (int u = 0; u < n_utt; ++u)
+    HIP_CHECK(hipMemcpyAsync(g->an_audio.p + abase[(size_t)u], audios[u], n_samples[u] * sizeof(float), hipMemcpyHostToDevice, st));
+  g->an_segs.upload(segs.data(), segs.size(), st);
+  g->an_S.alloc(Ftot * (size_t)g->nb);
+  const int NBP = xdtts_griffinlim::NBP;
+  if (want_mel) {
+    g->an_P.alloc(Ftot * (size_t)NBP);
+    g->an_melT.alloc(Ftot * (size_t)g->n_mels);
+  }
+  HIP_CHECK(hipStreamSynchronize(st));  // the host vector above
+  // the handle's exponent, inverted: mel -> linear takes x^(1/power) (mode 0) / x^power (1) / x (2)
+  const float e = g->gopts.power_mode == 0 ? g->power : (g->gopts.power_mode == 1 ? 1.0f / g->power : 1.0f);
+  HIP_CHECK(hipEventRecord(g->an_ev.e[0], st));
+  launch_stft_mag(g->an_audio.p, g->an_segs.p, (int)segs.size(), g->tw.p, g->win.p, g->an_S.p, want_mel ? g->an_P.p : nullptr, NBP, e, st);
+  HIP_CHECK(hipEventRecord(g->an_ev.e[1], st));
+  if (want_mel) {
+    GemmArgs a{};  // melT = P basis^T (the residual GEMM of the NNLS refinement without the residual)
+    a.A = g->an_P.p;
+    a.lda = NBP;
+    a.W = g->basis_p.p;  // [n_mels][NBP]
+    a.C = g->an_melT.p;
+    a.ldc = g->n_mels;
+    a.M = (int)Ftot;
+    a.N = g->n_mels;
+    a.K = NBP;
+    a.batch = 1;
+    a.tile = 32;  // one tile shape whatever the row count: a frame's mel does not depend on what else is in the batch
+    launch_gemm_nt(a, st);
+  }
+  return rows;
+}
+
+void gl_analysis_finish_timings(xdtts_griffinlim *g) {
+  HIP_CHECK(hipStreamSynchronize(g->stream));
+  HIP_CHECK(hipEventElapsedTime(&g->an_ms[0], g->an_ev.e[0], g->an_ev.e[1]));
+  HIP_CHECK(hipEventElapsedTime(&g->an_ms[1], g->an_ev.e[1], g->an_ev.e[2]));
+  HIP_CHECK(hipEventElapsedTime(&g->an_ms[2], g->an_ev.e[0], g->an_ev.e[2]));
+}
+
 }  // namespace xdtts

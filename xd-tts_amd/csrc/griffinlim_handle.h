@@ -51,6 +51,14 @@ struct xdtts_griffinlim {
     return copy_ev[k];
   }
 
+  // analysis (analysis.hip): audio -> magnitude -> mel, spectral convergence.  Buffers of its own: the iteration state
+  // (S, angles, previous spectrum) of the handle is not touched.
+  DevBuf<float> an_audio, an_S, an_P, an_melT, an_out, an_St;  // an_out: boundary-layout staging; an_St: a target, [F][nb]
+  DevBuf<xdtts::AnSeg> an_segs;
+  DevBuf<double> an_sums;  // 3 * SPD_PARTS partials, then the three sums
+  xdtts::Events an_ev;
+  float an_ms[3] = {0, 0, 0};
+
   ~xdtts_griffinlim();
   GlBufs bufs(int F);
   void mel_to_linear(const float *mel_dev_ptr, int F);
@@ -81,4 +89,14 @@ void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, i
 void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples);
 void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, float **audio, size_t *n_samples);
 void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples);
+
+// Analysis of n_utt audios in one k_stft_mag launch: g->an_S [Ftot][nb] = |STFT|, and with want_mel g->an_melT [Ftot][n_mels] =
+// an_S^e . basis^T (linear mel, before compression).  Returns each utterance's first row and frame count.  Everything is
+// enqueued on g->stream behind an_ev.e[0]; an_ev.e[1] follows the magnitude kernel.  Caller holds g->mu.
+struct AnRows {
+  std::vector<int> row0, F;
+  int Ftot = 0;
+};
+AnRows gl_analysis_enqueue(xdtts_griffinlim *g, const float *const *audios, const size_t *n_samples, int n_utt, bool want_mel);
+void gl_analysis_finish_timings(xdtts_griffinlim *g);  // drains the stream; an_ms from an_ev.e[0..2] (e[2]: recorded by the caller behind its last kernel)
 }  // namespace xdtts

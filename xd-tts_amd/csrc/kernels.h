@@ -294,4 +294,23 @@ void launch_transpose(const float *in, float *out, int rows, int cols, hipStream
 void launch_copy_rows(const float *src, size_t src_stride, float *dst, size_t dst_stride, const int *rows, int n, int cols,
                       hipStream_t s);
 
+// ---- analysis (analysis.hip): audio -> STFT magnitude -> mel, spectral convergence -----------------------------------------
+// One workgroup's share of launch_stft_mag: up to four consecutive frames (one wave each) of ONE utterance, so a launch covers
+// the frames of several utterances and a frame never reads another utterance's samples.
+struct AnSeg {
+  long long abase;  // offset of the utterance's first sample in the concatenated audio
+  int n;            // samples of the utterance
+  int F;            // its frames, n / hop + 1
+  int f0;           // the workgroup's first frame, within the utterance
+  int row0;         // row of the utterance's first frame in S / P
+};
+// S [rows][513] = |STFT|; P [rows][ldp] = S^e with zero padding columns (null: not wanted); nblk rows of segs_dev
+void launch_stft_mag(const float *audio, const AnSeg *segs_dev, int nblk, const float2 *tw, const float *win, float *S, float *P,
+                     int ldp, float e, hipStream_t s);
+// melT [F][n_mels] -> (n_mels x F), mode 0: ln(max(m, floor)), 1: m, 2: log10(max(m, floor)) -- launch_gl_exp_transpose inverted
+void launch_mel_compress(const float *melT, float *out_melsxF, int n_mels, int F, int mode, float floor, hipStream_t s);
+// sums[0..2] = sum x s, sum x x, sum s s over n cells (x = X, s = St) in fp64, in a fixed order: parts = 3 * SPD_PARTS doubles
+constexpr int SPD_PARTS = 256;
+void launch_spec_distance(const float *X, const float *St, size_t n, double *parts, double *sums, hipStream_t s);
+
 }  // namespace xdtts
