@@ -313,7 +313,8 @@ xdtts_status xdtts_griffinlim_mel_to_linear(xdtts_griffinlim *g, const float *me
 xdtts_status xdtts_griffinlim_step(xdtts_griffinlim *g, const float *S, float *angles,
                                    float *rebuilt, size_t n_frames, size_t n_iter);
 
-/* ms[0] mel->linear, ms[1] iterations, ms[2] total of the last call (HIP events). */
+/* ms[0] mel->linear (for the *_prosody entries: mel->linear and the prosody stage), ms[1] iterations, ms[2] total of the last
+ * call (HIP events).  After xdtts_griffinlim_prosody_linear: ms[0] the prosody stage alone, ms[1] the layout change behind it. */
 xdtts_status xdtts_griffinlim_last_timings(const xdtts_griffinlim *g, float ms[3]);
 
 /* The inverse direction of GriffinLim::infer's conventions: librosa.stft(y, 1024, hop 256, periodic hann, center, reflect)
@@ -341,6 +342,44 @@ xdtts_status xdtts_griffinlim_spectral_convergence(xdtts_griffinlim *g, const fl
 /* ms[0] transform + magnitude, ms[1] mel projection / distance, ms[2] total of the last analysis call. */
 xdtts_status xdtts_griffinlim_analysis_timings(const xdtts_griffinlim *g, float ms[3]);
 
+/* Prosody: speaking rate and pitch, applied to the linear magnitude between mel -> linear and the Griffin-Lim loop (the
+ * reference names prosody among what SSML steers, src/text_normaliser.rs:41-56, and left src/td_psola.rs empty; Tacotron2 has
+ * no duration or pitch input).  With S time-major [F][n_bins] and fp32 arithmetic, output frame j of F' is
+ *   F' = F if rate == 1, else max(floor((F - 1) / rate + 0.5), 1) + 1                  (xdtts_prosody_frames)
+ *   u = min(j * rate, F - 1), i = min(floor(u), F - 2), w = u - i;  St[k] = (1 - w) S[i][k] + w S[i + 1][k]
+ *   pitch == 1:  S'[j] = St                                                             (an exact zero stays one)
+ *   else  L = ln(max(St, log_floor)); c = real cepstrum of L (1024-point transform of its even extension);
+ *         E = the transform of c with c[n] = 0 for lifter < n < 1024 - lifter           (the smooth log envelope: the formants)
+ *         R = L - E                                                                     (the log fine structure: the harmonics)
+ *         p = k / pitch;  R'[k] = (1 - a) R[floor p] + a R[floor p + 1], a = p - floor p, if p <= 512, else 0
+ *         S'[j][k] = exp(E[k] + R'[k])
+ * rate > 1 speaks faster (fewer frames), pitch > 1 speaks higher; the envelope stays where it is, so a voice keeps its vowels.
+ * The audio has hop * (F' - 1) samples.  On a magnitude that came through the mel basis the pitch change is faithful for
+ * modest factors (0.8 .. 1.25) and falls short beyond: the mel bands no longer resolve the upper harmonics.
+ * Fields: rate in [0.25, 4], pitch in [0.5, 2], lifter in [1, 255], log_floor > 0, everything finite; F >= 2 unless rate and
+ * pitch are both 1 -- anything else is XDTTS_ERR_BAD_ARG, found before a device is touched.  rate == pitch == 1 launches
+ * nothing: the results are then the bits of the entries without a prosody argument.
+ * Out of scope: the batch and sequence entries (xdtts_griffinlim_infer_batch, xdtts_synthesize_batch, xdtts_synthesize_sequence)
+ * take no prosody, and the rate is uniform over the utterance (no per-frame rate). */
+typedef struct {
+  float rate;
+  float pitch;
+  int32_t lifter;
+  float log_floor;
+} xdtts_prosody;
+void xdtts_prosody_default(xdtts_prosody *p); /* 1, 1, 30, 1e-5 */
+/* F' for F = n_frames; host arithmetic (double), no handle.  0 for a bad argument: rate not in [0.25, 4] or not finite, or
+ * n_frames < 2 with rate != 1. */
+size_t xdtts_prosody_frames(size_t n_frames, float rate);
+/* Parity hook, the prosody stage alone: S (n_bins x F, C order, as xdtts_griffinlim_mel_to_linear returns it) -> S_out
+ * (n_bins x F'), a caller buffer sized by xdtts_prosody_frames; n_frames_out may be NULL. */
+xdtts_status xdtts_griffinlim_prosody_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_prosody *p,
+                                             float *S_out, size_t *n_frames_out);
+/* xdtts_griffinlim_infer with the prosody stage between mel -> linear and the loop: audio has hop * (F' - 1) samples.
+ * xdtts_griffinlim_last_timings then reports mel -> linear AND the prosody stage as ms[0]. */
+xdtts_status xdtts_griffinlim_infer_prosody(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
+                                            const xdtts_prosody *p, float **audio, size_t *n_samples);
+
 void xdtts_griffinlim_free(xdtts_griffinlim *g);
 
 /* ---- XdTts::infer pipeline (src/lib.rs:110-159): mel-gen then vocoder with the mel kept in
@@ -349,6 +388,12 @@ xdtts_status xdtts_synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const
                                   size_t n, const size_t *splits, size_t n_splits,
                                   const xdtts_infer_opts *opts, float **mel, size_t *n_frames,
                                   float **audio, size_t *n_samples);
+/* The same with a prosody (xdtts_prosody above) between mel -> linear and the loop: *mel is Tacotron2's own mel (*n_frames =
+ * the unmodified count F), *audio the modified utterance, hop * (xdtts_prosody_frames(F, p->rate) - 1) samples. */
+xdtts_status xdtts_synthesize_ids_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids,
+                                          size_t n, const size_t *splits, size_t n_splits,
+                                          const xdtts_infer_opts *opts, const xdtts_prosody *p, float **mel,
+                                          size_t *n_frames, float **audio, size_t *n_samples);
 
 /* XdTts::infer (src/lib.rs:110-159) for n_utt utterances in one call -- the "batched / parallel
  * sentences" the author notes at src/phonemes.rs:677-680, BASELINE.json configs[3].  The chunks of

@@ -127,6 +127,23 @@ class GriffinLim {
     xdtts_free(audio);
     return out;
   }
+  // Speaking rate and pitch in the vocoder (xdtts_prosody: rate > 1 faster, pitch > 1 higher; the formants stay): infer() with the
+  // stage between mel -> linear and the loop.  The audio has 256 * (xdtts_prosody_frames(mel.cols, p.rate) - 1) samples.
+  std::vector<float> infer(const Array2 &mel, const xdtts_prosody &p) const {
+    float *audio = nullptr;
+    size_t n = 0;
+    check(xdtts_griffinlim_infer_prosody(g_, mel.data.data(), mel.rows, mel.cols, &p, &audio, &n));
+    std::vector<float> out(audio, audio + n);
+    xdtts_free(audio);
+    return out;
+  }
+  // ... and the stage alone (parity hook): S (n_bins x F) -> S' (n_bins x F')
+  Array2 prosody_linear(const Array2 &S, const xdtts_prosody &p) const {
+    const size_t Fp = xdtts_prosody_frames(S.cols, p.rate);
+    Array2 out{n_bins_, Fp, std::vector<float>(n_bins_ * (Fp ? Fp : 1))};
+    check(xdtts_griffinlim_prosody_linear(g_, S.data.data(), S.cols, &p, out.data.data(), nullptr));
+    return out;
+  }
   // The conventions of the crate's mel->linear step as switches (xdtts_griffinlim_opts)
   void set_opts(const xdtts_griffinlim_opts &o) { check(xdtts_griffinlim_set_opts(g_, &o)); }
   xdtts_griffinlim_opts opts() const {
@@ -183,6 +200,41 @@ class GriffinLim {
 inline GriffinLim create_griffin_lim(int device_id = XDTTS_DEVICE_DEFAULT) {
   const Array2 mel_basis = create_mel_filter_bank(22050.0f, 1024, 80, 0.0f, 8000.0f);
   return GriffinLim(mel_basis, 1024 - 256, 1.7f, 30, 0.99f, device_id);
+}
+
+inline xdtts_prosody default_prosody() {  // rate 1, pitch 1, lifter 30, log_floor 1e-5: the identity
+  xdtts_prosody p;
+  xdtts_prosody_default(&p);
+  return p;
+}
+
+// XdTts::infer (src/lib.rs:110-159) for one utterance with a prosody -- what an SSML <prosody rate=".." pitch=".."> element asks
+// for (src/text_normaliser.rs:41-56): units -> ids -> find_splits -> mel-gen -> vocoder with the rate / pitch stage
+// (xdtts_synthesize_ids_prosody).  Returns (Tacotron2's own mel, the modified audio).
+inline std::pair<Array2, std::vector<float>> infer_prosody(const Tacotron2 &model, const GriffinLim &vocoder, const std::vector<Unit> &units,
+                                                            const xdtts_prosody &prosody, const xdtts_infer_opts *opts = nullptr) {
+  xdtts_infer_opts o;
+  xdtts_infer_opts_default(&o);
+  if (opts) o = *opts;
+  std::vector<int64_t> ids;
+  for (const Unit &u : units) {
+    const int64_t id = xdtts_unit_id(u.token.c_str(), u.is_character ? 1 : 0);
+    if (id >= 0) ids.push_back(id);
+  }
+  std::vector<size_t> splits(ids.size() + 2);
+  size_t n_splits = 0;
+  check(xdtts_find_splits(ids.data(), ids.size(), (size_t)o.max_chunk, splits.data(), splits.size(), &n_splits));
+  float *mel = nullptr, *audio = nullptr;
+  size_t nf = 0, ns = 0;
+  check(xdtts_synthesize_ids_prosody(model.raw(), vocoder.raw(), ids.data(), ids.size(), splits.data(), n_splits, &o, &prosody, &mel, &nf, &audio, &ns));
+  std::pair<Array2, std::vector<float>> out;
+  out.first.rows = 80;
+  out.first.cols = nf;
+  out.first.data.assign(mel, mel + 80 * nf);
+  out.second.assign(audio, audio + ns);
+  xdtts_free(mel);
+  xdtts_free(audio);
+  return out;
 }
 
 // XdTts::infer (src/lib.rs:110-159) for several utterances in one call (xdtts_synthesize_batch): units -> ids

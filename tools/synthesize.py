@@ -6,6 +6,7 @@ is out of scope: the input is already a unit sequence, ARPAbe
 
   python tools/synthesize.py --model DIR      --units "HH AH0 L OW1 , W ER1 L D ." --out hello.wav
   python tools/synthesize.py --synthetic      --chars "hello world." --out noise.wav   (random weights: noise)
+  python tools/synthesize.py --model DIR      --units "HH AH0 L OW1 ." --rate 0.8 --pitch 1.15 --out slow_high.wav
 DIR holds tacotron2.xdtw (make it from the reference's ONNX files with tools/onnx_to_xdtw.py)."""
 import argparse, importlib, os, sys, time
 import numpy as np
@@ -25,6 +26,8 @@ def main():
     ap.add_argument("--mel", help="also dump the (80, F) spectrogram as .npy (src/lib.rs:128-141)")
     ap.add_argument("--iters", type=int, default=30, help="Griffin-Lim iterations (reference: 30)")
     ap.add_argument("--seed", type=int, default=0, help="dropout / initial-phase seed")
+    ap.add_argument("--rate", type=float, default=1.0, help="speaking rate, 0.25 .. 4 (> 1: faster); the vocoder resamples its frames")
+    ap.add_argument("--pitch", type=float, default=1.0, help="pitch factor, 0.5 .. 2 (> 1: higher); the formants stay where they are")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
     pkg = importlib.import_module("xd-tts_amd")
@@ -41,7 +44,8 @@ def main():
     t0 = time.perf_counter()
     mel = model.infer(ids, splits=splits, opts=opts)
     t1 = time.perf_counter()
-    audio = vocoder.infer(mel)
+    prosody = pkg.Prosody(rate=a.rate, pitch=a.pitch)
+    audio = vocoder.infer(mel) if (a.rate, a.pitch) == (1.0, 1.0) else vocoder.infer_prosody(mel, prosody)
     t2 = time.perf_counter()
     print("Mel gen time: %.3f ms (%d ids -> %d frames)" % ((t1 - t0) * 1e3, len(ids), mel.shape[1]))
     print("Vocoder time: %.3f ms (%d samples)" % ((t2 - t1) * 1e3, audio.size))

@@ -43,6 +43,20 @@ class GriffinLimOpts(C.Structure):
     _fields_ = [("nnls_iters", C.c_int32), ("power_mode", C.c_int32), ("mel_decompress", C.c_int32), ("output_normalise", C.c_int32), ("batch_shape", C.c_int32), ("rms_target", C.c_float)]
 
 
+class Prosody(C.Structure):
+    """xdtts_prosody: speaking rate and pitch, applied to the linear magnitude between mel -> linear and the Griffin-Lim loop.
+    rate in [0.25, 4] (> 1: faster), pitch in [0.5, 2] (> 1: higher), lifter in [1, 255] cepstral bins of envelope, log_floor > 0.
+    Prosody() holds the library's defaults (1, 1, 30, 1e-5), i.e. the identity; keywords override fields."""
+
+    _fields_ = [("rate", C.c_float), ("pitch", C.c_float), ("lifter", C.c_int32), ("log_floor", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib.xdtts_prosody_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
 class InferOpts(C.Structure):
     _fields_ = [
         ("gate_threshold", C.c_float),
@@ -107,8 +121,13 @@ SYMBOLS = {
     "xdtts_griffinlim_analyze_batch": (_I32, [_VP, _VP, _VP, _I32, _F, _VP, _VP, _VP]),
     "xdtts_griffinlim_spectral_convergence": (_I32, [_VP, _VP, _SZ, _VP, _SZ, _I32, C.POINTER(C.c_float * 2)]),
     "xdtts_griffinlim_analysis_timings": (_I32, [_VP, C.POINTER(C.c_float * 3)]),
+    "xdtts_prosody_default": (None, [C.POINTER(Prosody)]),
+    "xdtts_prosody_frames": (_SZ, [_SZ, _F]),
+    "xdtts_griffinlim_prosody_linear": (_I32, [_VP, _VP, _SZ, C.POINTER(Prosody), _VP, C.POINTER(_SZ)]),
+    "xdtts_griffinlim_infer_prosody": (_I32, [_VP, _VP, _SZ, _SZ, C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_griffinlim_free": (None, [_VP]),
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
+    "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_batch": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP]),
     "xdtts_synthesize_sequence": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP]),
     "xdtts_symbol_count": (_I32, []),
@@ -619,9 +638,28 @@ class GriffinLim:
         return S
 
     def last_timings(self):
+        """(after infer_prosody / synthesize(prosody=...): mel_to_linear_ms covers mel -> linear and the prosody stage)"""
         ms = (C.c_float * 3)()
         _check(lib.xdtts_griffinlim_last_timings(self._h, C.byref(ms)))
         return {"mel_to_linear_ms": ms[0], "iterations_ms": ms[1], "total_ms": ms[2]}
+
+    # -- prosody: speaking rate and pitch on the magnitude, between mel -> linear and the loop ----
+    def prosody_linear(self, S, prosody):
+        """The prosody stage alone (parity hook): S (n_bins, F) -> S' (n_bins, F'), F' = prosody_frames(F, prosody.rate)."""
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        Fp = prosody_frames(S.shape[1], prosody.rate)
+        out = np.empty((self.n_bins, max(Fp, 1)), dtype=np.float32)
+        nf = C.c_size_t()
+        _check(lib.xdtts_griffinlim_prosody_linear(self._h, _ptr(S), S.shape[1], C.byref(prosody), _ptr(out), C.byref(nf)))
+        assert nf.value == Fp
+        return out
+
+    def infer_prosody(self, mel, prosody):
+        """infer() with the prosody stage behind mel -> linear: 256 * (F' - 1) samples."""
+        mel = np.ascontiguousarray(mel, dtype=np.float32)
+        audio, n = _PF(), C.c_size_t()
+        _check(lib.xdtts_griffinlim_infer_prosody(self._h, _ptr(mel), mel.shape[0], mel.shape[1], C.byref(prosody), C.byref(audio), C.byref(n)))
+        return _take(audio, n.value, (n.value,))
 
     # -- analysis: audio -> magnitude -> mel under the handle's conventions, spectral convergence ----
     def analysis_frames(self, n_samples):
@@ -672,16 +710,23 @@ def create_griffin_lim(device_id=0, iters=30, seed=0):
     return GriffinLim(mel_basis, 1024 - 256, 1.7, iters, 0.99, device_id=device_id, seed=seed)
 
 
-def synthesize(tacotron2, vocoder, ids, splits=None, opts=None):
-    """XdTts::infer (src/lib.rs:110-159): mel-gen then vocoder, mel kept in HBM in between."""
+def prosody_frames(n_frames, rate):
+    """xdtts_prosody_frames: the frame count behind the prosody stage (host arithmetic); 0 for a bad argument."""
+    return int(lib.xdtts_prosody_frames(int(n_frames), float(rate)))
+
+
+def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None):
+    """XdTts::infer (src/lib.rs:110-159): mel-gen then vocoder, mel kept in HBM in between.  prosody= (a Prosody) changes rate
+    and pitch in the vocoder (xdtts_synthesize_ids_prosody): the mel returned is Tacotron2's own, the audio the modified one."""
     ids = np.ascontiguousarray(ids, dtype=np.int64)
     sp = None if splits is None else np.ascontiguousarray(splits, dtype=np.uintp)
     mel, nf, audio, ns = _PF(), C.c_size_t(), _PF(), C.c_size_t()
-    _check(
-        lib.xdtts_synthesize_ids(
-            tacotron2._h, vocoder._h, _ptr(ids), ids.size, None if sp is None else _ptr(sp), 0 if sp is None else sp.size, C.byref(opts) if opts else None, C.byref(mel), C.byref(nf), C.byref(audio), C.byref(ns)
-        )
-    )
+    head = (tacotron2._h, vocoder._h, _ptr(ids), ids.size, None if sp is None else _ptr(sp), 0 if sp is None else sp.size, C.byref(opts) if opts else None)
+    tail = (C.byref(mel), C.byref(nf), C.byref(audio), C.byref(ns))
+    if prosody is None:
+        _check(lib.xdtts_synthesize_ids(*head, *tail))
+    else:
+        _check(lib.xdtts_synthesize_ids_prosody(*head, C.byref(prosody), *tail))
     return _take(mel, N_MEL * nf.value, (N_MEL, nf.value)), _take(audio, ns.value, (ns.value,))
 
 

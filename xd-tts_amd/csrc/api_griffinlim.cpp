@@ -253,6 +253,60 @@ xdtts_status xdtts_griffinlim_last_timings(const xdtts_griffinlim *g, float ms[3
   });
 }
 
+// ---- prosody: rate and pitch on the magnitude between mel -> linear and the loop (prosody.hip) --------------------------------
+
+void xdtts_prosody_default(xdtts_prosody *p) {
+  if (!p) return;
+  p->rate = 1.0f;
+  p->pitch = 1.0f;
+  p->lifter = 30;  // quefrencies below 1.4 ms: under the pitch period of any voice (2.5 ms at 400 Hz), above the formant ripple
+  p->log_floor = 1e-5f;
+}
+
+size_t xdtts_prosody_frames(size_t n_frames, float rate) { return prosody_frames(n_frames, rate); }
+
+xdtts_status xdtts_griffinlim_prosody_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_prosody *p,
+                                             float *S_out, size_t *n_frames_out) {
+  return guard([&] {
+    if (n_frames_out) *n_frames_out = 0;
+    if (!g || !S || !p || !S_out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (n_frames == 0) fail(XDTTS_ERR_BAD_ARG, "need at least 1 frame");
+    prosody_check(p, n_frames);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    const int F = (int)n_frames, Fmax = std::max(F, (int)prosody_frames(n_frames, p->rate));
+    g->bufs(Fmax);
+    // boundary layout (nb x F) -> device layout [F][nb], the stage, and back: (nb x F')
+    g->frames.upload(S, (size_t)F * g->nb, g->stream);
+    launch_transpose(g->frames.p, g->S.p, g->nb, F, g->stream);
+    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+    const int Fp = g->prosody(*p, F);
+    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));  // last_timings: ms[0] = the stage alone, ms[1] = the layout change behind it
+    launch_transpose(g->prosody_S(*p), g->frames.p, Fp, g->nb, g->stream);
+    HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+    HIP_CHECK(hipMemcpyAsync(S_out, g->frames.p, (size_t)Fp * g->nb * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    g->finish_timings();  // (drains the stream)
+    if (n_frames_out) *n_frames_out = (size_t)Fp;
+  });
+}
+
+xdtts_status xdtts_griffinlim_infer_prosody(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
+                                            const xdtts_prosody *p, float **audio, size_t *n_samples) {
+  return guard([&] {
+    if (audio) *audio = nullptr;
+    if (n_samples) *n_samples = 0;
+    if (!g || !mel || !p || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
+    if (n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "need at least 2 frames, got %zu", n_frames);
+    prosody_check(p, n_frames);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    g->mel_in.upload(mel, n_mels * n_frames, g->stream);
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+    gl_run_from_device_mel_prosody(g, g->mel_in.p, (int)n_frames, *p, audio, n_samples);
+  });
+}
+
 // ---- analysis: the inverse direction of GriffinLim::infer's conventions (analysis.hip).  No co-resident grid: no chip lock. ----
 
 // What one call takes: the row tiles of the mel GEMM and of the boundary transposes go into a grid dimension of at most 65535

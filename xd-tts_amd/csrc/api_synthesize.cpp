@@ -7,13 +7,12 @@
 
 using namespace xdtts;
 
-extern "C" {
-
 // ---- XdTts::infer (src/lib.rs:110-159) --------------------------------------------------------------
 
-xdtts_status xdtts_synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
-                                  const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts, float **mel,
-                                  size_t *n_frames, float **audio, size_t *n_samples) {
+// (pros == null: xdtts_synthesize_ids; else the prosody stage between mel -> linear and the loop, checked by the caller)
+static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n, const size_t *splits,
+                                   size_t n_splits, const xdtts_infer_opts *opts, const xdtts_prosody *pros, float **mel,
+                                   size_t *n_frames, float **audio, size_t *n_samples) {
   return guard([&] {
     if (!h || !g || !mel || !n_frames || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
@@ -35,11 +34,37 @@ xdtts_status xdtts_synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const
     HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));
     HIP_CHECK(hipMemcpyAsync(mel_host.p, h->mel_dev.p, (size_t)N_MEL * total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     Drain drain(h->stream);  // the pinned buffer does not go back to the pool with the copy in flight
-    gl_run_from_device_mel(g, h->mel_dev.p, total, audio, n_samples);
+    if (pros) {
+      prosody_check(pros, (size_t)total);  // (the frame count is known only now; nothing of the vocoder has been enqueued)
+      gl_run_from_device_mel_prosody(g, h->mel_dev.p, total, *pros, audio, n_samples);
+    } else {
+      gl_run_from_device_mel(g, h->mel_dev.p, total, audio, n_samples);
+    }
     h->finish_timings();  // (stream sync: the mel has landed)
     *mel = mel_host.release();
     *n_frames = (size_t)total;
   });
+}
+
+extern "C" {
+
+xdtts_status xdtts_synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
+                                  const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts, float **mel,
+                                  size_t *n_frames, float **audio, size_t *n_samples) {
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, nullptr, mel, n_frames, audio, n_samples);
+}
+
+// ... with a prosody: the mel returned is Tacotron2's own, the audio has hop * (F' - 1) samples
+xdtts_status xdtts_synthesize_ids_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
+                                          const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts,
+                                          const xdtts_prosody *p, float **mel, size_t *n_frames, float **audio,
+                                          size_t *n_samples) {
+  xdtts_status st = guard([&] {
+    if (!p) fail(XDTTS_ERR_BAD_ARG, "null prosody");
+    prosody_check(p, 2);  // the fields, before a device is touched
+  });
+  if (st != XDTTS_OK) return st;
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, p, mel, n_frames, audio, n_samples);
 }
 
 // XdTts::infer for a SEQUENCE of utterances, one after the other as the reference runs them (src/lib.rs:110-159: each utterance

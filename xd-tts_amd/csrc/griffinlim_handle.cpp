@@ -104,6 +104,15 @@ void xdtts_griffinlim::mel_to_linear(const float *mel_dev_ptr, int F) {
   launch_gl_pow_rows(nnls_x.p, NBP, S.p, nb, F, ex, stream);
 }
 
+// The prosody stage (prosody.hip) on the S that mel -> linear (or an upload) left in place: S_pros [F'][nb].
+int xdtts_griffinlim::prosody(const xdtts_prosody &p, int F) {
+  if (prosody_is_identity(p)) return F;
+  const int Fp = (int)prosody_frames((size_t)F, p.rate);
+  S_pros.alloc((size_t)Fp * nb);
+  launch_prosody(S.p, S_pros.p, F, Fp, p.rate, p.pitch, p.lifter, p.log_floor, tw.p, stream);
+  return Fp;
+}
+
 bool xdtts_griffinlim::persistent_usable() {
   if (env::equals(env::GL, "launch")) return false;  // developer comparison aid: launch-per-iteration engine
   gate.ensure_probed([&] { return gl_persistent_supported(device, &n_cu, &per_cu4); });
@@ -409,6 +418,39 @@ void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F
   g->mel_to_linear(mel_dev_ptr, F);
   HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
   gl_iterate_and_fetch(g, b, nullptr, g->iters, audio, n_samples, true);  // GriffinLim::infer: G1..G6
+}
+
+// F' = F at rate 1, else max(floor((F - 1) / rate + 0.5), 1) + 1, in double
+size_t prosody_frames(size_t F, float rate) {
+  if (!std::isfinite(rate) || rate < 0.25f || rate > 4.0f) return 0;
+  if (rate == 1.0f) return F;
+  if (F < 2) return 0;
+  const double n = std::floor((double)(F - 1) / (double)rate + 0.5);
+  return (size_t)std::max(n, 1.0) + 1;
+}
+
+// The argument rules of xdtts_prosody for a request of n_frames frames; at most 2^20 frames go in (F' <= 2^22: the frame
+// counts of the loop behind it are ints).
+void prosody_check(const xdtts_prosody *p, size_t n_frames) {
+  if (!p) fail(XDTTS_ERR_BAD_ARG, "null prosody");
+  if (!std::isfinite(p->rate) || p->rate < 0.25f || p->rate > 4.0f) fail(XDTTS_ERR_BAD_ARG, "prosody rate %g is not in [0.25, 4]", (double)p->rate);
+  if (!std::isfinite(p->pitch) || p->pitch < 0.5f || p->pitch > 2.0f) fail(XDTTS_ERR_BAD_ARG, "prosody pitch %g is not in [0.5, 2]", (double)p->pitch);
+  if (p->lifter < 1 || p->lifter > 255) fail(XDTTS_ERR_BAD_ARG, "prosody lifter %d is not in [1, 255]", p->lifter);
+  if (!std::isfinite(p->log_floor) || !(p->log_floor > 0.f)) fail(XDTTS_ERR_BAD_ARG, "prosody log_floor %g is not a positive number", (double)p->log_floor);
+  if (n_frames > ((size_t)1 << 20)) fail(XDTTS_ERR_BAD_ARG, "prosody takes at most 2^20 frames, got %zu", n_frames);
+  if (!prosody_is_identity(*p) && n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "prosody needs at least 2 frames, got %zu", n_frames);
+}
+
+void gl_run_from_device_mel_prosody(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const xdtts_prosody &p, float **audio,
+                                    size_t *n_samples) {
+  const int Fmax = std::max(F, (int)prosody_frames((size_t)F, p.rate));
+  GlBufs b = g->bufs(Fmax);  // (before mel -> linear: growing S would drop its contents)
+  HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+  g->mel_to_linear(mel_dev_ptr, F);
+  b.F = g->prosody(p, F);
+  b.S = g->prosody_S(p);
+  HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
+  gl_iterate_and_fetch(g, b, nullptr, g->iters, audio, n_samples, true);  // (a retry on the fallback engine finds S' intact)
 }
 
 // The vocoder half of a batch from a mel that is already in HBM (on g's device): [n_mels][sum Fu], utterance u at columns

@@ -5,6 +5,13 @@
 #include "kernels.h"
 #include "runtime.h"
 
+namespace xdtts {
+// xdtts_prosody (include/xdtts.h): the argument rules, F' and the case that launches nothing.  Host arithmetic only.
+inline bool prosody_is_identity(const xdtts_prosody &p) { return p.rate == 1.0f && p.pitch == 1.0f; }
+size_t prosody_frames(size_t F, float rate);                   // 0 for a bad argument
+void prosody_check(const xdtts_prosody *p, size_t n_frames);  // fails with XDTTS_ERR_BAD_ARG and a message
+}  // namespace xdtts
+
 struct xdtts_griffinlim {
   using GlBufs = xdtts::GlBufs;
   using GlPersist = xdtts::GlPersist;
@@ -59,9 +66,16 @@ struct xdtts_griffinlim {
   xdtts::Events an_ev;
   float an_ms[3] = {0, 0, 0};
 
+  // prosody (prosody.hip): the modified magnitude [F'][nb]; S itself stays as mel -> linear left it
+  DevBuf<float> S_pros;
+
   ~xdtts_griffinlim();
   GlBufs bufs(int F);
   void mel_to_linear(const float *mel_dev_ptr, int F);
+  // S [F][nb] -> S_pros [F'][nb] in one launch on the stream; returns F'.  The identity launches nothing and returns F.
+  // The caller then points GlBufs.S at prosody_S(p) with F' frames; its bufs() was sized for max(F, F').
+  int prosody(const xdtts_prosody &p, int F);
+  float *prosody_S(const xdtts_prosody &p) { return xdtts::prosody_is_identity(p) ? S.p : S_pros.p; }
   // Once per API call (never inside a retry attempt): a demoted handle counts the call and, after PROBE_AFTER of them,
   // gives the persistent engine another try -- the cause of a timed-out exchange may have been transient.
   void probe_tick() { gate.tick(); }
@@ -88,6 +102,9 @@ void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *pha
 void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host);
 void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples);
 void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, float **audio, size_t *n_samples);
+// ... with the prosody stage between mel -> linear and the loop (p checked by the caller: prosody_check); last_ms[0] covers both
+void gl_run_from_device_mel_prosody(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const xdtts_prosody &p, float **audio,
+                                    size_t *n_samples);
 void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples);
 
 // Analysis of n_utt audios in one k_stft_mag launch: g->an_S [Ftot][nb] = |STFT|, and with want_mel g->an_melT [Ftot][n_mels] =

@@ -313,4 +313,11 @@ void launch_mel_compress(const float *melT, float *out_melsxF, int n_mels, int F
 constexpr int SPD_PARTS = 256;
 void launch_spec_distance(const float *X, const float *St, size_t n, double *parts, double *sums, hipStream_t s);
 
+// ---- prosody (prosody.hip): speaking rate and pitch on the magnitude, between mel -> linear and the loop -------------------------
+// S [F][513] -> Sout [Fout][513]: frames resampled by `rate` (linear interpolation in time), then, unless pitch == 1, each frame's
+// log fine structure (what a cepstral lifter of `lifter` bins leaves of ln max(., log_floor)) resampled by `pitch` on the frequency
+// axis under the unchanged envelope.  Fout = prosody_frames(F, rate) (griffinlim_handle.h); F >= 2 unless rate == 1.  One launch.
+void launch_prosody(const float *S, float *Sout, int F, int Fout, float rate, float pitch, int lifter, float log_floor,
+                    const float2 *tw, hipStream_t s);
+
 }  // namespace xdtts

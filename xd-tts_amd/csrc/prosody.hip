@@ -1,0 +1,136 @@
+// prosody.hip -- speaking rate and pitch as a change of the STFT magnitude between mel -> linear and the Griffin-Lim loop
+// (Griffin & Lim's algorithm estimates a signal from a MODIFIED magnitude; the loop then finds a phase for it).
+//   rate : the frames are resampled on the time axis, linear interpolation between the two neighbouring frames
+//   pitch: per frame, the log magnitude is split by a cepstral lifter into its smooth envelope (the formants) and its fine
+//          structure (the harmonics); only the fine structure is resampled on the frequency axis, the envelope stays where it is.
+// One wave per OUTPUT frame, four frames per workgroup (the shape of k_stft_mag, analysis.hip); the two transforms are the
+// one-wave 512-point FFT of gl_fft.h on a private LDS slice.  Nothing here crosses workgroups: no barrier, no exchange, no
+// polling, no atomics.
+#include "gl_fft.h"
+#include "kernels.h"
+
+namespace xdtts {
+
+namespace {
+
+constexpr int NB = NFFT / 2 + 1;  // 513 bins
+
+// DFT (1024 points) of the real EVEN sequence x[m] = e[min(m, 1024 - m)], e = the 513 floats at the start of the wave's LDS
+// slice: real and even again, so the forward transform serves for both directions (the inverse differs by 1 / 1024).
+// Packed as z[m] = x[2m] + i x[2m + 1], one fft512, Hermitian split with the handle's table tw[k] = e^{-2 pi i k / 1024}, real
+// part kept: on return X[r] = the value of bin lane + 64 r (r < 8) and X[8] = bin 512 (the same in every lane).  The slice
+// holds the transform's packed spectrum afterwards; the caller orders its next stores behind with wave_lds_sync().
+__device__ __forceinline__ void even_dft(float2 *buf, const float2 *__restrict__ tw, const Twiddles &tws, int lane, float (&X)[9]) {
+  const float *e = reinterpret_cast<const float *>(buf);
+  float2 v[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int m = 2 * (lane + 64 * r);                      // 0 .. 1022, even
+    v[r] = make_float2(e[min(m, NFFT - m)], e[min(m + 1, NFFT - 1 - m)]);  // indices 0 .. 512
+  }
+  wave_lds_sync();
+  fft512(v, buf, tws, lane);
+  wave_lds_sync();
+#pragma unroll
+  for (int r = 0; r < 8; ++r) buf[lane + 64 * r] = v[r];
+  wave_lds_sync();
+#pragma unroll
+  for (int r = 0; r <= 8; ++r) {
+    const int k = r < 8 ? lane + 64 * r : 512;
+    const float2 zk = buf[k & 511], zc = buf[(512 - k) & 511];
+    const float2 od = make_float2(0.5f * (zk.y + zc.y), 0.5f * (zc.x - zk.x));  // (Z[k] - conj Z[512-k]) / (2i)
+    const float2 twk = k == 512 ? make_float2(-1.f, 0.f) : tw[k];
+    X[r] = 0.5f * (zk.x + zc.x) + fmaf(twk.x, od.x, -twk.y * od.y);  // Re((Z[k] + conj Z[512-k]) / 2 + tw[k] od)
+  }
+}
+
+// Sout[j][k], j < Fout, from S [F][513] (F >= 2 unless rate == 1):
+//   u = min(j rate, F - 1), i = min(floor u, F - 2), w = u - i;  St[k] = (1 - w) S[i][k] + w S[i + 1][k]
+//   pitch == 1: Sout[j] = St (an exact zero stays one)
+//   else      : L = ln(max(St, log_floor)); c = real cepstrum of L; E = the transform of c with c[n] = 0 for lifter < n <
+//               1024 - lifter; R = L - E; p = k / pitch; Sout[j][k] = exp(E[k] + (p <= 512 ? lerp(R, p) : 0))
+// A wave past the last frame computes the last frame again (clamped index) and leaves before the stores.
+__global__ __launch_bounds__(64 * FRAMES_PER_BLOCK) void k_prosody(const float *__restrict__ S, float *__restrict__ Sout, int F,
+                                                                   int Fout, float rate, float pitch, int lifter, float log_floor,
+                                                                   const float2 *__restrict__ tw) {
+  __shared__ float2 lds[FRAMES_PER_BLOCK][512];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int jr = blockIdx.x * FRAMES_PER_BLOCK + wave;
+  const bool ok = jr < Fout;
+  const int j = ok ? jr : Fout - 1;
+  int i = 0;
+  float w = 0.f;
+  if (rate != 1.0f) {
+    const float u = fminf((float)j * rate, (float)(F - 1));
+    i = min((int)floorf(u), F - 2);
+    w = u - (float)i;
+  } else {
+    i = j;  // (F == Fout; the row i + 1 is not read: F may be 1)
+  }
+  const float *s0 = S + (size_t)i * NB, *s1 = rate != 1.0f ? s0 + NB : s0;
+  float *out = Sout + (size_t)j * NB;
+  float L[9];  // bins lane + 64 r, and bin 512
+#pragma unroll
+  for (int r = 0; r <= 8; ++r) {
+    const int k = r < 8 ? lane + 64 * r : 512;
+    L[r] = (1.0f - w) * s0[k] + w * s1[k];
+  }
+  if (pitch == 1.0f) {
+    if (!ok) return;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) out[lane + 64 * r] = L[r];
+    if (lane == 0) out[512] = L[8];
+    return;
+  }
+  const Twiddles tws = load_twiddles(tw, lane);
+  float2 *buf = lds[wave];
+  float *e = reinterpret_cast<float *>(buf);
+  float X[9];
+#pragma unroll
+  for (int r = 0; r <= 8; ++r) L[r] = logf(fmaxf(L[r], log_floor));
+  // cepstrum
+#pragma unroll
+  for (int r = 0; r < 8; ++r) e[lane + 64 * r] = L[r];
+  if (lane == 0) e[512] = L[8];
+  wave_lds_sync();
+  even_dft(buf, tw, tws, lane, X);
+  wave_lds_sync();
+  // liftered cepstrum -> envelope
+#pragma unroll
+  for (int r = 0; r < 8; ++r) e[lane + 64 * r] = lane + 64 * r <= lifter ? X[r] * (1.0f / NFFT) : 0.f;
+  if (lane == 0) e[512] = 0.f;  // (lifter <= 255)
+  wave_lds_sync();
+  even_dft(buf, tw, tws, lane, X);  // X = E
+  wave_lds_sync();
+  // fine structure, warped
+#pragma unroll
+  for (int r = 0; r < 8; ++r) e[lane + 64 * r] = L[r] - X[r];
+  if (lane == 0) e[512] = L[8] - X[8];
+  wave_lds_sync();
+  if (!ok) return;
+#pragma unroll
+  for (int r = 0; r <= 8; ++r) {
+    if (r == 8 && lane != 0) break;
+    const int k = r < 8 ? lane + 64 * r : 512;
+    const float p = (float)k / pitch;
+    float Rw = 0.f;
+    if (p <= 512.0f) {
+      const float fl = floorf(p);
+      const int q = (int)fl;  // 0 .. 512
+      const float a = p - fl;
+      Rw = (1.0f - a) * e[q] + a * e[min(q + 1, 512)];
+    }
+    out[k] = expf(X[r] + Rw);
+  }
+}
+
+}  // namespace
+
+void launch_prosody(const float *S, float *Sout, int F, int Fout, float rate, float pitch, int lifter, float log_floor,
+                    const float2 *tw, hipStream_t s) {
+  const int nblk = (Fout + FRAMES_PER_BLOCK - 1) / FRAMES_PER_BLOCK;
+  hipLaunchKernelGGL(k_prosody, dim3(nblk), dim3(64 * FRAMES_PER_BLOCK), 0, s, S, Sout, F, Fout, rate, pitch, lifter, log_floor, tw);
+  HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace xdtts
