@@ -565,14 +565,22 @@ __global__ __launch_bounds__(64 * W, PC) void k_gl_persistent(GlBufs g, GlPersis
     }
   }
   {
-    // a thread's samples j = tid + m nthr all sit at the same offset r of their hop (Q0 and nthr are multiples of 256): its
-    // four window values once, not per sample
+    // a thread's samples j = tid + m nthr all sit at the same offset r of their hop when nthr is a multiple of 256 (Q0 is one):
+    // its four window values once, not per sample.  Launches of 5, 6 and 7 waves (320 / 384 / 448 threads) stride across the
+    // hop: they reload the window for each sample (once per call; it matters in the first and last three hops of the
+    // utterance only, where the window sum is not the constant 1.5)
+    const bool fixed_r = W == 4 || (nthr & (HOP - 1)) == 0;
     const int r = tid & (HOP - 1);
     float w4[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) w4[k] = g.win[r + k * HOP];
     for (int j = tid; j < range; j += nthr) {
       const int jb = (Q0 + j) >> 8;
+      if (!fixed_r) {
+        const int rj = j & (HOP - 1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w4[k] = g.win[rj + k * HOP];
+      }
       float wss = 0.f;
 #pragma unroll
       for (int k = 3; k >= 0; --k) {
