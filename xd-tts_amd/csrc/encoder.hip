@@ -86,16 +86,16 @@ __global__ __launch_bounds__(1024) void k_bilstm_coop(const float *__restrict__ 
     __syncthreads();
     if (tid < NC * CO_UNITS) {
       // the four column quarters of the unit's four gate rows meet here (one barrier, no staging pass); hardware exp2 / rcp
-      // forms as in the decoder engines
+      // forms as in the decoder engines, the tanh in the form that keeps its relative accuracy at small arguments
       const int j = tid / CO_UNITS, uu = tid % CO_UNITS;
       if (j < nc) {
         float gs[4];
 #pragma unroll
         for (int gi = 0; gi < 4; ++gi) gs[gi] = (part[j][0][64 * gi + uu] + part[j][1][64 * gi + uu]) + (part[j][2][64 * gi + uu] + part[j][3][64 * gi + uu]);
         const float ig = fast_sigmoid(gs[0]), fg = fast_sigmoid(gs[1]);
-        const float gg = fast_tanh(gs[2]), og = fast_sigmoid(gs[3]);
+        const float gg = fast_tanh_rel(gs[2]), og = fast_sigmoid(gs[3]);
         c = fmaf(fg, c, ig * gg);
-        const float hn = og * fast_tanh(c);
+        const float hn = og * fast_tanh_rel(c);
         const int u = CO_UNITS * k + uu;
         h[j][u] = hn;
         memory[((size_t)(b0 + bz + j) * T + t) * EMB + dir * ENC_H + u] = hn;
