@@ -359,8 +359,10 @@ xdtts_status xdtts_griffinlim_analysis_timings(const xdtts_griffinlim *g, float 
  * Fields: rate in [0.25, 4], pitch in [0.5, 2], lifter in [1, 255], log_floor > 0, everything finite; F >= 2 unless rate and
  * pitch are both 1 -- anything else is XDTTS_ERR_BAD_ARG, found before a device is touched.  rate == pitch == 1 launches
  * nothing: the results are then the bits of the entries without a prosody argument.
- * Out of scope: the batch and sequence entries (xdtts_griffinlim_infer_batch, xdtts_synthesize_batch, xdtts_synthesize_sequence)
- * take no prosody, and the rate is uniform over the utterance (no per-frame rate). */
+ * The batch and sequence entries take one prosody PER UTTERANCE (the *_batch_prosody / *_sequence_prosody entries below): a
+ * batch runs the stage as one ragged launch behind its one mel -> linear GEMM, a sequence runs the single-utterance stage in each
+ * utterance's vocoder half.  Out of scope: a prosody per chunk inside one utterance, and a per-frame rate (the rate is uniform
+ * over the utterance). */
 typedef struct {
   float rate;
   float pitch;
@@ -379,6 +381,24 @@ xdtts_status xdtts_griffinlim_prosody_linear(xdtts_griffinlim *g, const float *S
  * xdtts_griffinlim_last_timings then reports mel -> linear AND the prosody stage as ms[0]. */
 xdtts_status xdtts_griffinlim_infer_prosody(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
                                             const xdtts_prosody *p, float **audio, size_t *n_samples);
+/* The entries that take an ARRAY of prosodies, p[n_utt], one per utterance (these two, xdtts_synthesize_batch_prosody and
+ * xdtts_synthesize_sequence_prosody): n_utt > 0, p not NULL and the fields of every element are checked before the handles are
+ * looked at -- XDTTS_ERR_BAD_ARG, the message names the field and the utterance's index; nothing is returned then (the output
+ * pointers are NULL, the counts 0).  Utterances whose prosody is the identity pass through unchanged, and a call whose
+ * prosodies are all the identity launches nothing new: the bits of the entry without the array.
+ * xdtts_griffinlim_infer_batch with the stage behind the batch's one mel -> linear GEMM, as one ragged launch over all utterances:
+ * audios[u] has hop * (xdtts_prosody_frames(n_frames[u], p[u].rate) - 1) samples and is what xdtts_griffinlim_infer_prosody returns
+ * for that utterance alone (bit for bit with opts.batch_shape = 4, as for the plain pair).  last_timings: ms[0] covers mel ->
+ * linear and the stage. */
+xdtts_status xdtts_griffinlim_infer_batch_prosody(xdtts_griffinlim *g, const float *const *mels, size_t n_mels,
+                                                  const size_t *n_frames, int32_t n_utt, const xdtts_prosody *p /* [n_utt] */,
+                                                  float **audios, size_t *n_samples);
+/* Parity hook, the ragged stage alone: S[u] (n_bins x F_u) -> S_outs[u] (n_bins x F'_u), caller buffers sized by
+ * xdtts_prosody_frames; n_frames_out (per utterance) may be NULL.  F_u >= 1, and >= 2 unless p[u] is the identity.  Every
+ * S_outs[u] equals what xdtts_griffinlim_prosody_linear gives for S[u] alone bit for bit, whatever the mix and the order. */
+xdtts_status xdtts_griffinlim_prosody_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames,
+                                                   int32_t n_utt, const xdtts_prosody *p /* [n_utt] */, float *const *S_outs,
+                                                   size_t *n_frames_out);
 
 void xdtts_griffinlim_free(xdtts_griffinlim *g);
 
@@ -411,6 +431,15 @@ xdtts_status xdtts_synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, con
                                     const xdtts_infer_opts *opts,
                                     const int32_t *fixed_steps_per_item, float **mels,
                                     size_t *n_frames, float **audios, size_t *n_samples);
+/* The same with one prosody per utterance (the array rules above xdtts_griffinlim_infer_batch_prosody): mels[u] / n_frames[u] are
+ * Tacotron2's own mel and count F_u, audios[u] has hop * (xdtts_prosody_frames(F_u, p[u].rate) - 1) samples.  Results equal
+ * xdtts_tacotron2_infer_batch followed by xdtts_griffinlim_infer_batch_prosody bit for bit. */
+xdtts_status xdtts_synthesize_batch_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids,
+                                            const int32_t *lens, int32_t B, int32_t t_stride,
+                                            const int32_t *utt_chunks, int32_t n_utt,
+                                            const xdtts_infer_opts *opts, const int32_t *fixed_steps_per_item,
+                                            const xdtts_prosody *p /* [n_utt] */, float **mels, size_t *n_frames,
+                                            float **audios, size_t *n_samples);
 
 /* XdTts::infer (src/lib.rs:110-159) for a SEQUENCE of n_utt utterances, each decoded alone (batch 1) exactly as
  * xdtts_synthesize_ids does it -- what a loop over src/lib.rs:122-141 does -- with the vocoder of utterance u overlapped with the
@@ -423,6 +452,14 @@ xdtts_status xdtts_synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, 
                                        const size_t *n_ids, const size_t *const *splits, const size_t *n_splits,
                                        int32_t n_utt, const xdtts_infer_opts *opts, float **mels,
                                        size_t *n_frames, float **audios, size_t *n_samples);
+/* The same with one prosody per utterance (the array rules above xdtts_griffinlim_infer_batch_prosody) -- a text cut at its
+ * <break>s (src/lib.rs:83-104) whose pieces carry their own <prosody>: mels[u] / n_frames[u] are Tacotron2's own, audios[u] has
+ * hop * (xdtts_prosody_frames(n_frames[u], p[u].rate) - 1) samples.  Same bits as n_utt calls of xdtts_synthesize_ids_prosody. */
+xdtts_status xdtts_synthesize_sequence_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids,
+                                               const size_t *n_ids, const size_t *const *splits, const size_t *n_splits,
+                                               int32_t n_utt, const xdtts_infer_opts *opts,
+                                               const xdtts_prosody *p /* [n_utt] */, float **mels, size_t *n_frames,
+                                               float **audios, size_t *n_samples);
 
 /* ---- host-side front of Tacotron2::infer (stays on the CPU side of the FFI) ---------------- */
 /* generate_id_list -- src/tacotron2/mod.rs:90-122: 148 symbols; token text of an id. */

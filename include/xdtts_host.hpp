@@ -144,6 +144,44 @@ class GriffinLim {
     check(xdtts_griffinlim_prosody_linear(g_, S.data.data(), S.cols, &p, out.data.data(), nullptr));
     return out;
   }
+  // infer() for several utterances in one call, one prosody per utterance (xdtts_griffinlim_infer_batch_prosody): the stage
+  // runs as one ragged launch behind the batch's mel -> linear GEMM
+  std::vector<std::vector<float>> infer_batch(const std::vector<Array2> &mels, const std::vector<xdtts_prosody> &p) const {
+    const size_t n = mels.size();
+    if (p.size() != n) throw std::runtime_error("xdtts: one prosody per utterance");
+    std::vector<const float *> mp(n);
+    std::vector<size_t> nf(n), ns(n, 0);
+    std::vector<float *> audios(n, nullptr);
+    for (size_t u = 0; u < n; ++u) {
+      mp[u] = mels[u].data.data();
+      nf[u] = mels[u].cols;
+    }
+    check(xdtts_griffinlim_infer_batch_prosody(g_, mp.data(), n ? mels[0].rows : 0, nf.data(), (int32_t)n, p.data(), audios.data(), ns.data()));
+    std::vector<std::vector<float>> out(n);
+    for (size_t u = 0; u < n; ++u) {
+      out[u].assign(audios[u], audios[u] + ns[u]);
+      xdtts_free(audios[u]);
+    }
+    return out;
+  }
+  // ... and the ragged stage alone (parity hook, xdtts_griffinlim_prosody_linear_batch)
+  std::vector<Array2> prosody_linear_batch(const std::vector<Array2> &S, const std::vector<xdtts_prosody> &p) const {
+    const size_t n = S.size();
+    if (p.size() != n) throw std::runtime_error("xdtts: one prosody per utterance");
+    std::vector<Array2> out(n);
+    std::vector<const float *> sp(n);
+    std::vector<float *> op(n);
+    std::vector<size_t> nf(n);
+    for (size_t u = 0; u < n; ++u) {
+      const size_t Fp = xdtts_prosody_frames(S[u].cols, p[u].rate);
+      out[u] = Array2{n_bins_, Fp, std::vector<float>(n_bins_ * (Fp ? Fp : 1))};
+      sp[u] = S[u].data.data();
+      op[u] = out[u].data.data();
+      nf[u] = S[u].cols;
+    }
+    check(xdtts_griffinlim_prosody_linear_batch(g_, sp.data(), nf.data(), (int32_t)n, p.data(), op.data(), nullptr));
+    return out;
+  }
   // The conventions of the crate's mel->linear step as switches (xdtts_griffinlim_opts)
   void set_opts(const xdtts_griffinlim_opts &o) { check(xdtts_griffinlim_set_opts(g_, &o)); }
   xdtts_griffinlim_opts opts() const {
@@ -240,9 +278,12 @@ inline std::pair<Array2, std::vector<float>> infer_prosody(const Tacotron2 &mode
 // XdTts::infer (src/lib.rs:110-159) for several utterances in one call (xdtts_synthesize_batch): units -> ids
 // (units with no id are dropped, mod.rs:403-406), find_splits per utterance (mod.rs:399,412-414), all chunks in one
 // lock-step batch, the mel kept in HBM between mel-gen and vocoder.  Returns (mel, audio) per utterance.
+// (prosody: null, or one per text -- xdtts_synthesize_batch_prosody: the mels stay Tacotron2's own, the audios are the modified ones)
 inline std::vector<std::pair<Array2, std::vector<float>>> infer_many(const Tacotron2 &model, const GriffinLim &vocoder,
                                                                        const std::vector<std::vector<Unit>> &texts,
-                                                                       const xdtts_infer_opts *opts = nullptr) {
+                                                                       const xdtts_infer_opts *opts = nullptr,
+                                                                       const std::vector<xdtts_prosody> *prosody = nullptr) {
+  if (prosody && prosody->size() != texts.size()) throw std::runtime_error("xdtts: one prosody per text");
   xdtts_infer_opts o;
   xdtts_infer_opts_default(&o);
   if (opts) o = *opts;
@@ -276,8 +317,12 @@ inline std::vector<std::pair<Array2, std::vector<float>>> infer_many(const Tacot
   const size_t n_utt = texts.size();
   std::vector<float *> mels(n_utt, nullptr), audios(n_utt, nullptr);
   std::vector<size_t> nf(n_utt, 0), ns(n_utt, 0);
-  check(xdtts_synthesize_batch(model.raw(), vocoder.raw(), ids.data(), lens.data(), (int32_t)lens.size(), (int32_t)T, utt_chunks.data(),
-                               (int32_t)n_utt, &o, nullptr, mels.data(), nf.data(), audios.data(), ns.data()));
+  if (prosody)
+    check(xdtts_synthesize_batch_prosody(model.raw(), vocoder.raw(), ids.data(), lens.data(), (int32_t)lens.size(), (int32_t)T, utt_chunks.data(),
+                                         (int32_t)n_utt, &o, nullptr, prosody->data(), mels.data(), nf.data(), audios.data(), ns.data()));
+  else
+    check(xdtts_synthesize_batch(model.raw(), vocoder.raw(), ids.data(), lens.data(), (int32_t)lens.size(), (int32_t)T, utt_chunks.data(),
+                                 (int32_t)n_utt, &o, nullptr, mels.data(), nf.data(), audios.data(), ns.data()));
   std::vector<std::pair<Array2, std::vector<float>>> out(n_utt);
   for (size_t i = 0; i < n_utt; ++i) {
     out[i].first.rows = 80;
@@ -292,9 +337,12 @@ inline std::vector<std::pair<Array2, std::vector<float>>> infer_many(const Tacot
 
 // XdTts::infer for a sequence of sentences, each decoded alone as the reference does (a loop over src/lib.rs:122-141), the vocoder
 // of one overlapped with the encoder of the next (xdtts_synthesize_sequence): what `app` would call for a text of several sentences.
+// (prosody: null, or one per sentence -- xdtts_synthesize_sequence_prosody: one SSML <prosody> span per element)
 inline std::vector<std::pair<Array2, std::vector<float>>> infer_sequence(const Tacotron2 &model, const GriffinLim &vocoder,
                                                                            const std::vector<std::vector<Unit>> &texts,
-                                                                           const xdtts_infer_opts *opts = nullptr) {
+                                                                           const xdtts_infer_opts *opts = nullptr,
+                                                                           const std::vector<xdtts_prosody> *prosody = nullptr) {
+  if (prosody && prosody->size() != texts.size()) throw std::runtime_error("xdtts: one prosody per sentence");
   xdtts_infer_opts o;
   xdtts_infer_opts_default(&o);
   if (opts) o = *opts;
@@ -320,8 +368,12 @@ inline std::vector<std::pair<Array2, std::vector<float>>> infer_sequence(const T
   }
   std::vector<float *> mels(n_utt, nullptr), audios(n_utt, nullptr);
   std::vector<size_t> nf(n_utt, 0), ns(n_utt, 0);
-  check(xdtts_synthesize_sequence(model.raw(), vocoder.raw(), ids_p.data(), n_ids.data(), sp_p.data(), n_sp.data(), (int32_t)n_utt, &o, mels.data(),
-                                  nf.data(), audios.data(), ns.data()));
+  if (prosody)
+    check(xdtts_synthesize_sequence_prosody(model.raw(), vocoder.raw(), ids_p.data(), n_ids.data(), sp_p.data(), n_sp.data(), (int32_t)n_utt, &o,
+                                            prosody->data(), mels.data(), nf.data(), audios.data(), ns.data()));
+  else
+    check(xdtts_synthesize_sequence(model.raw(), vocoder.raw(), ids_p.data(), n_ids.data(), sp_p.data(), n_sp.data(), (int32_t)n_utt, &o, mels.data(),
+                                    nf.data(), audios.data(), ns.data()));
   std::vector<std::pair<Array2, std::vector<float>>> out(n_utt);
   for (size_t i = 0; i < n_utt; ++i) {
     out[i].first.rows = 80;

@@ -1,6 +1,7 @@
 """The prosody stage (speaking rate and pitch in the vocoder) through the product alone: device time of
 k_prosody at F = 800 for a rate change, a pitch change and both, next to one Griffin-Lim iteration of the same run, and what the
-stage does to a synthetic voiced sound (F0 of the audio before and after, true magnitude and mel path).
+stage does to a synthetic voiced sound (F0 of the audio before and after, true magnitude and mel path); then the ragged stage
+of the batch entries: one k_prosody_batch launch for 32 utterances of F = 25 next to the same 32 as a loop of k_prosody launches.
 
   python tools/prosody_check.py                       # prints the table
   python tools/prosody_check.py > profiles/prosody.txt
@@ -50,6 +51,32 @@ def timing(voc, F):
         print("  %-24s = %.2f iterations = %.2f x k_stft_mag" % (name, us / it, us / min(an)))
 
 
+def ragged(voc, n_utt=32, F=25):
+    """One k_prosody_batch launch against n_utt k_prosody launches (XDTTS_PROSODY_BATCH=loop), same inputs, same stream, HIP
+    events around the launches alone; best of 5 each."""
+    rng = np.random.default_rng(2)
+    Ss = [np.exp(rng.uniform(-9.0, 0.0, size=(513, F))).astype(np.float32) for _ in range(n_utt)]
+    print("the ragged stage, %d utterances of F = %d (best of 5, HIP events on the handle's stream):" % (n_utt, F))
+    for name, kw in (("rate 1.25", dict(rate=1.25)), ("pitch 1.25", dict(pitch=1.25)), ("rate 1.25 + pitch 1.25", dict(rate=1.25, pitch=1.25))):
+        ps = [pkg.Prosody(**kw)] * n_utt
+        us = {}
+        for form in ("one launch", "loop"):
+            if form == "loop":
+                os.environ["XDTTS_PROSODY_BATCH"] = "loop"
+            try:
+                out = voc.prosody_linear_batch(Ss, ps)  # warm: buffers
+                best = 1e30
+                for _ in range(5):
+                    voc.prosody_linear_batch(Ss, ps)
+                    best = min(best, voc.last_timings()["mel_to_linear_ms"] * 1e3)
+            finally:
+                os.environ.pop("XDTTS_PROSODY_BATCH", None)
+            us[form] = (best, out)
+        same = all(np.array_equal(a, b) for a, b in zip(us["one launch"][1], us["loop"][1]))
+        print("  %-24s k_prosody_batch %7.1f us   %d x k_prosody %7.1f us   ratio %.2f   outputs %s" % (
+            name, us["one launch"][0], n_utt, us["loop"][0], us["loop"][0] / us["one launch"][0], "bit for bit" if same else "DIFFER"))
+
+
 def effect(voc):
     y = pr.voiced_signal(256 * 47)
     S, mel = voc.analyze(y)
@@ -74,6 +101,7 @@ def main():
     voc.set_opts(output_normalise=0)
     timing(voc, a.frames)
     effect(voc)
+    ragged(voc)
 
 
 if __name__ == "__main__":

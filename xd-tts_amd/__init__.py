@@ -125,11 +125,15 @@ SYMBOLS = {
     "xdtts_prosody_frames": (_SZ, [_SZ, _F]),
     "xdtts_griffinlim_prosody_linear": (_I32, [_VP, _VP, _SZ, C.POINTER(Prosody), _VP, C.POINTER(_SZ)]),
     "xdtts_griffinlim_infer_prosody": (_I32, [_VP, _VP, _SZ, _SZ, C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ)]),
+    "xdtts_griffinlim_infer_batch_prosody": (_I32, [_VP, _VP, _SZ, _VP, _I32, _VP, _VP, _VP]),
+    "xdtts_griffinlim_prosody_linear_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP, _VP]),
     "xdtts_griffinlim_free": (None, [_VP]),
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_batch": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP]),
     "xdtts_synthesize_sequence": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP]),
+    "xdtts_synthesize_batch_prosody": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "xdtts_synthesize_sequence_prosody": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP]),
     "xdtts_symbol_count": (_I32, []),
     "xdtts_symbol_token": (C.c_char_p, [_I32]),
     "xdtts_unit_id": (C.c_int64, [C.c_char_p, _I32]),
@@ -201,6 +205,14 @@ def _check(status):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _prosody_array(prosody, n):
+    """A list of n Prosody -> the C array xdtts_prosody[n] the batch and sequence entries take."""
+    ps = list(prosody)
+    if len(ps) != n:
+        raise ValueError("prosody= takes one Prosody per utterance: %d for %d utterances" % (len(ps), n))
+    return (Prosody * n)(*ps)
 
 
 def default_opts(**kw):
@@ -604,15 +616,20 @@ class GriffinLim:
         _check(lib.xdtts_griffinlim_infer(self._h, _ptr(mel), mel.shape[0], mel.shape[1], C.byref(audio), C.byref(n)))
         return _take(audio, n.value, (n.value,))
 
-    def infer_batch(self, mels):
-        """GriffinLim::infer for a list of (80, F_u) mels in one call; returns the list of audios."""
+    def infer_batch(self, mels, prosody=None):
+        """GriffinLim::infer for a list of (80, F_u) mels in one call; returns the list of audios.  prosody= (a list of one
+        Prosody per utterance) runs the rate / pitch stage as one ragged launch behind the batch's mel -> linear
+        (xdtts_griffinlim_infer_batch_prosody): audio u has 256 * (prosody_frames(F_u, rate_u) - 1) samples."""
         ms = [np.ascontiguousarray(m, dtype=np.float32) for m in mels]
         n = len(ms)
         ptrs = (C.c_void_p * n)(*[m.ctypes.data for m in ms])
         nf = (C.c_size_t * n)(*[m.shape[1] for m in ms])
         audios = (_PF * n)()
         ns = (C.c_size_t * n)()
-        _check(lib.xdtts_griffinlim_infer_batch(self._h, ptrs, ms[0].shape[0], nf, n, audios, ns))
+        if prosody is None:
+            _check(lib.xdtts_griffinlim_infer_batch(self._h, ptrs, ms[0].shape[0], nf, n, audios, ns))
+        else:
+            _check(lib.xdtts_griffinlim_infer_batch_prosody(self._h, ptrs, ms[0].shape[0], nf, n, _prosody_array(prosody, n), audios, ns))
         return [_take(audios[u], ns[u], (ns[u],)) for u in range(n)]
 
     def infer_linear(self, S, phase0=None, iters=0):
@@ -653,6 +670,22 @@ class GriffinLim:
         _check(lib.xdtts_griffinlim_prosody_linear(self._h, _ptr(S), S.shape[1], C.byref(prosody), _ptr(out), C.byref(nf)))
         assert nf.value == Fp
         return out
+
+    def prosody_linear_batch(self, S_list, prosody_list):
+        """The ragged stage alone (parity hook): a list of S_u (n_bins, F_u) and one Prosody each -> the list of S'_u
+        (n_bins, F'_u), one k_prosody_batch launch for all of them."""
+        Ss = [np.ascontiguousarray(S, dtype=np.float32) for S in S_list]
+        n = len(Ss)
+        pa = _prosody_array(prosody_list, n)
+        Fp = [prosody_frames(S.shape[1], p.rate) for S, p in zip(Ss, pa)]
+        outs = [np.empty((self.n_bins, max(f, 1)), dtype=np.float32) for f in Fp]
+        sp = (C.c_void_p * n)(*[S.ctypes.data for S in Ss])
+        op = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        nf = (C.c_size_t * n)(*[S.shape[1] for S in Ss])
+        nfo = (C.c_size_t * n)()
+        _check(lib.xdtts_griffinlim_prosody_linear_batch(self._h, sp, nf, n, pa, op, nfo))
+        assert list(nfo) == Fp
+        return outs
 
     def infer_prosody(self, mel, prosody):
         """infer() with the prosody stage behind mel -> linear: 256 * (F' - 1) samples."""
@@ -730,12 +763,13 @@ def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None):
     return _take(mel, N_MEL * nf.value, (N_MEL, nf.value)), _take(audio, ns.value, (ns.value,))
 
 
-def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_steps=None, want_mels=True):
+def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_steps=None, want_mels=True, prosody=None):
     """XdTts::infer (src/lib.rs:110-159) for several utterances in one call: `utterance_chunks[u]` is the
     list of <=window-id chunks of utterance u (find_splits + the trailing split, mod.rs:399,412-414);
     `fixed_steps`, if given, holds one frame count per chunk in the same nested shape.  All chunks decode
     in one lock-step batch and the vocoder batch reads the concatenated mel in HBM.  Returns
-    (mels or None, audios), one entry per utterance."""
+    (mels or None, audios), one entry per utterance.  prosody= (a list of one Prosody per utterance): the mels stay Tacotron2's
+    own, the audios go through the rate / pitch stage (xdtts_synthesize_batch_prosody)."""
     chunks = [c for u in utterance_chunks for c in u]
     B, n_utt = len(chunks), len(utterance_chunks)
     lens = np.array([len(x) for x in chunks], dtype=np.int32)
@@ -748,18 +782,19 @@ def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_step
     mels = (_PF * n_utt)() if want_mels else None
     audios = (_PF * n_utt)()
     nf, ns = (C.c_size_t * n_utt)(), (C.c_size_t * n_utt)()
-    _check(
-        lib.xdtts_synthesize_batch(
-            tacotron2._h, vocoder._h, _ptr(ids), _ptr(lens), B, stride, _ptr(uc), n_utt, C.byref(opts) if opts else None, None if fs is None else _ptr(fs), mels, nf, audios, ns
-        )
-    )
+    head = (tacotron2._h, vocoder._h, _ptr(ids), _ptr(lens), B, stride, _ptr(uc), n_utt, C.byref(opts) if opts else None, None if fs is None else _ptr(fs))
+    if prosody is None:
+        _check(lib.xdtts_synthesize_batch(*head, mels, nf, audios, ns))
+    else:
+        _check(lib.xdtts_synthesize_batch_prosody(*head, _prosody_array(prosody, n_utt), mels, nf, audios, ns))
     out_m = [_take(mels[u], N_MEL * nf[u], (N_MEL, nf[u])) for u in range(n_utt)] if want_mels else None
     return out_m, [_take(audios[u], ns[u], (ns[u],)) for u in range(n_utt)]
 
 
-def synthesize_sequence(tacotron2, vocoder, ids_list, splits_list=None, opts=None, want_mels=True):
+def synthesize_sequence(tacotron2, vocoder, ids_list, splits_list=None, opts=None, want_mels=True, prosody=None):
     """XdTts::infer (src/lib.rs:110-159) for a sequence of utterances, each decoded alone as `synthesize` does, the vocoder of one
-    overlapped with the encoder of the next (xdtts_synthesize_sequence).  Returns (mels or None, audios)."""
+    overlapped with the encoder of the next (xdtts_synthesize_sequence).  Returns (mels or None, audios).  prosody= (a list of
+    one Prosody per utterance): what `synthesize(ids_u, prosody=prosody[u])` returns for each (xdtts_synthesize_sequence_prosody)."""
     n = len(ids_list)
     idv = [np.ascontiguousarray(x, dtype=np.int64) for x in ids_list]
     spv = [None if (splits_list is None or splits_list[u] is None) else np.ascontiguousarray(splits_list[u], dtype=np.uintp) for u in range(n)]
@@ -770,6 +805,10 @@ def synthesize_sequence(tacotron2, vocoder, ids_list, splits_list=None, opts=Non
     mels = (_PF * n)() if want_mels else None
     audios = (_PF * n)()
     nf, ns = (C.c_size_t * n)(), (C.c_size_t * n)()
-    _check(lib.xdtts_synthesize_sequence(tacotron2._h, vocoder._h, ids_p, n_ids, sp_p, n_sp, n, C.byref(opts) if opts else None, mels, nf, audios, ns))
+    head = (tacotron2._h, vocoder._h, ids_p, n_ids, sp_p, n_sp, n, C.byref(opts) if opts else None)
+    if prosody is None:
+        _check(lib.xdtts_synthesize_sequence(*head, mels, nf, audios, ns))
+    else:
+        _check(lib.xdtts_synthesize_sequence_prosody(*head, _prosody_array(prosody, n), mels, nf, audios, ns))
     out_m = [_take(mels[u], N_MEL * nf[u], (N_MEL, nf[u])) for u in range(n)] if want_mels else None
     return out_m, [_take(audios[u], ns[u], (ns[u],)) for u in range(n)]

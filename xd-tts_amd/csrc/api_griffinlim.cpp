@@ -3,9 +3,45 @@
 #include <cmath>
 #include <memory>
 
+#include "env.h"
 #include "griffinlim_handle.h"
 
 using namespace xdtts;
+
+// GriffinLim::infer for several utterances at once (the vocoder half of a batch, BASELINE.json configs[3]):
+// the utterances' frames are concatenated, mel -> linear is one GEMM over all of them, and the persistent
+// kernel takes as many utterances per launch as fit one workgroup per CU.  Every utterance's audio is bit-identical to what
+// xdtts_griffinlim_infer returns for it alone.  (pros == null: xdtts_griffinlim_infer_batch; else one prosody per utterance,
+// its fields checked by the caller)
+static xdtts_status infer_batch(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames, int32_t n_utt,
+                                const xdtts_prosody *pros, float **audios, size_t *n_samples) {
+  return guard([&] {
+    if (!g || !mels || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "bad argument");
+    if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
+    std::vector<int> fbase(n_utt), Fu(n_utt);
+    size_t Ftot = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      audios[u] = nullptr;
+      n_samples[u] = 0;
+      if (!mels[u] || n_frames[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 2 frames", u);
+      if (pros) prosody_check_at(&pros[u], u, n_frames[u]);
+      fbase[u] = (int)Ftot;
+      Fu[u] = (int)n_frames[u];
+      Ftot += n_frames[u];
+      if (Ftot > (1u << 24)) fail(XDTTS_ERR_BAD_ARG, "batch too large");
+    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    // mel of all utterances side by side: [n_mels][Ftot], staged in pinned memory (one fast upload)
+    PinnedGuard mel_all((size_t)n_mels * Ftot);
+    for (int u = 0; u < n_utt; ++u)
+      for (size_t m = 0; m < n_mels; ++m)
+        std::memcpy(mel_all.p + m * Ftot + fbase[u], mels[u] + m * n_frames[u], sizeof(float) * n_frames[u]);
+    g->mel_in.upload(mel_all.p, (size_t)n_mels * Ftot, g->stream);
+    HIP_CHECK(hipStreamSynchronize(g->stream));  // the staging buffer goes back to the pool
+    gl_batch_from_device(g, g->mel_in.p, Fu, audios, n_samples, pros);
+  });
+}
 
 extern "C" {
 
@@ -125,37 +161,9 @@ xdtts_status xdtts_griffinlim_infer(xdtts_griffinlim *g, const float *mel, size_
   });
 }
 
-// GriffinLim::infer for several utterances at once (the vocoder half of a batch, BASELINE.json configs[3]):
-// the utterances' frames are concatenated, mel -> linear is one GEMM over all of them, and the persistent
-// kernel takes as many utterances per launch as fit one workgroup per CU.  Every utterance's audio is bit-identical to what
-// xdtts_griffinlim_infer returns for it alone.
 xdtts_status xdtts_griffinlim_infer_batch(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames,
                                           int32_t n_utt, float **audios, size_t *n_samples) {
-  return guard([&] {
-    if (!g || !mels || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "bad argument");
-    if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
-    std::vector<int> fbase(n_utt), Fu(n_utt);
-    size_t Ftot = 0;
-    for (int u = 0; u < n_utt; ++u) {
-      audios[u] = nullptr;
-      n_samples[u] = 0;
-      if (!mels[u] || n_frames[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 2 frames", u);
-      fbase[u] = (int)Ftot;
-      Fu[u] = (int)n_frames[u];
-      Ftot += n_frames[u];
-      if (Ftot > (1u << 24)) fail(XDTTS_ERR_BAD_ARG, "batch too large");
-    }
-    std::lock_guard<std::mutex> lk(g->mu);
-    HIP_CHECK(hipSetDevice(g->device));
-    // mel of all utterances side by side: [n_mels][Ftot], staged in pinned memory (one fast upload)
-    PinnedGuard mel_all((size_t)n_mels * Ftot);
-    for (int u = 0; u < n_utt; ++u)
-      for (size_t m = 0; m < n_mels; ++m)
-        std::memcpy(mel_all.p + m * Ftot + fbase[u], mels[u] + m * n_frames[u], sizeof(float) * n_frames[u]);
-    g->mel_in.upload(mel_all.p, (size_t)n_mels * Ftot, g->stream);
-    HIP_CHECK(hipStreamSynchronize(g->stream));  // the staging buffer goes back to the pool
-    gl_batch_from_device(g, g->mel_in.p, Fu, audios, n_samples);
-  });
+  return infer_batch(g, mels, n_mels, n_frames, n_utt, nullptr, audios, n_samples);
 }
 
 xdtts_status xdtts_griffinlim_mel_to_linear(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
@@ -304,6 +312,71 @@ xdtts_status xdtts_griffinlim_infer_prosody(xdtts_griffinlim *g, const float *me
     g->mel_in.upload(mel, n_mels * n_frames, g->stream);
     HIP_CHECK(hipStreamSynchronize(g->stream));
     gl_run_from_device_mel_prosody(g, g->mel_in.p, (int)n_frames, *p, audio, n_samples);
+  });
+}
+
+// ... for a batch, one prosody per utterance: audios[u] has hop * (F'_u - 1) samples.  The prosody array is checked first, so
+// that a bad field is reported without a handle.
+xdtts_status xdtts_griffinlim_infer_batch_prosody(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames,
+                                                  int32_t n_utt, const xdtts_prosody *p, float **audios, size_t *n_samples) {
+  xdtts_status st = guard([&] {
+    for (int u = 0; u < n_utt; ++u) {
+      if (audios) audios[u] = nullptr;
+      if (n_samples) n_samples[u] = 0;
+    }
+    prosody_check_array(p, n_utt);
+  });
+  if (st != XDTTS_OK) return st;
+  return infer_batch(g, mels, n_mels, n_frames, n_utt, p, audios, n_samples);
+}
+
+// Parity hook of the ragged stage alone: the utterances' magnitudes one behind the other on the device, one k_prosody_batch
+// launch, and back.  last_timings as after xdtts_griffinlim_prosody_linear: ms[0] = the stage alone.
+xdtts_status xdtts_griffinlim_prosody_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
+                                                   const xdtts_prosody *p, float *const *S_outs, size_t *n_frames_out) {
+  return guard([&] {
+    for (int u = 0; n_frames_out && u < n_utt; ++u) n_frames_out[u] = 0;
+    prosody_check_array(p, n_utt);
+    if (!g || !S || !n_frames || !S_outs) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::vector<ProsodyUtt> tab((size_t)n_utt);
+    size_t Fin = 0, Fout = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      if (!S[u] || !S_outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
+      if (n_frames[u] == 0) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 1 frame", u);
+      prosody_check_at(&p[u], u, n_frames[u]);
+      const size_t Fp = prosody_frames(n_frames[u], p[u].rate);
+      tab[(size_t)u] = {(int)Fin, (int)n_frames[u], (int)Fout, (int)Fp, p[u].rate, p[u].pitch, p[u].lifter, p[u].log_floor};
+      Fin += n_frames[u];
+      Fout += Fp;
+      if (Fin > (1u << 24) || Fout > (1u << 24)) fail(XDTTS_ERR_BAD_ARG, "batch too large");
+    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    const size_t nb = (size_t)g->nb;
+    g->bufs((int)std::max(Fin, Fout));  // (frames: the boundary-layout staging of both directions)
+    g->S_pros.alloc(Fout * nb);
+    g->pros_tab.upload(tab.data(), tab.size(), g->stream);
+    for (int u = 0; u < n_utt; ++u) {  // boundary layout (nb x F_u) -> rows src0 .. of the device layout [F][nb]
+      const ProsodyUtt &t = tab[(size_t)u];
+      HIP_CHECK(hipMemcpyAsync(g->frames.p + (size_t)t.src0 * nb, S[u], (size_t)t.F * nb * sizeof(float), hipMemcpyHostToDevice, g->stream));
+      launch_transpose(g->frames.p + (size_t)t.src0 * nb, g->S.p + (size_t)t.src0 * nb, g->nb, t.F, g->stream);
+    }
+    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+    if (env::equals(env::PROSODY_BATCH, "loop")) {  // developer comparison aid (tools/prosody_check.py): one k_prosody launch per utterance
+      for (const ProsodyUtt &t : tab)
+        launch_prosody(g->S.p + (size_t)t.src0 * nb, g->S_pros.p + (size_t)t.dst0 * nb, t.F, t.Fout, t.rate, t.pitch, t.lifter, t.log_floor, g->tw.p, g->stream);
+    } else {
+      launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)Fout, g->tw.p, g->stream);
+    }
+    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
+    for (const ProsodyUtt &t : tab) launch_transpose(g->S_pros.p + (size_t)t.dst0 * nb, g->frames.p + (size_t)t.dst0 * nb, t.Fout, g->nb, g->stream);
+    HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+    for (int u = 0; u < n_utt; ++u) {
+      const ProsodyUtt &t = tab[(size_t)u];
+      HIP_CHECK(hipMemcpyAsync(S_outs[u], g->frames.p + (size_t)t.dst0 * nb, (size_t)t.Fout * nb * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    }
+    g->finish_timings();  // (drains the stream: the table and the outputs)
+    for (int u = 0; n_frames_out && u < n_utt; ++u) n_frames_out[u] = (size_t)tab[(size_t)u].Fout;
   });
 }
 

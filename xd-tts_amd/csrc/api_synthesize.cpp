@@ -46,25 +46,18 @@ static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, cons
   });
 }
 
-extern "C" {
-
-xdtts_status xdtts_synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
-                                  const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts, float **mel,
-                                  size_t *n_frames, float **audio, size_t *n_samples) {
-  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, nullptr, mel, n_frames, audio, n_samples);
-}
-
-// ... with a prosody: the mel returned is Tacotron2's own, the audio has hop * (F' - 1) samples
-xdtts_status xdtts_synthesize_ids_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
-                                          const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts,
-                                          const xdtts_prosody *p, float **mel, size_t *n_frames, float **audio,
-                                          size_t *n_samples) {
-  xdtts_status st = guard([&] {
-    if (!p) fail(XDTTS_ERR_BAD_ARG, "null prosody");
-    prosody_check(p, 2);  // the fields, before a device is touched
+// The prosody array of the batch and sequence entries, before a handle is looked at; the outputs are cleared first, so that a
+// rejected call returns nothing.
+static xdtts_status check_prosody_array(const xdtts_prosody *p, int32_t n_utt, float **mels, size_t *n_frames, float **audios, size_t *n_samples) {
+  return guard([&] {
+    for (int u = 0; u < n_utt; ++u) {
+      if (mels) mels[u] = nullptr;
+      if (audios) audios[u] = nullptr;
+      if (n_frames) n_frames[u] = 0;
+      if (n_samples) n_samples[u] = 0;
+    }
+    prosody_check_array(p, n_utt);
   });
-  if (st != XDTTS_OK) return st;
-  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, p, mel, n_frames, audio, n_samples);
 }
 
 // XdTts::infer for a SEQUENCE of utterances, one after the other as the reference runs them (src/lib.rs:110-159: each utterance
@@ -73,9 +66,11 @@ xdtts_status xdtts_synthesize_ids_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *
 // stream) with utterance u + 1's ENCODER (embedding, three convolutions, BiLSTM on 16 CUs, memory layer).  The frame loop of
 // u + 1 is ordered behind the vocoder of u by an event (two grids that each want the chip co-resident never meet), and the host
 // collects u's audio while u + 1 decodes.  Same bits as xdtts_synthesize_ids called once per utterance.
-xdtts_status xdtts_synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
-                                       const size_t *const *splits, const size_t *n_splits, int32_t n_utt, const xdtts_infer_opts *opts,
-                                       float **mels, size_t *n_frames, float **audios, size_t *n_samples) {
+// (pros == null: xdtts_synthesize_sequence; else one prosody per utterance, fields checked by the caller: utterance u's vocoder
+// half runs the single-utterance stage, the bits of xdtts_synthesize_ids_prosody)
+static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
+                                        const size_t *const *splits, const size_t *n_splits, int32_t n_utt, const xdtts_infer_opts *opts,
+                                        const xdtts_prosody *pros, float **mels, size_t *n_frames, float **audios, size_t *n_samples) {
   return guard([&] {
     if (!h || !g || !ids || !n_ids || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "null argument / no utterance");
     if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
@@ -137,7 +132,8 @@ xdtts_status xdtts_synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, 
         if (predicted >= 2)
           h->while_decoding = [&, u, predicted] {
             if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * predicted);
-            if (!audio_host[u].p) audio_host[u] = PinnedGuard((size_t)g->hop * (size_t)(predicted - 1));
+            const size_t Fp = pros ? prosody_frames((size_t)predicted, pros[u].rate) : (size_t)predicted;  // the vocoder's frames, not the mel's
+            if (!audio_host[u].p) audio_host[u] = PinnedGuard((size_t)g->hop * (Fp - 1));
           };
         for (int i = 0; i < 4; ++i) std::swap(h->ev.e[i], per[u].e[i]);  // (per[u] now holds what the handle had: utterance u - 1's set, or its own)
         h->infer_batch_device(padded.data(), lens.data(), (int)lens.size(), o.max_chunk, o, nullptr, &total[u]);
@@ -146,17 +142,18 @@ xdtts_status xdtts_synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, 
         if (predicted != total[u]) mel_host[u] = PinnedGuard(), audio_host[u] = PinnedGuard();  // (the stop rule decided otherwise: sized below)
         steps_sum += h->last_steps;
         if (total[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: mel has %d frame(s); the vocoder needs at least 2", u, total[u]);
+        if (pros) prosody_check_at(&pros[u], u, (size_t)total[u]);  // (the frame count is known only now)
         // the frame loop of u has drained, and it waited for the vocoder of u - 1: collect that audio now
         if (u > 0) {
-          gl_collect(g, total[u - 1], audio_host[u - 1], &audio_out[u - 1], &n_samples[u - 1]);
+          gl_collect(g, total[u - 1], audio_host[u - 1], &audio_out[u - 1], &n_samples[u - 1], pros ? &pros[u - 1] : nullptr);
           add_gl();
         }
         if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * total[u]);
         HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));  // the vocoder reads the mel behind the post-net
         HIP_CHECK(hipMemcpyAsync(mel_host[u].p, h->mel_dev.p, (size_t)N_MEL * total[u] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        gl_enqueue_from_device_mel(g, h->mel_dev.p, total[u], audio_host[u]);
+        gl_enqueue_from_device_mel(g, h->mel_dev.p, total[u], audio_host[u], pros ? &pros[u] : nullptr);
       }
-      gl_collect(g, total[n_utt - 1], audio_host[n_utt - 1], &audio_out[n_utt - 1], &n_samples[n_utt - 1]);
+      gl_collect(g, total[n_utt - 1], audio_host[n_utt - 1], &audio_out[n_utt - 1], &n_samples[n_utt - 1], pros ? &pros[n_utt - 1] : nullptr);
       add_gl();
       h->finish_timings();  // (stream sync: every mel has landed; last_ms = the last utterance's phases)
       float hsum[4] = {h->last_ms[0], h->last_ms[1], h->last_ms[2], h->last_ms[3]};
@@ -191,10 +188,11 @@ xdtts_status xdtts_synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, 
 // src/tacotron2/mod.rs:422-434), the post-net writes every utterance's chunks side by side on the time axis
 // (mod.rs:430), and the vocoder batch reads that mel where it lies in HBM -- no copy to the host and back, no
 // re-staging between the two halves.  The per-utterance mels leave for the host while the vocoder runs.
-xdtts_status xdtts_synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
-                                    int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
-                                    const int32_t *fixed_steps_per_item, float **mels, size_t *n_frames, float **audios,
-                                    size_t *n_samples) {
+// (pros == null: xdtts_synthesize_batch; else one prosody per utterance, fields checked by the caller)
+static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
+                                     int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
+                                     const int32_t *fixed_steps_per_item, const xdtts_prosody *pros, float **mels, size_t *n_frames,
+                                     float **audios, size_t *n_samples) {
   return guard([&] {
     if (!h || !g || !ids || !lens || !utt_chunks || !n_frames || !audios || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
@@ -221,6 +219,7 @@ xdtts_status xdtts_synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, con
       for (int k = 0; k < utt_chunks[u]; ++k) Fu[u] += F[b++];
       off += Fu[u];
       if (Fu[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d has %d mel frame(s); the vocoder needs at least 2", u, Fu[u]);
+      if (pros) prosody_check_at(&pros[u], u, (size_t)Fu[u]);  // (nothing of the vocoder has been enqueued)
     }
     // the vocoder stream reads the mel behind the post-net (event 3 of infer_batch_device); the host copies of the
     // mel follow on the mel-gen stream and overlap the vocoder
@@ -235,7 +234,7 @@ xdtts_status xdtts_synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, con
                                    sizeof(float) * (size_t)Fu[u], N_MEL, hipMemcpyDeviceToHost, h->stream));
       }
     }
-    gl_batch_from_device(g, h->mel_dev.p, Fu, audios, n_samples);
+    gl_batch_from_device(g, h->mel_dev.p, Fu, audios, n_samples, pros);
     try {
       h->finish_timings();  // (stream sync: the mel copies have landed)
     } catch (...) {  // the caller gets either every buffer of the call or none
@@ -251,6 +250,61 @@ xdtts_status xdtts_synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, con
       if (mels) mels[u] = mel_out[(size_t)u].release();
     }
   });
+}
+
+extern "C" {
+
+xdtts_status xdtts_synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
+                                  const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts, float **mel,
+                                  size_t *n_frames, float **audio, size_t *n_samples) {
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, nullptr, mel, n_frames, audio, n_samples);
+}
+
+// ... with a prosody: the mel returned is Tacotron2's own, the audio has hop * (F' - 1) samples
+xdtts_status xdtts_synthesize_ids_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
+                                          const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts,
+                                          const xdtts_prosody *p, float **mel, size_t *n_frames, float **audio,
+                                          size_t *n_samples) {
+  xdtts_status st = guard([&] {
+    if (!p) fail(XDTTS_ERR_BAD_ARG, "null prosody");
+    prosody_check(p, 2);  // the fields, before a device is touched
+  });
+  if (st != XDTTS_OK) return st;
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, p, mel, n_frames, audio, n_samples);
+}
+
+xdtts_status xdtts_synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
+                                       const size_t *const *splits, const size_t *n_splits, int32_t n_utt, const xdtts_infer_opts *opts,
+                                       float **mels, size_t *n_frames, float **audios, size_t *n_samples) {
+  return synthesize_sequence(h, g, ids, n_ids, splits, n_splits, n_utt, opts, nullptr, mels, n_frames, audios, n_samples);
+}
+
+// ... one prosody per utterance (what a text cut at its <break>s into pieces with their own <prosody> asks for): mels[u] is
+// Tacotron2's own, audios[u] has hop * (xdtts_prosody_frames(n_frames[u], p[u].rate) - 1) samples
+xdtts_status xdtts_synthesize_sequence_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
+                                               const size_t *const *splits, const size_t *n_splits, int32_t n_utt,
+                                               const xdtts_infer_opts *opts, const xdtts_prosody *p, float **mels, size_t *n_frames,
+                                               float **audios, size_t *n_samples) {
+  const xdtts_status st = check_prosody_array(p, n_utt, mels, n_frames, audios, n_samples);
+  if (st != XDTTS_OK) return st;
+  return synthesize_sequence(h, g, ids, n_ids, splits, n_splits, n_utt, opts, p, mels, n_frames, audios, n_samples);
+}
+
+xdtts_status xdtts_synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
+                                    int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
+                                    const int32_t *fixed_steps_per_item, float **mels, size_t *n_frames, float **audios,
+                                    size_t *n_samples) {
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, nullptr, mels, n_frames, audios, n_samples);
+}
+
+// ... one prosody per utterance: the ragged stage behind the batch's one mel -> linear GEMM
+xdtts_status xdtts_synthesize_batch_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
+                                            int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
+                                            const int32_t *fixed_steps_per_item, const xdtts_prosody *p, float **mels, size_t *n_frames,
+                                            float **audios, size_t *n_samples) {
+  const xdtts_status st = check_prosody_array(p, n_utt, mels, n_frames, audios, n_samples);
+  if (st != XDTTS_OK) return st;
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, p, mels, n_frames, audios, n_samples);
 }
 
 }  // extern "C"

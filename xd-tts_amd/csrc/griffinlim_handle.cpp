@@ -387,11 +387,19 @@ void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *pha
 // The two halves of gl_run_from_device_mel for a caller that overlaps the vocoder with other work (xdtts_synthesize_sequence):
 // everything enqueued on g->stream, nothing waited for; then the wait, the engine's error word and -- after a timed-out
 // exchange -- the request again on the fallback engine (S is intact until the next enqueue).  Caller holds g->mu and the chip lock.
-void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host) {
-  GlBufs b = g->bufs(F);
-  const size_t N = (size_t)g->hop * (size_t)(F - 1);
+// (p: null, or a prosody the caller has checked against F -- the stage then sits between mel -> linear and the loop, which
+// runs on S' with F' frames; gl_collect takes the same p)
+void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const xdtts_prosody *p) {
+  const int Fp = p ? (int)prosody_frames((size_t)F, p->rate) : F;
+  GlBufs b = g->bufs(std::max(F, Fp));  // (before mel -> linear: growing S would drop its contents)
+  b.F = Fp;
+  const size_t N = (size_t)g->hop * (size_t)(Fp - 1);
   HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
   g->mel_to_linear(mel_dev_ptr, F);
+  if (p) {
+    g->prosody(*p, F);
+    b.S = g->prosody_S(*p);
+  }
   HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
   g->probe_tick();
   g->iterate(b, nullptr, g->iters);
@@ -401,15 +409,19 @@ void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, i
   HIP_CHECK(hipMemcpyAsync(host.p, g->audio.p, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
   g->fetch_error_word();
 }
-void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples) {
+void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const xdtts_prosody *p) {
+  const int Fp = p ? (int)prosody_frames((size_t)F, p->rate) : F;
   g->finish_timings();  // (drains the stream)
   if (g->persistent_failed()) {
     host = PinnedGuard();
-    gl_iterate_and_fetch(g, g->bufs(F), nullptr, g->iters, audio, n_samples, true);
+    GlBufs b = g->bufs(std::max(F, Fp));  // (the size of the enqueue: nothing is reallocated, S and S' are intact)
+    b.F = Fp;
+    if (p) b.S = g->prosody_S(*p);
+    gl_iterate_and_fetch(g, b, nullptr, g->iters, audio, n_samples, true);
     return;
   }
   *audio = host.release();
-  *n_samples = (size_t)g->hop * (size_t)(F - 1);
+  *n_samples = (size_t)g->hop * (size_t)(Fp - 1);
 }
 
 void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, float **audio, size_t *n_samples) {
@@ -441,6 +453,20 @@ void prosody_check(const xdtts_prosody *p, size_t n_frames) {
   if (!prosody_is_identity(*p) && n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "prosody needs at least 2 frames, got %zu", n_frames);
 }
 
+void prosody_check_at(const xdtts_prosody *p, int u, size_t n_frames) {
+  try {
+    prosody_check(p, n_frames);
+  } catch (const Error &e) {
+    fail(e.code, "utterance %d: %s", u, e.what());
+  }
+}
+
+void prosody_check_array(const xdtts_prosody *p, int n_utt) {
+  if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+  if (!p) fail(XDTTS_ERR_BAD_ARG, "null prosody array");
+  for (int u = 0; u < n_utt; ++u) prosody_check_at(&p[u], u, 2);
+}
+
 void gl_run_from_device_mel_prosody(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const xdtts_prosody &p, float **audio,
                                     size_t *n_samples) {
   const int Fmax = std::max(F, (int)prosody_frames((size_t)F, p.rate));
@@ -458,12 +484,27 @@ void gl_run_from_device_mel_prosody(xdtts_griffinlim *g, const float *mel_dev_pt
 // utterances per launch as fit one workgroup per CU (a workgroup never spans two utterances and exchanges overlaps only
 // inside its own).  Caller holds g->mu.  The reads of the mel are enqueued on g->stream: the caller orders them behind
 // the mel's producer (a stream sync or an event wait on g->stream).
-void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples) {
+// pros: null, or one prosody per utterance, each checked by the caller against its frame count.  With one that is not the
+// identity the ragged stage (k_prosody_batch) follows the GEMM: S [sum F_u] -> S_pros [sum F'_u], and everything behind it --
+// the rows of the loop's arrays, the packing into launches, the audio -- works from F'_u and reads S_pros.  Without one,
+// nothing new is launched.
+void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fin, float **audios, size_t *n_samples,
+                          const xdtts_prosody *pros) {
   {
-    const int n_utt = (int)Fu.size();
+    const int n_utt = (int)Fin.size();
+    bool staged = false;
+    for (int u = 0; pros && u < n_utt; ++u) staged = staged || !prosody_is_identity(pros[u]);
+    std::vector<int> Fu(Fin);  // frames behind the stage: F'_u
+    std::vector<ProsodyUtt> ptab;
     std::vector<int> fbase(n_utt), abase(n_utt);
-    size_t Ftot = 0, Ntot = 0;
+    size_t Fin_tot = 0, Ftot = 0, Ntot = 0;
     for (int u = 0; u < n_utt; ++u) {
+      if (staged) {
+        Fu[u] = (int)prosody_frames((size_t)Fin[u], pros[u].rate);
+        ptab.push_back({(int)Fin_tot, Fin[u], (int)Ftot, Fu[u], pros[u].rate, pros[u].pitch, pros[u].lifter, pros[u].log_floor});
+      }
+      Fin_tot += (size_t)Fin[u];
+      if (Fin_tot > (1u << 24)) fail(XDTTS_ERR_BAD_ARG, "batch too large");
       fbase[u] = (int)Ftot;
       abase[u] = (int)Ntot;
       Ftot += (size_t)Fu[u];
@@ -476,7 +517,13 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     for (int u = 0; u < n_utt; ++u)
       for (int f = 0; f < Fu[u]; ++f) fl[(size_t)fbase[u] + f] = f;
     g->frame_local.upload(fl.data(), fl.size(), st);
-    GlBufs all = g->bufs((int)Ftot);
+    GlBufs all = g->bufs((int)std::max(Fin_tot, Ftot));
+    all.F = (int)Ftot;
+    if (staged) {
+      g->pros_tab.upload(ptab.data(), ptab.size(), st);
+      g->S_pros.alloc(Ftot * (size_t)g->nb);
+      all.S = g->S_pros.p;
+    }
     g->audio.alloc(std::max<size_t>(Ntot, 1));
     HIP_CHECK(hipStreamSynchronize(st));  // the host vector above
     const float alpha = g->momentum / (1.0f + g->momentum);
@@ -484,7 +531,8 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     g->probe_tick();
     for (int attempt = 0;; ++attempt) {
       HIP_CHECK(hipEventRecord(g->ev.e[0], st));
-      g->mel_to_linear(mel_dev_all, (int)Ftot);
+      g->mel_to_linear(mel_dev_all, (int)Fin_tot);
+      if (staged) launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)Ftot, g->tw.p, st);  // (inside the loop: a retry starts from an intact S)
       HIP_CHECK(hipEventRecord(g->ev.e[1], st));
       launch_gl_phase_init_batch(all, g->seed, g->frame_local.p, st);
       // pack consecutive utterances into persistent launches of <= one workgroup per CU.  A workgroup owns up to

@@ -68,6 +68,7 @@ struct xdtts_griffinlim {
 
   // prosody (prosody.hip): the modified magnitude [F'][nb]; S itself stays as mel -> linear left it
   DevBuf<float> S_pros;
+  DevBuf<xdtts::ProsodyUtt> pros_tab;  // vocoder batch: per-utterance rows and parameters of the ragged stage (k_prosody_batch)
 
   ~xdtts_griffinlim();
   GlBufs bufs(int F);
@@ -99,13 +100,21 @@ void mel_filter_bank(double sr, int n_fft, int n_mels, double fmin, double fmax,
 
 void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, float **audio, size_t *n_samples,
                           bool normalise);
-void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host);
-void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples);
+// (p: null, or a checked prosody -- the single-utterance stage behind mel -> linear; F stays the mel's frame count in both halves)
+void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const xdtts_prosody *p = nullptr);
+void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const xdtts_prosody *p = nullptr);
 void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, float **audio, size_t *n_samples);
 // ... with the prosody stage between mel -> linear and the loop (p checked by the caller: prosody_check); last_ms[0] covers both
 void gl_run_from_device_mel_prosody(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const xdtts_prosody &p, float **audio,
                                     size_t *n_samples);
-void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples);
+// (pros: null, or one checked prosody per utterance -- the ragged stage behind the one mel -> linear GEMM; audios[u] then has
+// hop * (F'_u - 1) samples)
+void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples,
+                          const xdtts_prosody *pros = nullptr);
+// The fields of n_utt prosodies before any handle is looked at (entries that take an array): fails with XDTTS_ERR_BAD_ARG,
+// the message names the field and the utterance.
+void prosody_check_array(const xdtts_prosody *p, int n_utt);
+void prosody_check_at(const xdtts_prosody *p, int u, size_t n_frames);  // prosody_check for utterance u of a batch or sequence
 
 // Analysis of n_utt audios in one k_stft_mag launch: g->an_S [Ftot][nb] = |STFT|, and with want_mel g->an_melT [Ftot][n_mels] =
 // an_S^e . basis^T (linear mel, before compression).  Returns each utterance's first row and frame count.  Everything is

@@ -319,5 +319,16 @@ void launch_spec_distance(const float *X, const float *St, size_t n, double *par
 // axis under the unchanged envelope.  Fout = prosody_frames(F, rate) (griffinlim_handle.h); F >= 2 unless rate == 1.  One launch.
 void launch_prosody(const float *S, float *Sout, int F, int Fout, float rate, float pitch, int lifter, float log_floor,
                     const float2 *tw, hipStream_t s);
+// The ragged form, one launch for the utterances of a batch: utterance u's F rows start at row src0 of S, its Fout =
+// prosody_frames(F, rate) rows at row dst0 of Sout (dst0 ascending, the utterances back to back: dst0[u + 1] = dst0[u] + Fout[u]);
+// Fout_all = the sum.  tab is device memory.  Every row equals what launch_prosody gives for the utterance alone, bit for bit;
+// an utterance with rate == pitch == 1 is copied.
+struct ProsodyUtt {
+  int src0, F, dst0, Fout;
+  float rate, pitch;
+  int lifter;
+  float log_floor;
+};
+void launch_prosody_batch(const float *S, float *Sout, const ProsodyUtt *tab, int n_utt, int Fout_all, const float2 *tw, hipStream_t s);
 
 }  // namespace xdtts

@@ -5,7 +5,8 @@
 //          structure (the harmonics); only the fine structure is resampled on the frequency axis, the envelope stays where it is.
 // One wave per OUTPUT frame, four frames per workgroup (the shape of k_stft_mag, analysis.hip); the two transforms are the
 // one-wave 512-point FFT of gl_fft.h on a private LDS slice.  Nothing here crosses workgroups: no barrier, no exchange, no
-// polling, no atomics.
+// polling, no atomics.  k_prosody takes one utterance, k_prosody_batch the concatenated utterances of a batch, each with its own
+// parameters; both run prosody_frame().
 #include "gl_fft.h"
 #include "kernels.h"
 
@@ -44,20 +45,17 @@ __device__ __forceinline__ void even_dft(float2 *buf, const float2 *__restrict__
   }
 }
 
+// One output frame of one utterance -- the arithmetic of both kernels, so that a frame leaves either with the same bits.
 // Sout[j][k], j < Fout, from S [F][513] (F >= 2 unless rate == 1):
 //   u = min(j rate, F - 1), i = min(floor u, F - 2), w = u - i;  St[k] = (1 - w) S[i][k] + w S[i + 1][k]
 //   pitch == 1: Sout[j] = St (an exact zero stays one)
 //   else      : L = ln(max(St, log_floor)); c = real cepstrum of L; E = the transform of c with c[n] = 0 for lifter < n <
 //               1024 - lifter; R = L - E; p = k / pitch; Sout[j][k] = exp(E[k] + (p <= 512 ? lerp(R, p) : 0))
-// A wave past the last frame computes the last frame again (clamped index) and leaves before the stores.
-__global__ __launch_bounds__(64 * FRAMES_PER_BLOCK) void k_prosody(const float *__restrict__ S, float *__restrict__ Sout, int F,
-                                                                   int Fout, float rate, float pitch, int lifter, float log_floor,
-                                                                   const float2 *__restrict__ tw) {
-  __shared__ float2 lds[FRAMES_PER_BLOCK][512];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int jr = blockIdx.x * FRAMES_PER_BLOCK + wave;
-  const bool ok = jr < Fout;
-  const int j = ok ? jr : Fout - 1;
+// j is the wave's frame (already clamped into the utterance); a wave with !ok computes it and leaves before the stores.
+// buf = the wave's private LDS slice.
+__device__ __forceinline__ void prosody_frame(const float *__restrict__ S, float *__restrict__ Sout, int F, int j, bool ok, float rate,
+                                              float pitch, int lifter, float log_floor, const float2 *__restrict__ tw, float2 *buf,
+                                              int lane) {
   int i = 0;
   float w = 0.f;
   if (rate != 1.0f) {
@@ -83,7 +81,6 @@ __global__ __launch_bounds__(64 * FRAMES_PER_BLOCK) void k_prosody(const float *
     return;
   }
   const Twiddles tws = load_twiddles(tw, lane);
-  float2 *buf = lds[wave];
   float *e = reinterpret_cast<float *>(buf);
   float X[9];
 #pragma unroll
@@ -124,12 +121,63 @@ __global__ __launch_bounds__(64 * FRAMES_PER_BLOCK) void k_prosody(const float *
   }
 }
 
+// One utterance: a wave past the last frame computes the last frame again (clamped index) and leaves before the stores.
+__global__ __launch_bounds__(64 * FRAMES_PER_BLOCK) void k_prosody(const float *__restrict__ S, float *__restrict__ Sout, int F,
+                                                                   int Fout, float rate, float pitch, int lifter, float log_floor,
+                                                                   const float2 *__restrict__ tw) {
+  __shared__ float2 lds[FRAMES_PER_BLOCK][512];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int jr = blockIdx.x * FRAMES_PER_BLOCK + wave;
+  const bool ok = jr < Fout;
+  prosody_frame(S, Sout, F, ok ? jr : Fout - 1, ok, rate, pitch, lifter, log_floor, tw, lds[wave], lane);
+}
+
+// The ragged form: the utterances of a batch lie one behind the other in S [sum F_u][513] and Sout [sum F'_u][513]; tab[u]
+// (ProsodyUtt, kernels.h) says where, and with which parameters.  One wave per row of Sout, FRAMES_PER_BLOCK rows per
+// workgroup over the concatenated axis, so the waves of a workgroup may belong to different utterances: each looks its own
+// up (a bounded search over dst0, ascending; the index stays in [0, n_utt) whatever the table holds), takes its own branch
+// and reads no row but its utterance's.  rate == pitch == 1: the row is copied, no arithmetic.  A wave past the last row
+// of the batch computes the last row again and leaves before the stores.
+__global__ __launch_bounds__(64 * FRAMES_PER_BLOCK) void k_prosody_batch(const float *__restrict__ S, float *__restrict__ Sout,
+                                                                         const ProsodyUtt *__restrict__ tab, int n_utt, int Fout_all,
+                                                                         const float2 *__restrict__ tw) {
+  __shared__ float2 lds[FRAMES_PER_BLOCK][512];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (the same in every lane: scalar)
+  const int jr = blockIdx.x * FRAMES_PER_BLOCK + wave;
+  const bool ok = jr < Fout_all;
+  const int row = ok ? jr : Fout_all - 1;
+  int lo = 0, hi = n_utt - 1;  // the last utterance with dst0 <= row
+  for (int it = 0; it < 32 && lo < hi; ++it) {
+    const int mid = (lo + hi + 1) >> 1;  // lo < mid <= hi
+    if (tab[mid].dst0 <= row) lo = mid; else hi = mid - 1;
+  }
+  const ProsodyUtt t = tab[lo];
+  const int j = min(max(row - t.dst0, 0), t.Fout - 1);
+  const float *Su = S + (size_t)t.src0 * NB;
+  float *So = Sout + (size_t)t.dst0 * NB;
+  if (t.rate == 1.0f && t.pitch == 1.0f) {
+    if (!ok) return;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) So[(size_t)j * NB + lane + 64 * r] = Su[(size_t)j * NB + lane + 64 * r];
+    if (lane == 0) So[(size_t)j * NB + 512] = Su[(size_t)j * NB + 512];
+    return;
+  }
+  prosody_frame(Su, So, t.F, j, ok, t.rate, t.pitch, t.lifter, t.log_floor, tw, lds[wave], lane);
+}
+
 }  // namespace
 
 void launch_prosody(const float *S, float *Sout, int F, int Fout, float rate, float pitch, int lifter, float log_floor,
                     const float2 *tw, hipStream_t s) {
   const int nblk = (Fout + FRAMES_PER_BLOCK - 1) / FRAMES_PER_BLOCK;
   hipLaunchKernelGGL(k_prosody, dim3(nblk), dim3(64 * FRAMES_PER_BLOCK), 0, s, S, Sout, F, Fout, rate, pitch, lifter, log_floor, tw);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_prosody_batch(const float *S, float *Sout, const ProsodyUtt *tab, int n_utt, int Fout_all, const float2 *tw, hipStream_t s) {
+  if (n_utt <= 0 || Fout_all <= 0) return;
+  const int nblk = (Fout_all + FRAMES_PER_BLOCK - 1) / FRAMES_PER_BLOCK;
+  hipLaunchKernelGGL(k_prosody_batch, dim3(nblk), dim3(64 * FRAMES_PER_BLOCK), 0, s, S, Sout, tab, n_utt, Fout_all, tw);
   HIP_CHECK(hipGetLastError());
 }
 
