@@ -313,8 +313,10 @@ xdtts_status xdtts_griffinlim_mel_to_linear(xdtts_griffinlim *g, const float *me
 xdtts_status xdtts_griffinlim_step(xdtts_griffinlim *g, const float *S, float *angles,
                                    float *rebuilt, size_t n_frames, size_t n_iter);
 
-/* ms[0] mel->linear (for the *_prosody entries: mel->linear and the prosody stage), ms[1] iterations, ms[2] total of the last
- * call (HIP events).  After xdtts_griffinlim_prosody_linear: ms[0] the prosody stage alone, ms[1] the layout change behind it. */
+/* ms[0] mel->linear (for the *_prosody entries: mel->linear and the prosody stage; with phase_init 1 the SPSI stage as well:
+ * everything in front of the loop), ms[1] iterations, ms[2] total of the last call (HIP events).  After
+ * xdtts_griffinlim_prosody_linear and xdtts_griffinlim_spsi_phase (and their _batch forms): ms[0] the stage alone, ms[1] the
+ * layout change behind it. */
 xdtts_status xdtts_griffinlim_last_timings(const xdtts_griffinlim *g, float ms[3]);
 
 /* The inverse direction of GriffinLim::infer's conventions: librosa.stft(y, 1024, hop 256, periodic hann, center, reflect)
@@ -399,6 +401,42 @@ xdtts_status xdtts_griffinlim_infer_batch_prosody(xdtts_griffinlim *g, const flo
 xdtts_status xdtts_griffinlim_prosody_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames,
                                                    int32_t n_utt, const xdtts_prosody *p /* [n_utt] */, float *const *S_outs,
                                                    size_t *n_frames_out);
+
+/* The initial phase of the loop.  Mode 0 (the default, the crate's behaviour) draws it from the seeded random stream; mode 1
+ * computes it from the magnitude by Single Pass Spectrogram Inversion (Beauregard, Harish, Wyse 2015), which lowers the
+ * spectral convergence a small iteration budget reaches (about half at 2 and 5 iterations on a voiced signal;
+ * not on fast chirps beyond 10 iterations, hence an option).  The definition, on S time-major [F][513] fp32 -- the magnitude
+ * that enters the loop: S, or S' behind a prosody stage.  For frame t, m = S[t]:
+ *   peaks   k is a peak iff 1 <= k <= 511, m[k] > m[k-1] and m[k] >= m[k+1]           (exact fp32 comparisons; NaN compares false)
+ *   offset  a = m[k-1], b = m[k], c = m[k+1];  d = (a - b) + (c - b);  p = d == 0 ? 0 : 0.5f * (a - c) / d, clamped to
+ *           [-0.5, 0.5] by fminf(fmaxf(p, -0.5f), 0.5f)                                (all fp32)
+ *   phases  are uint32 in units of 2^-32 turn, every sum modulo 2^32.  A peak advances by hop (k + p) / n_fft = (k + p) / 4
+ *           turns per frame:  adv(k) = ((k & 3) << 30) + (uint32)(int32) rint(p * 2^30)
+ *   owner   o_t(j) = the peak of frame t nearest to bin j by |j - k|, a tie goes to the lower k, a peak owns itself.  A frame
+ *           without peaks has o_t(j) = j and delta_t(j) = 0: a silent frame carries the phase through.
+ *   sign    the frame starts at sample 0 of its window, so adjacent bins of one sinusoid alternate in sign inside the Hann main
+ *           lobe.  With pp = p of the owner o:  shift(j) = 0 for j == o;  pp > 0: 2^31 if j < o or j == o + 1, else 0;
+ *           pp <= 0: 2^31 if j > o or j == o - 1, else 0
+ *   delta_t(j) = adv(o_t(j)) + shift_t(j)
+ *   phi_t[j] = phi_{t-1}[o_t(j)] + delta_t(j),  phi_{-1} = 0; it restarts at 0 for each utterance of a batch or sequence
+ *   output  u = (float)(phi >> 8) * 2^-24, angles = (cos 2 pi u, sin 2 pi u) by sincospif(2 u); the previous spectrum is 0.
+ * Integers make the recurrence exact in any order of evaluation: the device runs it as a scan over segments of frames, the
+ * ragged batch form gives the bits of the single form, and the one place where a device may differ from a host restatement is
+ * the rounding of the division in p.
+ * The mode is honoured by every entry that draws the initial phase itself: _infer, _infer_prosody, _infer_linear with phase0 ==
+ * NULL, _infer_batch, _infer_batch_prosody, xdtts_synthesize_ids / _batch / _sequence and their prosody forms; batch audio ==
+ * single audio bit for bit with batch_shape = 4 holds in mode 1 as well.  xdtts_griffinlim_step and _infer_linear with a phase0
+ * are unaffected.  With mode 0 every result keeps the bits it had. */
+/* 0: the seeded random stream (default; the crate's behaviour)   1: SPSI (definition above) */
+xdtts_status xdtts_griffinlim_set_phase_init(xdtts_griffinlim *g, int32_t mode);   /* other values: XDTTS_ERR_BAD_ARG */
+xdtts_status xdtts_griffinlim_get_phase_init(const xdtts_griffinlim *g, int32_t *mode);
+/* Parity hook, the stage alone, whatever the handle's mode: S (n_bins x F, C order, as xdtts_griffinlim_mel_to_linear
+ * returns it), F >= 1 -> turns (n_bins x F, uint32, may be NULL) and angles (n_bins x F x 2 (cos, sin), the layout of
+ * infer_linear's phase0, may be NULL). */
+xdtts_status xdtts_griffinlim_spsi_phase(xdtts_griffinlim *g, const float *S, size_t n_frames, uint32_t *turns, float *angles);
+/* The ragged form the batch entries run: every output equals the single hook's bit for bit, whatever the mix and order. */
+xdtts_status xdtts_griffinlim_spsi_phase_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
+                                               uint32_t *const *turns, float *const *angles);
 
 void xdtts_griffinlim_free(xdtts_griffinlim *g);
 

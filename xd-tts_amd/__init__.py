@@ -127,6 +127,10 @@ SYMBOLS = {
     "xdtts_griffinlim_infer_prosody": (_I32, [_VP, _VP, _SZ, _SZ, C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_griffinlim_infer_batch_prosody": (_I32, [_VP, _VP, _SZ, _VP, _I32, _VP, _VP, _VP]),
     "xdtts_griffinlim_prosody_linear_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "xdtts_griffinlim_set_phase_init": (_I32, [_VP, _I32]),
+    "xdtts_griffinlim_get_phase_init": (_I32, [_VP, C.POINTER(_I32)]),
+    "xdtts_griffinlim_spsi_phase": (_I32, [_VP, _VP, _SZ, _VP, _VP]),
+    "xdtts_griffinlim_spsi_phase_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
     "xdtts_griffinlim_free": (None, [_VP]),
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
@@ -655,7 +659,8 @@ class GriffinLim:
         return S
 
     def last_timings(self):
-        """(after infer_prosody / synthesize(prosody=...): mel_to_linear_ms covers mel -> linear and the prosody stage)"""
+        """(after infer_prosody / synthesize(prosody=...): mel_to_linear_ms covers mel -> linear and the prosody stage; with
+        phase_init 1 the SPSI stage too; after prosody_linear / spsi_phase it is the stage alone)"""
         ms = (C.c_float * 3)()
         _check(lib.xdtts_griffinlim_last_timings(self._h, C.byref(ms)))
         return {"mel_to_linear_ms": ms[0], "iterations_ms": ms[1], "total_ms": ms[2]}
@@ -693,6 +698,40 @@ class GriffinLim:
         audio, n = _PF(), C.c_size_t()
         _check(lib.xdtts_griffinlim_infer_prosody(self._h, _ptr(mel), mel.shape[0], mel.shape[1], C.byref(prosody), C.byref(audio), C.byref(n)))
         return _take(audio, n.value, (n.value,))
+
+    # -- initial phase: the seeded random stream (0) or Single Pass Spectrogram Inversion (1) ----
+    def set_phase_init(self, mode):
+        """0: the seeded random stream (default), 1: SPSI on the magnitude that enters the loop; honoured by every entry
+        that draws the initial phase itself (not by step, nor by infer_linear with a phase0)."""
+        _check(lib.xdtts_griffinlim_set_phase_init(self._h, int(mode)))
+
+    def get_phase_init(self):
+        mode = C.c_int32()
+        _check(lib.xdtts_griffinlim_get_phase_init(self._h, C.byref(mode)))
+        return mode.value
+
+    def spsi_phase(self, S):
+        """The SPSI stage alone (parity hook), whatever the mode: S (n_bins, F) -> (turns (n_bins, F) uint32 in units of
+        2^-32 turn, angles (n_bins, F, 2) (cos, sin): what infer_linear takes as phase0)."""
+        turns, angles = self.spsi_phase_batch([S])
+        return turns[0], angles[0]
+
+    def spsi_phase_batch(self, S_list):
+        """The ragged stage alone (parity hook): a list of S_u (n_bins, F_u) -> (list of turns, list of angles), every one
+        the single hook's bit for bit."""
+        Ss = [np.ascontiguousarray(S, dtype=np.float32) for S in S_list]
+        n = len(Ss)
+        turns = [np.empty(S.shape, dtype=np.uint32) for S in Ss]
+        angles = [np.empty(S.shape + (2,), dtype=np.float32) for S in Ss]
+        sp = (C.c_void_p * n)(*[S.ctypes.data for S in Ss])
+        nf = (C.c_size_t * n)(*[S.shape[1] for S in Ss])
+        tp = (C.c_void_p * n)(*[t.ctypes.data for t in turns])
+        ap = (C.c_void_p * n)(*[a.ctypes.data for a in angles])
+        if n == 1:
+            _check(lib.xdtts_griffinlim_spsi_phase(self._h, sp[0], nf[0], tp[0], ap[0]))
+        else:
+            _check(lib.xdtts_griffinlim_spsi_phase_batch(self._h, sp, nf, n, tp, ap))
+        return turns, angles
 
     # -- analysis: audio -> magnitude -> mel under the handle's conventions, spectral convergence ----
     def analysis_frames(self, n_samples):

@@ -380,6 +380,81 @@ xdtts_status xdtts_griffinlim_prosody_linear_batch(xdtts_griffinlim *g, const fl
   });
 }
 
+// ---- initial phase: the seeded random stream (0) or Single Pass Spectrogram Inversion (1; phase_spsi.hip) ---------------------
+
+xdtts_status xdtts_griffinlim_set_phase_init(xdtts_griffinlim *g, int32_t mode) {
+  return guard([&] {
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    if (mode != 0 && mode != 1) fail(XDTTS_ERR_BAD_ARG, "phase_init must be 0 (seeded random) or 1 (SPSI), got %d", mode);
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->phase_init = mode;
+  });
+}
+
+xdtts_status xdtts_griffinlim_get_phase_init(const xdtts_griffinlim *g, int32_t *mode) {
+  return guard([&] {
+    if (!g || !mode) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    *mode = g->phase_init;
+  });
+}
+
+// Parity hook of the ragged stage alone: the utterances' magnitudes one behind the other on the device, the launches of
+// phase_spsi.hip, and back.  last_timings: ms[0] = the stage alone, ms[1] = the layout change behind it.
+xdtts_status xdtts_griffinlim_spsi_phase_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
+                                               uint32_t *const *turns, float *const *angles) {
+  return guard([&] {
+    if (!g || !S || !n_frames) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    std::vector<int> Fu((size_t)n_utt), row0((size_t)n_utt);
+    size_t Ftot = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      if (!S[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
+      if (n_frames[u] == 0) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 1 frame", u);
+      if (n_frames[u] > ((size_t)1 << 20)) fail(XDTTS_ERR_BAD_ARG, "utterance %d: at most 2^20 frames, got %zu", u, n_frames[u]);
+      row0[(size_t)u] = (int)Ftot;
+      Fu[(size_t)u] = (int)n_frames[u];
+      Ftot += n_frames[u];
+      if (Ftot > ((size_t)1 << 20)) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^20 frames");
+    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    const size_t nb = (size_t)g->nb, ne = Ftot * nb;
+    GlBufs b = g->bufs((int)Ftot);
+    for (int u = 0; u < n_utt; ++u) {  // boundary layout (nb x F_u) -> rows row0 .. of the device layout [F][nb]
+      const size_t r0 = (size_t)row0[(size_t)u] * nb;
+      HIP_CHECK(hipMemcpyAsync(g->frames.p + r0, S[u], (size_t)Fu[(size_t)u] * nb * sizeof(float), hipMemcpyHostToDevice, g->stream));
+      launch_transpose(g->frames.p + r0, g->S.p + r0, g->nb, Fu[(size_t)u], g->stream);
+    }
+    xdtts_griffinlim::SpsiTables tab;
+    g->spsi_tables(Fu, tab);
+    g->spsi_turns.alloc(ne);
+    g->phase0.alloc(ne * 3);  // staging in the boundary layout: the angles, then the turns
+    float2 *ang_out = reinterpret_cast<float2 *>(g->phase0.p);
+    unsigned *turns_out = reinterpret_cast<unsigned *>(g->phase0.p + ne * 2);
+    HIP_CHECK(hipStreamSynchronize(g->stream));  // the host tables
+    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+    if (n_utt == 1) g->spsi(g->S.p, Fu[0], b.ang, b.tprev, g->spsi_turns.p);  // (the form the single-utterance entries run)
+    else g->spsi_batch(g->S.p, tab, b.ang, b.tprev, g->spsi_turns.p);
+    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
+    for (int u = 0; u < n_utt; ++u) {
+      const size_t r0 = (size_t)row0[(size_t)u] * nb;
+      launch_spsi_export(g->spsi_turns.p + r0, b.ang + r0, Fu[(size_t)u], g->nb, turns_out + r0, ang_out + r0, g->stream);
+    }
+    HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+    for (int u = 0; u < n_utt; ++u) {
+      const size_t r0 = (size_t)row0[(size_t)u] * nb, n = (size_t)Fu[(size_t)u] * nb;
+      if (turns && turns[u]) HIP_CHECK(hipMemcpyAsync(turns[u], turns_out + r0, n * sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream));
+      if (angles && angles[u]) HIP_CHECK(hipMemcpyAsync(angles[u], ang_out + r0, n * sizeof(float2), hipMemcpyDeviceToHost, g->stream));
+    }
+    g->finish_timings();  // (drains the stream)
+  });
+}
+
+xdtts_status xdtts_griffinlim_spsi_phase(xdtts_griffinlim *g, const float *S, size_t n_frames, uint32_t *turns, float *angles) {
+  return xdtts_griffinlim_spsi_phase_batch(g, &S, &n_frames, 1, &turns, &angles);
+}
+
 // ---- analysis: the inverse direction of GriffinLim::infer's conventions (analysis.hip).  No co-resident grid: no chip lock. ----
 
 // What one call takes: the row tiles of the mel GEMM and of the boundary transposes go into a grid dimension of at most 65535

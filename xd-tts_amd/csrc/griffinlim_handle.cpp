@@ -113,6 +113,36 @@ int xdtts_griffinlim::prosody(const xdtts_prosody &p, int F) {
   return Fp;
 }
 
+// The initial phase by SPSI (phase_spsi.hip) on a magnitude in place.  Scratch grows with the request and stays.
+void xdtts_griffinlim::spsi(const float *S_dev, int F, float2 *ang_out, float2 *tprev_out, unsigned *turns) {
+  const size_t nseg = spsi_segments(F);
+  spsi_map.alloc((size_t)F * nb);
+  spsi_comp.alloc(nseg * nb);
+  spsi_entry.alloc(nseg * nb);
+  launch_spsi(S_dev, F, nullptr, nullptr, (int)nseg, 1, nseg > 1, SpsiBufs{spsi_map.p, spsi_comp.p, spsi_entry.p}, ang_out, tprev_out, turns, stream);
+}
+
+void xdtts_griffinlim::spsi_tables(const std::vector<int> &Fu, SpsiTables &t) {
+  t = SpsiTables();
+  for (int F : Fu) {
+    const int nseg = (int)spsi_segments(F);
+    t.utts.push_back({(int)t.segs.size(), nseg});
+    for (int k = 0; k < nseg; ++k) t.segs.push_back({t.rows + k * SPSI_L, std::min(SPSI_L, F - k * SPSI_L), k == 0, k + 1 == nseg});
+    t.chained = t.chained || nseg > 1;
+    t.rows += F;
+  }
+  spsi_segs.upload(t.segs.data(), t.segs.size(), stream);
+  spsi_utts.upload(t.utts.data(), t.utts.size(), stream);
+  spsi_map.alloc((size_t)t.rows * nb);
+  spsi_comp.alloc(t.segs.size() * nb);
+  spsi_entry.alloc(t.segs.size() * nb);
+}
+
+void xdtts_griffinlim::spsi_batch(const float *S_dev, const SpsiTables &t, float2 *ang_out, float2 *tprev_out, unsigned *turns) {
+  launch_spsi(S_dev, t.rows, spsi_segs.p, spsi_utts.p, (int)t.segs.size(), (int)t.utts.size(), t.chained,
+              SpsiBufs{spsi_map.p, spsi_comp.p, spsi_entry.p}, ang_out, tprev_out, turns, stream);
+}
+
 bool xdtts_griffinlim::persistent_usable() {
   if (env::equals(env::GL, "launch")) return false;  // developer comparison aid: launch-per-iteration engine
   gate.ensure_probed([&] { return gl_persistent_supported(device, &n_cu, &per_cu4); });
@@ -223,17 +253,26 @@ bool xdtts_griffinlim::persistent_failed() {
 }
 
 // phase init + iterations + final ISTFT; S already in place.  Result in audio (device).
+// phase_init 1 without a caller's phase0: the SPSI stage on g.S (S, or S' behind a prosody stage) writes the angles and the
+// zero previous spectrum, and the engines then take the route of a caller-supplied phase0.  The stage counts as preparation:
+// ev.e[1] moves behind it, so last_ms[0] covers mel -> linear, prosody and the initial phase.  A retry after a demotion
+// comes through here again and recomputes the phase from the intact S.
 void xdtts_griffinlim::iterate(const GlBufs &g, const float *phase0_dev, int n_iter) {
   const float alpha = momentum / (1.0f + momentum);
   int TF = 0, nblk = 0;
+  const bool use_spsi = !phase0_dev && phase_init == 1;
+  if (use_spsi) {
+    spsi(g.S, g.F, g.ang, g.tprev);
+    HIP_CHECK(hipEventRecord(ev.e[1], stream));
+  }
   if (persistent_usable() && gl_persistent_plan(g.F, n_cu, &TF, &nblk)) {
     // one launch: nothing to capture; with the seeded stream the kernel draws the phase itself (no
     // phase-init launch, no window-sum table: the kernel keeps its own)
     if (phase0_dev) launch_gl_phase_init(g, seed, phase0_dev, stream);
-    run_iterations(g, n_iter, alpha, audio.p, false, nullptr, phase0_dev == nullptr);
+    run_iterations(g, n_iter, alpha, audio.p, false, nullptr, !phase0_dev && !use_spsi);
     return;
   }
-  launch_gl_phase_init(g, seed, phase0_dev, stream);
+  if (!use_spsi) launch_gl_phase_init(g, seed, phase0_dev, stream);
   launch_gl_prepare(g, stream);
   last_persistent = false;
   // the launch-per-iteration loop is launch-bound: replay it as one hipGraph
@@ -517,6 +556,9 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     for (int u = 0; u < n_utt; ++u)
       for (int f = 0; f < Fu[u]; ++f) fl[(size_t)fbase[u] + f] = f;
     g->frame_local.upload(fl.data(), fl.size(), st);
+    const bool use_spsi = g->phase_init == 1;
+    xdtts_griffinlim::SpsiTables spsi_tab;
+    if (use_spsi) g->spsi_tables(Fu, spsi_tab);  // (of the frames behind the prosody stage)
     GlBufs all = g->bufs((int)std::max(Fin_tot, Ftot));
     all.F = (int)Ftot;
     if (staged) {
@@ -533,8 +575,9 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
       HIP_CHECK(hipEventRecord(g->ev.e[0], st));
       g->mel_to_linear(mel_dev_all, (int)Fin_tot);
       if (staged) launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)Ftot, g->tw.p, st);  // (inside the loop: a retry starts from an intact S)
+      if (use_spsi) g->spsi_batch(all.S, spsi_tab, all.ang, all.tprev);  // (a retry recomputes it from the intact S / S')
       HIP_CHECK(hipEventRecord(g->ev.e[1], st));
-      launch_gl_phase_init_batch(all, g->seed, g->frame_local.p, st);
+      if (!use_spsi) launch_gl_phase_init_batch(all, g->seed, g->frame_local.p, st);
       // pack consecutive utterances into persistent launches of <= one workgroup per CU.  A workgroup owns up to
       // 4 frames (one wave each) or up to 8 (two waves per SIMD): an iteration of the 8-frame shape takes 6.8 us
       // against 5.35 us (tools/gl_tf_sweep.py), so it wins as soon as it saves launches.  Two 4-frame workgroups

@@ -70,6 +70,25 @@ struct xdtts_griffinlim {
   DevBuf<float> S_pros;
   DevBuf<xdtts::ProsodyUtt> pros_tab;  // vocoder batch: per-utterance rows and parameters of the ragged stage (k_prosody_batch)
 
+  // initial phase (phase_spsi.hip): 0 = the seeded random stream, 1 = SPSI on the magnitude that enters the loop
+  int phase_init = 0;
+  DevBuf<uint2> spsi_map, spsi_comp;
+  DevBuf<unsigned> spsi_entry, spsi_turns;  // spsi_turns: the parity hooks only
+  DevBuf<xdtts::SpsiSeg> spsi_segs;         // vocoder batch: the segments of all utterances
+  DevBuf<xdtts::SpsiUtt> spsi_utts;
+  // The SPSI stage on the stream: S [F][nb] -> ang, tprev (and turns, if wanted).  One utterance ...
+  void spsi(const float *S_dev, int F, float2 *ang_out, float2 *tprev_out, unsigned *turns = nullptr);
+  // ... and the ragged form: spsi_tables() (uploads; the caller drains the stream before the host vectors go), then any
+  // number of spsi_batch() launches on the rows the tables describe.
+  struct SpsiTables {
+    std::vector<xdtts::SpsiSeg> segs;
+    std::vector<xdtts::SpsiUtt> utts;
+    int rows = 0;
+    bool chained = false;
+  };
+  void spsi_tables(const std::vector<int> &Fu, SpsiTables &t);
+  void spsi_batch(const float *S_dev, const SpsiTables &t, float2 *ang_out, float2 *tprev_out, unsigned *turns = nullptr);
+
   ~xdtts_griffinlim();
   GlBufs bufs(int F);
   void mel_to_linear(const float *mel_dev_ptr, int F);

@@ -331,4 +331,32 @@ struct ProsodyUtt {
 };
 void launch_prosody_batch(const float *S, float *Sout, const ProsodyUtt *tab, int n_utt, int Fout_all, const float2 *tw, hipStream_t s);
 
+// ---- initial phase by Single Pass Spectrogram Inversion (phase_spsi.hip; phase_init mode 1, include/xdtts.h) -----------------
+// The recurrence over the frames runs as a scan over segments of SPSI_L consecutive frames of one utterance: the dependent
+// depth is 2 SPSI_L + F / SPSI_L LDS gathers (82 at F = 800 with 24; 20 .. 32 are within 10 % of it), against F.
+constexpr int SPSI_L = 24;
+struct SpsiSeg {
+  int row0;   // row of the segment's first frame in S / ang / tprev (the utterances of a batch lie one behind the other)
+  int n;      // its frames, 1 .. SPSI_L
+  int first;  // the utterance's first segment: it starts from phase 0
+  int last;   // the utterance's last segment: nothing enters behind it
+};
+struct SpsiUtt {
+  int seg0, nseg;  // the utterance's segments in the table
+};
+struct SpsiBufs {
+  uint2 *map;       // [F][513]     (owner, delta) of every cell
+  uint2 *comp;      // [nseg][513]  the segments' composites
+  unsigned *entry;  // [nseg][513]  the phase in front of each segment
+};
+size_t spsi_segments(int F);  // of one utterance
+// S [F][513] -> ang = (cos, sin) of the SPSI phase, tprev = 0, and with turns != null the phase itself (uint32, 2^-32 turn),
+// all [F][513].  segs_dev / utts_dev == null: one utterance of F frames (nseg = spsi_segments(F), n_utt = 1); else the device
+// tables of a batch, F = its rows in all.  chained: some utterance has more than one segment (else two launches instead of four).
+// An utterance's result does not depend on what else is in the batch, bit for bit.
+void launch_spsi(const float *S, int F, const SpsiSeg *segs_dev, const SpsiUtt *utts_dev, int nseg, int n_utt, bool chained,
+                 const SpsiBufs &b, float2 *ang, float2 *tprev, unsigned *turns, hipStream_t s);
+// parity hook: turns / ang [F][nb] -> the boundary layout (nb x F)
+void launch_spsi_export(const unsigned *turns, const float2 *ang, int F, int nb, unsigned *turns_out, float2 *ang_out, hipStream_t s);
+
 }  // namespace xdtts
