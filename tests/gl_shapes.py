@@ -2,8 +2,8 @@
 work-split rules restated in plain Python, the frame counts that reach every shape they produce, the
 input of the sweep, and the two metrics that look at one hop / one frame at a time.
 
-The rules restated here (csrc/griffinlim.hip: gl_persistent_plan, glp_fstart, launch_gl_iterate;
-csrc/griffinlim_handle.cpp: the batch packer):
+The rules restated here (csrc/gl_plan.h: gl_persistent_plan and the batch packer; csrc/griffinlim.hip: glp_fstart,
+launch_gl_iterate):
 
   F < 16                      two kernels per iteration (reflect padding folds more than once)
   tf = max(4, ceil(F / n_cu)) frames per workgroup of the persistent kernel; tf > GLP_TF_MAX -> launch engine
@@ -16,7 +16,7 @@ import numpy as np
 
 HOP = 256
 N_BINS = 513
-GLP_TF_MAX = 8    # csrc/kernels.h
+GLP_TF_MAX = 8    # csrc/gl_plan.h
 TINY_BELOW = 16   # gl_persistent_plan: "if (F < 16) return false"; launch_gl_iterate: "if (g.F >= 16)"
 MIN_OWN = 3       # the edge sums of k_gl_persistent reach three frames back
 

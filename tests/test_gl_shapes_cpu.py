@@ -20,19 +20,20 @@ def _src(name):
 
 
 def test_the_restated_rules_use_the_constants_of_the_sources():
-    assert int(re.search(r"constexpr int GLP_TF_MAX = (\d+);", _src("kernels.h")).group(1)) == gs.GLP_TF_MAX == 8
+    assert int(re.search(r"constexpr int GLP_TF_MAX = (\d+);", _src("gl_plan.h")).group(1)) == gs.GLP_TF_MAX == 8
     assert int(re.search(r"constexpr int FRAMES_PER_BLOCK = (\d+);", _src("gl_fft.h")).group(1)) == 4
     hop = re.search(r"constexpr int NFFT = (\d+), HOP = (\d+);", _src("gl_fft.h"))
     assert (int(hop.group(1)), int(hop.group(2))) == (2 * (gs.N_BINS - 1), gs.HOP)
-    gl = _src("griffinlim.hip")
-    body = gl[gl.index("bool gl_persistent_plan("):]
+    gl, plan = _src("griffinlim.hip"), _src("gl_plan.h")
+    body = plan[plan.index("bool gl_persistent_plan("):]
     body = body[:body.index("\n}")]
     assert "if (F < %d) return false;" % gs.TINY_BELOW in body
     assert "std::max(4, (F + n_cu - 1) / n_cu)" in body and "if (tf > GLP_TF_MAX) return false;" in body
     assert "(F + tf - 1) / tf" in body and "nb > n_cu || F / nb < %d" % gs.MIN_OWN in body
     assert "if (g.F >= %d)" % gs.TINY_BELOW in gl  # launch_gl_iterate: fused kernel from 16 frames on
     assert "return (int)(((long long)b * F) / nblk);" in gl  # glp_fstart
-    assert "Fu[u] < %d || nb > g->n_cu || Fu[u] / nb < %d" % (gs.TINY_BELOW, gs.MIN_OWN) in _src("griffinlim_handle.cpp")
+    assert "return (int)(((long long)b * F) / nblk);" in plan  # gl_fstart, the header's statement of the same rule
+    assert "Fu[u] < %d || nb > n_cu || Fu[u] / nb < %d" % (gs.TINY_BELOW, gs.MIN_OWN) in plan  # gl_batch_pack
 
 
 def test_plan_at_the_thresholds():

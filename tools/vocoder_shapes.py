@@ -1,5 +1,5 @@
 """Developer timing aid: the three workgroup shapes of the vocoder batch (XDTTS_GL_BATCH_FORCE) on the 32-utterance batch of
-tools/vocoder_batch.py -> the relative costs in gl_batch_from_device's packing model (griffinlim_handle.cpp)."""
+tools/vocoder_batch.py -> the relative costs in the vocoder batch's packing model (gl_batch_pack, csrc/gl_plan.h)."""
 import importlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

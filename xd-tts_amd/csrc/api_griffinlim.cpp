@@ -18,28 +18,25 @@ static xdtts_status infer_batch(xdtts_griffinlim *g, const float *const *mels, s
   return guard([&] {
     if (!g || !mels || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "bad argument");
     if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
-    std::vector<int> fbase(n_utt), Fu(n_utt);
-    size_t Ftot = 0;
+    Rows rows;
     for (int u = 0; u < n_utt; ++u) {
       audios[u] = nullptr;
       n_samples[u] = 0;
       if (!mels[u] || n_frames[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 2 frames", u);
       if (pros) prosody_check_at(&pros[u], u, n_frames[u]);
-      fbase[u] = (int)Ftot;
-      Fu[u] = (int)n_frames[u];
-      Ftot += n_frames[u];
-      if (Ftot > (1u << 24)) fail(XDTTS_ERR_BAD_ARG, "batch too large");
+      rows_add(rows, n_frames[u], (size_t)1 << 24, "batch too large");
     }
+    const size_t Ftot = rows.total;
     std::lock_guard<std::mutex> lk(g->mu);
     HIP_CHECK(hipSetDevice(g->device));
     // mel of all utterances side by side: [n_mels][Ftot], staged in pinned memory (one fast upload)
     PinnedGuard mel_all((size_t)n_mels * Ftot);
     for (int u = 0; u < n_utt; ++u)
       for (size_t m = 0; m < n_mels; ++m)
-        std::memcpy(mel_all.p + m * Ftot + fbase[u], mels[u] + m * n_frames[u], sizeof(float) * n_frames[u]);
+        std::memcpy(mel_all.p + m * Ftot + rows.row0[u], mels[u] + m * n_frames[u], sizeof(float) * n_frames[u]);
     g->mel_in.upload(mel_all.p, (size_t)n_mels * Ftot, g->stream);
     HIP_CHECK(hipStreamSynchronize(g->stream));  // the staging buffer goes back to the pool
-    gl_batch_from_device(g, g->mel_in.p, Fu, audios, n_samples, pros);
+    gl_batch_from_device(g, g->mel_in.p, rows.F, audios, n_samples, pros);
   });
 }
 
@@ -157,7 +154,7 @@ xdtts_status xdtts_griffinlim_infer(xdtts_griffinlim *g, const float *mel, size_
     HIP_CHECK(hipSetDevice(g->device));
     g->mel_in.upload(mel, n_mels * n_frames, g->stream);
     HIP_CHECK(hipStreamSynchronize(g->stream));
-    gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, audio, n_samples);
+    gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, nullptr, audio, n_samples);
   });
 }
 
@@ -311,7 +308,7 @@ xdtts_status xdtts_griffinlim_infer_prosody(xdtts_griffinlim *g, const float *me
     HIP_CHECK(hipSetDevice(g->device));
     g->mel_in.upload(mel, n_mels * n_frames, g->stream);
     HIP_CHECK(hipStreamSynchronize(g->stream));
-    gl_run_from_device_mel_prosody(g, g->mel_in.p, (int)n_frames, *p, audio, n_samples);
+    gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, p, audio, n_samples);
   });
 }
 
@@ -339,28 +336,24 @@ xdtts_status xdtts_griffinlim_prosody_linear_batch(xdtts_griffinlim *g, const fl
     prosody_check_array(p, n_utt);
     if (!g || !S || !n_frames || !S_outs) fail(XDTTS_ERR_BAD_ARG, "null argument");
     std::vector<ProsodyUtt> tab((size_t)n_utt);
-    size_t Fin = 0, Fout = 0;
+    Rows in, out;
     for (int u = 0; u < n_utt; ++u) {
       if (!S[u] || !S_outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
       if (n_frames[u] == 0) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 1 frame", u);
       prosody_check_at(&p[u], u, n_frames[u]);
       const size_t Fp = prosody_frames(n_frames[u], p[u].rate);
-      tab[(size_t)u] = {(int)Fin, (int)n_frames[u], (int)Fout, (int)Fp, p[u].rate, p[u].pitch, p[u].lifter, p[u].log_floor};
-      Fin += n_frames[u];
-      Fout += Fp;
-      if (Fin > (1u << 24) || Fout > (1u << 24)) fail(XDTTS_ERR_BAD_ARG, "batch too large");
+      tab[(size_t)u] = {(int)in.total, (int)n_frames[u], (int)out.total, (int)Fp, p[u].rate, p[u].pitch, p[u].lifter, p[u].log_floor};
+      rows_add(in, n_frames[u], (size_t)1 << 24, "batch too large");
+      rows_add(out, Fp, (size_t)1 << 24, "batch too large");
     }
+    const size_t Fout = out.total;
     std::lock_guard<std::mutex> lk(g->mu);
     HIP_CHECK(hipSetDevice(g->device));
     const size_t nb = (size_t)g->nb;
-    g->bufs((int)std::max(Fin, Fout));  // (frames: the boundary-layout staging of both directions)
+    g->bufs((int)std::max(in.total, Fout));  // (frames: the boundary-layout staging of both directions)
     g->S_pros.alloc(Fout * nb);
     g->pros_tab.upload(tab.data(), tab.size(), g->stream);
-    for (int u = 0; u < n_utt; ++u) {  // boundary layout (nb x F_u) -> rows src0 .. of the device layout [F][nb]
-      const ProsodyUtt &t = tab[(size_t)u];
-      HIP_CHECK(hipMemcpyAsync(g->frames.p + (size_t)t.src0 * nb, S[u], (size_t)t.F * nb * sizeof(float), hipMemcpyHostToDevice, g->stream));
-      launch_transpose(g->frames.p + (size_t)t.src0 * nb, g->S.p + (size_t)t.src0 * nb, g->nb, t.F, g->stream);
-    }
+    g->upload_rows(S, in);
     HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
     if (env::equals(env::PROSODY_BATCH, "loop")) {  // developer comparison aid (tools/prosody_check.py): one k_prosody launch per utterance
       for (const ProsodyUtt &t : tab)
@@ -406,26 +399,20 @@ xdtts_status xdtts_griffinlim_spsi_phase_batch(xdtts_griffinlim *g, const float 
   return guard([&] {
     if (!g || !S || !n_frames) fail(XDTTS_ERR_BAD_ARG, "null argument");
     if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
-    std::vector<int> Fu((size_t)n_utt), row0((size_t)n_utt);
-    size_t Ftot = 0;
+    Rows rows;
     for (int u = 0; u < n_utt; ++u) {
       if (!S[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
       if (n_frames[u] == 0) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 1 frame", u);
       if (n_frames[u] > ((size_t)1 << 20)) fail(XDTTS_ERR_BAD_ARG, "utterance %d: at most 2^20 frames, got %zu", u, n_frames[u]);
-      row0[(size_t)u] = (int)Ftot;
-      Fu[(size_t)u] = (int)n_frames[u];
-      Ftot += n_frames[u];
-      if (Ftot > ((size_t)1 << 20)) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^20 frames");
+      rows_add(rows, n_frames[u], (size_t)1 << 20, "batch too large: more than 2^20 frames");
     }
+    const std::vector<int> &Fu = rows.F, &row0 = rows.row0;
+    const size_t Ftot = rows.total;
     std::lock_guard<std::mutex> lk(g->mu);
     HIP_CHECK(hipSetDevice(g->device));
     const size_t nb = (size_t)g->nb, ne = Ftot * nb;
     GlBufs b = g->bufs((int)Ftot);
-    for (int u = 0; u < n_utt; ++u) {  // boundary layout (nb x F_u) -> rows row0 .. of the device layout [F][nb]
-      const size_t r0 = (size_t)row0[(size_t)u] * nb;
-      HIP_CHECK(hipMemcpyAsync(g->frames.p + r0, S[u], (size_t)Fu[(size_t)u] * nb * sizeof(float), hipMemcpyHostToDevice, g->stream));
-      launch_transpose(g->frames.p + r0, g->S.p + r0, g->nb, Fu[(size_t)u], g->stream);
-    }
+    g->upload_rows(S, rows);
     xdtts_griffinlim::SpsiTables tab;
     g->spsi_tables(Fu, tab);
     g->spsi_turns.alloc(ne);
@@ -470,23 +457,22 @@ xdtts_status xdtts_griffinlim_analyze_batch(xdtts_griffinlim *g, const float *co
   return guard([&] {
     if (!g || !audios || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     if (n_utt < 1) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
-    size_t Ftot = 0;
+    Rows rows;
     bool want_S = false, want_mel = false;
     for (int u = 0; u < n_utt; ++u) {
       if (!audios[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null audio", u);
       if (n_samples[u] == 0 || n_samples[u] >= AN_MAX_SAMPLES) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need 1 .. 2^28 - 1 samples, got %zu", u, n_samples[u]);
-      Ftot += n_samples[u] / (size_t)g->hop + 1;
-      if (Ftot > AN_MAX_FRAMES) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^20 frames");
+      rows_add(rows, n_samples[u] / (size_t)g->hop + 1, AN_MAX_FRAMES, "batch too large: more than 2^20 frames");
       want_S = want_S || (S_outs && S_outs[u]);
       want_mel = want_mel || (mel_outs && mel_outs[u]);
     }
     const float floor = mel_floor > 0.f ? mel_floor : 1e-5f;  // Tacotron2's clamp
     std::lock_guard<std::mutex> lk(g->mu);
     HIP_CHECK(hipSetDevice(g->device));
-    const AnRows rows = gl_analysis_enqueue(g, audios, n_samples, n_utt, want_mel);
+    gl_analysis_enqueue(g, audios, n_samples, rows, want_mel);
     // boundary layouts, utterance by utterance: mel (n_mels x F) compressed, S (n_bins x F)
-    const size_t mel_at = (size_t)rows.Ftot * g->nb;
-    g->an_out.alloc((size_t)rows.Ftot * (size_t)(g->nb + g->n_mels));
+    const size_t mel_at = rows.total * g->nb;
+    g->an_out.alloc(rows.total * (size_t)(g->nb + g->n_mels));
     for (int u = 0; u < n_utt; ++u) {
       const size_t r0 = (size_t)rows.row0[(size_t)u];
       const int F = rows.F[(size_t)u];
@@ -528,7 +514,9 @@ xdtts_status xdtts_griffinlim_spectral_convergence(xdtts_griffinlim *g, const fl
     g->an_St.alloc(ne);
     launch_transpose(g->an_out.p, g->an_St.p, g->nb, (int)F, g->stream);
     g->an_sums.alloc(3 * SPD_PARTS + 3);
-    gl_analysis_enqueue(g, &audio, &n_samples, 1, false);
+    Rows rows;
+    rows_add(rows, F, AN_MAX_FRAMES, "batch too large: more than 2^20 frames");  // (never: the sample count was checked above)
+    gl_analysis_enqueue(g, &audio, &n_samples, rows, false);
     double *sums = g->an_sums.p + 3 * SPD_PARTS;
     launch_spec_distance(g->an_S.p, g->an_St.p, ne, g->an_sums.p, sums, g->stream);
     HIP_CHECK(hipEventRecord(g->an_ev.e[2], g->stream));

@@ -34,12 +34,8 @@ static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, cons
     HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));
     HIP_CHECK(hipMemcpyAsync(mel_host.p, h->mel_dev.p, (size_t)N_MEL * total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     Drain drain(h->stream);  // the pinned buffer does not go back to the pool with the copy in flight
-    if (pros) {
-      prosody_check(pros, (size_t)total);  // (the frame count is known only now; nothing of the vocoder has been enqueued)
-      gl_run_from_device_mel_prosody(g, h->mel_dev.p, total, *pros, audio, n_samples);
-    } else {
-      gl_run_from_device_mel(g, h->mel_dev.p, total, audio, n_samples);
-    }
+    if (pros) prosody_check(pros, (size_t)total);  // (the frame count is known only now; nothing of the vocoder has been enqueued)
+    gl_run_from_device_mel(g, h->mel_dev.p, total, pros, audio, n_samples);
     h->finish_timings();  // (stream sync: the mel has landed)
     *mel = mel_host.release();
     *n_frames = (size_t)total;

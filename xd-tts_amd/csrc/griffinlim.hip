@@ -1067,17 +1067,7 @@ void launch_gl_state_export(const GlBufs &g, const float2 *ang, const float2 *tp
   HIP_CHECK(hipGetLastError());
 }
 
-// ---- persistent engine: plan, resources, launch ----
-bool gl_persistent_plan(int F, int n_cu, int *TF, int *nblk) {
-  if (F < 16) return false;  // reflect padding folds more than once: two-kernel path
-  int tf = std::max(4, (F + n_cu - 1) / n_cu);
-  if (tf > GLP_TF_MAX) return false;
-  const int nb = (F + tf - 1) / tf;
-  if (nb > n_cu || F / nb < 3) return false;  // one workgroup per CU; every block needs >= 3 frames
-  *TF = tf;
-  *nblk = nb;
-  return true;
-}
+// ---- persistent engine: resources, launch (the plan: gl_plan.h) ----
 size_t gl_persistent_lds_bytes(int TF) { return sizeof(float) * ((size_t)TF * (516 + 2 * 1026 + FBS) + 2 * (size_t)(TF + 3) * HOP + 4); }
 size_t gl_persistent_xch_words(int nblk) { return (size_t)nblk * 4 * GLP_HALO; }
 

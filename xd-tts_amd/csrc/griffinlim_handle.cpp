@@ -143,6 +143,14 @@ void xdtts_griffinlim::spsi_batch(const float *S_dev, const SpsiTables &t, float
               SpsiBufs{spsi_map.p, spsi_comp.p, spsi_entry.p}, ang_out, tprev_out, turns, stream);
 }
 
+void xdtts_griffinlim::upload_rows(const float *const *S_host, const Rows &rows) {
+  for (int u = 0; u < rows.n(); ++u) {
+    const size_t r0 = (size_t)rows.row0[(size_t)u] * nb;
+    HIP_CHECK(hipMemcpyAsync(frames.p + r0, S_host[u], (size_t)rows.F[(size_t)u] * nb * sizeof(float), hipMemcpyHostToDevice, stream));
+    launch_transpose(frames.p + r0, S.p + r0, nb, rows.F[(size_t)u], stream);
+  }
+}
+
 bool xdtts_griffinlim::persistent_usable() {
   if (env::equals(env::GL, "launch")) return false;  // developer comparison aid: launch-per-iteration engine
   gate.ensure_probed([&] { return gl_persistent_supported(device, &n_cu, &per_cu4); });
@@ -395,44 +403,58 @@ void mel_filter_bank(double sr, int n_fft, int n_mels, double fmin, double fmax,
   }
 }
 
-// Phase init + iterations + final ISTFT on the S in place, then the audio to a pinned host buffer.
-// The persistent engine needs its grid co-resident: the chip lock is held from the launch until the
-// stream has drained; a timed-out exchange demotes the handle and the request runs again on the
-// launch-per-iteration engine (S and the phase seed are intact).
-void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, float **audio, size_t *n_samples,
-                          bool normalise) {
+// "Iterations enqueued" -> "audio on its way to a pinned buffer": phase init + iterations + final ISTFT on the S in place
+// (iterate()), the output normalisation if wanted, ev.e[2], the copy into `host` (taken from the pool here unless the caller
+// brought one) and the engine's error word behind it.  Nothing is waited for.
+static void enqueue_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, bool normalise, PinnedGuard &host) {
   const size_t N = (size_t)g->hop * (size_t)(b.F - 1);
-  std::lock_guard<ChipLock> chip(chip_mutex(g->device));
-  g->probe_tick();
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    g->iterate(b, phase0_dev, iters);
-    if (normalise) launch_gl_output_normalise(g->audio.p, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
-    HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
-    PinnedGuard host(N);
-    HIP_CHECK(hipMemcpyAsync(host.p, g->audio.p, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
-    g->fetch_error_word();
-    g->finish_timings();  // (drains the stream)
-    if (g->persistent_failed()) {
-      HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));  // time the run that counts
-      continue;
-    }
-    *audio = host.release();
-    *n_samples = N;
-    return;
+  g->iterate(b, phase0_dev, iters);
+  if (normalise) launch_gl_output_normalise(g->audio.p, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
+  HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+  if (!host.p) host = PinnedGuard(N);
+  HIP_CHECK(hipMemcpyAsync(host.p, g->audio.p, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+  g->fetch_error_word();
+}
+// ... and its counterpart: the wait and the engine's error word.  The persistent engine needs its grid co-resident (the
+// caller holds the chip lock from enqueue_run until here); a timed-out exchange demotes the handle and the same run goes
+// once more, on the launch-per-iteration engine (S, S' and the phase seed are intact until the next enqueue).
+static void collect_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, bool normalise, PinnedGuard &host,
+                        float **audio, size_t *n_samples) {
+  g->finish_timings();  // (drains the stream)
+  if (g->persistent_failed()) {
+    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));  // time the run that counts
+    enqueue_run(g, b, phase0_dev, iters, normalise, host);
+    g->finish_timings();
+    if (g->persistent_failed()) fail(XDTTS_ERR_HIP, "Griffin-Lim: the fallback engine reported an exchange failure");
   }
-  fail(XDTTS_ERR_HIP, "Griffin-Lim: the fallback engine reported an exchange failure");
+  *audio = host.release();
+  *n_samples = (size_t)g->hop * (size_t)(b.F - 1);
 }
 
-// The two halves of gl_run_from_device_mel for a caller that overlaps the vocoder with other work (xdtts_synthesize_sequence):
-// everything enqueued on g->stream, nothing waited for; then the wait, the engine's error word and -- after a timed-out
-// exchange -- the request again on the fallback engine (S is intact until the next enqueue).  Caller holds g->mu and the chip lock.
-// (p: null, or a prosody the caller has checked against F -- the stage then sits between mel -> linear and the loop, which
-// runs on S' with F' frames; gl_collect takes the same p)
-void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const xdtts_prosody *p) {
+// The loop alone on a state the caller has put in place (xdtts_griffinlim_infer_linear), then the audio in a pinned host buffer.
+void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, float **audio, size_t *n_samples,
+                          bool normalise) {
+  std::lock_guard<ChipLock> chip(chip_mutex(g->device));
+  g->probe_tick();
+  PinnedGuard host;
+  enqueue_run(g, b, phase0_dev, iters, normalise, host);
+  collect_run(g, b, phase0_dev, iters, normalise, host, audio, n_samples);
+}
+
+// The loop's buffers for a mel of F frames and prosody p (null: none): F' frames, sized for max(F, F')
+static GlBufs request_bufs(xdtts_griffinlim *g, int F, const xdtts_prosody *p) {
   const int Fp = p ? (int)prosody_frames((size_t)F, p->rate) : F;
-  GlBufs b = g->bufs(std::max(F, Fp));  // (before mel -> linear: growing S would drop its contents)
+  GlBufs b = g->bufs(std::max(F, Fp));  // (before mel -> linear: growing S would drop its contents; in gl_collect nothing grows)
   b.F = Fp;
-  const size_t N = (size_t)g->hop * (size_t)(Fp - 1);
+  return b;
+}
+// GriffinLim::infer (G1..G6) from a mel in HBM, in two halves for a caller that overlaps the vocoder with other work
+// (xdtts_synthesize_sequence): everything enqueued on g->stream, nothing waited for; then collect_run.  Caller holds g->mu and the
+// chip lock.
+// (p: null, or a prosody the caller has checked against F -- the stage then sits between mel -> linear and the loop, which
+// runs on S' with F' frames; the identity launches nothing.  gl_collect takes the same F and p.)
+void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const xdtts_prosody *p) {
+  GlBufs b = request_bufs(g, F, p);
   HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
   g->mel_to_linear(mel_dev_ptr, F);
   if (p) {
@@ -441,34 +463,19 @@ void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, i
   }
   HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
   g->probe_tick();
-  g->iterate(b, nullptr, g->iters);
-  launch_gl_output_normalise(g->audio.p, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
-  HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
-  if (!host.p) host = PinnedGuard(N);  // (the sequence hands in one it took from the pool while the frame loop ran)
-  HIP_CHECK(hipMemcpyAsync(host.p, g->audio.p, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
-  g->fetch_error_word();
+  enqueue_run(g, b, nullptr, g->iters, true, host);  // (the sequence hands in a buffer it took from the pool while the frame loop ran)
 }
 void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const xdtts_prosody *p) {
-  const int Fp = p ? (int)prosody_frames((size_t)F, p->rate) : F;
-  g->finish_timings();  // (drains the stream)
-  if (g->persistent_failed()) {
-    host = PinnedGuard();
-    GlBufs b = g->bufs(std::max(F, Fp));  // (the size of the enqueue: nothing is reallocated, S and S' are intact)
-    b.F = Fp;
-    if (p) b.S = g->prosody_S(*p);
-    gl_iterate_and_fetch(g, b, nullptr, g->iters, audio, n_samples, true);
-    return;
-  }
-  *audio = host.release();
-  *n_samples = (size_t)g->hop * (size_t)(Fp - 1);
+  GlBufs b = request_bufs(g, F, p);
+  if (p) b.S = g->prosody_S(*p);
+  collect_run(g, b, nullptr, g->iters, true, host, audio, n_samples);
 }
 
-void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, float **audio, size_t *n_samples) {
-  GlBufs b = g->bufs(F);
-  HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
-  g->mel_to_linear(mel_dev_ptr, F);
-  HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
-  gl_iterate_and_fetch(g, b, nullptr, g->iters, audio, n_samples, true);  // GriffinLim::infer: G1..G6
+void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const xdtts_prosody *p, float **audio, size_t *n_samples) {
+  std::lock_guard<ChipLock> chip(chip_mutex(g->device));
+  PinnedGuard host;
+  gl_enqueue_from_device_mel(g, mel_dev_ptr, F, host, p);
+  gl_collect(g, F, host, audio, n_samples, p);
 }
 
 // F' = F at rate 1, else max(floor((F - 1) / rate + 0.5), 1) + 1, in double
@@ -506,264 +513,169 @@ void prosody_check_array(const xdtts_prosody *p, int n_utt) {
   for (int u = 0; u < n_utt; ++u) prosody_check_at(&p[u], u, 2);
 }
 
-void gl_run_from_device_mel_prosody(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const xdtts_prosody &p, float **audio,
-                                    size_t *n_samples) {
-  const int Fmax = std::max(F, (int)prosody_frames((size_t)F, p.rate));
-  GlBufs b = g->bufs(Fmax);  // (before mel -> linear: growing S would drop its contents)
-  HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
-  g->mel_to_linear(mel_dev_ptr, F);
-  b.F = g->prosody(p, F);
-  b.S = g->prosody_S(p);
-  HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
-  gl_iterate_and_fetch(g, b, nullptr, g->iters, audio, n_samples, true);  // (a retry on the fallback engine finds S' intact)
-}
-
 // The vocoder half of a batch from a mel that is already in HBM (on g's device): [n_mels][sum Fu], utterance u at columns
 // fbase[u] .. fbase[u] + Fu[u].  mel -> linear is one GEMM over all frames, and the persistent kernel takes as many
-// utterances per launch as fit one workgroup per CU (a workgroup never spans two utterances and exchanges overlaps only
-// inside its own).  Caller holds g->mu.  The reads of the mel are enqueued on g->stream: the caller orders them behind
-// the mel's producer (a stream sync or an event wait on g->stream).
+// utterances per launch as fit one workgroup per CU (gl_plan.h: gl_batch_plan).  Caller holds g->mu.  The reads of the mel
+// are enqueued on g->stream: the caller orders them behind the mel's producer (a stream sync or an event wait on g->stream).
 // pros: null, or one prosody per utterance, each checked by the caller against its frame count.  With one that is not the
 // identity the ragged stage (k_prosody_batch) follows the GEMM: S [sum F_u] -> S_pros [sum F'_u], and everything behind it --
 // the rows of the loop's arrays, the packing into launches, the audio -- works from F'_u and reads S_pros.  Without one,
 // nothing new is launched.
 void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fin, float **audios, size_t *n_samples,
                           const xdtts_prosody *pros) {
-  {
-    const int n_utt = (int)Fin.size();
-    bool staged = false;
-    for (int u = 0; pros && u < n_utt; ++u) staged = staged || !prosody_is_identity(pros[u]);
-    std::vector<int> Fu(Fin);  // frames behind the stage: F'_u
-    std::vector<ProsodyUtt> ptab;
-    std::vector<int> fbase(n_utt), abase(n_utt);
-    size_t Fin_tot = 0, Ftot = 0, Ntot = 0;
+  const int n_utt = (int)Fin.size();
+  bool staged = false;
+  for (int u = 0; pros && u < n_utt; ++u) staged = staged || !prosody_is_identity(pros[u]);
+  Rows in, rows;  // the mel's frames F_u, and the frames behind the stage: F'_u
+  std::vector<ProsodyUtt> ptab;
+  std::vector<int> abase(n_utt);
+  size_t Ntot = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    const int Fp = staged ? (int)prosody_frames((size_t)Fin[u], pros[u].rate) : Fin[u];
+    if (staged) ptab.push_back({(int)in.total, Fin[u], (int)rows.total, Fp, pros[u].rate, pros[u].pitch, pros[u].lifter, pros[u].log_floor});
+    rows_add(in, (size_t)Fin[u], (size_t)1 << 24, "batch too large");
+    rows_add(rows, (size_t)Fp, (size_t)1 << 24, "batch too large");
+    abase[u] = (int)Ntot;
+    Ntot += (size_t)g->hop * (size_t)(Fp - 1);
+  }
+  const std::vector<int> &Fu = rows.F, &fbase = rows.row0;
+  HIP_CHECK(hipSetDevice(g->device));
+  hipStream_t st = g->stream;
+  std::vector<int> fl(rows.total);
+  for (int u = 0; u < n_utt; ++u)
+    for (int f = 0; f < Fu[u]; ++f) fl[(size_t)fbase[u] + f] = f;
+  g->frame_local.upload(fl.data(), fl.size(), st);
+  const bool use_spsi = g->phase_init == 1;
+  xdtts_griffinlim::SpsiTables spsi_tab;
+  if (use_spsi) g->spsi_tables(Fu, spsi_tab);  // (of the frames behind the prosody stage)
+  GlBufs all = g->bufs((int)std::max(in.total, rows.total));
+  all.F = (int)rows.total;
+  if (staged) {
+    g->pros_tab.upload(ptab.data(), ptab.size(), st);
+    g->S_pros.alloc(rows.total * (size_t)g->nb);
+    all.S = g->S_pros.p;
+  }
+  g->audio.alloc(std::max<size_t>(Ntot, 1));
+  HIP_CHECK(hipStreamSynchronize(st));  // the host vector above
+  const float alpha = g->momentum / (1.0f + g->momentum);
+  const int norm_mode = g->gopts.output_normalise;
+  std::lock_guard<ChipLock> chip(chip_mutex(g->device));
+  g->probe_tick();
+  for (int attempt = 0;; ++attempt) {
+    // mel -> linear, the ragged stages, the initial phase: all from the mel, so a retry starts from an intact S / S'
+    HIP_CHECK(hipEventRecord(g->ev.e[0], st));
+    g->mel_to_linear(mel_dev_all, (int)in.total);
+    if (staged) launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)rows.total, g->tw.p, st);
+    if (use_spsi) g->spsi_batch(all.S, spsi_tab, all.ang, all.tprev);
+    HIP_CHECK(hipEventRecord(g->ev.e[1], st));
+    if (!use_spsi) launch_gl_phase_init_batch(all, g->seed, g->frame_local.p, st);
+    // the plan, on the host while the device works on the above.  A handle without a usable persistent engine (demoted: the
+    // retry) gets the empty one: everything runs one by one on the launch-per-iteration kernels.
+    const GlBatchPlan plan = gl_batch_plan(Fu, g->hop, g->persistent_usable() ? g->n_cu : 0, g->per_cu4, g->gopts.batch_shape,
+                                           env::int_or(env::GL_BATCH_FORCE, 0));
+    std::vector<PinnedGuard> out;  // each utterance straight into the buffer the caller receives
+    out.reserve((size_t)n_utt);
+    for (int u = 0; u < n_utt; ++u) out.emplace_back((size_t)g->hop * (size_t)(Fu[u] - 1));
+    Drain drain(g->copy_stream);  // no buffer of `out` goes back to the pool while a copy into it may be in flight
+    // Output normalisation (G6): the utterances of one fetch are consecutive rows of `tab` (plan.order), so each fetch is
+    // preceded by ONE two-launch normalisation of exactly its utterances.
+    std::vector<int> tab_pos((size_t)n_utt, 0);
+    if (norm_mode) {
+      std::vector<int2> tab;
+      tab.reserve((size_t)n_utt);
+      for (int u : plan.order) {
+        tab_pos[(size_t)u] = (int)tab.size();
+        tab.push_back(make_int2(abase[u], g->hop * (Fu[u] - 1)));
+      }
+      g->norm_tab.upload(tab.data(), tab.size(), st);
+      g->norm_parts.alloc((size_t)GLN_SCRATCH * (size_t)n_utt);
+      HIP_CHECK(hipStreamSynchronize(st));
+    }
+    size_t n_ev = 0;
+    auto fetch_audio = [&](const std::vector<int> &utts) {  // after the work just enqueued on `st`
+      if (norm_mode && !utts.empty()) {
+        int n_max = 0;
+        for (int u : utts) n_max = std::max(n_max, g->hop * (Fu[u] - 1));
+        const int r0 = tab_pos[(size_t)utts[0]];
+        launch_gl_output_normalise(g->audio.p, g->norm_tab.p + r0, (int)utts.size(), 0, n_max, norm_mode, g->gopts.rms_target,
+                                   g->norm_parts.p + (size_t)r0 * GLN_SCRATCH, st);
+      }
+      hipEvent_t e = g->launch_done(n_ev++);
+      HIP_CHECK(hipEventRecord(e, st));
+      HIP_CHECK(hipStreamWaitEvent(g->copy_stream, e, 0));
+      for (int u : utts)
+        HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, g->audio.p + abase[u], sizeof(float) * (size_t)g->hop * (size_t)(Fu[u] - 1),
+                                 hipMemcpyDeviceToHost, g->copy_stream));
+    };
+    // the persistent launches, each followed by the fetch of its utterances
+    bool used_persistent = false;
+    if (!plan.segs.empty()) {
+      g->segs.upload(plan.segs.data(), plan.segs.size(), st);
+      HIP_CHECK(hipStreamSynchronize(st));
+      g->persist_prepare(gl_persistent_xch_words(g->n_cu * std::max(1, std::min(g->per_cu4, 2))),
+                         (unsigned)plan.launches.size() * ((unsigned)g->iters + 2u));
+      for (const GlBatchPlan::Launch &L : plan.launches) {
+        GlPersist p = g->persist_args(g->iters);
+        p.segs = g->segs.p + L.seg0;
+        p.nblk = L.nblk;
+        p.TF = plan.TF;
+        p.per_cu = plan.WG;
+        launch_gl_persistent(all, p, all.ang, all.tprev, g->iters, alpha, g->audio.p, st);
+        fetch_audio(L.utts);
+      }
+      used_persistent = true;
+    }
+    // the rest one by one (tiny / very long utterances, or a demoted handle)
     for (int u = 0; u < n_utt; ++u) {
-      if (staged) {
-        Fu[u] = (int)prosody_frames((size_t)Fin[u], pros[u].rate);
-        ptab.push_back({(int)Fin_tot, Fin[u], (int)Ftot, Fu[u], pros[u].rate, pros[u].pitch, pros[u].lifter, pros[u].log_floor});
-      }
-      Fin_tot += (size_t)Fin[u];
-      if (Fin_tot > (1u << 24)) fail(XDTTS_ERR_BAD_ARG, "batch too large");
-      fbase[u] = (int)Ftot;
-      abase[u] = (int)Ntot;
-      Ftot += (size_t)Fu[u];
-      Ntot += (size_t)g->hop * (size_t)(Fu[u] - 1);
-      if (Ftot > (1u << 24)) fail(XDTTS_ERR_BAD_ARG, "batch too large");
+      if (plan.batched[(size_t)u]) continue;
+      GlBufs v = all;
+      v.F = Fu[u];
+      v.S = all.S + (size_t)fbase[u] * g->nb;
+      v.ang = all.ang + (size_t)fbase[u] * g->nb;
+      v.ang2 = all.ang2 + (size_t)fbase[u] * g->nb;
+      v.tprev = all.tprev + (size_t)fbase[u] * g->nb;
+      v.frames = all.frames + (size_t)fbase[u] * g->n_fft;
+      v.wss_inv = all.wss_inv + abase[u];
+      launch_gl_prepare(v, st);
+      g->run_iterations(v, g->iters, alpha, g->audio.p + abase[u]);  // the engine the single-utterance call uses
+      used_persistent = used_persistent || g->last_persistent;
+      fetch_audio(std::vector<int>(1, u));
     }
-    HIP_CHECK(hipSetDevice(g->device));
-    hipStream_t st = g->stream;
-    std::vector<int> fl(Ftot);
-    for (int u = 0; u < n_utt; ++u)
-      for (int f = 0; f < Fu[u]; ++f) fl[(size_t)fbase[u] + f] = f;
-    g->frame_local.upload(fl.data(), fl.size(), st);
-    const bool use_spsi = g->phase_init == 1;
-    xdtts_griffinlim::SpsiTables spsi_tab;
-    if (use_spsi) g->spsi_tables(Fu, spsi_tab);  // (of the frames behind the prosody stage)
-    GlBufs all = g->bufs((int)std::max(Fin_tot, Ftot));
-    all.F = (int)Ftot;
-    if (staged) {
-      g->pros_tab.upload(ptab.data(), ptab.size(), st);
-      g->S_pros.alloc(Ftot * (size_t)g->nb);
-      all.S = g->S_pros.p;
+    HIP_CHECK(hipEventRecord(g->ev.e[2], st));
+    g->finish_timings();
+    HIP_CHECK(hipStreamSynchronize(g->copy_stream));
+    g->last_persistent = used_persistent;
+    if (g->persistent_failed()) {
+      if (attempt) fail(XDTTS_ERR_HIP, "Griffin-Lim batch: exchange failure on the fallback engine");
+      continue;  // demoted
     }
-    g->audio.alloc(std::max<size_t>(Ntot, 1));
-    HIP_CHECK(hipStreamSynchronize(st));  // the host vector above
-    const float alpha = g->momentum / (1.0f + g->momentum);
-    std::lock_guard<ChipLock> chip(chip_mutex(g->device));
-    g->probe_tick();
-    for (int attempt = 0;; ++attempt) {
-      HIP_CHECK(hipEventRecord(g->ev.e[0], st));
-      g->mel_to_linear(mel_dev_all, (int)Fin_tot);
-      if (staged) launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)Ftot, g->tw.p, st);  // (inside the loop: a retry starts from an intact S)
-      if (use_spsi) g->spsi_batch(all.S, spsi_tab, all.ang, all.tprev);  // (a retry recomputes it from the intact S / S')
-      HIP_CHECK(hipEventRecord(g->ev.e[1], st));
-      if (!use_spsi) launch_gl_phase_init_batch(all, g->seed, g->frame_local.p, st);
-      // pack consecutive utterances into persistent launches of <= one workgroup per CU.  A workgroup owns up to
-      // 4 frames (one wave each) or up to 8 (two waves per SIMD): an iteration of the 8-frame shape takes 6.8 us
-      // against 5.35 us (tools/gl_tf_sweep.py), so it wins as soon as it saves launches.  Two 4-frame workgroups
-      // per CU (k_gl_persistent<4, 2>: the state in LDS, 256 registers) take 7.1 us for the same eight frames
-      // (tools/vocoder_batch.py) and keep the 4-frame split, i.e. the single call's audio bit for bit.
-      const bool pers = g->persistent_usable();
-      std::vector<GlSeg> segs;
-      struct Launch { int seg0, nblk; std::vector<int> utts; };
-      std::vector<Launch> launches;
-      std::vector<char> batched(n_utt, 0);
-      auto pack = [&](int tf, int wg, bool build) {  // returns the relative cost: launches x time per iteration of the shape
-        // first-fit decreasing over launches of n_cu workgroups (which launch an utterance rides in does not
-        // change its audio: its own split into workgroups depends on its frame count alone)
-        std::vector<std::pair<int, int>> items;  // (workgroups, utterance)
-        int n_alone = 0;
-        for (int u = 0; u < n_utt; ++u) {
-          const int nb = (Fu[u] + tf - 1) / tf;
-          if (Fu[u] < 16 || nb > g->n_cu || Fu[u] / nb < 3) {  // on its own below
-            n_alone += Fu[u] >= 16;  // (a launch of the 5..8-frame shape; the tiny ones cost next to nothing)
-            continue;
-          }
-          items.emplace_back(nb, u);
-        }
-        std::stable_sort(items.begin(), items.end(), [](const std::pair<int, int> &a, const std::pair<int, int> &b) { return a.first > b.first; });
-        std::vector<int> room;                 // free workgroups of each launch
-        std::vector<std::vector<int>> riders;  // its utterances
-        for (const auto &it : items) {
-          size_t k = 0;
-          while (k < room.size() && room[k] < it.first) ++k;
-          if (k == room.size()) {
-            room.push_back(g->n_cu * wg);
-            riders.emplace_back();
-          }
-          room[k] -= it.first;
-          riders[k].push_back(it.second);
-        }
-        if (build)
-          for (size_t k = 0; k < riders.size(); ++k) {
-            const int seg0 = (int)segs.size();
-            for (int u : riders[k]) {
-              const int nb = (Fu[u] + tf - 1) / tf;
-              for (int b = 0; b < nb; ++b) {
-                GlSeg sg{};
-                sg.fbase = fbase[u];
-                sg.F = Fu[u];
-                sg.f0 = (int)(((long long)b * Fu[u]) / nb);
-                sg.n_own = (int)(((long long)(b + 1) * Fu[u]) / nb) - sg.f0;
-                sg.first = b == 0;
-                sg.last = b + 1 == nb;
-                sg.abase = abase[u];
-                segs.push_back(sg);
-              }
-              batched[u] = 1;
-            }
-            launches.push_back({seg0, (int)segs.size() - seg0, riders[k]});
-          }
-        // us per iteration of one launch of each shape (tools/vocoder_shapes.py, round 4 with the 16-byte exchange granules:
-        // 4.5-5.2 / 5.8-6.3 / 5.9-6.3; round 3: 5.35 / 7.1 / 6.8) -- at equal cost the 4-frame shape, whose audio is the single call's
-        return (tf <= 4 ? (wg > 1 ? 6.0 : 4.85) : 6.1) * (double)riders.size() + 6.1 * n_alone;
-      };
-      int TF = 4, WG = 1;
-      if (pers) {
-        // (the 4-frame shape splits an utterance the way its own call does, one or two workgroups per CU: batch_shape 4)
-        if (g->per_cu4 >= 2 && pack(4, 2, false) < pack(4, 1, false)) WG = 2;
-        if (g->gopts.batch_shape == 0 && pack(GLP_TF_MAX, 1, false) < pack(4, WG, false)) TF = GLP_TF_MAX, WG = 1;
-        if (env::is_set(env::GL_BATCH_FORCE)) {  // developer: "8" = 8-frame workgroups, "41" / "42" = 4-frame, one / two per CU
-          const int v = env::int_or(env::GL_BATCH_FORCE, 0);
-          if (v == 8) TF = GLP_TF_MAX, WG = 1;
-          if (v == 41) TF = 4, WG = 1;
-          if (v == 42 && g->per_cu4 >= 2) TF = 4, WG = 2;
-        }
-        pack(TF, WG, true);
-      }
-      bool used_persistent = false;
-      std::vector<PinnedGuard> out;  // each utterance straight into the buffer the caller receives
-      out.reserve((size_t)n_utt);
-      for (int u = 0; u < n_utt; ++u) out.emplace_back((size_t)g->hop * (size_t)(Fu[u] - 1));
-      Drain drain(g->copy_stream);  // no buffer of `out` goes back to the pool while a copy into it may be in flight
-      // Output normalisation (G6): the utterances of one fetch are consecutive rows of `tab` (launch by launch, then the
-      // ones that run alone), so each fetch is preceded by ONE two-launch normalisation of exactly its utterances.
-      const int norm_mode = g->gopts.output_normalise;
-      std::vector<int> tab_pos((size_t)n_utt, 0);
-      if (norm_mode) {
-        std::vector<int2> tab;
-        tab.reserve((size_t)n_utt);
-        auto add = [&](int u) {
-          tab_pos[(size_t)u] = (int)tab.size();
-          tab.push_back(make_int2(abase[u], g->hop * (Fu[u] - 1)));
-        };
-        for (const Launch &L : launches)
-          for (int u : L.utts) add(u);
-        for (int u = 0; u < n_utt; ++u)
-          if (!batched[u]) add(u);
-        g->norm_tab.upload(tab.data(), tab.size(), st);
-        g->norm_parts.alloc((size_t)GLN_SCRATCH * (size_t)n_utt);
-        HIP_CHECK(hipStreamSynchronize(st));
-      }
-      size_t n_ev = 0;
-      auto fetch_audio = [&](const std::vector<int> &utts) {  // after the work just enqueued on `st`
-        if (norm_mode && !utts.empty()) {
-          int n_max = 0;
-          for (int u : utts) n_max = std::max(n_max, g->hop * (Fu[u] - 1));
-          const int r0 = tab_pos[(size_t)utts[0]];
-          launch_gl_output_normalise(g->audio.p, g->norm_tab.p + r0, (int)utts.size(), 0, n_max, norm_mode, g->gopts.rms_target,
-                                     g->norm_parts.p + (size_t)r0 * GLN_SCRATCH, st);
-        }
-        hipEvent_t e = g->launch_done(n_ev++);
-        HIP_CHECK(hipEventRecord(e, st));
-        HIP_CHECK(hipStreamWaitEvent(g->copy_stream, e, 0));
-        for (int u : utts)
-          HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, g->audio.p + abase[u], sizeof(float) * (size_t)g->hop * (size_t)(Fu[u] - 1),
-                                   hipMemcpyDeviceToHost, g->copy_stream));
-      };
-      if (!segs.empty()) {
-        g->segs.upload(segs.data(), segs.size(), st);
-        HIP_CHECK(hipStreamSynchronize(st));
-        g->persist_prepare(gl_persistent_xch_words(g->n_cu * std::max(1, std::min(g->per_cu4, 2))),
-                           (unsigned)launches.size() * ((unsigned)g->iters + 2u));
-        for (const Launch &L : launches) {
-          GlPersist p = g->persist_args(g->iters);
-          p.segs = g->segs.p + L.seg0;
-          p.nblk = L.nblk;
-          p.TF = TF;
-          p.per_cu = WG;
-          launch_gl_persistent(all, p, all.ang, all.tprev, g->iters, alpha, g->audio.p, st);
-          fetch_audio(L.utts);
-        }
-        used_persistent = true;
-      }
-      for (int u = 0; u < n_utt; ++u) {  // the rest one by one (tiny / very long utterances, or a demoted handle)
-        if (batched[u]) continue;
-        GlBufs v = all;
-        v.F = Fu[u];
-        v.S = all.S + (size_t)fbase[u] * g->nb;
-        v.ang = all.ang + (size_t)fbase[u] * g->nb;
-        v.ang2 = all.ang2 + (size_t)fbase[u] * g->nb;
-        v.tprev = all.tprev + (size_t)fbase[u] * g->nb;
-        v.frames = all.frames + (size_t)fbase[u] * g->n_fft;
-        v.wss_inv = all.wss_inv + abase[u];
-        launch_gl_prepare(v, st);
-        g->run_iterations(v, g->iters, alpha, g->audio.p + abase[u]);  // the engine the single-utterance call uses
-        used_persistent = used_persistent || g->last_persistent;
-        fetch_audio(std::vector<int>(1, u));
-      }
-      HIP_CHECK(hipEventRecord(g->ev.e[2], st));
-      g->finish_timings();
-      HIP_CHECK(hipStreamSynchronize(g->copy_stream));
-      g->last_persistent = used_persistent;
-      if (g->persistent_failed()) {
-        if (attempt) fail(XDTTS_ERR_HIP, "Griffin-Lim batch: exchange failure on the fallback engine");
-        continue;  // demoted: everything runs one by one on the launch-per-iteration kernels
-      }
-      for (int u = 0; u < n_utt; ++u) {
-        audios[u] = out[(size_t)u].release();
-        n_samples[u] = (size_t)g->hop * (size_t)(Fu[u] - 1);
-      }
-      return;
+    for (int u = 0; u < n_utt; ++u) {
+      audios[u] = out[(size_t)u].release();
+      n_samples[u] = (size_t)g->hop * (size_t)(Fu[u] - 1);
     }
+    return;
   }
 }
 
-AnRows gl_analysis_enqueue(xdtts_griffinlim *g, const float *const *audios, const size_t *n_samples, int n_utt, bool want_mel) {
-  AnRows rows;
-  rows.row0.resize((size_t)n_utt);
-  rows.F.resize((size_t)n_utt);
+void gl_analysis_enqueue(xdtts_griffinlim *g, const float *const *audios, const size_t *n_samples, const Rows &rows, bool want_mel) {
+  const int n_utt = rows.n();
   std::vector<long long> abase((size_t)n_utt);
   std::vector<AnSeg> segs;
-  size_t Ftot = 0, Ntot = 0;
+  size_t Ntot = 0;
   for (int u = 0; u < n_utt; ++u) {
-    const size_t n = n_samples[u], F = n / (size_t)g->hop + 1;
-    rows.row0[(size_t)u] = (int)Ftot;
-    rows.F[(size_t)u] = (int)F;
     abase[(size_t)u] = (long long)Ntot;
-    for (size_t f0 = 0; f0 < F; f0 += 4) {  // a workgroup: four consecutive frames of one utterance
+    for (int f0 = 0; f0 < rows.F[(size_t)u]; f0 += 4) {  // a workgroup: four consecutive frames of one utterance
       AnSeg sg{};
       sg.abase = (long long)Ntot;
-      sg.n = (int)n;
-      sg.F = (int)F;
-      sg.f0 = (int)f0;
-      sg.row0 = (int)Ftot;
+      sg.n = (int)n_samples[u];
+      sg.F = rows.F[(size_t)u];
+      sg.f0 = f0;
+      sg.row0 = rows.row0[(size_t)u];
       segs.push_back(sg);
     }
-    Ftot += F;
-    Ntot += n;
+    Ntot += n_samples[u];
   }
-  rows.Ftot = (int)Ftot;
+  const size_t Ftot = rows.total;
   hipStream_t st = g->stream;
   g->an_audio.alloc(Ntot);
   for (int u = 0; u < n_utt; ++u)
@@ -795,7 +707,6 @@ AnRows gl_analysis_enqueue(xdtts_griffinlim *g, const float *const *audios, cons
     a.tile = 32;  // one tile shape whatever the row count: a frame's mel does not depend on what else is in the batch
     launch_gemm_nt(a, st);
   }
-  return rows;
 }
 
 void gl_analysis_finish_timings(xdtts_griffinlim *g) {

@@ -10,6 +10,14 @@ namespace xdtts {
 inline bool prosody_is_identity(const xdtts_prosody &p) { return p.rate == 1.0f && p.pitch == 1.0f; }
 size_t prosody_frames(size_t F, float rate);                   // 0 for a bad argument
 void prosody_check(const xdtts_prosody *p, size_t n_frames);  // fails with XDTTS_ERR_BAD_ARG and a message
+// Rows::add (gl_plan.h, which knows no status codes) inside a request: past the cap it fails with XDTTS_ERR_BAD_ARG and the text
+inline void rows_add(Rows &r, size_t rows, size_t cap, const char *too_large) {
+  try {
+    r.add(rows, cap, too_large);
+  } catch (const std::length_error &e) {
+    fail(XDTTS_ERR_BAD_ARG, "%s", e.what());
+  }
+}
 }  // namespace xdtts
 
 struct xdtts_griffinlim {
@@ -91,6 +99,9 @@ struct xdtts_griffinlim {
 
   ~xdtts_griffinlim();
   GlBufs bufs(int F);
+  // The ragged parity hooks: utterance u's magnitude in the boundary layout (nb x F_u), uploaded through `frames` and transposed
+  // into its rows of S [rows.total][nb], on the stream.  bufs(>= rows.total) first.
+  void upload_rows(const float *const *S_host, const xdtts::Rows &rows);
   void mel_to_linear(const float *mel_dev_ptr, int F);
   // S [F][nb] -> S_pros [F'][nb] in one launch on the stream; returns F'.  The identity launches nothing and returns F.
   // The caller then points GlBufs.S at prosody_S(p) with F' frames; its bufs() was sized for max(F, F').
@@ -117,15 +128,16 @@ void host_pinv(const float *basis, int n, int nbins, std::vector<float> &out);
 double host_lipschitz(const float *basis, int n, int nbins);
 void mel_filter_bank(double sr, int n_fft, int n_mels, double fmin, double fmax, float *out);
 
+// The loop alone on the S in place (infer_linear: a caller's phase0 and iteration count, no normalisation); takes the chip lock.
 void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, float **audio, size_t *n_samples,
                           bool normalise);
-// (p: null, or a checked prosody -- the single-utterance stage behind mel -> linear; F stays the mel's frame count in both halves)
+// GriffinLim::infer from a mel in HBM, the one single-utterance request path: chip lock, gl_enqueue_from_device_mel, gl_collect.
+// (p: null, or a checked prosody -- the single-utterance stage behind mel -> linear, last_ms[0] covers both; F stays the mel's
+// frame count everywhere)
+void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const xdtts_prosody *p, float **audio, size_t *n_samples);
+// ... and its two halves for a caller that holds the chip lock itself and works between them (the sequence entry)
 void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const xdtts_prosody *p = nullptr);
 void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const xdtts_prosody *p = nullptr);
-void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, float **audio, size_t *n_samples);
-// ... with the prosody stage between mel -> linear and the loop (p checked by the caller: prosody_check); last_ms[0] covers both
-void gl_run_from_device_mel_prosody(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const xdtts_prosody &p, float **audio,
-                                    size_t *n_samples);
 // (pros: null, or one checked prosody per utterance -- the ragged stage behind the one mel -> linear GEMM; audios[u] then has
 // hop * (F'_u - 1) samples)
 void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples,
@@ -135,13 +147,9 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
 void prosody_check_array(const xdtts_prosody *p, int n_utt);
 void prosody_check_at(const xdtts_prosody *p, int u, size_t n_frames);  // prosody_check for utterance u of a batch or sequence
 
-// Analysis of n_utt audios in one k_stft_mag launch: g->an_S [Ftot][nb] = |STFT|, and with want_mel g->an_melT [Ftot][n_mels] =
-// an_S^e . basis^T (linear mel, before compression).  Returns each utterance's first row and frame count.  Everything is
-// enqueued on g->stream behind an_ev.e[0]; an_ev.e[1] follows the magnitude kernel.  Caller holds g->mu.
-struct AnRows {
-  std::vector<int> row0, F;
-  int Ftot = 0;
-};
-AnRows gl_analysis_enqueue(xdtts_griffinlim *g, const float *const *audios, const size_t *n_samples, int n_utt, bool want_mel);
+// Analysis of the audios in one k_stft_mag launch: utterance u's n_samples[u] / hop + 1 frames are its rows of `rows`;
+// g->an_S [rows.total][nb] = |STFT|, and with want_mel g->an_melT [rows.total][n_mels] = an_S^e . basis^T (linear mel, before
+// compression).  Everything is enqueued on g->stream behind an_ev.e[0]; an_ev.e[1] follows the magnitude kernel.  Caller holds g->mu.
+void gl_analysis_enqueue(xdtts_griffinlim *g, const float *const *audios, const size_t *n_samples, const Rows &rows, bool want_mel);
 void gl_analysis_finish_timings(xdtts_griffinlim *g);  // drains the stream; an_ms from an_ev.e[0..2] (e[2]: recorded by the caller behind its last kernel)
 }  // namespace xdtts

@@ -1,6 +1,7 @@
 // kernels.h -- host-side launch interface of the HIP kernels (gfx950).
 #pragma once
 #include "common.h"
+#include "gl_plan.h"
 #include "weights.h"
 
 namespace xdtts {
@@ -232,20 +233,7 @@ struct GlBufs {
 // Persistent Griffin-Lim (griffinlim.hip: k_gl_persistent): all iterations + the final ISTFT in one
 // launch, one workgroup per CU owning 3..TF consecutive frames, state in LDS, 768-sample overlaps
 // exchanged with the two neighbours as tagged 8-byte granules.
-constexpr int GLP_TF_MAX = 8;  // frames per workgroup (LDS: 10.3 KB of state + 4 KB of frame each; 8 waves = 2 per SIMD)
-// One workgroup's share when a launch covers SEVERAL utterances (vocoder batch): the utterances' frames
-// are concatenated in S / angles / previous spectrum, workgroups never span two utterances and exchange
-// overlaps only inside their own.
-struct GlSeg {
-  int fbase;   // row of the utterance's first frame in the concatenated arrays
-  int F;       // frames of the utterance
-  int f0;      // first own frame, within the utterance
-  int n_own;   // own frames (3..TF)
-  int first;   // no left neighbour
-  int last;    // no right neighbour
-  int abase;   // offset of the utterance's samples in the audio output
-  int pad;
-};
+// (GLP_TF_MAX, GlSeg and the host's planning arithmetic: gl_plan.h)
 struct GlPersist {
   const GlSeg *segs;        // [nblk] or null = one utterance of g.F frames split evenly over the workgroups
   unsigned long long *xch;  // [nblk][2 parities][2 sides][768] granules
@@ -261,7 +249,6 @@ struct GlPersist {
   float2 *ang_out, *tprev_out;  // parity hook: final state, or null
   unsigned long long *prof;     // developer profile build only: [nblk][12] phase clocks, else null
 };
-bool gl_persistent_plan(int F, int n_cu, int *TF, int *nblk);
 size_t gl_persistent_xch_words(int nblk);
 bool gl_persistent_supported(int device, int *n_cu, int *per_cu4);
 void launch_gl_persistent(const GlBufs &g, const GlPersist &p, const float2 *ang_in, const float2 *tprev_in, int n_iter,
