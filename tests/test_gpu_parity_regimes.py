@@ -31,7 +31,7 @@ wl = importlib.import_module("xd-tts_amd.workloads")
 
 NAMES = {"attention_hidden": "att_h", "attention_cell": "att_c", "decoder_hidden": "dec_h", "decoder_cell": "dec_c",
          "attention_weights": "aw", "attention_weights_cum": "awc", "attention_context": "ctx"}
-ENGINES = [("persistent", 1), ("persistent", 2), ("batched", 6), ("launch", 3), ("persistent8", 3), ("persistent8", 8)]
+ENGINES = [("persistent", 1), ("persistent", 2), ("batched", 6), ("launch", 3), ("persistent8", 3), ("persistent8", 8), ("persistent8", 12)]  # (12: the 16-slot kernel)
 REGIMES = ["plain-7", "plain-99", "trained-20240327", "trained-7"]
 REPORT = {}
 
@@ -77,7 +77,7 @@ def snapshot(states, T):
 
 
 def chunks_for(orc, blob, B):
-    lens = [37, 91, 12, 58, 23, 100, 64, 5][:B]
+    lens = [37, 91, 12, 58, 23, 100, 64, 5, 77, 19, 46, 83][:B]
     mem, pm = [], []
     for i, n in enumerate(lens):
         ids = np.zeros(100, dtype=np.int64)
