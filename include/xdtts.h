@@ -313,7 +313,7 @@ xdtts_status xdtts_griffinlim_mel_to_linear(xdtts_griffinlim *g, const float *me
 xdtts_status xdtts_griffinlim_step(xdtts_griffinlim *g, const float *S, float *angles,
                                    float *rebuilt, size_t n_frames, size_t n_iter);
 
-/* ms[0] mel->linear (for the *_prosody entries: mel->linear and the prosody stage; with phase_init 1 the SPSI stage as well:
+/* ms[0] mel->linear (for the *_prosody and *_contour entries: mel->linear and the prosody stage; with phase_init 1 the SPSI stage as well:
  * everything in front of the loop), ms[1] iterations, ms[2] total of the last call (HIP events).  After
  * xdtts_griffinlim_prosody_linear and xdtts_griffinlim_spsi_phase (and their _batch forms): ms[0] the stage alone, ms[1] the
  * layout change behind it. */
@@ -363,8 +363,8 @@ xdtts_status xdtts_griffinlim_analysis_timings(const xdtts_griffinlim *g, float 
  * nothing: the results are then the bits of the entries without a prosody argument.
  * The batch and sequence entries take one prosody PER UTTERANCE (the *_batch_prosody / *_sequence_prosody entries below): a
  * batch runs the stage as one ragged launch behind its one mel -> linear GEMM, a sequence runs the single-utterance stage in each
- * utterance's vocoder half.  Out of scope: a prosody per chunk inside one utterance, and a per-frame rate (the rate is uniform
- * over the utterance). */
+ * utterance's vocoder half.  xdtts_prosody is uniform over its utterance; rate, pitch and gain that vary inside one are
+ * xdtts_prosody_contour below. */
 typedef struct {
   float rate;
   float pitch;
@@ -401,6 +401,72 @@ xdtts_status xdtts_griffinlim_infer_batch_prosody(xdtts_griffinlim *g, const flo
 xdtts_status xdtts_griffinlim_prosody_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames,
                                                    int32_t n_utt, const xdtts_prosody *p /* [n_utt] */, float *const *S_outs,
                                                    size_t *n_frames_out);
+
+/* Prosody contours: rate, pitch and gain that VARY inside one utterance -- what nested SSML <prosody> spans and
+ * <prosody contour="(0%,+20%) (40%,-10%)"> ask for, without cutting the sentence at every span boundary (which would lose
+ * coarticulation and Tacotron2's own phrasing; INTEGRATION.md section 1 maps the SSML to points).  A contour is a list of
+ * points (pos, rate, pitch, gain); pos is a FRACTION OF THE UTTERANCE'S OWN DURATION (0 = first frame, 1 = last frame), as in
+ * an SSML contour, so no attention alignment is needed.  xdtts_prosody itself is unchanged.
+ * Argument rules: n_points in [1, 64]; pos finite, in [0, 1] and non-decreasing over the points (two points at one pos make a
+ * step); rate in [0.25, 4]; pitch in [0.5, 2]; gain in [0, 8] (a linear amplitude factor, 0 mutes); every field finite; lifter
+ * in [1, 255] and log_floor > 0 as in xdtts_prosody.  The contour is the IDENTITY when every point has rate == pitch == gain
+ * == 1.  F >= 2 and F <= 16384 unless the contour is the identity (which takes what xdtts_prosody takes, F = 1 included).
+ * Anything else is XDTTS_ERR_BAD_ARG, found before a device is touched; the message names the field and the point's index, in
+ * the array entries the utterance's index too.
+ * Value of a field v at position x -- host arithmetic in double, in exactly this order of operations:
+ *   k = the number of points with pos <= x;  k == 0: v[0];  k == n: v[n-1];  else with a = k - 1, b = k:
+ *   v[a] + (v[b] - v[a]) * ((x - pos[a]) / (pos[b] - pos[a]))
+ * (a step is right-continuous; values hold constant before the first point and after the last).
+ * Frame table, host arithmetic, one entry per input frame m = 0 .. F - 1:
+ *   q[m] = (uint32) floor(65536.0 / rate((m + 0.5) / (F - 1)) + 0.5) for m < F - 1: the slowness of interval m in 2^-16 output frames
+ *   c[0] = 0, c[m + 1] = c[m] + q[m];  C = c[F - 1]  (F <= 16384 keeps C below 2^32)
+ *   pitch_m = (float) pitch(m / (F - 1)),  gain_m = (float) gain(m / (F - 1))
+ *   F' = max((C + 32768) >> 16, 1) + 1;  the audio has hop * (F' - 1) samples.
+ * Output frame j, device arithmetic in fp32 on integers that are exact:
+ *   t = min(j * 65536, C);  i = the interval with c[i] <= t < c[i + 1] (t == C: i = F - 2);  w = (float)(t - c[i]) / (float)q[i]
+ *   St[k] = (1 - w) S[i][k] + w S[i + 1][k]                      (the magnitude interpolation of xdtts_prosody)
+ *   pj = fmaf(w, pitch_{i+1} - pitch_i, pitch_i),  gj = fmaf(w, gain_{i+1} - gain_i, gain_i)
+ *   pj == 1:  S'[j] = gj * St                                     (an exact zero stays one)
+ *   else      S'[j][k] = gj * exp(E[k] + R'[k]), with E, R and R' exactly as in xdtts_prosody and p = k / pj.
+ * The contours ride the same warp as the frames, so a step becomes a one-frame ramp; the a + w (b - a) form keeps pj at
+ * exactly 1 wherever both neighbours are 1, so the cheap branch covers whole unmodified spans.
+ * Properties: a one-point contour of rate r is NOT the bits of xdtts_prosody{r} (the slowness is quantised), and F' can differ
+ * by one from xdtts_prosody_frames (at most one for F in {2, 3, 5, 37, 48, 800, 16384} and ten rates; e.g. F = 3, r = 0.8).  A
+ * rate-1 contour maps frame j to frame j exactly: c[m] = 65536 m.  The identity contour launches nothing and returns the bits
+ * of the plain entries; an identity utterance inside a mixed batch is copied.  Batch == single, bit for bit: one kernel serves both.
+ * Out of scope: the sequence entries (a caller loops over xdtts_synthesize_ids_contour); absolute-Hz and semitone targets (the
+ * host converts them to factors); positions in seconds or phonemes (these need alignments). */
+typedef struct { float pos, rate, pitch, gain; } xdtts_prosody_point;   /* 16 bytes */
+typedef struct {
+  const xdtts_prosody_point *points;   /* host memory, read during the call only */
+  int32_t n_points;                    /* 1 .. 64 */
+  int32_t lifter;                      /* as xdtts_prosody: 1 .. 255, default 30 */
+  float   log_floor;                   /* > 0, default 1e-5 */
+} xdtts_prosody_contour;
+void xdtts_prosody_contour_default(xdtts_prosody_contour *c); /* no points (NULL, 0), lifter 30, log_floor 1e-5 */
+/* F' for F = n_frames; host arithmetic, no handle.  0 for a bad argument. */
+size_t xdtts_prosody_contour_frames(const xdtts_prosody_contour *c, size_t n_frames);
+/* The frame table: cum (c), pitch and gain hold n_frames entries each, each pointer may be NULL.  Host arithmetic, no handle.
+ * 1 <= n_frames <= 16384 (one frame: the identity alone, as everywhere). */
+xdtts_status xdtts_prosody_contour_table(const xdtts_prosody_contour *c, size_t n_frames, uint32_t *cum, float *pitch, float *gain);
+/* Parity hooks, the contour stage alone, shaped like xdtts_griffinlim_prosody_linear and _prosody_linear_batch: S_out /
+ * S_outs[u] are caller buffers sized by xdtts_prosody_contour_frames.  Every S_outs[u] of the ragged form equals the single
+ * hook's bit for bit, whatever the mix and the order.  last_timings: ms[0] = the launch alone, ms[1] = the layout change behind
+ * it, ms[2] = both and the upload of the table in front of them. */
+xdtts_status xdtts_griffinlim_contour_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_prosody_contour *c,
+                                             float *S_out, size_t *n_frames_out);
+xdtts_status xdtts_griffinlim_contour_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames,
+                                                   int32_t n_utt, const xdtts_prosody_contour *c /* [n_utt] */, float *const *S_outs,
+                                                   size_t *n_frames_out);
+/* xdtts_griffinlim_infer / _infer_batch with the contour stage between mel -> linear and the loop: audio has hop * (F' - 1)
+ * samples; last_timings ms[0] covers mel -> linear and the stage.  The array entry follows the array rules above
+ * xdtts_griffinlim_infer_batch_prosody (arguments checked before the handles are looked at, outputs cleared on error); with
+ * opts.batch_shape = 4 audios[u] is what xdtts_griffinlim_infer_contour returns for that utterance alone, bit for bit. */
+xdtts_status xdtts_griffinlim_infer_contour(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
+                                            const xdtts_prosody_contour *c, float **audio, size_t *n_samples);
+xdtts_status xdtts_griffinlim_infer_batch_contour(xdtts_griffinlim *g, const float *const *mels, size_t n_mels,
+                                                  const size_t *n_frames, int32_t n_utt, const xdtts_prosody_contour *c /* [n_utt] */,
+                                                  float **audios, size_t *n_samples);
 
 /* The initial phase of the loop.  Mode 0 (the default, the crate's behaviour) draws it from the seeded random stream; mode 1
  * computes it from the magnitude by Single Pass Spectrogram Inversion (Beauregard, Harish, Wyse 2015), which lowers the
@@ -452,6 +518,12 @@ xdtts_status xdtts_synthesize_ids_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *
                                           size_t n, const size_t *splits, size_t n_splits,
                                           const xdtts_infer_opts *opts, const xdtts_prosody *p, float **mel,
                                           size_t *n_frames, float **audio, size_t *n_samples);
+/* ... and with a contour (xdtts_prosody_contour above): *mel is Tacotron2's own mel, *audio has hop * (F' - 1) samples, F' =
+ * xdtts_prosody_contour_frames(c, *n_frames).  The table is built once the frame count is known. */
+xdtts_status xdtts_synthesize_ids_contour(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids,
+                                          size_t n, const size_t *splits, size_t n_splits,
+                                          const xdtts_infer_opts *opts, const xdtts_prosody_contour *c, float **mel,
+                                          size_t *n_frames, float **audio, size_t *n_samples);
 
 /* XdTts::infer (src/lib.rs:110-159) for n_utt utterances in one call -- the "batched / parallel
  * sentences" the author notes at src/phonemes.rs:677-680, BASELINE.json configs[3].  The chunks of
@@ -477,6 +549,14 @@ xdtts_status xdtts_synthesize_batch_prosody(xdtts_tacotron2 *h, xdtts_griffinlim
                                             const int32_t *utt_chunks, int32_t n_utt,
                                             const xdtts_infer_opts *opts, const int32_t *fixed_steps_per_item,
                                             const xdtts_prosody *p /* [n_utt] */, float **mels, size_t *n_frames,
+                                            float **audios, size_t *n_samples);
+/* ... and with one contour per utterance (array rules as above).  Results equal xdtts_tacotron2_infer_batch followed by
+ * xdtts_griffinlim_infer_batch_contour bit for bit. */
+xdtts_status xdtts_synthesize_batch_contour(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids,
+                                            const int32_t *lens, int32_t B, int32_t t_stride,
+                                            const int32_t *utt_chunks, int32_t n_utt,
+                                            const xdtts_infer_opts *opts, const int32_t *fixed_steps_per_item,
+                                            const xdtts_prosody_contour *c /* [n_utt] */, float **mels, size_t *n_frames,
                                             float **audios, size_t *n_samples);
 
 /* XdTts::infer (src/lib.rs:110-159) for a SEQUENCE of n_utt utterances, each decoded alone (batch 1) exactly as

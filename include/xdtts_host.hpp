@@ -182,6 +182,60 @@ class GriffinLim {
     check(xdtts_griffinlim_prosody_linear_batch(g_, sp.data(), nf.data(), (int32_t)n, p.data(), op.data(), nullptr));
     return out;
   }
+  // Rate, pitch and gain that vary INSIDE an utterance (xdtts_prosody_contour: points (pos, rate, pitch, gain), pos a fraction of
+  // the utterance's duration): infer() with the contour stage between mel -> linear and the loop.  The audio has
+  // 256 * (xdtts_prosody_contour_frames(&c, mel.cols) - 1) samples.
+  std::vector<float> infer(const Array2 &mel, const xdtts_prosody_contour &c) const {
+    float *audio = nullptr;
+    size_t n = 0;
+    check(xdtts_griffinlim_infer_contour(g_, mel.data.data(), mel.rows, mel.cols, &c, &audio, &n));
+    std::vector<float> out(audio, audio + n);
+    xdtts_free(audio);
+    return out;
+  }
+  // ... the stage alone (parity hooks: xdtts_griffinlim_contour_linear, and the ragged xdtts_griffinlim_contour_linear_batch)
+  Array2 contour_linear(const Array2 &S, const xdtts_prosody_contour &c) const {
+    const size_t Fp = xdtts_prosody_contour_frames(&c, S.cols);
+    Array2 out{n_bins_, Fp, std::vector<float>(n_bins_ * (Fp ? Fp : 1))};
+    check(xdtts_griffinlim_contour_linear(g_, S.data.data(), S.cols, &c, out.data.data(), nullptr));
+    return out;
+  }
+  std::vector<Array2> contour_linear_batch(const std::vector<Array2> &S, const std::vector<xdtts_prosody_contour> &c) const {
+    const size_t n = S.size();
+    if (c.size() != n) throw std::runtime_error("xdtts: one contour per utterance");
+    std::vector<Array2> out(n);
+    std::vector<const float *> sp(n);
+    std::vector<float *> op(n);
+    std::vector<size_t> nf(n);
+    for (size_t u = 0; u < n; ++u) {
+      const size_t Fp = xdtts_prosody_contour_frames(&c[u], S[u].cols);
+      out[u] = Array2{n_bins_, Fp, std::vector<float>(n_bins_ * (Fp ? Fp : 1))};
+      sp[u] = S[u].data.data();
+      op[u] = out[u].data.data();
+      nf[u] = S[u].cols;
+    }
+    check(xdtts_griffinlim_contour_linear_batch(g_, sp.data(), nf.data(), (int32_t)n, c.data(), op.data(), nullptr));
+    return out;
+  }
+  // ... and for several utterances in one call, one contour per utterance (xdtts_griffinlim_infer_batch_contour)
+  std::vector<std::vector<float>> infer_batch(const std::vector<Array2> &mels, const std::vector<xdtts_prosody_contour> &c) const {
+    const size_t n = mels.size();
+    if (c.size() != n) throw std::runtime_error("xdtts: one contour per utterance");
+    std::vector<const float *> mp(n);
+    std::vector<size_t> nf(n), ns(n, 0);
+    std::vector<float *> audios(n, nullptr);
+    for (size_t u = 0; u < n; ++u) {
+      mp[u] = mels[u].data.data();
+      nf[u] = mels[u].cols;
+    }
+    check(xdtts_griffinlim_infer_batch_contour(g_, mp.data(), n ? mels[0].rows : 0, nf.data(), (int32_t)n, c.data(), audios.data(), ns.data()));
+    std::vector<std::vector<float>> out(n);
+    for (size_t u = 0; u < n; ++u) {
+      out[u].assign(audios[u], audios[u] + ns[u]);
+      xdtts_free(audios[u]);
+    }
+    return out;
+  }
   // The conventions of the crate's mel->linear step as switches (xdtts_griffinlim_opts)
   void set_opts(const xdtts_griffinlim_opts &o) { check(xdtts_griffinlim_set_opts(g_, &o)); }
   xdtts_griffinlim_opts opts() const {
@@ -246,6 +300,35 @@ inline xdtts_prosody default_prosody() {  // rate 1, pitch 1, lifter 30, log_flo
   return p;
 }
 
+// A contour that owns its points (xdtts_prosody_contour borrows them): rate, pitch and gain that vary inside an utterance, what
+// nested SSML <prosody> spans and contour="(0%,+20%) (40%,-10%)" attributes map to.
+struct ProsodyContour {
+  std::vector<xdtts_prosody_point> points;  // (pos, rate, pitch, gain), pos in [0, 1] non-decreasing
+  int32_t lifter = 30;
+  float log_floor = 1e-5f;
+  xdtts_prosody_contour c() const {  // valid while this object lives and its points are not resized
+    xdtts_prosody_contour o;
+    xdtts_prosody_contour_default(&o);
+    o.points = points.data();
+    o.n_points = (int32_t)points.size();
+    o.lifter = lifter;
+    o.log_floor = log_floor;
+    return o;
+  }
+  size_t frames(size_t n_frames) const {  // F' (xdtts_prosody_contour_frames); 0 for a bad argument
+    const xdtts_prosody_contour o = c();
+    return xdtts_prosody_contour_frames(&o, n_frames);
+  }
+  // The frame table the device reads (xdtts_prosody_contour_table): cumulative slowness c, pitch and gain per input frame
+  void table(size_t n_frames, std::vector<uint32_t> &cum, std::vector<float> &pitch, std::vector<float> &gain) const {
+    const xdtts_prosody_contour o = c();
+    cum.assign(n_frames, 0);
+    pitch.assign(n_frames, 0.f);
+    gain.assign(n_frames, 0.f);
+    check(xdtts_prosody_contour_table(&o, n_frames, cum.data(), pitch.data(), gain.data()));
+  }
+};
+
 // XdTts::infer (src/lib.rs:110-159) for one utterance with a prosody -- what an SSML <prosody rate=".." pitch=".."> element asks
 // for (src/text_normaliser.rs:41-56): units -> ids -> find_splits -> mel-gen -> vocoder with the rate / pitch stage
 // (xdtts_synthesize_ids_prosody).  Returns (Tacotron2's own mel, the modified audio).
@@ -275,15 +358,47 @@ inline std::pair<Array2, std::vector<float>> infer_prosody(const Tacotron2 &mode
   return out;
 }
 
+// ... and with a contour (xdtts_synthesize_ids_contour): one sentence synthesised whole, its <prosody> spans applied inside it.
+inline std::pair<Array2, std::vector<float>> infer_contour(const Tacotron2 &model, const GriffinLim &vocoder, const std::vector<Unit> &units,
+                                                            const ProsodyContour &contour, const xdtts_infer_opts *opts = nullptr) {
+  xdtts_infer_opts o;
+  xdtts_infer_opts_default(&o);
+  if (opts) o = *opts;
+  std::vector<int64_t> ids;
+  for (const Unit &u : units) {
+    const int64_t id = xdtts_unit_id(u.token.c_str(), u.is_character ? 1 : 0);
+    if (id >= 0) ids.push_back(id);
+  }
+  std::vector<size_t> splits(ids.size() + 2);
+  size_t n_splits = 0;
+  check(xdtts_find_splits(ids.data(), ids.size(), (size_t)o.max_chunk, splits.data(), splits.size(), &n_splits));
+  float *mel = nullptr, *audio = nullptr;
+  size_t nf = 0, ns = 0;
+  const xdtts_prosody_contour c = contour.c();
+  check(xdtts_synthesize_ids_contour(model.raw(), vocoder.raw(), ids.data(), ids.size(), splits.data(), n_splits, &o, &c, &mel, &nf, &audio, &ns));
+  std::pair<Array2, std::vector<float>> out;
+  out.first.rows = 80;
+  out.first.cols = nf;
+  out.first.data.assign(mel, mel + 80 * nf);
+  out.second.assign(audio, audio + ns);
+  xdtts_free(mel);
+  xdtts_free(audio);
+  return out;
+}
+
 // XdTts::infer (src/lib.rs:110-159) for several utterances in one call (xdtts_synthesize_batch): units -> ids
 // (units with no id are dropped, mod.rs:403-406), find_splits per utterance (mod.rs:399,412-414), all chunks in one
 // lock-step batch, the mel kept in HBM between mel-gen and vocoder.  Returns (mel, audio) per utterance.
-// (prosody: null, or one per text -- xdtts_synthesize_batch_prosody: the mels stay Tacotron2's own, the audios are the modified ones)
+// (prosody: null, or one per text -- xdtts_synthesize_batch_prosody: the mels stay Tacotron2's own, the audios are the modified ones;
+// contour: null, or one per text -- xdtts_synthesize_batch_contour; not both)
 inline std::vector<std::pair<Array2, std::vector<float>>> infer_many(const Tacotron2 &model, const GriffinLim &vocoder,
                                                                        const std::vector<std::vector<Unit>> &texts,
                                                                        const xdtts_infer_opts *opts = nullptr,
-                                                                       const std::vector<xdtts_prosody> *prosody = nullptr) {
+                                                                       const std::vector<xdtts_prosody> *prosody = nullptr,
+                                                                       const std::vector<ProsodyContour> *contour = nullptr) {
   if (prosody && prosody->size() != texts.size()) throw std::runtime_error("xdtts: one prosody per text");
+  if (contour && contour->size() != texts.size()) throw std::runtime_error("xdtts: one contour per text");
+  if (prosody && contour) throw std::runtime_error("xdtts: a prosody or a contour per text, not both");
   xdtts_infer_opts o;
   xdtts_infer_opts_default(&o);
   if (opts) o = *opts;
@@ -317,7 +432,12 @@ inline std::vector<std::pair<Array2, std::vector<float>>> infer_many(const Tacot
   const size_t n_utt = texts.size();
   std::vector<float *> mels(n_utt, nullptr), audios(n_utt, nullptr);
   std::vector<size_t> nf(n_utt, 0), ns(n_utt, 0);
-  if (prosody)
+  if (contour) {
+    std::vector<xdtts_prosody_contour> cs;
+    for (const ProsodyContour &c : *contour) cs.push_back(c.c());
+    check(xdtts_synthesize_batch_contour(model.raw(), vocoder.raw(), ids.data(), lens.data(), (int32_t)lens.size(), (int32_t)T, utt_chunks.data(),
+                                         (int32_t)n_utt, &o, nullptr, cs.data(), mels.data(), nf.data(), audios.data(), ns.data()));
+  } else if (prosody)
     check(xdtts_synthesize_batch_prosody(model.raw(), vocoder.raw(), ids.data(), lens.data(), (int32_t)lens.size(), (int32_t)T, utt_chunks.data(),
                                          (int32_t)n_utt, &o, nullptr, prosody->data(), mels.data(), nf.data(), audios.data(), ns.data()));
   else

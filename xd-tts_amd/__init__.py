@@ -57,6 +57,35 @@ class Prosody(C.Structure):
             setattr(self, k, v)
 
 
+class ProsodyPoint(C.Structure):
+    """xdtts_prosody_point: (pos, rate, pitch, gain), pos a fraction of the utterance's duration in [0, 1]."""
+
+    _fields_ = [("pos", C.c_float), ("rate", C.c_float), ("pitch", C.c_float), ("gain", C.c_float)]
+
+
+class ProsodyContour(C.Structure):
+    """xdtts_prosody_contour: rate, pitch and gain that vary inside one utterance.  ProsodyContour([(pos, rate, pitch, gain), ...])
+    -- pos in [0, 1] and non-decreasing (two points at one pos make a step), rate in [0.25, 4], pitch in [0.5, 2], gain in [0, 8];
+    values are interpolated linearly between the points and held before the first and after the last.  lifter and log_floor as
+    in Prosody.  The identity (every point 1, 1, 1) launches nothing."""
+
+    _fields_ = [("points", C.POINTER(ProsodyPoint)), ("n_points", C.c_int32), ("lifter", C.c_int32), ("log_floor", C.c_float)]
+
+    def __init__(self, points=(), lifter=None, log_floor=None):
+        super().__init__()
+        lib.xdtts_prosody_contour_default(C.byref(self))
+        pts = [tuple(float(x) for x in p) for p in points]
+        if any(len(p) != 4 for p in pts):
+            raise ValueError("a contour point is (pos, rate, pitch, gain)")
+        self._pts = (ProsodyPoint * max(len(pts), 1))(*pts)  # kept alive with the struct
+        self.points = C.cast(self._pts, C.POINTER(ProsodyPoint)) if pts else None
+        self.n_points = len(pts)
+        if lifter is not None:
+            self.lifter = lifter
+        if log_floor is not None:
+            self.log_floor = log_floor
+
+
 class InferOpts(C.Structure):
     _fields_ = [
         ("gate_threshold", C.c_float),
@@ -127,6 +156,13 @@ SYMBOLS = {
     "xdtts_griffinlim_infer_prosody": (_I32, [_VP, _VP, _SZ, _SZ, C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_griffinlim_infer_batch_prosody": (_I32, [_VP, _VP, _SZ, _VP, _I32, _VP, _VP, _VP]),
     "xdtts_griffinlim_prosody_linear_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "xdtts_prosody_contour_default": (None, [C.POINTER(ProsodyContour)]),
+    "xdtts_prosody_contour_frames": (_SZ, [C.POINTER(ProsodyContour), _SZ]),
+    "xdtts_prosody_contour_table": (_I32, [C.POINTER(ProsodyContour), _SZ, _VP, _VP, _VP]),
+    "xdtts_griffinlim_contour_linear": (_I32, [_VP, _VP, _SZ, C.POINTER(ProsodyContour), _VP, C.POINTER(_SZ)]),
+    "xdtts_griffinlim_contour_linear_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "xdtts_griffinlim_infer_contour": (_I32, [_VP, _VP, _SZ, _SZ, C.POINTER(ProsodyContour), C.POINTER(_PF), C.POINTER(_SZ)]),
+    "xdtts_griffinlim_infer_batch_contour": (_I32, [_VP, _VP, _SZ, _VP, _I32, _VP, _VP, _VP]),
     "xdtts_griffinlim_set_phase_init": (_I32, [_VP, _I32]),
     "xdtts_griffinlim_get_phase_init": (_I32, [_VP, C.POINTER(_I32)]),
     "xdtts_griffinlim_spsi_phase": (_I32, [_VP, _VP, _SZ, _VP, _VP]),
@@ -134,6 +170,8 @@ SYMBOLS = {
     "xdtts_griffinlim_free": (None, [_VP]),
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
+    "xdtts_synthesize_ids_contour": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(ProsodyContour), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
+    "xdtts_synthesize_batch_contour": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP, _VP]),
     "xdtts_synthesize_batch": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP]),
     "xdtts_synthesize_sequence": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP]),
     "xdtts_synthesize_batch_prosody": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP, _VP]),
@@ -217,6 +255,23 @@ def _prosody_array(prosody, n):
     if len(ps) != n:
         raise ValueError("prosody= takes one Prosody per utterance: %d for %d utterances" % (len(ps), n))
     return (Prosody * n)(*ps)
+
+
+def _contour_array(contour, n):
+    """A list of n ProsodyContour -> the C array xdtts_prosody_contour[n] the batch entries take."""
+    cs = list(contour)
+    if len(cs) != n:
+        raise ValueError("contour= takes one ProsodyContour per utterance: %d for %d utterances" % (len(cs), n))
+    arr = (ProsodyContour * n)()
+    for u, c in enumerate(cs):
+        arr[u].points, arr[u].n_points, arr[u].lifter, arr[u].log_floor = c.points, c.n_points, c.lifter, c.log_floor
+    arr._keep = cs  # the point arrays
+    return arr
+
+
+def _one_of(prosody, contour):
+    if prosody is not None and contour is not None:
+        raise ValueError("pass prosody= or contour=, not both")
 
 
 def default_opts(**kw):
@@ -620,17 +675,21 @@ class GriffinLim:
         _check(lib.xdtts_griffinlim_infer(self._h, _ptr(mel), mel.shape[0], mel.shape[1], C.byref(audio), C.byref(n)))
         return _take(audio, n.value, (n.value,))
 
-    def infer_batch(self, mels, prosody=None):
+    def infer_batch(self, mels, prosody=None, contour=None):
         """GriffinLim::infer for a list of (80, F_u) mels in one call; returns the list of audios.  prosody= (a list of one
         Prosody per utterance) runs the rate / pitch stage as one ragged launch behind the batch's mel -> linear
-        (xdtts_griffinlim_infer_batch_prosody): audio u has 256 * (prosody_frames(F_u, rate_u) - 1) samples."""
+        (xdtts_griffinlim_infer_batch_prosody): audio u has 256 * (prosody_frames(F_u, rate_u) - 1) samples.  contour= (a list of
+        one ProsodyContour per utterance) runs the contour stage there instead (xdtts_griffinlim_infer_batch_contour)."""
+        _one_of(prosody, contour)
         ms = [np.ascontiguousarray(m, dtype=np.float32) for m in mels]
         n = len(ms)
         ptrs = (C.c_void_p * n)(*[m.ctypes.data for m in ms])
         nf = (C.c_size_t * n)(*[m.shape[1] for m in ms])
         audios = (_PF * n)()
         ns = (C.c_size_t * n)()
-        if prosody is None:
+        if contour is not None:
+            _check(lib.xdtts_griffinlim_infer_batch_contour(self._h, ptrs, ms[0].shape[0], nf, n, _contour_array(contour, n), audios, ns))
+        elif prosody is None:
             _check(lib.xdtts_griffinlim_infer_batch(self._h, ptrs, ms[0].shape[0], nf, n, audios, ns))
         else:
             _check(lib.xdtts_griffinlim_infer_batch_prosody(self._h, ptrs, ms[0].shape[0], nf, n, _prosody_array(prosody, n), audios, ns))
@@ -697,6 +756,40 @@ class GriffinLim:
         mel = np.ascontiguousarray(mel, dtype=np.float32)
         audio, n = _PF(), C.c_size_t()
         _check(lib.xdtts_griffinlim_infer_prosody(self._h, _ptr(mel), mel.shape[0], mel.shape[1], C.byref(prosody), C.byref(audio), C.byref(n)))
+        return _take(audio, n.value, (n.value,))
+
+    # -- prosody contours: rate, pitch and gain that vary inside an utterance ----
+    def contour_linear(self, S, contour):
+        """The contour stage alone (parity hook): S (n_bins, F) -> S' (n_bins, F'), F' = prosody_contour_frames(contour, F)."""
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        Fp = prosody_contour_frames(contour, S.shape[1])
+        out = np.empty((self.n_bins, max(Fp, 1)), dtype=np.float32)
+        nf = C.c_size_t()
+        _check(lib.xdtts_griffinlim_contour_linear(self._h, _ptr(S), S.shape[1], C.byref(contour), _ptr(out), C.byref(nf)))
+        assert nf.value == Fp
+        return out
+
+    def contour_linear_batch(self, S_list, contour_list):
+        """The ragged contour stage alone (parity hook): a list of S_u (n_bins, F_u) and one ProsodyContour each -> the list of
+        S'_u (n_bins, F'_u), one k_prosody_contour launch for all of them."""
+        Ss = [np.ascontiguousarray(S, dtype=np.float32) for S in S_list]
+        n = len(Ss)
+        ca = _contour_array(contour_list, n)
+        Fp = [prosody_contour_frames(c, S.shape[1]) for S, c in zip(Ss, contour_list)]
+        outs = [np.empty((self.n_bins, max(f, 1)), dtype=np.float32) for f in Fp]
+        sp = (C.c_void_p * n)(*[S.ctypes.data for S in Ss])
+        op = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        nf = (C.c_size_t * n)(*[S.shape[1] for S in Ss])
+        nfo = (C.c_size_t * n)()
+        _check(lib.xdtts_griffinlim_contour_linear_batch(self._h, sp, nf, n, ca, op, nfo))
+        assert list(nfo) == Fp
+        return outs
+
+    def infer_contour(self, mel, contour):
+        """infer() with the contour stage behind mel -> linear: 256 * (F' - 1) samples."""
+        mel = np.ascontiguousarray(mel, dtype=np.float32)
+        audio, n = _PF(), C.c_size_t()
+        _check(lib.xdtts_griffinlim_infer_contour(self._h, _ptr(mel), mel.shape[0], mel.shape[1], C.byref(contour), C.byref(audio), C.byref(n)))
         return _take(audio, n.value, (n.value,))
 
     # -- initial phase: the seeded random stream (0) or Single Pass Spectrogram Inversion (1) ----
@@ -787,28 +880,47 @@ def prosody_frames(n_frames, rate):
     return int(lib.xdtts_prosody_frames(int(n_frames), float(rate)))
 
 
-def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None):
+def prosody_contour_frames(contour, n_frames):
+    """xdtts_prosody_contour_frames: the frame count behind the contour stage (host arithmetic); 0 for a bad argument."""
+    return int(lib.xdtts_prosody_contour_frames(C.byref(contour), int(n_frames)))
+
+
+def prosody_contour_table(contour, n_frames):
+    """xdtts_prosody_contour_table: (c uint32, pitch float32, gain float32), n_frames entries each -- the table the device reads."""
+    n = int(n_frames)
+    c, pitch, gain = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+    _check(lib.xdtts_prosody_contour_table(C.byref(contour), n, _ptr(c), _ptr(pitch), _ptr(gain)))
+    return c[:n], pitch[:n], gain[:n]
+
+
+def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, contour=None):
     """XdTts::infer (src/lib.rs:110-159): mel-gen then vocoder, mel kept in HBM in between.  prosody= (a Prosody) changes rate
-    and pitch in the vocoder (xdtts_synthesize_ids_prosody): the mel returned is Tacotron2's own, the audio the modified one."""
+    and pitch in the vocoder (xdtts_synthesize_ids_prosody): the mel returned is Tacotron2's own, the audio the modified one.
+    contour= (a ProsodyContour) does so with values that vary inside the utterance (xdtts_synthesize_ids_contour)."""
+    _one_of(prosody, contour)
     ids = np.ascontiguousarray(ids, dtype=np.int64)
     sp = None if splits is None else np.ascontiguousarray(splits, dtype=np.uintp)
     mel, nf, audio, ns = _PF(), C.c_size_t(), _PF(), C.c_size_t()
     head = (tacotron2._h, vocoder._h, _ptr(ids), ids.size, None if sp is None else _ptr(sp), 0 if sp is None else sp.size, C.byref(opts) if opts else None)
     tail = (C.byref(mel), C.byref(nf), C.byref(audio), C.byref(ns))
-    if prosody is None:
+    if contour is not None:
+        _check(lib.xdtts_synthesize_ids_contour(*head, C.byref(contour), *tail))
+    elif prosody is None:
         _check(lib.xdtts_synthesize_ids(*head, *tail))
     else:
         _check(lib.xdtts_synthesize_ids_prosody(*head, C.byref(prosody), *tail))
     return _take(mel, N_MEL * nf.value, (N_MEL, nf.value)), _take(audio, ns.value, (ns.value,))
 
 
-def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_steps=None, want_mels=True, prosody=None):
+def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_steps=None, want_mels=True, prosody=None, contour=None):
     """XdTts::infer (src/lib.rs:110-159) for several utterances in one call: `utterance_chunks[u]` is the
     list of <=window-id chunks of utterance u (find_splits + the trailing split, mod.rs:399,412-414);
     `fixed_steps`, if given, holds one frame count per chunk in the same nested shape.  All chunks decode
     in one lock-step batch and the vocoder batch reads the concatenated mel in HBM.  Returns
     (mels or None, audios), one entry per utterance.  prosody= (a list of one Prosody per utterance): the mels stay Tacotron2's
-    own, the audios go through the rate / pitch stage (xdtts_synthesize_batch_prosody)."""
+    own, the audios go through the rate / pitch stage (xdtts_synthesize_batch_prosody); contour= (a list of one ProsodyContour per
+    utterance) likewise with the contour stage (xdtts_synthesize_batch_contour)."""
+    _one_of(prosody, contour)
     chunks = [c for u in utterance_chunks for c in u]
     B, n_utt = len(chunks), len(utterance_chunks)
     lens = np.array([len(x) for x in chunks], dtype=np.int32)
@@ -822,7 +934,9 @@ def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_step
     audios = (_PF * n_utt)()
     nf, ns = (C.c_size_t * n_utt)(), (C.c_size_t * n_utt)()
     head = (tacotron2._h, vocoder._h, _ptr(ids), _ptr(lens), B, stride, _ptr(uc), n_utt, C.byref(opts) if opts else None, None if fs is None else _ptr(fs))
-    if prosody is None:
+    if contour is not None:
+        _check(lib.xdtts_synthesize_batch_contour(*head, _contour_array(contour, n_utt), mels, nf, audios, ns))
+    elif prosody is None:
         _check(lib.xdtts_synthesize_batch(*head, mels, nf, audios, ns))
     else:
         _check(lib.xdtts_synthesize_batch_prosody(*head, _prosody_array(prosody, n_utt), mels, nf, audios, ns))

@@ -11,19 +11,24 @@ using namespace xdtts;
 // GriffinLim::infer for several utterances at once (the vocoder half of a batch, BASELINE.json configs[3]):
 // the utterances' frames are concatenated, mel -> linear is one GEMM over all of them, and the persistent
 // kernel takes as many utterances per launch as fit one workgroup per CU.  Every utterance's audio is bit-identical to what
-// xdtts_griffinlim_infer returns for it alone.  (pros == null: xdtts_griffinlim_infer_batch; else one prosody per utterance,
-// its fields checked by the caller)
+// xdtts_griffinlim_infer returns for it alone.  (pros == cont == null: xdtts_griffinlim_infer_batch; else one prosody or one
+// contour per utterance, its fields checked by the caller)
 static xdtts_status infer_batch(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames, int32_t n_utt,
-                                const xdtts_prosody *pros, float **audios, size_t *n_samples) {
+                                const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **audios, size_t *n_samples) {
   return guard([&] {
     if (!g || !mels || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "bad argument");
     if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
     Rows rows;
+    std::vector<ContourTable> tabs(cont ? (size_t)n_utt : 0);
     for (int u = 0; u < n_utt; ++u) {
       audios[u] = nullptr;
       n_samples[u] = 0;
       if (!mels[u] || n_frames[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 2 frames", u);
       if (pros) prosody_check_at(&pros[u], u, n_frames[u]);
+      if (cont) {
+        contour_check_at(&cont[u], u, n_frames[u]);
+        contour_table(cont[u], n_frames[u], tabs[(size_t)u]);
+      }
       rows_add(rows, n_frames[u], (size_t)1 << 24, "batch too large");
     }
     const size_t Ftot = rows.total;
@@ -36,7 +41,7 @@ static xdtts_status infer_batch(xdtts_griffinlim *g, const float *const *mels, s
         std::memcpy(mel_all.p + m * Ftot + rows.row0[u], mels[u] + m * n_frames[u], sizeof(float) * n_frames[u]);
     g->mel_in.upload(mel_all.p, (size_t)n_mels * Ftot, g->stream);
     HIP_CHECK(hipStreamSynchronize(g->stream));  // the staging buffer goes back to the pool
-    gl_batch_from_device(g, g->mel_in.p, rows.F, audios, n_samples, pros);
+    gl_batch_from_device(g, g->mel_in.p, rows.F, audios, n_samples, cont ? ProsodyArg(tabs.data()) : ProsodyArg(pros));
   });
 }
 
@@ -160,7 +165,7 @@ xdtts_status xdtts_griffinlim_infer(xdtts_griffinlim *g, const float *mel, size_
 
 xdtts_status xdtts_griffinlim_infer_batch(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames,
                                           int32_t n_utt, float **audios, size_t *n_samples) {
-  return infer_batch(g, mels, n_mels, n_frames, n_utt, nullptr, audios, n_samples);
+  return infer_batch(g, mels, n_mels, n_frames, n_utt, nullptr, nullptr, audios, n_samples);
 }
 
 xdtts_status xdtts_griffinlim_mel_to_linear(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
@@ -285,9 +290,9 @@ xdtts_status xdtts_griffinlim_prosody_linear(xdtts_griffinlim *g, const float *S
     g->frames.upload(S, (size_t)F * g->nb, g->stream);
     launch_transpose(g->frames.p, g->S.p, g->nb, F, g->stream);
     HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
-    const int Fp = g->prosody(*p, F);
+    const int Fp = g->prosody(ProsodyArg(p), F);
     HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));  // last_timings: ms[0] = the stage alone, ms[1] = the layout change behind it
-    launch_transpose(g->prosody_S(*p), g->frames.p, Fp, g->nb, g->stream);
+    launch_transpose(g->prosody_S(ProsodyArg(p)), g->frames.p, Fp, g->nb, g->stream);
     HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
     HIP_CHECK(hipMemcpyAsync(S_out, g->frames.p, (size_t)Fp * g->nb * sizeof(float), hipMemcpyDeviceToHost, g->stream));
     g->finish_timings();  // (drains the stream)
@@ -308,7 +313,7 @@ xdtts_status xdtts_griffinlim_infer_prosody(xdtts_griffinlim *g, const float *me
     HIP_CHECK(hipSetDevice(g->device));
     g->mel_in.upload(mel, n_mels * n_frames, g->stream);
     HIP_CHECK(hipStreamSynchronize(g->stream));
-    gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, p, audio, n_samples);
+    gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, ProsodyArg(p), audio, n_samples);
   });
 }
 
@@ -324,7 +329,7 @@ xdtts_status xdtts_griffinlim_infer_batch_prosody(xdtts_griffinlim *g, const flo
     prosody_check_array(p, n_utt);
   });
   if (st != XDTTS_OK) return st;
-  return infer_batch(g, mels, n_mels, n_frames, n_utt, p, audios, n_samples);
+  return infer_batch(g, mels, n_mels, n_frames, n_utt, p, nullptr, audios, n_samples);
 }
 
 // Parity hook of the ragged stage alone: the utterances' magnitudes one behind the other on the device, one k_prosody_batch
@@ -371,6 +376,115 @@ xdtts_status xdtts_griffinlim_prosody_linear_batch(xdtts_griffinlim *g, const fl
     g->finish_timings();  // (drains the stream: the table and the outputs)
     for (int u = 0; n_frames_out && u < n_utt; ++u) n_frames_out[u] = (size_t)tab[(size_t)u].Fout;
   });
+}
+
+// ---- prosody contours: rate, pitch and gain that vary inside an utterance (prosody_contour.h, prosody.hip: k_prosody_contour) ----
+
+void xdtts_prosody_contour_default(xdtts_prosody_contour *c) {
+  if (!c) return;
+  c->points = nullptr;
+  c->n_points = 0;
+  c->lifter = 30;
+  c->log_floor = 1e-5f;
+}
+
+size_t xdtts_prosody_contour_frames(const xdtts_prosody_contour *c, size_t n_frames) {
+  if (!c) return 0;
+  return contour_frames(reinterpret_cast<const ContourPoint *>(c->points), c->n_points, c->lifter, c->log_floor, n_frames);
+}
+
+xdtts_status xdtts_prosody_contour_table(const xdtts_prosody_contour *c, size_t n_frames, uint32_t *cum, float *pitch, float *gain) {
+  return guard([&] {
+    contour_check(c, n_frames);
+    if (n_frames < 1 || n_frames > CONTOUR_MAX_FRAMES) fail(XDTTS_ERR_BAD_ARG, "contour n_frames: the table takes 1 .. %zu frames, got %zu", CONTOUR_MAX_FRAMES, n_frames);
+    contour_fill(reinterpret_cast<const ContourPoint *>(c->points), c->n_points, n_frames, cum, pitch, gain);
+  });
+}
+
+// Parity hook of the stage alone: the utterances' magnitudes one behind the other on the device, the table upload and one
+// k_prosody_contour launch (identity utterances are copied), and back.  last_timings: ms[0] = the launch alone, ms[1] = the
+// layout change behind it, ms[2] = both and the table's upload in front of them.
+xdtts_status xdtts_griffinlim_contour_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
+                                                   const xdtts_prosody_contour *c, float *const *S_outs, size_t *n_frames_out) {
+  return guard([&] {
+    for (int u = 0; n_frames_out && u < n_utt; ++u) n_frames_out[u] = 0;
+    contour_check_array(c, n_utt);
+    if (!S || !n_frames || !S_outs) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::vector<ContourTable> tabs((size_t)n_utt);
+    Rows in, out;
+    for (int u = 0; u < n_utt; ++u) {
+      if (!S[u] || !S_outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
+      if (n_frames[u] == 0) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 1 frame", u);
+      contour_check_at(&c[u], u, n_frames[u]);
+      contour_table(c[u], n_frames[u], tabs[(size_t)u]);
+      rows_add(in, n_frames[u], (size_t)1 << 24, "batch too large");
+      rows_add(out, (size_t)tabs[(size_t)u].Fout, (size_t)1 << 24, "batch too large");
+    }
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");  // (behind the contours and their frame counts: those need no device)
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    const size_t nb = (size_t)g->nb;
+    g->bufs((int)std::max(in.total, out.total));  // (frames: the boundary-layout staging of both directions)
+    g->upload_rows(S, in);
+    HIP_CHECK(hipEventRecord(g->ev.e[3], g->stream));
+    g->contour_upload(tabs.data(), n_utt);
+    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+    g->contour_launch();
+    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
+    for (int u = 0; u < n_utt; ++u) {
+      const size_t r0 = (size_t)out.row0[(size_t)u] * nb;
+      launch_transpose(g->S_pros.p + r0, g->frames.p + r0, out.F[(size_t)u], g->nb, g->stream);
+    }
+    HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+    for (int u = 0; u < n_utt; ++u) {
+      const size_t r0 = (size_t)out.row0[(size_t)u] * nb;
+      HIP_CHECK(hipMemcpyAsync(S_outs[u], g->frames.p + r0, (size_t)out.F[(size_t)u] * nb * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    }
+    g->finish_timings();  // (drains the stream: the tables and the outputs)
+    HIP_CHECK(hipEventElapsedTime(&g->last_ms[2], g->ev.e[3], g->ev.e[2]));  // the total takes the table's upload in
+    for (int u = 0; n_frames_out && u < n_utt; ++u) n_frames_out[u] = (size_t)out.F[(size_t)u];
+  });
+}
+
+xdtts_status xdtts_griffinlim_contour_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_prosody_contour *c,
+                                             float *S_out, size_t *n_frames_out) {
+  if (!c) {
+    if (n_frames_out) *n_frames_out = 0;
+    return guard([&] { fail(XDTTS_ERR_BAD_ARG, "null contour"); });
+  }
+  return xdtts_griffinlim_contour_linear_batch(g, &S, &n_frames, 1, c, &S_out, n_frames_out);
+}
+
+xdtts_status xdtts_griffinlim_infer_contour(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
+                                            const xdtts_prosody_contour *c, float **audio, size_t *n_samples) {
+  return guard([&] {
+    if (audio) *audio = nullptr;
+    if (n_samples) *n_samples = 0;
+    contour_check(c, std::max<size_t>(n_frames, 2));  // the fields first: reported without a handle
+    if (!g || !mel || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
+    if (n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "need at least 2 frames, got %zu", n_frames);
+    ContourTable tab;
+    contour_table(*c, n_frames, tab);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    g->mel_in.upload(mel, n_mels * n_frames, g->stream);
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+    gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, ProsodyArg(&tab), audio, n_samples);
+  });
+}
+
+xdtts_status xdtts_griffinlim_infer_batch_contour(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames,
+                                                  int32_t n_utt, const xdtts_prosody_contour *c, float **audios, size_t *n_samples) {
+  xdtts_status st = guard([&] {
+    for (int u = 0; u < n_utt; ++u) {
+      if (audios) audios[u] = nullptr;
+      if (n_samples) n_samples[u] = 0;
+    }
+    contour_check_array(c, n_utt);
+  });
+  if (st != XDTTS_OK) return st;
+  return infer_batch(g, mels, n_mels, n_frames, n_utt, nullptr, c, audios, n_samples);
 }
 
 // ---- initial phase: the seeded random stream (0) or Single Pass Spectrogram Inversion (1; phase_spsi.hip) ---------------------

@@ -9,9 +9,9 @@ using namespace xdtts;
 
 // ---- XdTts::infer (src/lib.rs:110-159) --------------------------------------------------------------
 
-// (pros == null: xdtts_synthesize_ids; else the prosody stage between mel -> linear and the loop, checked by the caller)
+// (pros == cont == null: xdtts_synthesize_ids; else the prosody stage between mel -> linear and the loop, fields checked by the caller)
 static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n, const size_t *splits,
-                                   size_t n_splits, const xdtts_infer_opts *opts, const xdtts_prosody *pros, float **mel,
+                                   size_t n_splits, const xdtts_infer_opts *opts, const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **mel,
                                    size_t *n_frames, float **audio, size_t *n_samples) {
   return guard([&] {
     if (!h || !g || !mel || !n_frames || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
@@ -35,7 +35,12 @@ static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, cons
     HIP_CHECK(hipMemcpyAsync(mel_host.p, h->mel_dev.p, (size_t)N_MEL * total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     Drain drain(h->stream);  // the pinned buffer does not go back to the pool with the copy in flight
     if (pros) prosody_check(pros, (size_t)total);  // (the frame count is known only now; nothing of the vocoder has been enqueued)
-    gl_run_from_device_mel(g, h->mel_dev.p, total, pros, audio, n_samples);
+    ContourTable tab;
+    if (cont) {
+      contour_check(cont, (size_t)total);
+      contour_table(*cont, (size_t)total, tab);
+    }
+    gl_run_from_device_mel(g, h->mel_dev.p, total, cont ? ProsodyArg(&tab) : ProsodyArg(pros), audio, n_samples);
     h->finish_timings();  // (stream sync: the mel has landed)
     *mel = mel_host.release();
     *n_frames = (size_t)total;
@@ -184,10 +189,10 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
 // src/tacotron2/mod.rs:422-434), the post-net writes every utterance's chunks side by side on the time axis
 // (mod.rs:430), and the vocoder batch reads that mel where it lies in HBM -- no copy to the host and back, no
 // re-staging between the two halves.  The per-utterance mels leave for the host while the vocoder runs.
-// (pros == null: xdtts_synthesize_batch; else one prosody per utterance, fields checked by the caller)
+// (pros == cont == null: xdtts_synthesize_batch; else one prosody or one contour per utterance, fields checked by the caller)
 static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
                                      int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
-                                     const int32_t *fixed_steps_per_item, const xdtts_prosody *pros, float **mels, size_t *n_frames,
+                                     const int32_t *fixed_steps_per_item, const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **mels, size_t *n_frames,
                                      float **audios, size_t *n_samples) {
   return guard([&] {
     if (!h || !g || !ids || !lens || !utt_chunks || !n_frames || !audios || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
@@ -210,12 +215,17 @@ static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, co
     int total = 0;
     const std::vector<int> F = h->infer_batch_device(padded.data(), lens, B, T, o, fixed_steps_per_item, &total);
     std::vector<int> Fu(n_utt, 0), col0(n_utt, 0);
+    std::vector<ContourTable> tabs(cont ? (size_t)n_utt : 0);
     for (int u = 0, b = 0, off = 0; u < n_utt; ++u) {
       col0[u] = off;
       for (int k = 0; k < utt_chunks[u]; ++k) Fu[u] += F[b++];
       off += Fu[u];
       if (Fu[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d has %d mel frame(s); the vocoder needs at least 2", u, Fu[u]);
       if (pros) prosody_check_at(&pros[u], u, (size_t)Fu[u]);  // (nothing of the vocoder has been enqueued)
+      if (cont) {
+        contour_check_at(&cont[u], u, (size_t)Fu[u]);
+        contour_table(cont[u], (size_t)Fu[u], tabs[(size_t)u]);
+      }
     }
     // the vocoder stream reads the mel behind the post-net (event 3 of infer_batch_device); the host copies of the
     // mel follow on the mel-gen stream and overlap the vocoder
@@ -230,7 +240,7 @@ static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, co
                                    sizeof(float) * (size_t)Fu[u], N_MEL, hipMemcpyDeviceToHost, h->stream));
       }
     }
-    gl_batch_from_device(g, h->mel_dev.p, Fu, audios, n_samples, pros);
+    gl_batch_from_device(g, h->mel_dev.p, Fu, audios, n_samples, cont ? ProsodyArg(tabs.data()) : ProsodyArg(pros));
     try {
       h->finish_timings();  // (stream sync: the mel copies have landed)
     } catch (...) {  // the caller gets either every buffer of the call or none
@@ -253,7 +263,7 @@ extern "C" {
 xdtts_status xdtts_synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
                                   const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts, float **mel,
                                   size_t *n_frames, float **audio, size_t *n_samples) {
-  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, nullptr, mel, n_frames, audio, n_samples);
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, nullptr, nullptr, mel, n_frames, audio, n_samples);
 }
 
 // ... with a prosody: the mel returned is Tacotron2's own, the audio has hop * (F' - 1) samples
@@ -266,7 +276,18 @@ xdtts_status xdtts_synthesize_ids_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *
     prosody_check(p, 2);  // the fields, before a device is touched
   });
   if (st != XDTTS_OK) return st;
-  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, p, mel, n_frames, audio, n_samples);
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, p, nullptr, mel, n_frames, audio, n_samples);
+}
+
+// ... with a contour (rate, pitch and gain that vary inside the utterance): the audio has hop * (F' - 1) samples, F' from the
+// table, which is built once the frame count is known
+xdtts_status xdtts_synthesize_ids_contour(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
+                                          const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts,
+                                          const xdtts_prosody_contour *c, float **mel, size_t *n_frames, float **audio,
+                                          size_t *n_samples) {
+  xdtts_status st = guard([&] { contour_check(c, 2); });  // the fields, before a device is touched
+  if (st != XDTTS_OK) return st;
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, nullptr, c, mel, n_frames, audio, n_samples);
 }
 
 xdtts_status xdtts_synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
@@ -290,7 +311,7 @@ xdtts_status xdtts_synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, con
                                     int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
                                     const int32_t *fixed_steps_per_item, float **mels, size_t *n_frames, float **audios,
                                     size_t *n_samples) {
-  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, nullptr, mels, n_frames, audios, n_samples);
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, nullptr, nullptr, mels, n_frames, audios, n_samples);
 }
 
 // ... one prosody per utterance: the ragged stage behind the batch's one mel -> linear GEMM
@@ -300,7 +321,25 @@ xdtts_status xdtts_synthesize_batch_prosody(xdtts_tacotron2 *h, xdtts_griffinlim
                                             float **audios, size_t *n_samples) {
   const xdtts_status st = check_prosody_array(p, n_utt, mels, n_frames, audios, n_samples);
   if (st != XDTTS_OK) return st;
-  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, p, mels, n_frames, audios, n_samples);
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, p, nullptr, mels, n_frames, audios, n_samples);
+}
+
+// ... one contour per utterance: the ragged contour stage behind the batch's one mel -> linear GEMM
+xdtts_status xdtts_synthesize_batch_contour(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
+                                            int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
+                                            const int32_t *fixed_steps_per_item, const xdtts_prosody_contour *c, float **mels, size_t *n_frames,
+                                            float **audios, size_t *n_samples) {
+  const xdtts_status st = guard([&] {
+    for (int u = 0; u < n_utt; ++u) {
+      if (mels) mels[u] = nullptr;
+      if (audios) audios[u] = nullptr;
+      if (n_frames) n_frames[u] = 0;
+      if (n_samples) n_samples[u] = 0;
+    }
+    contour_check_array(c, n_utt);
+  });
+  if (st != XDTTS_OK) return st;
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, nullptr, c, mels, n_frames, audios, n_samples);
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
+#include <cstring>
 
 using namespace xdtts;
 
@@ -105,12 +107,49 @@ void xdtts_griffinlim::mel_to_linear(const float *mel_dev_ptr, int F) {
 }
 
 // The prosody stage (prosody.hip) on the S that mel -> linear (or an upload) left in place: S_pros [F'][nb].
-int xdtts_griffinlim::prosody(const xdtts_prosody &p, int F) {
-  if (prosody_is_identity(p)) return F;
+int xdtts_griffinlim::prosody(const ProsodyArg &arg, int F) {
+  if (arg.identity(0)) return F;
+  if (arg.contour) {
+    const int Fp = contour_upload(arg.contour, 1);
+    contour_launch();
+    return Fp;
+  }
+  const xdtts_prosody &p = *arg.uniform;
   const int Fp = (int)prosody_frames((size_t)F, p.rate);
   S_pros.alloc((size_t)Fp * nb);
   launch_prosody(S.p, S_pros.p, F, Fp, p.rate, p.pitch, p.lifter, p.log_floor, tw.p, stream);
   return Fp;
+}
+
+int xdtts_griffinlim::contour_upload(const ContourTable *tabs, int n_utt) {
+  contour_utts_host.clear();
+  int src = 0, dst = 0, ntab = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    const ContourTable &t = tabs[u];
+    contour_utts_host.push_back({src, t.F, dst, t.Fout, ntab, t.lifter, t.log_floor, t.identity ? 1 : 0});
+    src += t.F;
+    dst += t.Fout;
+    ntab += (int)t.c.size();
+  }
+  contour_n_tab = ntab;
+  contour_rows = dst;
+  contour_ftab_host.assign((size_t)3 * std::max(ntab, 1), 0u);
+  for (int u = 0; u < n_utt; ++u) {
+    const ContourTable &t = tabs[u];
+    const size_t at = (size_t)contour_utts_host[(size_t)u].tab0, n = t.c.size();
+    if (!n) continue;
+    std::memcpy(&contour_ftab_host[at], t.c.data(), n * sizeof(unsigned));
+    std::memcpy(&contour_ftab_host[(size_t)ntab + at], t.pitch.data(), n * sizeof(float));
+    std::memcpy(&contour_ftab_host[(size_t)2 * ntab + at], t.gain.data(), n * sizeof(float));
+  }
+  contour_utts.upload(contour_utts_host.data(), contour_utts_host.size(), stream);
+  contour_ftab.upload(contour_ftab_host.data(), contour_ftab_host.size(), stream);
+  S_pros.alloc((size_t)std::max(dst, 1) * nb);
+  return dst;
+}
+
+void xdtts_griffinlim::contour_launch() {
+  launch_prosody_contour(S.p, S_pros.p, contour_utts.p, (int)contour_utts_host.size(), contour_ftab.p, contour_n_tab, contour_rows, tw.p, stream);
 }
 
 // The initial phase by SPSI (phase_spsi.hip) on a magnitude in place.  Scratch grows with the request and stays.
@@ -441,9 +480,9 @@ void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *pha
   collect_run(g, b, phase0_dev, iters, normalise, host, audio, n_samples);
 }
 
-// The loop's buffers for a mel of F frames and prosody p (null: none): F' frames, sized for max(F, F')
-static GlBufs request_bufs(xdtts_griffinlim *g, int F, const xdtts_prosody *p) {
-  const int Fp = p ? (int)prosody_frames((size_t)F, p->rate) : F;
+// The loop's buffers for a mel of F frames and prosody p (or none): F' frames, sized for max(F, F')
+static GlBufs request_bufs(xdtts_griffinlim *g, int F, const ProsodyArg &p) {
+  const int Fp = p.frames(0, F);
   GlBufs b = g->bufs(std::max(F, Fp));  // (before mel -> linear: growing S would drop its contents; in gl_collect nothing grows)
   b.F = Fp;
   return b;
@@ -451,27 +490,27 @@ static GlBufs request_bufs(xdtts_griffinlim *g, int F, const xdtts_prosody *p) {
 // GriffinLim::infer (G1..G6) from a mel in HBM, in two halves for a caller that overlaps the vocoder with other work
 // (xdtts_synthesize_sequence): everything enqueued on g->stream, nothing waited for; then collect_run.  Caller holds g->mu and the
 // chip lock.
-// (p: null, or a prosody the caller has checked against F -- the stage then sits between mel -> linear and the loop, which
-// runs on S' with F' frames; the identity launches nothing.  gl_collect takes the same F and p.)
-void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const xdtts_prosody *p) {
+// (p: nothing, a prosody the caller has checked against F, or the table of a contour built for F -- the stage then sits between
+// mel -> linear and the loop, which runs on S' with F' frames; the identity launches nothing.  gl_collect takes the same F and p.)
+void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const ProsodyArg &p) {
   GlBufs b = request_bufs(g, F, p);
   HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
   g->mel_to_linear(mel_dev_ptr, F);
   if (p) {
-    g->prosody(*p, F);
-    b.S = g->prosody_S(*p);
+    g->prosody(p, F);
+    b.S = g->prosody_S(p);
   }
   HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
   g->probe_tick();
   enqueue_run(g, b, nullptr, g->iters, true, host);  // (the sequence hands in a buffer it took from the pool while the frame loop ran)
 }
-void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const xdtts_prosody *p) {
+void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const ProsodyArg &p) {
   GlBufs b = request_bufs(g, F, p);
-  if (p) b.S = g->prosody_S(*p);
+  if (p) b.S = g->prosody_S(p);
   collect_run(g, b, nullptr, g->iters, true, host, audio, n_samples);
 }
 
-void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const xdtts_prosody *p, float **audio, size_t *n_samples) {
+void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const ProsodyArg &p, float **audio, size_t *n_samples) {
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
   PinnedGuard host;
   gl_enqueue_from_device_mel(g, mel_dev_ptr, F, host, p);
@@ -499,6 +538,34 @@ void prosody_check(const xdtts_prosody *p, size_t n_frames) {
   if (!prosody_is_identity(*p) && n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "prosody needs at least 2 frames, got %zu", n_frames);
 }
 
+static_assert(sizeof(xdtts_prosody_point) == sizeof(ContourPoint) && offsetof(xdtts_prosody_point, gain) == offsetof(ContourPoint, gain),
+              "xdtts_prosody_point and ContourPoint share one layout");
+static const ContourPoint *contour_points(const xdtts_prosody_contour &c) { return reinterpret_cast<const ContourPoint *>(c.points); }
+
+void contour_check(const xdtts_prosody_contour *c, size_t n_frames) {
+  if (!c) fail(XDTTS_ERR_BAD_ARG, "null contour");
+  const std::string msg = xdtts::contour_check(contour_points(*c), c->n_points, c->lifter, c->log_floor, n_frames);
+  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+}
+
+void contour_check_at(const xdtts_prosody_contour *c, int u, size_t n_frames) {
+  try {
+    contour_check(c, n_frames);
+  } catch (const Error &e) {
+    fail(e.code, "utterance %d: %s", u, e.what());
+  }
+}
+
+void contour_check_array(const xdtts_prosody_contour *c, int n_utt) {
+  if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+  if (!c) fail(XDTTS_ERR_BAD_ARG, "null contour array");
+  for (int u = 0; u < n_utt; ++u) contour_check_at(&c[u], u, 2);
+}
+
+void contour_table(const xdtts_prosody_contour &c, size_t n_frames, ContourTable &t) {
+  contour_build(contour_points(c), c.n_points, c.lifter, c.log_floor, n_frames, t);
+}
+
 void prosody_check_at(const xdtts_prosody *p, int u, size_t n_frames) {
   try {
     prosody_check(p, n_frames);
@@ -517,22 +584,27 @@ void prosody_check_array(const xdtts_prosody *p, int n_utt) {
 // fbase[u] .. fbase[u] + Fu[u].  mel -> linear is one GEMM over all frames, and the persistent kernel takes as many
 // utterances per launch as fit one workgroup per CU (gl_plan.h: gl_batch_plan).  Caller holds g->mu.  The reads of the mel
 // are enqueued on g->stream: the caller orders them behind the mel's producer (a stream sync or an event wait on g->stream).
-// pros: null, or one prosody per utterance, each checked by the caller against its frame count.  With one that is not the
-// identity the ragged stage (k_prosody_batch) follows the GEMM: S [sum F_u] -> S_pros [sum F'_u], and everything behind it --
+// pros: nothing, or one prosody per utterance, each checked by the caller against its frame count, or one contour table per
+// utterance, each built for its frame count.  With one that is not the identity the ragged stage (k_prosody_batch, or
+// k_prosody_contour) follows the GEMM: S [sum F_u] -> S_pros [sum F'_u], and everything behind it --
 // the rows of the loop's arrays, the packing into launches, the audio -- works from F'_u and reads S_pros.  Without one,
 // nothing new is launched.
 void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fin, float **audios, size_t *n_samples,
-                          const xdtts_prosody *pros) {
+                          const ProsodyArg &pros) {
   const int n_utt = (int)Fin.size();
   bool staged = false;
-  for (int u = 0; pros && u < n_utt; ++u) staged = staged || !prosody_is_identity(pros[u]);
+  for (int u = 0; pros && u < n_utt; ++u) staged = staged || !pros.identity(u);
+  const bool contour = staged && pros.contour;
   Rows in, rows;  // the mel's frames F_u, and the frames behind the stage: F'_u
   std::vector<ProsodyUtt> ptab;
   std::vector<int> abase(n_utt);
   size_t Ntot = 0;
   for (int u = 0; u < n_utt; ++u) {
-    const int Fp = staged ? (int)prosody_frames((size_t)Fin[u], pros[u].rate) : Fin[u];
-    if (staged) ptab.push_back({(int)in.total, Fin[u], (int)rows.total, Fp, pros[u].rate, pros[u].pitch, pros[u].lifter, pros[u].log_floor});
+    const int Fp = staged ? pros.frames(u, Fin[u]) : Fin[u];
+    if (staged && !contour) {
+      const xdtts_prosody &p = pros.uniform[u];
+      ptab.push_back({(int)in.total, Fin[u], (int)rows.total, Fp, p.rate, p.pitch, p.lifter, p.log_floor});
+    }
     rows_add(in, (size_t)Fin[u], (size_t)1 << 24, "batch too large");
     rows_add(rows, (size_t)Fp, (size_t)1 << 24, "batch too large");
     abase[u] = (int)Ntot;
@@ -551,7 +623,8 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
   GlBufs all = g->bufs((int)std::max(in.total, rows.total));
   all.F = (int)rows.total;
   if (staged) {
-    g->pros_tab.upload(ptab.data(), ptab.size(), st);
+    if (contour) g->contour_upload(pros.contour, n_utt);  // (its rows are `in` and `rows`: the utterances back to back)
+    else g->pros_tab.upload(ptab.data(), ptab.size(), st);
     g->S_pros.alloc(rows.total * (size_t)g->nb);
     all.S = g->S_pros.p;
   }
@@ -565,7 +638,8 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     // mel -> linear, the ragged stages, the initial phase: all from the mel, so a retry starts from an intact S / S'
     HIP_CHECK(hipEventRecord(g->ev.e[0], st));
     g->mel_to_linear(mel_dev_all, (int)in.total);
-    if (staged) launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)rows.total, g->tw.p, st);
+    if (contour) g->contour_launch();
+    else if (staged) launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)rows.total, g->tw.p, st);
     if (use_spsi) g->spsi_batch(all.S, spsi_tab, all.ang, all.tprev);
     HIP_CHECK(hipEventRecord(g->ev.e[1], st));
     if (!use_spsi) launch_gl_phase_init_batch(all, g->seed, g->frame_local.p, st);

@@ -3,6 +3,7 @@
 #pragma once
 #include "engine_gate.h"
 #include "kernels.h"
+#include "prosody_contour.h"
 #include "runtime.h"
 
 namespace xdtts {
@@ -10,6 +11,26 @@ namespace xdtts {
 inline bool prosody_is_identity(const xdtts_prosody &p) { return p.rate == 1.0f && p.pitch == 1.0f; }
 size_t prosody_frames(size_t F, float rate);                   // 0 for a bad argument
 void prosody_check(const xdtts_prosody *p, size_t n_frames);  // fails with XDTTS_ERR_BAD_ARG and a message
+// xdtts_prosody_contour (include/xdtts.h) on top of prosody_contour.h, which knows no status codes: the argument rules for a
+// request of n_frames frames (fails with XDTTS_ERR_BAD_ARG, the message names the field and the point), and the table.
+void contour_check(const xdtts_prosody_contour *c, size_t n_frames);
+void contour_check_at(const xdtts_prosody_contour *c, int u, size_t n_frames);  // ... for utterance u of a batch
+void contour_check_array(const xdtts_prosody_contour *c, int n_utt);            // the fields of n_utt contours, before a handle is looked at
+void contour_table(const xdtts_prosody_contour &c, size_t n_frames, ContourTable &t);  // (checked arguments)
+// What a request path puts between mel -> linear and the loop, as ONE argument: nothing, a uniform prosody (checked by the
+// caller), or the table of a contour (built by the caller once the frame count is known).  The single-utterance path reads
+// element 0, the batch path one element per utterance.
+struct ProsodyArg {
+  const xdtts_prosody *uniform = nullptr;
+  const ContourTable *contour = nullptr;
+  ProsodyArg() = default;
+  ProsodyArg(std::nullptr_t) {}
+  ProsodyArg(const xdtts_prosody *p) : uniform(p) {}
+  ProsodyArg(const ContourTable *t) : contour(t) {}
+  explicit operator bool() const { return uniform || contour; }
+  bool identity(int u) const { return contour ? contour[u].identity : (!uniform || prosody_is_identity(uniform[u])); }
+  int frames(int u, int F) const { return contour ? contour[u].Fout : (uniform ? (int)prosody_frames((size_t)F, uniform[u].rate) : F); }  // F'
+};
 // Rows::add (gl_plan.h, which knows no status codes) inside a request: past the cap it fails with XDTTS_ERR_BAD_ARG and the text
 inline void rows_add(Rows &r, size_t rows, size_t cap, const char *too_large) {
   try {
@@ -77,6 +98,18 @@ struct xdtts_griffinlim {
   // prosody (prosody.hip): the modified magnitude [F'][nb]; S itself stays as mel -> linear left it
   DevBuf<float> S_pros;
   DevBuf<xdtts::ProsodyUtt> pros_tab;  // vocoder batch: per-utterance rows and parameters of the ragged stage (k_prosody_batch)
+  // ... and the contour form (k_prosody_contour), single call and batch alike: the per-utterance records and the concatenated
+  // frame table {c, pitch, gain}.  The host vectors are the upload's source: they stay until the next contour request of this
+  // handle, which every path starts behind a drained stream.
+  DevBuf<xdtts::ContourUtt> contour_utts;
+  DevBuf<unsigned> contour_ftab;
+  std::vector<xdtts::ContourUtt> contour_utts_host;
+  std::vector<unsigned> contour_ftab_host;
+  int contour_n_tab = 0, contour_rows = 0;  // entries per array of the frame table; sum of F'
+  // Uploads (on the stream) the records and tables of n_utt utterances lying back to back in S (rows F_u) and S_pros (rows
+  // F'_u, allocated here); returns sum F'.  contour_launch() then runs the stage, any number of times (a retry).
+  int contour_upload(const xdtts::ContourTable *tabs, int n_utt);
+  void contour_launch();
 
   // initial phase (phase_spsi.hip): 0 = the seeded random stream, 1 = SPSI on the magnitude that enters the loop
   int phase_init = 0;
@@ -105,8 +138,9 @@ struct xdtts_griffinlim {
   void mel_to_linear(const float *mel_dev_ptr, int F);
   // S [F][nb] -> S_pros [F'][nb] in one launch on the stream; returns F'.  The identity launches nothing and returns F.
   // The caller then points GlBufs.S at prosody_S(p) with F' frames; its bufs() was sized for max(F, F').
-  int prosody(const xdtts_prosody &p, int F);
-  float *prosody_S(const xdtts_prosody &p) { return xdtts::prosody_is_identity(p) ? S.p : S_pros.p; }
+  // (a contour: its table goes up on the stream in front of the launch of k_prosody_contour)
+  int prosody(const xdtts::ProsodyArg &p, int F);
+  float *prosody_S(const xdtts::ProsodyArg &p) { return p.identity(0) ? S.p : S_pros.p; }
   // Once per API call (never inside a retry attempt): a demoted handle counts the call and, after PROBE_AFTER of them,
   // gives the persistent engine another try -- the cause of a timed-out exchange may have been transient.
   void probe_tick() { gate.tick(); }
@@ -132,16 +166,16 @@ void mel_filter_bank(double sr, int n_fft, int n_mels, double fmin, double fmax,
 void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, float **audio, size_t *n_samples,
                           bool normalise);
 // GriffinLim::infer from a mel in HBM, the one single-utterance request path: chip lock, gl_enqueue_from_device_mel, gl_collect.
-// (p: null, or a checked prosody -- the single-utterance stage behind mel -> linear, last_ms[0] covers both; F stays the mel's
-// frame count everywhere)
-void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const xdtts_prosody *p, float **audio, size_t *n_samples);
+// (p: nothing, a checked prosody or a contour's table -- the single-utterance stage behind mel -> linear, last_ms[0] covers
+// both; F stays the mel's frame count everywhere)
+void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const ProsodyArg &p, float **audio, size_t *n_samples);
 // ... and its two halves for a caller that holds the chip lock itself and works between them (the sequence entry)
-void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const xdtts_prosody *p = nullptr);
-void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const xdtts_prosody *p = nullptr);
-// (pros: null, or one checked prosody per utterance -- the ragged stage behind the one mel -> linear GEMM; audios[u] then has
-// hop * (F'_u - 1) samples)
+void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const ProsodyArg &p = ProsodyArg());
+void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const ProsodyArg &p = ProsodyArg());
+// (pros: nothing, or one checked prosody / one contour table per utterance -- the ragged stage behind the one mel -> linear
+// GEMM; audios[u] then has hop * (F'_u - 1) samples)
 void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples,
-                          const xdtts_prosody *pros = nullptr);
+                          const ProsodyArg &pros = ProsodyArg());
 // The fields of n_utt prosodies before any handle is looked at (entries that take an array): fails with XDTTS_ERR_BAD_ARG,
 // the message names the field and the utterance.
 void prosody_check_array(const xdtts_prosody *p, int n_utt);

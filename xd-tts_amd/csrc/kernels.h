@@ -317,6 +317,17 @@ struct ProsodyUtt {
   float log_floor;
 };
 void launch_prosody_batch(const float *S, float *Sout, const ProsodyUtt *tab, int n_utt, int Fout_all, const float2 *tw, hipStream_t s);
+// The contour form (xdtts_prosody_contour), single call (n_utt = 1) and ragged batch in one kernel: utterance u's F rows start at
+// row src0 of S, its Fout rows at row dst0 of Sout (ascending, back to back), its frame table at entry tab0 of ftab.  ftab
+// (device) = the cumulative slownesses c of all utterances, then their pitches, then their gains (float bits), n_tab entries
+// each: ContourTable of prosody_contour.h, concatenated.  identity != 0: the rows are copied, no table is read.
+struct ContourUtt {
+  int src0, F, dst0, Fout, tab0, lifter;
+  float log_floor;
+  int identity;
+};
+void launch_prosody_contour(const float *S, float *Sout, const ContourUtt *utt, int n_utt, const unsigned *ftab, int n_tab, int Fout_all,
+                            const float2 *tw, hipStream_t s);
 
 // ---- initial phase by Single Pass Spectrogram Inversion (phase_spsi.hip; phase_init mode 1, include/xdtts.h) -----------------
 // The recurrence over the frames runs as a scan over segments of SPSI_L consecutive frames of one utterance: the dependent
