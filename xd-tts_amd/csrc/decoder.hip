@@ -444,13 +444,6 @@ __global__ __launch_bounds__(PRENET_BT) void k_prenet_b(DecoderBufs d, int i, in
       location_blocks(d, i, (int)blockIdx.x - PRENET_SPLIT * d.B, loc_convT, loc_denseT);
     return;
   }
-#ifdef XDTTS_LSTM_PROBE
-  unsigned long long pp[8];
-  pp[0] = wall_clock64();
-#define PPROBE(i) pp[i] = wall_clock64()
-#else
-#define PPROBE(i) do { } while (0)
-#endif
   constexpr int HALF = PRENET / PRENET_SPLIT;          // layer-2 columns of this block
   // The partial-mel rows are dense in memory (84 floats = 21 16-byte vectors each, no gap between rows), so the reduction reads
   // them as one run of 264 x 21 vectors: thread (part = tid / 21, m4 = tid % 21) of the first 1008 takes vectors tid + 1008 k --
@@ -502,7 +495,6 @@ __global__ __launch_bounds__(PRENET_BT) void k_prenet_b(DecoderBufs d, int i, in
   const int nf = nf_v;
   const int chunk = d.item_perm ? perm_v : b;
   const uint32_t item = d.item_base + (uint32_t)chunk;
-  PPROBE(1);
   // ---- projection of the previous step: sum of the 264 partial rows in a fixed order ----
   {
     float4 r = rv[0];  // (row `part` < NPART <= PM_ROWS always exists; the spare threads' sums are dropped)
@@ -517,7 +509,6 @@ __global__ __launch_bounds__(PRENET_BT) void k_prenet_b(DecoderBufs d, int i, in
     if (col_ok) *reinterpret_cast<float4 *>(&s_red[part][4 * m4]) = r;
   }
   __syncthreads();
-  PPROBE(2);
   const bool forced = d.dec_in != nullptr && !flush;  // parity hook: the caller supplies decoder_input
   const bool have_prev = !forced && step >= 1 && step - 1 < nf;  // the chunk was active at the previous step
   if (tid < MEL_LD) {
@@ -541,7 +532,6 @@ __global__ __launch_bounds__(PRENET_BT) void k_prenet_b(DecoderBufs d, int i, in
     }
   }
   if (flush || fired || step >= nf) return;
-  PPROBE(3);
   // ---- prenet layer 1 (every block, all 256 outputs) ----
   {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -565,7 +555,6 @@ __global__ __launch_bounds__(PRENET_BT) void k_prenet_b(DecoderBufs d, int i, in
     s_x1[tid] = v;
   }
   __syncthreads();
-  PPROBE(4);
   // ---- prenet layer 2, this block's HALF columns ----
   {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -590,12 +579,6 @@ __global__ __launch_bounds__(PRENET_BT) void k_prenet_b(DecoderBufs d, int i, in
     d.x[b * PRENET + j] = o;
     d.xf[((size_t)(j >> 2) * d.Bpad + b) * 4 + (j & 3)] = o;
   }
-#ifdef XDTTS_LSTM_PROBE
-  PPROBE(5);
-  if (tid == 0 && (step == 100 || step == 101) && (b == 1 || b == 30) && half == 0)
-    printf("probe prenet_b chunk %d step %d: loads issued %llu  rows summed+sync %llu  mel+sync %llu  layer 1 %llu  layer 2 + store %llu (x10ns)\n", b, step,
-           pp[1] - pp[0], pp[2] - pp[1], pp[3] - pp[2], pp[4] - pp[3], pp[5] - pp[4]);
-#endif
 }
 
 // D2 / D4: LSTM cell as a weight-streaming GEMV with the cell update fused.  One wave owns one
@@ -762,10 +745,15 @@ struct NoHook {
 // PART, adds the early partial of the remaining columns (DecoderBufs::att_part) in the cell-update waves.
 // TAIL (decoder LSTM, two-launch form): h_dec leaves as granules d.hdg for the chunk's projection / prenet blocks of the same
 // launch (dec_tail_chunk) instead of the partial-mel rows the prenet launch would sum.
+// Prefetch depths of the k-loop, in k-steps: weights ahead (DW) and activations ahead (DX) of the MFMAs that consume them; the
+// sweeps are in the comment inside lstm_mfma_pass.
+constexpr int HI_ATT_DW = 2, HI_ATT_DX = 1;  // from two active tiles on: attention LSTM ...
+constexpr int HI_DEC_DW = 1, HI_DEC_DX = 1;  // ... and decoder LSTM (two-launch engine: 1 + 1: 32.8, 2 + 1: 33.0, 2 + 2: 33.2, 3 + 2: 33.4 us per configs[2] iteration)
+constexpr int LO_DW = 3, LO_DX = 2;          // with one active tile (both LSTMs, and the early blocks; two tiles with one k-step ahead: 24 / 32 chunks 28.7 / 29.2 -> 27.7 / 28.0 us)
 template <int NCOLS, int KIND, int NTA, class Hook = NoHook, int C0 = 0, int CN = NCOLS, bool PART = false, bool TAIL = false>
 __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int cur, int step, int blk, const float4 *__restrict__ wsrc,
                                                const float4 bz, const float (&wa)[6], float *s_acc, unsigned long long active,
-                                               unsigned long long d_probe_entry = 0, Hook after_loop = Hook()) {  // active: bit j = chunk n0 + j still runs at this step
+                                               Hook after_loop = Hook()) {  // active: bit j = chunk n0 + j still runs at this step
   constexpr int NW = MFMA_WAVES, KW = CN / NW, JJ = KW / 16;
   static_assert(CN % (16 * NW) == 0 && C0 % 16 == 0, "whole k-steps per wave");
   constexpr int N0 = KIND == 0 ? PRENET : ATT_RNN, N1 = EMB;
@@ -779,13 +767,6 @@ __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int
                                 : (col < N0 + N1 ? seg1 + (size_t)((col - N0) >> 2) * d.Bpad : seg2 + (size_t)((col - N0 - N1) >> 2) * d.Bpad);
     return sb + (size_t)fg * d.Bpad + n0 + fi;
   };
-#ifdef XDTTS_LSTM_PROBE
-  unsigned long long tp[6];
-  tp[0] = wall_clock64();
-#define PROBE(i) tp[i] = wall_clock64()
-#else
-#define PROBE(i) do { } while (0)
-#endif
   f32x4 acc[NTA];
 #pragma unroll
   for (int t = 0; t < NTA; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -798,26 +779,8 @@ __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int
   // 8 / 32 / 48 / 52 / 64 chunks): weights 3 + activations 2 ahead 29.6 / 32.6 / 39.0 / 44.8 / 45.7; 3 + 1: 30.5 / 33.8 / 39.4 / 44.1 / 44.8;
   // 2 + 1: 30.3 / 33.4 / 38.5 / 43.7 / 44.6; 2 + 2: 29.6 / 32.8 / 38.7 / 44.6 / 45.5; 4 + 2: 29.9 / 32.9 / 40.1 / 44.7 / 45.5 -- with three or
   // four tiles in flight per k-step every activation vector queues behind more loads, so they run one k-step shallower.
-  // (-DXDTTS_LSTM_DW / -DXDTTS_LSTM_DX override both cases.)
-#ifndef XDTTS_HI_ATT
-#define XDTTS_HI_ATT 21  // weights / activations ahead (two digits) from two active tiles on: attention LSTM ...
-#endif
-#ifndef XDTTS_LO
-#define XDTTS_LO 32  // ... and with one active tile (both LSTMs, and the early blocks; two tiles with one k-step ahead: 24 / 32 chunks 28.7 / 29.2 -> 27.7 / 28.0 us)
-#endif
-#ifndef XDTTS_HI_DEC
-#define XDTTS_HI_DEC 11  // ... and decoder LSTM (two-launch engine: 11: 32.8, 21: 33.0, 22: 33.2, 32: 33.4 us per configs[2] iteration)
-#endif
-#ifdef XDTTS_LSTM_DW
-  constexpr int DW = XDTTS_LSTM_DW;
-#else
-  constexpr int DW = NTA >= 2 ? (KIND == 0 ? XDTTS_HI_ATT : XDTTS_HI_DEC) / 10 : XDTTS_LO / 10;
-#endif
-#ifdef XDTTS_LSTM_DX
-  constexpr int DX = XDTTS_LSTM_DX;
-#else
-  constexpr int DX = NTA >= 2 ? (KIND == 0 ? XDTTS_HI_ATT : XDTTS_HI_DEC) % 10 : XDTTS_LO % 10;
-#endif
+  constexpr int DW = NTA >= 2 ? (KIND == 0 ? HI_ATT_DW : HI_DEC_DW) : LO_DW;
+  constexpr int DX = NTA >= 2 ? (KIND == 0 ? HI_ATT_DX : HI_DEC_DX) : LO_DX;
   constexpr int RX = DX + 1;
   float4 ring[RX][NTA], wring[8];
 #pragma unroll
@@ -867,7 +830,6 @@ __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int
 #pragma unroll
     for (int t = 0; t < NTA; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.w, xv[t].w, acc[t], 0, 0, 0);
   }
-  PROBE(1);
   float *h_out = KIND == 0 ? d.att_h[cur ^ 1] : d.dec_h[cur ^ 1];
   float *hf_out = KIND == 0 ? d.att_hf[cur ^ 1] : d.dec_hf[cur ^ 1];
   // (Cell state and gate biases are first used behind the conditional hook below, so the compiler waits for vmcnt(0) there --
@@ -880,7 +842,6 @@ __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int
 #pragma unroll
   for (int t = 0; t < NTA; ++t) *reinterpret_cast<f32x4 *>(s_acc + ((size_t)(wave * 4 + t) * 64 + lane) * 4) = acc[t];
   __syncthreads();
-  PROBE(2);
   if (wave < NTA) {  // wave t finalises chunk tile t: lane = (chunk fi, unit fg), regs = gates i,f,g,o
     f32x4 g = *reinterpret_cast<const f32x4 *>(s_acc + ((size_t)wave * 64 + lane) * 4);
 #pragma unroll
@@ -922,14 +883,7 @@ __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int
       }
     }
   }
-  PROBE(3);
   __syncthreads();
-  PROBE(4);
-#ifdef XDTTS_LSTM_PROBE
-  if ((blk == 3 || blk == 200) && (tid == 0 || tid == 64 * 9) && (step == 100 || step == 101))
-    printf("probe kind %d blk %d wave %d step %d NTA %d: entry->loop %llu  loop %llu  store+sync %llu  cell %llu  pmel+sync %llu (x10ns)\n", KIND, blk, wave, step, NTA,
-           tp[0] - d_probe_entry, tp[1] - tp[0], tp[2] - tp[1], tp[3] - tp[2], tp[4] - tp[3]);
-#endif
 }
 
 
@@ -948,29 +902,16 @@ __device__ __forceinline__ void lstm_mfma_pass(const DecoderBufs &d, int n0, int
 // (its 1024-thread blocks hold 128 VGPRs: ONE block per CU, so the two roles ran one after the other, 14.4 us); ONE block per
 // CU that feeds the shared operand [h_att ; ctx] to both weight slabs (k-loop of 12 + 8 k-steps per wave, activation reads
 // 214 -> 139 MB per iteration: 39.9 us per iteration against 36.4, with 16 waves 42.0); see DESIGN.md, Appendix A.
-#ifdef XDTTS_LSTM_PROBE
-__device__ __forceinline__ unsigned hw_place() {  // (xcc << 16) | HW_ID: which CU a block landed on
-  unsigned xcc, hw;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-  return ((xcc & 15u) << 16) | (hw & 0xffffu);
-}
-#endif
 // KIND 1 (two-launch form, d.dec_part): the same for the DECODER LSTM's own-state columns -- W_dec[:, 1536..2559] . h_dec(s-1), 40 % of its
 // pass, complete when the decoder-LSTM launch of step s-1 ends -- by 256 extra blocks of the ATTENTION launch of step s, whose own
 // blocks are a latency chain; the decoder-LSTM launch of step s then multiplies [h_att(s) ; ctx(s)] only.  hcur: half of dec_hf.
 constexpr int EARLY_K0 = PRENET / 16, EARLY_KS = (ATT_COLS - PRENET) / 16;  // k-steps 16 .. 111 of the 112
 constexpr int EARLY_K0_D = (ATT_RNN + EMB) / 16, EARLY_KS_D = DEC_RNN / 16;  // decoder LSTM: k-steps 96 .. 159 of the 160
 template <int NTA, int KIND = 0>
-__device__ __forceinline__ void att_early_partial(const DecoderBufs &d, int hcur, int blk, const float4 *__restrict__ Wm, float *lds,
-                                                  unsigned long long t_entry = 0, int step = 0) {
+__device__ __forceinline__ void att_early_partial(const DecoderBufs &d, int hcur, int blk, const float4 *__restrict__ Wm, float *lds) {
   constexpr int NWV = MFMA_WAVES, K0 = KIND ? EARLY_K0_D : EARLY_K0, KS = KIND ? EARLY_KS_D : EARLY_KS, JJ = KS / NWV;
   constexpr int KSTEPS = (KIND ? DEC_COLS : ATT_COLS) / 16;
   static_assert(KS % NWV == 0, "whole k-steps per wave");
-#ifdef XDTTS_LSTM_PROBE
-  unsigned long long ep[4];
-  ep[0] = wall_clock64();
-#endif
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fi = lane & 15, fg = lane >> 4;
   const float4 *wsrc = Wm + ((size_t)blk * KSTEPS + K0 + wave * JJ) * 64 + lane;
   const float4 *seg1 = reinterpret_cast<const float4 *>(d.ctxf), *seg2 = reinterpret_cast<const float4 *>(KIND ? d.dec_hf[hcur] : d.att_hf[hcur]);
@@ -979,10 +920,9 @@ __device__ __forceinline__ void att_early_partial(const DecoderBufs &d, int hcur
     const float4 *sb = KIND ? seg2 + (size_t)(col >> 2) * d.Bpad : (col < EMB ? seg1 + (size_t)(col >> 2) * d.Bpad : seg2 + (size_t)((col - EMB) >> 2) * d.Bpad);
     return sb + (size_t)fg * d.Bpad + fi;
   };
-#ifndef XDTTS_EARLY_HI
-#define XDTTS_EARLY_HI 11  // weights / activations ahead from two active tiles on (11: 32.7, 21: 33.0, 22: 33.6, 31: 33.3 us per configs[2] iteration)
-#endif
-  constexpr int DW = NTA >= 2 ? XDTTS_EARLY_HI / 10 : XDTTS_LO / 10, DX = NTA >= 2 ? XDTTS_EARLY_HI % 10 : XDTTS_LO % 10, RX = DX + 1;  // prefetch depths of lstm_mfma_pass
+  // weights / activations ahead from two active tiles on (1 + 1: 32.7, 2 + 1: 33.0, 2 + 2: 33.6, 3 + 1: 33.3 us per configs[2] iteration)
+  constexpr int EARLY_HI_DW = 1, EARLY_HI_DX = 1;
+  constexpr int DW = NTA >= 2 ? EARLY_HI_DW : LO_DW, DX = NTA >= 2 ? EARLY_HI_DX : LO_DX, RX = DX + 1;  // (with one active tile: the depths of lstm_mfma_pass)
   f32x4 acc[NTA];
 #pragma unroll
   for (int t = 0; t < NTA; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1019,9 +959,6 @@ __device__ __forceinline__ void att_early_partial(const DecoderBufs &d, int hcur
 #pragma unroll
     for (int t = 0; t < NTA; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.w, xv[t].w, acc[t], 0, 0, 0);
   }
-#ifdef XDTTS_LSTM_PROBE
-  ep[1] = wall_clock64();
-#endif
   f32x4 *red = reinterpret_cast<f32x4 *>(lds);  // [wave][tile][lane]
 #pragma unroll
   for (int t = 0; t < NTA; ++t) red[(wave * 4 + t) * 64 + lane] = acc[t];
@@ -1032,33 +969,27 @@ __device__ __forceinline__ void att_early_partial(const DecoderBufs &d, int hcur
     for (int q = 1; q < NWV; ++q) g += red[(q * 4 + wave) * 64 + lane];
     reinterpret_cast<f32x4 *>(KIND ? d.dec_part : d.att_part)[((size_t)blk * 4 + wave) * 64 + lane] = g;
   }
-#ifdef XDTTS_LSTM_PROBE
-  ep[2] = wall_clock64();
-  if ((blk == 3 || blk == 100 || blk == 200 || blk == 255) && (tid == 0 || tid == 64 * 5) && (step == 100 || step == 101))
-    printf("probe early blk %d wave %d step %d NTA %d place %05x: entry %llu  entry->loop %llu  loop %llu  reduce %llu  (x10ns)\n", blk, wave, step, NTA, hw_place(),
-           t_entry % 100000ull, ep[0] - t_entry, ep[1] - ep[0], ep[2] - ep[1]);
-#endif
 }
 // the role as a whole: tiles by the chunks still active at step `next`
 template <int KIND = 0>
-__device__ __forceinline__ void att_early_role(const DecoderBufs &d, int next, int hcur, int blk, const float4 *__restrict__ Wm, float *lds, unsigned long long t_entry) {
+__device__ __forceinline__ void att_early_role(const DecoderBufs &d, int next, int hcur, int blk, const float4 *__restrict__ Wm, float *lds) {
   const int lane = threadIdx.x & 63;
   const bool a = lane < d.B && next < d.nframes[min(lane, d.B - 1)];  // (a chunk the next prenet launch stops still counts: its tile's partial is not read then)
   const unsigned long long m = __ballot(a);
   const int nta = m ? (63 - __clzll((long long)m)) / 16 + 1 : 0;
   switch (nta) {
-    case 1: att_early_partial<1, KIND>(d, hcur, blk, Wm, lds, t_entry, next); break;
-    case 2: att_early_partial<2, KIND>(d, hcur, blk, Wm, lds, t_entry, next); break;
-    case 3: att_early_partial<3, KIND>(d, hcur, blk, Wm, lds, t_entry, next); break;
-    case 4: att_early_partial<4, KIND>(d, hcur, blk, Wm, lds, t_entry, next); break;
+    case 1: att_early_partial<1, KIND>(d, hcur, blk, Wm, lds); break;
+    case 2: att_early_partial<2, KIND>(d, hcur, blk, Wm, lds); break;
+    case 3: att_early_partial<3, KIND>(d, hcur, blk, Wm, lds); break;
+    case 4: att_early_partial<4, KIND>(d, hcur, blk, Wm, lds); break;
     default: break;
   }
 }
 // stand-alone form (parity hooks: a sequence that starts from caller-held state has no preceding decoder-LSTM launch)
 __global__ __launch_bounds__(64 * MFMA_WAVES) void k_att_early(DecoderBufs d, int i, const float4 *__restrict__ att_wm, const float4 *__restrict__ dec_wm) {
   __shared__ __attribute__((aligned(16))) float s_acc[MFMA_WAVES * 4 * 64 * 4];
-  if ((int)blockIdx.x < NBLK) att_early_role<0>(d, d.ctl[0] + i, i & 1, blockIdx.x, att_wm, s_acc, 0);
-  else att_early_role<1>(d, d.ctl[0] + i, i & 1, (int)blockIdx.x - NBLK, dec_wm, s_acc, 0);  // (grid 512 with d.dec_part)
+  if ((int)blockIdx.x < NBLK) att_early_role<0>(d, d.ctl[0] + i, i & 1, blockIdx.x, att_wm, s_acc);
+  else att_early_role<1>(d, d.ctl[0] + i, i & 1, (int)blockIdx.x - NBLK, dec_wm, s_acc);  // (grid 512 with d.dec_part)
 }
 
 
@@ -1085,13 +1016,6 @@ __device__ __forceinline__ void dec_tail_chunk(const DecoderBufs &d, int step, i
   float *s_h = lds, *s_c = s_h + DEC_RNN, *s_mel = s_c + EMB, *s_p1 = s_mel + 96, *s_x1 = s_p1 + KG1 * PRENET, *s_p2 = s_x1 + PRENET;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned want = (unsigned)step + 1u, spin_limit = d.att_spins > 0 ? (unsigned)d.att_spins : AB_SPIN_LIMIT;
-#ifdef XDTTS_LSTM_PROBE
-  unsigned long long tq[8];
-  tq[0] = wall_clock64();
-#define TPROBE(i) tq[i] = wall_clock64()
-#else
-#define TPROBE(i) do { } while (0)
-#endif
   // the wave's three projection rows (18 KB) do not depend on h_dec: in flight while it is gathered (issued behind the gather,
   // row by row, the phase measured 2.4 - 4 us: three exposed round trips through an L1 the co-resident early block is filling)
   constexpr int C4 = (DEC_RNN + EMB) / 4 / 64;  // 6 vectors per lane and row
@@ -1113,7 +1037,6 @@ __device__ __forceinline__ void dec_tail_chunk(const DecoderBufs &d, int step, i
     s_c[tid] = d.ctx[b * EMB + tid];
   }
   __syncthreads();
-  TPROBE(1);
   // ---- projection rows m = part + 4 r, r = wave, wave + 8, wave + 16: lane takes float4 columns lane + 64 k of the 384 ----
   {
     float4 hv[C4];
@@ -1129,7 +1052,6 @@ __device__ __forceinline__ void dec_tail_chunk(const DecoderBufs &d, int step, i
       if (lane == 0 && m <= N_MEL) granule_store(d.melg + (size_t)b * 96 + m, want, a + proj_b[m]);
     }
   }
-  TPROBE(2);
   // the prenet weights of this thread, in flight while the mel crosses
   const int o4 = tid & 63, kg1 = tid >> 6;
   const int c4 = tid % (COLS2 / 4), kg2 = tid / (COLS2 / 4);
@@ -1152,7 +1074,6 @@ __device__ __forceinline__ void dec_tail_chunk(const DecoderBufs &d, int step, i
     s_mel[tid] = g[0];
   }
   __syncthreads();
-  TPROBE(3);
   const float gate = s_mel[N_MEL];
   const bool fired = d.use_gate && gate_fires(gate, d.gate_lo, d.gate_hi, d.gate_threshold);
   const int nf = d.nframes[b];
@@ -1187,7 +1108,6 @@ __device__ __forceinline__ void dec_tail_chunk(const DecoderBufs &d, int step, i
     s_x1[tid] = v;
   }
   __syncthreads();
-  TPROBE(4);
   // ---- prenet layer 2, this block's 64 columns ----
   {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1212,12 +1132,6 @@ __device__ __forceinline__ void dec_tail_chunk(const DecoderBufs &d, int step, i
     d.x[b * PRENET + j] = o;
     d.xf[((size_t)(j >> 2) * d.Bpad + b) * 4 + (j & 3)] = o;
   }
-#ifdef XDTTS_LSTM_PROBE
-  TPROBE(5);
-  if (tid == 0 && step == 100 && (b == 0 || b == 17 || b == 40) && part == 0)
-    printf("probe tail chunk %d step %d: entry %llu  h gathered %llu  rows + publish %llu  mel gathered %llu  layer 1 %llu  layer 2 + store %llu (x10ns)\n", b, step,
-           tq[0] % 100000ull, tq[1] - tq[0], tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
-#endif
 }
 
 template <int NCOLS, int KIND>
@@ -1225,18 +1139,13 @@ __global__ __launch_bounds__(64 * MFMA_WAVES) void k_lstm_mfma(DecoderBufs d, in
                                                                const float *__restrict__ bias, const float4 *__restrict__ Wepi,
                                                                const float4 *__restrict__ att_wm, TailWeights tw) {
   constexpr int NW = MFMA_WAVES, KW = NCOLS / NW, JJ = KW / 16;
-#ifdef XDTTS_LSTM_PROBE
-  const unsigned long long t_entry = wall_clock64();
-#else
-  const unsigned long long t_entry = 0;
-#endif
   __shared__ __attribute__((aligned(16))) float s_acc[NW * 4 * 64 * 4];  // [K-slice][tile][lane][gate]
   // Blocks 256..511 of a decoder-LSTM launch with the early role: the NEXT step's attention-LSTM partial (att_early_partial).
   // Two 512-thread blocks of this kernel fit a CU; which role's blocks are dispatched first, and s_setprio for either role,
   // measured the same to 0.1 us per iteration.
   if (KIND == 1 && (int)blockIdx.x >= NBLK) {
     const int e = (int)blockIdx.x - NBLK;
-    att_early_role(d, d.ctl[0] + i + 1, cur ^ 1, e, att_wm, s_acc, t_entry);  // (this step's attention launch wrote h_att into half cur ^ 1)
+    att_early_role(d, d.ctl[0] + i + 1, cur ^ 1, e, att_wm, s_acc);  // (this step's attention launch wrote h_att into half cur ^ 1)
     // two-launch form: the first 2 B early blocks also compute the next step's location features (the prenet launch's location role)
     // two-launch form: the next step's location features (the prenet launch's location role, 2 units per chunk): one unit each for
     // the decoder-LSTM blocks that are no chunk's tail (below), the rest behind the partial of the LAST early blocks (the first
@@ -1245,10 +1154,6 @@ __global__ __launch_bounds__(64 * MFMA_WAVES) void k_lstm_mfma(DecoderBufs d, in
       const int nfree = NBLK - TAIL_PARTS * d.B, ne = max(0, 2 * d.B - nfree);
       if (e >= NBLK - ne) location_chunk_mfma<MFMA_WAVES>(d, i + 1, nfree + e - (NBLK - ne), tw.loc_convT, tw.loc_denseT);
     }
-#ifdef XDTTS_LSTM_PROBE
-    if (threadIdx.x == 0 && d.ctl[0] + i == 100 && (e == 3 || e == 100 || e == 200))
-      printf("probe early+loc blk %d: entry %llu  end %llu (x10ns)\n", e, t_entry % 100000ull, wall_clock64() % 100000ull);
-#endif
     return;
   }
   const int blk = blockIdx.x;
@@ -1272,27 +1177,23 @@ __global__ __launch_bounds__(64 * MFMA_WAVES) void k_lstm_mfma(DecoderBufs d, in
       constexpr int CNS = KIND == 1 ? ATT_RNN + EMB : NCOLS;
       const float4 *ws = Wm + ((size_t)blk * (NCOLS / 16) + wave * (CNS / NW / 16)) * 64 + lane;
       switch (nta) {
-        case 1: lstm_mfma_pass<NCOLS, KIND, 1, NoHook, 0, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m, t_entry); break;
-        case 2: lstm_mfma_pass<NCOLS, KIND, 2, NoHook, 0, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m, t_entry); break;
-        case 3: lstm_mfma_pass<NCOLS, KIND, 3, NoHook, 0, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m, t_entry); break;
-        case 4: lstm_mfma_pass<NCOLS, KIND, 4, NoHook, 0, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m, t_entry); break;
+        case 1: lstm_mfma_pass<NCOLS, KIND, 1, NoHook, 0, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m); break;
+        case 2: lstm_mfma_pass<NCOLS, KIND, 2, NoHook, 0, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m); break;
+        case 3: lstm_mfma_pass<NCOLS, KIND, 3, NoHook, 0, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m); break;
+        case 4: lstm_mfma_pass<NCOLS, KIND, 4, NoHook, 0, CNS, KIND == 1, KIND == 1>(d, n0, cur, step, blk, ws, bz, wa, s_acc, m); break;
         default: return;
       }
     } else {
       switch (nta) {
-        case 1: lstm_mfma_pass<NCOLS, KIND, 1, NoHook, 0, NCOLS, false, KIND == 1>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m, t_entry); break;
-        case 2: lstm_mfma_pass<NCOLS, KIND, 2, NoHook, 0, NCOLS, false, KIND == 1>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m, t_entry); break;
-        case 3: lstm_mfma_pass<NCOLS, KIND, 3, NoHook, 0, NCOLS, false, KIND == 1>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m, t_entry); break;
-        case 4: lstm_mfma_pass<NCOLS, KIND, 4, NoHook, 0, NCOLS, false, KIND == 1>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m, t_entry); break;
+        case 1: lstm_mfma_pass<NCOLS, KIND, 1, NoHook, 0, NCOLS, false, KIND == 1>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m); break;
+        case 2: lstm_mfma_pass<NCOLS, KIND, 2, NoHook, 0, NCOLS, false, KIND == 1>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m); break;
+        case 3: lstm_mfma_pass<NCOLS, KIND, 3, NoHook, 0, NCOLS, false, KIND == 1>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m); break;
+        case 4: lstm_mfma_pass<NCOLS, KIND, 4, NoHook, 0, NCOLS, false, KIND == 1>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m); break;
         default: return;
       }
     }
     const int b = blk >> 2;
     static_assert(TAIL_LDS_FLOATS <= NW * 4 * 64 * 4, "the tail reuses the accumulator exchange area");
-#ifdef XDTTS_LSTM_PROBE
-    if (threadIdx.x == 0 && step == 100 && (blk == 0 || blk == 68 || blk == 160 || blk == 250))
-      printf("probe D blk %d: entry %llu  pass done %llu (x10ns)\n", blk, t_entry % 100000ull, wall_clock64() % 100000ull);
-#endif
     batched_straggle(d, blk, step, 2);  // (between its publish of h_dec and its share of the chunk's mel rows)
     if (b < d.B && step < d.nframes[b]) dec_tail_chunk(d, step, b, blk & 3, s_acc, tw.proj_w4, tw.proj_b, tw.W0T, tw.W1T);
     if (blk >= TAIL_PARTS * d.B && blk - TAIL_PARTS * d.B < 2 * d.B)  // free after the pass: one location unit, done well inside the tails' time
@@ -1300,10 +1201,10 @@ __global__ __launch_bounds__(64 * MFMA_WAVES) void k_lstm_mfma(DecoderBufs d, in
     return;
   }
   switch (nta) {
-    case 1: lstm_mfma_pass<NCOLS, KIND, 1>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m, t_entry); break;
-    case 2: lstm_mfma_pass<NCOLS, KIND, 2>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m, t_entry); break;
-    case 3: lstm_mfma_pass<NCOLS, KIND, 3>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m, t_entry); break;
-    case 4: lstm_mfma_pass<NCOLS, KIND, 4>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m, t_entry); break;
+    case 1: lstm_mfma_pass<NCOLS, KIND, 1>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m); break;
+    case 2: lstm_mfma_pass<NCOLS, KIND, 2>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m); break;
+    case 3: lstm_mfma_pass<NCOLS, KIND, 3>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m); break;
+    case 4: lstm_mfma_pass<NCOLS, KIND, 4>(d, n0, cur, step, blk, wsrc, bz, wa, s_acc, m); break;
     default: break;
   }
 }
@@ -1316,9 +1217,6 @@ __global__ __launch_bounds__(64 * MFMA_WAVES) void k_lstm_mfma(DecoderBufs d, in
 constexpr int QE_GROUP = 4;
 __global__ __launch_bounds__(256) void k_qenergy(DecoderBufs d, int i, int cur, const float4 *__restrict__ Wq,
                                                  const float *__restrict__ v_w) {
-#ifdef XDTTS_LSTM_PROBE
-  const unsigned long long t_in = wall_clock64();
-#endif
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blk = blockIdx.x;
   const int row = blk * 4 + wave;
   float4 w[4];
@@ -1374,10 +1272,6 @@ __global__ __launch_bounds__(256) void k_qenergy(DecoderBufs d, int i, int cur, 
     }
     __syncthreads();
   }
-#ifdef XDTTS_LSTM_PROBE
-  if (tid == 0 && step == 100 && (blockIdx.y % 17 == 0) && (blk == 0 || blk == 31))
-    printf("probe qenergy blk (%d,%d) in %llu out %llu\n", blk, (int)blockIdx.y, t_in % 1000000ull, wall_clock64() % 1000000ull);
-#endif
 }
 
 // D3b: e_t = sum of the 32 partial energies, -inf where t >= n_valid (mask, mod.rs:219-220);
@@ -1387,10 +1281,6 @@ __global__ __launch_bounds__(256) void k_qenergy(DecoderBufs d, int i, int cur, 
 // prefetched at kernel entry (addresses do not depend on the softmax).  Block 0 also stores the
 // new attention weights.
 __global__ __launch_bounds__(256) void k_softmax_ctx(DecoderBufs d, int i, const float *__restrict__ proj_wc) {
-#ifdef XDTTS_LSTM_PROBE
-  const unsigned long long t_in = wall_clock64();
-  unsigned long long t_sm = 0, t_ctx = 0;
-#endif
   const int b = blockIdx.x / CTX_BLOCKS, cblk = blockIdx.x % CTX_BLOCKS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = d.T;
@@ -1470,9 +1360,6 @@ __global__ __launch_bounds__(256) void k_softmax_ctx(DecoderBufs d, int i, const
       awc_out[b * T + t] = cum;
     }
   }
-#ifdef XDTTS_LSTM_PROBE
-  t_sm = wall_clock64();
-#endif
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   int k = 0;
   for (int t0 = tg; t0 < T; t0 += TG * CTX_PF) {
@@ -1512,13 +1399,6 @@ __global__ __launch_bounds__(256) void k_softmax_ctx(DecoderBufs d, int i, const
     pv += dpp_move<0xB1, 0xf>(0.f, pv);  // lanes 2j, 2j+1 hold the two halves of row m
     if (act && pm_half == 0 && pm_m <= N_MEL) d.pmel[((size_t)b * PM_ROWS + cblk) * MEL_LD + pm_m] = pv;
   }
-#ifdef XDTTS_LSTM_PROBE
-  t_ctx = wall_clock64();
-#endif
-#ifdef XDTTS_LSTM_PROBE
-  if (tid == 0 && step == 100 && (b % 17 == 0) && (cblk == 0 || cblk == 7))
-    printf("probe softmax_ctx blk (%d,%d) in %llu softmax_done %llu ctx_pmel_done %llu out %llu\n", b, cblk, t_in % 1000000ull, t_sm % 1000000ull, t_ctx % 1000000ull, wall_clock64() % 1000000ull);
-#endif
 }
 
 
@@ -1600,13 +1480,6 @@ __device__ __forceinline__ void attention_chunk(const DecoderBufs &d, int i, int
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = d.T;
   const unsigned want = (unsigned)step + 1u, spin_limit = d.att_spins > 0 ? (unsigned)d.att_spins : AB_SPIN_LIMIT;
-#ifdef XDTTS_LSTM_PROBE
-  unsigned long long ap[8];
-  ap[0] = wall_clock64();
-#define APROBE(i) ap[i] = wall_clock64()
-#else
-#define APROBE(i) do { } while (0)
-#endif
   const int gq = NWV * part + wave;
   const float *locg = d.loc + ((size_t)b * (ATT_DIM / 4) + gq) * T * 4, *pmg = d.pmem_t + ((size_t)b * (ATT_DIM / 4) + gq) * T * 4;
   float4 (&hv)[4] = L.hv;
@@ -1625,7 +1498,6 @@ __device__ __forceinline__ void attention_chunk(const DecoderBufs &d, int i, int
   // (two-launch form: the memory slice is fetched behind the energies instead -- below -- so that the block fits 128 VGPRs and a
   // second block, the decoder LSTM's early partial, shares the CU)
   if (HG && PMEL) attention_loads_late<NT, PMEL>(L, d, b, part, proj_wc);
-  APROBE(1);
   if (HG) {  // the 256 LSTM blocks of this launch each publish four units of every chunk
     constexpr int NG = ATT_RNN / NT;
     float g[NG];
@@ -1636,7 +1508,6 @@ __device__ __forceinline__ void attention_chunk(const DecoderBufs &d, int i, int
 #pragma unroll
     for (int k = 0; k < 4; ++k) hv[k] = *reinterpret_cast<const float4 *>(s_hv + 256 * k + 4 * lane);
   }
-  APROBE(2);
   // ---- processed query: the four rows of this wave's dims, no LDS (wave_sum leaves the total in every lane) ----
   float4 q4;
   {
@@ -1663,7 +1534,6 @@ __device__ __forceinline__ void attention_chunk(const DecoderBufs &d, int i, int
   for (int t = lane + 128; t < T; t += 64)
     s_eg[wave * T_MAX + t] = energy(*reinterpret_cast<const float4 *>(locg + 4 * t), *reinterpret_cast<const float4 *>(pmg + 4 * t));
   __syncthreads();
-  APROBE(3);
   // ---- exchange: publish this block's partial, collect the chunk's NB ----
   u64 *slots = d.ep_g + (size_t)b * ATT_EXCHANGE_BLOCKS * T;
   for (int t = tid; t < T; t += NT) {
@@ -1682,7 +1552,6 @@ __device__ __forceinline__ void attention_chunk(const DecoderBufs &d, int i, int
     s_e[t] = t >= nv ? -INFINITY : e;
   }
   __syncthreads();
-  APROBE(4);
   // ---- softmax (every block of the chunk computes the same one), new weights, context slice, partial mel:
   //      as k_softmax_ctx ----
   if (wave == 0) {
@@ -1699,7 +1568,6 @@ __device__ __forceinline__ void attention_chunk(const DecoderBufs &d, int i, int
     for (int t = lane; t < T; t += 64) s_e[t] = s_e[t] / sum;
   }
   __syncthreads();
-  APROBE(5);
   if (part == 0)
     for (int t = tid; t < T; t += NT) {
       const float wv = s_e[t];
@@ -1740,12 +1608,6 @@ __device__ __forceinline__ void attention_chunk(const DecoderBufs &d, int i, int
     pv += dpp_move<0xB1, 0xf>(0.f, pv);  // lanes 2j, 2j+1 hold the two halves of row m
     if (pm_half == 0 && pm_m <= N_MEL) d.pmel[((size_t)b * PM_ROWS + cblk) * MEL_LD + pm_m] = pv;
   }
-#ifdef XDTTS_LSTM_PROBE
-  APROBE(6);
-  if (tid == 0 && (step == 100 || step == 101) && (b == 0 || b == 17 || b == 40) && part == 0)
-    printf("probe attention NT %d chunk %d step %d: loads issued %llu  h gathered %llu  energies %llu  e gathered %llu  softmax %llu  ctx+pmel %llu (x10ns)\n", NT, b, step,
-           ap[1] - ap[0], ap[2] - ap[1], ap[3] - ap[2], ap[4] - ap[3], ap[5] - ap[4], ap[6] - ap[5]);
-#endif
 }
 
 constexpr int attention_lds_floats(int nt) { return T_MAX + nt / 64 * T_MAX + 17 * (EMB / (ATT_DIM / (nt / 16))) + ATT_RNN; }
@@ -1788,7 +1650,7 @@ __global__ __launch_bounds__(64 * MFMA_WAVES, TWO ? 4 : 2) void k_att_lstm_atten
   const float wa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   __shared__ __attribute__((aligned(16))) float s_acc[NW * 4 * 64 * 4];
   if (TWO && (int)blockIdx.x >= NBLK) {  // blocks 256..511 (with d.dec_part): the early partial of THIS step's decoder-LSTM pass over h_dec(s-1)
-    att_early_role<1>(d, d.ctl[0] + i, cur, (int)blockIdx.x - NBLK, dec_wm, s_acc, 0);
+    att_early_role<1>(d, d.ctl[0] + i, cur, (int)blockIdx.x - NBLK, dec_wm, s_acc);
     return;
   }
   // blocks 4 b .. 4 b + 3 are the attention blocks of chunk b; their loads for that phase go out as soon as the wave has
@@ -1800,10 +1662,10 @@ __global__ __launch_bounds__(64 * MFMA_WAVES, TWO ? 4 : 2) void k_att_lstm_atten
     if (attn) attention_loads<512, true>(L, d, i, cur, b, part, Wq, v_w);  // (the late group follows the publish of h: attention_chunk)
   };
   switch (nta) {
-    case 1: lstm_mfma_pass<ATT_COLS, 0, 1, decltype(hook), 0, CN, EARLY>(d, 0, cur, step, blk, wsrc, bz, wa, s_acc, m, 0, hook); break;
-    case 2: lstm_mfma_pass<ATT_COLS, 0, 2, decltype(hook), 0, CN, EARLY>(d, 0, cur, step, blk, wsrc, bz, wa, s_acc, m, 0, hook); break;
-    case 3: lstm_mfma_pass<ATT_COLS, 0, 3, decltype(hook), 0, CN, EARLY>(d, 0, cur, step, blk, wsrc, bz, wa, s_acc, m, 0, hook); break;
-    case 4: lstm_mfma_pass<ATT_COLS, 0, 4, decltype(hook), 0, CN, EARLY>(d, 0, cur, step, blk, wsrc, bz, wa, s_acc, m, 0, hook); break;
+    case 1: lstm_mfma_pass<ATT_COLS, 0, 1, decltype(hook), 0, CN, EARLY>(d, 0, cur, step, blk, wsrc, bz, wa, s_acc, m, hook); break;
+    case 2: lstm_mfma_pass<ATT_COLS, 0, 2, decltype(hook), 0, CN, EARLY>(d, 0, cur, step, blk, wsrc, bz, wa, s_acc, m, hook); break;
+    case 3: lstm_mfma_pass<ATT_COLS, 0, 3, decltype(hook), 0, CN, EARLY>(d, 0, cur, step, blk, wsrc, bz, wa, s_acc, m, hook); break;
+    case 4: lstm_mfma_pass<ATT_COLS, 0, 4, decltype(hook), 0, CN, EARLY>(d, 0, cur, step, blk, wsrc, bz, wa, s_acc, m, hook); break;
     default: return;  // (no chunk is active: nothing to attend to either)
   }
   if (!attn) return;

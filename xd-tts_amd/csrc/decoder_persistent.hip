@@ -41,14 +41,11 @@
 // drains the whole launch in microseconds and surfaces as XDTTS_ERR_HIP on the host.
 #include <type_traits>
 
-#include "device_utils.h"
-#include "kernels.h"
+#include "p8_exchange.h"  // publish, peek, PollCtl, give_up, lds4 (its gather takes a sink; the one below fills arrays)
 
 namespace xdtts {
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int PT = 512;                  // threads per workgroup (8 waves, 256 VGPRs each)
 constexpr int NW = PT / 64;
@@ -56,37 +53,15 @@ constexpr int P_NCU = ATT_RNN / 4;       // 256 workgroups = LSTM slices
 constexpr int TP = PERSIST_T_MAX;        // encoder-step capacity of the attention role
 constexpr int ATTN_CU = 8, PRE_CU = 16;  // role workgroups per chunk
 constexpr int EP_LD = TP, MEL_GL = 96;
-#ifndef XDTTS_MEL_ST
-#define XDTTS_MEL_ST 1
-#endif
-constexpr int MEL_ST = XDTTS_MEL_ST;     // granules between two mel values in the exchange (16 = one 128-byte line each: measured, no gain over 1)
+constexpr int MEL_ST = 1;                // granules between two mel values in the exchange (16 = one 128-byte line each: measured, no gain over 1)
 constexpr int GS = PERSIST_B_MAX;        // chunk stride of the granule arrays: the same for every launch width, so a
                                          // 1-chunk launch can continue a sequence that a 2-chunk launch began
 constexpr unsigned P_SPIN_LIMIT = 1u << 21;
-constexpr unsigned ACT_BIT = 0x80000000u;
 constexpr int PERSIST_LAZY_DEFAULT = 9;  // x 256 clocks: ~0.95 us (6 / 7 / 8 / 9 / 10 -> 8.53 / 8.45 / 8.38 / 8.26 / 8.35 us per 1-chunk step; 0: +1.3 us)
 
 constexpr int WPAD = TP + 32;            // zero-padded attention-weight window, index t + 15
 static_assert(ATT_RNN == DEC_RNN && P_NCU == 256, "one workgroup per 4 + 4 hidden units");
 
-__device__ __forceinline__ void publish(u64 *slot, unsigned tag, float v) {
-  __hip_atomic_store(slot, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ u64 peek(const u64 *slot) {
-  return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-struct PollCtl {
-  int *err;
-  unsigned limit;
-};
-__device__ __forceinline__ bool give_up(unsigned &spins, const PollCtl &pc) {
-  if (++spins > pc.limit || ((spins & 127u) == 0 && __hip_atomic_load(pc.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-    atomicExch(pc.err, 1);
-    return true;
-  }
-  __builtin_amdgcn_s_sleep(1);
-  return false;
-}
 // N granules at base[idx + i * stride], all loads in flight together; `base` is uniform and the
 // offsets are 32-bit so the loads use the SGPR-base addressing form (no 64-bit VGPR addresses kept
 // live across the step loop).  A timed-out slot reads as {tag 0, 0.0f}.
@@ -152,7 +127,6 @@ __device__ __forceinline__ void straggle(bool me, int s, int at) {
   if (me && s % 6 == at)
     for (int i = 0; i < 2; ++i) __builtin_amdgcn_s_sleep(127);  // 2 x 8128 clocks ~ 7 us
 }
-__device__ __forceinline__ float4 lds4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 // Hides a thread-index expression's known bits from the optimiser.  Without this `idx + CONST`
 // is canonicalised to `idx | CONST` wherever the bits are disjoint, the constant no longer folds
 // into the ds instruction's offset field, and every unrolled access gets its own address register,

@@ -20,8 +20,8 @@
 //   * ROLE FIRST: a role workgroup fetches its own chunk's vector (one quad per thread, row-major into LDS), requests the first
 //     operand rounds behind its arrival, runs its role and publishes; the attention role multiplies ONE round of h_att while its
 //     partial energies travel and the rest behind its context publish, the projection / prenet role multiplies h_dec behind its x
-//     publish -- the step's critical chain never waits for the bulk.  (The -D knobs below are the experiments of DESIGN_NOTES.md,
-//     round 6; the defaults are the measured best.)
+//     publish -- the step's critical chain never waits for the bulk.  (The other orders that were tried, and the sweeps behind the
+//     constants below, are in DESIGN_NOTES.md, round 6 and Appendix B "Removed".)
 //   * the chunks' active bits are per-lane state (the sign of x(s), as before) combined by a ballot, shared through one LDS word.
 // Per step:  x -> [attention LSTM] -> h_att -> [query, energies] -> e -> [softmax, context] -> ctx -> [decoder LSTM] -> h_dec
 //            -> [projection rows] -> mel -> [stop rule, prenet] -> x(s+1)
@@ -40,41 +40,21 @@ namespace {
 constexpr int PT = 256, NW = PT / 64, NB = P8_B_MAX, P_NCU = ATT_RNN / 4, TP = PERSIST_T_MAX;
 constexpr int ATTN_CU = 8, PRE_CU = 8, EP_LD = TP, MEL_GL = 96, WPAD = TP + 32;
 constexpr int L2C = PRENET / PRE_CU;  // layer-2 columns per projection / prenet workgroup
-#ifndef XDTTS_P16_HSPLIT
-#define XDTTS_P16_HSPLIT 4
-#endif
-#ifndef XDTTS_P16_NBUF
-#define XDTTS_P16_NBUF 2
-#endif
-constexpr int HSPLIT = XDTTS_P16_HSPLIT, HQ = 16 / HSPLIT, NBUF = XDTTS_P16_NBUF;  // NBUF: rounds of operand registers (rounds in flight)  // the sixteen operand quads of a hidden vector in this many gather + MFMA rounds
-#ifndef XDTTS_P16_AUX
-#define XDTTS_P16_AUX 16
-#endif
-constexpr int AUX1 = XDTTS_P16_AUX;  // cache policy of the FIRST poll of an operand quad (16 = sc1; retries are sc0 sc1 always)
-#ifndef XDTTS_P16_ROLE_FIRST
-#define XDTTS_P16_ROLE_FIRST 1
-#endif
-#ifndef XDTTS_P16_EP_RD
-#define XDTTS_P16_EP_RD 2
-#endif
-constexpr bool ROLE_FIRST = XDTTS_P16_ROLE_FIRST != 0;  // role workgroups: the exchange chain first, the hidden vector's MFMAs behind the role's publish
-#ifndef XDTTS_P16_RF_SPLIT
-#define XDTTS_P16_RF_SPLIT 1
-#endif
-#ifndef XDTTS_P16_RF_SPLIT_P
-#define XDTTS_P16_RF_SPLIT_P 0
-#endif
-constexpr int RF_SPLIT = XDTTS_P16_RF_SPLIT, RF_SPLIT_P = XDTTS_P16_RF_SPLIT_P;            // ROLE_FIRST: rounds of a hidden vector's MFMAs a role workgroup runs inside its exchange's shadow (the rest behind its publish)
-#ifndef XDTTS_P16_EARLY_BEGIN
-#define XDTTS_P16_EARLY_BEGIN 0
-#endif
-constexpr bool EARLY_BEGIN = XDTTS_P16_EARLY_BEGIN != 0;  // role workgroups: the first operand rounds in flight next to the row's first poll (1) or behind its arrival (0)
-constexpr int EP_RD = XDTTS_P16_EP_RD;                  // !ROLE_FIRST: the first poll of the partial energies leaves behind this round of the h_att MFMAs
-constexpr int PROWS = 3;                              // rows of [W_p ; w_gate] per wave: rk + 8 (wave + 4 r), r < 3
+constexpr int HSPLIT = 4, HQ = 16 / HSPLIT;  // the sixteen operand quads of a hidden vector in this many gather + MFMA rounds
+constexpr int NBUF = 2;                      // rounds of operand registers (rounds in flight)
+constexpr int AUX1 = 16;                     // cache policy of the FIRST poll of an operand quad (16 = sc1; retries are sc0 sc1 always)
+constexpr int RF_SPLIT = 1, RF_SPLIT_P = 0;  // rounds of h_att's / h_dec's MFMAs a role workgroup runs in the shadow of its exchange (the rest behind its publish)
+// Two spots of the step loop keep the text of an order that is never built, because the compiler allocates the kernel's registers
+// differently without them (profiles/knobs_removed_device_code.txt): the energies poll inside h_att_mfmas, which only a
+// workgroup that multiplies BEFORE its role (!ROLE_FIRST) would issue, behind round EP_RD; and the zero-round h_dec_mfmas call.
+constexpr bool ROLE_FIRST = true;
+constexpr int EP_RD = 2;
+constexpr int PROWS = 3;                     // rows of [W_p ; w_gate] per wave: rk + 8 (wave + 4 r), r < 3
 constexpr unsigned P_SPIN_LIMIT = 1u << 21;
 static_assert(NB == 16 && ATT_RNN == DEC_RNN && P_NCU == 256 && (ATTN_CU + PRE_CU) * NB == P_NCU, "the role workgroups of 16 chunks are the grid");
 static_assert(TP == 128 && PRENET == PT && EMB == 2 * PT && ATT_RNN == 4 * PT, "thread <-> quad maps below");
 static_assert(PRE_CU * NW * PROWS >= N_MEL + 1, "every row of [W_p ; w_gate] has a wave");
+static_assert(16 % HSPLIT == 0 && HQ % 2 == 0 && NBUF <= HSPLIT && RF_SPLIT > 0 && RF_SPLIT < HSPLIT && RF_SPLIT_P == 0 && ROLE_FIRST, "rounds of a hidden vector: whole, in pairs of column groups, some behind the publish");
 
 // N quads of a write-once slab straight into the registers they are multiplied from: quad i at byte offset at(i); a quad is
 // complete once none of its four words is the fill pattern.  Lanes with `on` false (a chunk slot that is empty or has
@@ -181,16 +161,6 @@ __device__ __forceinline__ void mfma_regs(f32x4 &acc, const float4 (&A)[NQ], con
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q].y, bits(b[q].y), acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q].z, bits(b[q].z), acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q].w, bits(b[q].w), acc, 0, 0, 0);
-  }
-}
-template <int NQ, int NA>
-__device__ __forceinline__ void mfma_half(f32x4 &acc, const float4 (&A)[NA], const u32x4 (&b)[NQ], int q0) {
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q0 + q].x, bits(b[q].x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q0 + q].y, bits(b[q].y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q0 + q].z, bits(b[q].z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q0 + q].w, bits(b[q].w), acc, 0, 0, 0);
   }
 }
 // two independent accumulators fed from the same operand quads, their MFMAs alternating (each chain's next MFMA issues 64 cycles
@@ -482,9 +452,8 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent16(DecoderBufs d, P8Bu
       // the workgroup's own chunk first (one quad per thread, row-major into LDS), the first operand rounds in flight behind it
       const unsigned roff = 4u * (unsigned)(rb * ATT_RNN + 4 * tid);
       u32x4 hr = __builtin_amdgcn_raw_buffer_load_b128(slab_rsrc(slab_h), (int)roff, 0, 16);
-      if (EARLY_BEGIN) stream_begin<HQ>(hb, slab_h, hbase);
       quad_wait(hr, slab_h, roff, pc);
-      if (!EARLY_BEGIN) stream_begin<HQ>(hb, slab_h, hbase);  // (every producer of the row has published: so have, for the other chunks, most of them)
+      stream_begin<HQ>(hb, slab_h, hbase);  // (every producer of the row has published: so have, for the other chunks, most of them)
       *reinterpret_cast<float4 *>(s_hrow + 4 * tid) = as_f4(hr);
       P16_MARK(3);
       __syncthreads();
@@ -530,17 +499,17 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent16(DecoderBufs d, P8Bu
     P16_MARK(5);
     // both LSTMs that consume h_att(s) -- the decoder LSTM of this step, the attention LSTM of the next -- out of ONE gather.  The
     // attention workgroups are the step's critical chain: they go on to the partial energies at once and multiply behind their
-    // context publish, in the time the context travels (ROLE_FIRST); everybody else multiplies now.
+    // context publish, in the time the context travels; everybody else multiplies now.
     auto h_att_mfmas = [&](auto from, auto to) {
       stream_finish<HQ, HSPLIT, decltype(from)::value, decltype(to)::value>(hb, slab_h, hbase, act_n, pc, [&](int rd, const u32x4(&hq)[HQ]) {
         mfma_pair<HQ>(accD, dh, accA, ah, hq, HQ * rd);
-        if (!ROLE_FIRST && rd == EP_RD && ep_need) gather_issue<4>(ep_v, ep_base, ep_need, ep_at);
+        if (!ROLE_FIRST && rd == EP_RD && ep_need) gather_issue<4>(ep_v, ep_base, ep_need, ep_at);  // (never taken: see ROLE_FIRST above)
       });
     };
     using I0 = std::integral_constant<int, 0>;
     using IH = std::integral_constant<int, RF_SPLIT>;
     using IR = std::integral_constant<int, HSPLIT>;
-    if (!(ROLE_FIRST && attn_on)) h_att_mfmas(I0{}, IR{});
+    if (!attn_on) h_att_mfmas(I0{}, IR{});
     else {
       // the first rounds (prefetched at the row gather) in the time the partial energies travel, the loads of the rest behind them
       h_att_mfmas(I0{}, IH{});
@@ -605,7 +574,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent16(DecoderBufs d, P8Bu
         ctx_valid = true;
         put(g.rctx + (slot + rb) * EMB + 64 * rk + (tid + oz), value_bits(v));
       }
-      if (ROLE_FIRST) h_att_mfmas(IH{}, IR{});
+      h_att_mfmas(IH{}, IR{});
     }
     P16_MARK(7);
     // ---- P4: ctx(s) of every active chunk -> decoder LSTM ------------------------------------------------------------------------
@@ -660,9 +629,8 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent16(DecoderBufs d, P8Bu
       // ctx(rb), long arrived
       const unsigned roff = 4u * (unsigned)(rb * DEC_RNN + 4 * tid);
       u32x4 hr = __builtin_amdgcn_raw_buffer_load_b128(slab_rsrc(slab_d), (int)roff, 0, 16);
-      if (EARLY_BEGIN) stream_begin<HQ>(db, slab_d, dbase);
       quad_wait(hr, slab_d, roff, pc);
-      if (!EARLY_BEGIN) stream_begin<HQ>(db, slab_d, dbase);
+      stream_begin<HQ>(db, slab_d, dbase);
       *reinterpret_cast<float4 *>(s_hrow + 4 * tid) = as_f4(hr);
       if (tid < EMB / 4) {
         u32x4 cr[1];
@@ -691,16 +659,16 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent16(DecoderBufs d, P8Bu
     }
     P16_MARK(14);
     // decoder LSTM of the next step: h_dec(s) (two accumulator chains: the dependent-MFMA latency is 40 cycles, the issue rate 32).
-    // The projection / prenet workgroups go on to the mel exchange and multiply behind their x publish (ROLE_FIRST).
+    // The projection / prenet workgroups go on to the mel exchange and multiply behind their x publish.
     f32x4 acc2 = (f32x4){0.f, 0.f, 0.f, 0.f};
     auto h_dec_mfmas = [&](auto from, auto to) {
       stream_finish<HQ, HSPLIT, decltype(from)::value, decltype(to)::value>(db, slab_d, dbase, act_n, pc,
                                                                             [&](int rd, const u32x4(&dq)[HQ]) { mfma_two<HQ>(accD, acc2, dd, dq, HQ * rd); });
     };
     using IP = std::integral_constant<int, RF_SPLIT_P>;
-    if (!(ROLE_FIRST && pre_on)) h_dec_mfmas(I0{}, IR{});
+    if (!pre_on) h_dec_mfmas(I0{}, IR{});
     else {
-      h_dec_mfmas(I0{}, IP{});  // (in the time the mel rows travel)
+      h_dec_mfmas(I0{}, IP{});  // (no round: see RF_SPLIT_P above)
       nap(g.delay[5]);
     }
     P16_MARK(15);
@@ -767,7 +735,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent16(DecoderBufs d, P8Bu
         }
         put(g.rx + (slot + NB + rb) * PRENET + L2C * rk + (tid + oz), (value_bits(o) & 0x7fffffffu) | (nxt ? 0u : 0x80000000u));  // (x >= 0; a -0.0 must not read as "stopped")
       }
-      if (ROLE_FIRST) h_dec_mfmas(IP{}, IR{});
+      h_dec_mfmas(IP{}, IR{});
     }
     accD += acc2;
     P16_MARK(16);

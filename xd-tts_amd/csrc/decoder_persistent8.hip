@@ -44,14 +44,7 @@ namespace {
 constexpr int PT = 256, NW = PT / 64, NBMAX = 8, GSLOTS = P8_B_MAX, P_NCU = ATT_RNN / 4, TP = PERSIST_T_MAX;  // GSLOTS: chunk slots the granule arrays are laid out for (the 16-slot kernel's too)
 constexpr int ATTN_CU = 8, PRE_CU = 16, EP_LD = TP, MEL_GL = 96, WPAD = TP + 32;
 constexpr unsigned P_SPIN_LIMIT = 1u << 21;
-#ifndef XDTTS_P8_ATTN_SCHED
-#define XDTTS_P8_ATTN_SCHED 0
-#endif
-constexpr int DH_A = 8;  // column groups of the decoder LSTM's h_att segment ahead of the first energies poll (schedule 0)
-// 1: the attention workgroups put nothing but a nap between their energies and the poll of the other seven's, and run their
-// h_att MFMAs behind the context / the decoder cell instead.  Measured equal (14.6-14.9 us at 4 chunks either way: what the
-// energies edge gains, the later h_dec of those 32 workgroups loses for everybody), so the simpler order is the default.
-constexpr bool ATTN_SCHED = XDTTS_P8_ATTN_SCHED != 0;
+constexpr int DH_A = 8;  // column groups of the decoder LSTM's h_att segment ahead of the first energies poll
 static_assert(NBMAX == 8 && ATT_RNN == DEC_RNN && P_NCU == 256 && (ATTN_CU + PRE_CU) * NBMAX <= P_NCU, "role workgroups of 8 chunks fit the grid");
 static_assert(TP == 128 && PRENET == PT && EMB == 2 * PT && ATT_RNN == 4 * PT, "thread <-> granule maps below");
 
@@ -61,33 +54,12 @@ __host__ __device__ constexpr int p8_slots(int B) { return B <= 4 ? 4 : (B <= NB
 
 // NQ b128 loads of the wave's slice of one state segment (seg: LDS base of the segment in B order [k/4][NB][4]; q0: the wave's
 // first column quad-of-quads), 4 MFMAs each, into acc.  A[q] = the lane's four weights of columns 16 (q0 + q) + 4 kk .. + 3.
-#ifndef XDTTS_P8_TWO_CHAINS
-#define XDTTS_P8_TWO_CHAINS 0
-#endif
 template <int NB, int NQ, int FROM = 0, int TO = NQ>
 __device__ __forceinline__ void mfma_segment(f32x4 &acc, const float4 (&A)[NQ], const float *seg, int q0, int kk, int n) {
   // one B vector ahead of the MFMAs that consume it, and no further
   if constexpr (FROM >= TO) return;
   const float *bp = seg + ((4 * q0 + kk) * NB + n) * 4;
   float4 b = lds4(bp + FROM * 4 * NB * 4);
-#if XDTTS_P8_TWO_CHAINS
-  // two accumulator chains (x / z and y / w components): a dependent v_mfma_f32_16x16x4_f32 issues 40 cycles after its predecessor, an
-  // independent one 32 (round 6, from the 16-slot kernel).  NOT the default: this kernel sits at 256 + 253 registers, the second chain's
-  // four push it into scratch (36 spill instructions) -- 16.3 / 15.6 / 18.0 / 18.2 us at 3 / 4 / 5 / 8 chunks against 14.8 / 14.7 / 15.9 / 17.0
-  f32x4 acc1 = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int q = FROM; q < TO; ++q) {
-    const float4 bn = q + 1 < TO ? lds4(bp + (q + 1) * 4 * NB * 4) : b;
-    asm volatile("" ::: "memory");
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q].x, b.x, acc, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q].y, b.y, acc1, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q].z, b.z, acc, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(A[q].w, b.w, acc1, 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    b = bn;
-  }
-  acc += acc1;
-#else
 #pragma unroll
   for (int q = FROM; q < TO; ++q) {
     const float4 bn = q + 1 < TO ? lds4(bp + (q + 1) * 4 * NB * 4) : b;
@@ -99,7 +71,6 @@ __device__ __forceinline__ void mfma_segment(f32x4 &acc, const float4 (&A)[NQ], 
     __builtin_amdgcn_sched_barrier(0);
     b = bn;
   }
-#endif
 }
 
 // Developer build (-DXDTTS_P8_PROFILE): thread 0 of three workgroups (one per role) accumulates the 100 MHz wall clock between
@@ -442,18 +413,9 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent8(DecoderBufs d, P8Buf
     const unsigned ep_need = (attn && act_r) ? ((ep_t < T ? 3u : 0u) | (ep_t + 64 < T ? 12u : 0u)) : 0u;
     auto ep_at = [](int i) { return (unsigned)((i & 1) * 4 * EP_LD + (i >> 1) * 64); };
     u64 ep_v[4] = {0, 0, 0, 0};
-    const bool attn_on = attn && act_r;
-    if (ATTN_SCHED && attn_on) {
-      // the attention workgroups are the step's critical chain here: nothing but a nap between their energies and the poll of
-      // the chunk's other seven; their h_att MFMAs follow the context (and the next step's follow the decoder cell)
-      nap(g.delay[4]);
-      gather_issue<4>(ep_v, ep_base, ep_need, ep_at);
-    } else {
-      mfma_segment<NB, 16, 0, DH_A>(accD, dh, s_hatt, 16 * wave, kk, n);
-      if (ep_need) gather_issue<4>(ep_v, ep_base, ep_need, ep_at);
-      mfma_segment<NB, 16, DH_A, 16>(accD, dh, s_hatt, 16 * wave, kk, n);
-      if (ATTN_SCHED) mfma_segment<NB, 16>(accA, ah, s_hatt, 16 * wave, kk, n);  // attention LSTM of the next step: h_att(s)
-    }
+    mfma_segment<NB, 16, 0, DH_A>(accD, dh, s_hatt, 16 * wave, kk, n);
+    if (ep_need) gather_issue<4>(ep_v, ep_base, ep_need, ep_at);
+    mfma_segment<NB, 16, DH_A, 16>(accD, dh, s_hatt, 16 * wave, kk, n);
     P8_MARK(6);
     // ---- P3 (attention role): the 8 partial-energy rows of the chunk -> softmax -> this workgroup's 64 context columns ------------
     if (attn && act_r) {
@@ -508,8 +470,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent8(DecoderBufs d, P8Buf
       }
     }
     P8_MARK(23);
-    if (!ATTN_SCHED) mfma_segment<NB, 16>(accA, ah, s_hatt, 16 * wave, kk, n);  // attention LSTM of the next step: h_att(s) (while ctx travels)
-    else if (attn_on) mfma_segment<NB, 16>(accD, dh, s_hatt, 16 * wave, kk, n);
+    mfma_segment<NB, 16>(accA, ah, s_hatt, 16 * wave, kk, n);  // attention LSTM of the next step: h_att(s) (while ctx travels)
     P8_MARK(7);
     // ---- P4: ctx(s) of every active chunk -> decoder LSTM ------------------------------------------------------------------------
     // quad tid + 256 i of the slab: chunk 2 i + tid / 128, columns 4 (tid % 128) .. + 3
@@ -541,7 +502,6 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent8(DecoderBufs d, P8Buf
     }
     accD = (f32x4){0.f, 0.f, 0.f, 0.f};
     P8_MARK(10);
-    if (ATTN_SCHED && attn_on) mfma_segment<NB, 16>(accA, ah, s_hatt, 16 * wave, kk, n);
     mfma_segment<NB, 8>(accA, ac, s_ctx, 8 * wave, kk, n);  // attention LSTM of the next step: ctx(s)
     if (attn && act_r) location();                           // ... and its location features
     P8_MARK(11);

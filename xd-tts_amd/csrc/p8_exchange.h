@@ -1,6 +1,7 @@
 // p8_exchange.h -- the exchange primitives of the persistent MFMA decoders (decoder_persistent8.hip: 3..8 chunks, decoder_persistent16.hip:
 // 9..16 chunks): {tag, value} granules for the narrow edges, write-once rings of plain values (a value is its own arrival flag)
-// for the vectors every workgroup gathers, bounded polls that watch a global error word.  Included by both translation units.
+// for the vectors every workgroup gathers, bounded polls that watch a global error word.  Included by both translation units, and by
+// decoder_persistent.hip for the granule primitives (publish, peek, PollCtl, give_up) and lds4; its own gather is another overload.
 #pragma once
 #include "device_utils.h"
 #include "kernels.h"
@@ -115,7 +116,6 @@ __device__ __forceinline__ unsigned gather16(const unsigned *slab, unsigned need
 }
 __device__ __forceinline__ float4 as_f4(u32x4 v) { return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)); }
 __device__ __forceinline__ float4 lds4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
 
 }  // namespace
 }  // namespace xdtts
