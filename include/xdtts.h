@@ -150,6 +150,12 @@ xdtts_status xdtts_tacotron2_infer_batch(xdtts_tacotron2 *h, const int64_t *ids,
  * encoder.onnx (mod.rs:379): ids (T) -> memory (T x 512), processed_memory (T x 128). */
 xdtts_status xdtts_tacotron2_encoder(xdtts_tacotron2 *h, const int64_t *ids, int32_t T,
                                      float *memory, float *processed_memory);
+/* The same for B chunks of T ids each (ids [B][T], zero-padded by the caller) through the code a batch request runs:
+ * memory [B][T][512], processed_memory [B][T][128].  engine: -1 = the BiLSTM engine the handle would use, 1 = the cooperative
+ * recurrence (one chunk per group of workgroups up to CUs / 8 chunks, two per group beyond, several launches beyond twice
+ * that), 0 = the single-workgroup recurrence.  B in 1..4096, T in 1..512, every id in range, as for xdtts_tacotron2_infer_batch. */
+xdtts_status xdtts_tacotron2_encoder_batch(xdtts_tacotron2 *h, int32_t engine, const int64_t *ids, int32_t B, int32_t T,
+                                           float *memory, float *processed_memory);
 /* run_decoder frame loop (mod.rs:272-342) on caller-supplied encoder outputs: frames are
  * n_frames x 80 (pre-postnet, time-major), gates n_frames. Buffers sized for max_steps. */
 xdtts_status xdtts_tacotron2_decoder(xdtts_tacotron2 *h, const float *memory,
@@ -220,6 +226,12 @@ xdtts_status xdtts_edge_floor_us(int32_t device_id, int32_t steps, int32_t T, in
 /* postnet.onnx (mod.rs:345-355): frames (F x 80) -> mel_outputs_postnet (80 x F). */
 xdtts_status xdtts_tacotron2_postnet(xdtts_tacotron2 *h, const float *frames, int32_t F,
                                      float *mel_out);
+/* The same for n >= 1 chunks through the code behind a batch request's decode (groups of at most 64 chunks per launch): chunk i
+ * has F[i] >= 1 rows of 80 at frames + i * frame_stride (frame_stride a multiple of 80, in floats; only those rows are read).
+ * out receives sum(F) * 80 floats: one (80 x sum F) matrix with the chunks side by side in the caller's order, or with
+ * per_chunk != 0 one dense (80 x F[i]) matrix per chunk back to back -- the two layouts of xdtts_tacotron2_infer_ids / _batch. */
+xdtts_status xdtts_tacotron2_postnet_batch(xdtts_tacotron2 *h, const float *frames, size_t frame_stride, const int32_t *F,
+                                           int32_t n, int32_t per_chunk, float *out);
 
 /* Phase timings of the last infer call on this handle, measured with HIP events on the
  * handle's stream: ms[0] encoder, ms[1] decoder loop, ms[2] postnet, ms[3] total;

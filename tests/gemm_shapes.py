@@ -68,18 +68,21 @@ def cdiv(a, b):
 
 
 def plan(site, M, batch=1, force_tile=0, force_nosplit=False):
-    """What launch_gemm_nt / gemm_splitk_plan choose for `batch` items of M rows at a call site.
+    """What launch_gemm_nt / gemm_splitk_plan choose for `batch` items of M rows at a call site, or, with M a sequence of
+    per-item row counts, for that ragged batch (the post-net's: g.M = the longest item, Mz the items).
     force_tile / force_nosplit: XDTTS_GEMM_TILE / XDTTS_GEMM_SPLITK=1 of the forced-tile child process."""
     s = SITES[site]
     N, K, lda = s["N"], s["K"], s["lda"]
+    Mz = [M] * batch if isinstance(M, (int, np.integer)) else [int(m) for m in M]
+    M, batch = max(Mz), len(Mz)
     tiles64 = cdiv(N, 64) * cdiv(M, 64) * batch
     natural_big = N >= 64 and tiles64 >= 512 and not (M <= 128 and N >= 4096)
-    rows = M * batch
+    rows = sum(Mz)
     xcd = rows * lda > N * K
     nslab = cdiv(K, BK)
     sk = 1
     if s["split"] and not force_nosplit and not natural_big and not xcd:
-        blocks = batch * cdiv(M, 32) * cdiv(N, 32)
+        blocks = sum(cdiv(m, 32) for m in Mz) * cdiv(N, 32)
         sk = min(4, 512 // max(blocks, 1))
         sk = min(sk, nslab // 8)
         if sk < 2:
@@ -94,7 +97,7 @@ def plan(site, M, batch=1, force_tile=0, force_nosplit=False):
         tile = 64 if natural_big else 32
     kper = cdiv(nslab, sk) * BK
     slabs = tuple(cdiv(min(K - ks * kper, kper), BK) for ks in range(sk))
-    row_tiles = cdiv(M, tile) * batch
+    row_tiles = sum(cdiv(m, tile) for m in Mz)
     return dict(tile=tile, mapping="xcd" if xcd else "plain", slices=sk, slabs=slabs, row_tiles=row_tiles,
                 col_tiles=cdiv(N, tile), padded=bool(xcd and row_tiles % 8 != 0))
 
@@ -153,11 +156,14 @@ def rms(a, b):
 
 # ---- fp64 numpy post-net, optionally spoilt ---------------------------------------------------------------------
 
-def postnet_numpy(orc, blob, frames, spoil=None):
+def postnet_numpy(orc, blob, frames, spoil=None, stale=None):
     """postnet.onnx from the blob's tensors in fp64: 5 x [conv k5 pad 2 + BN(eval)], tanh after the first four, the
     residual added at the end; (80, F).  spoil = (layer, row tile, column tile, K group): that layer's GEMM loses the
     products of one 16-wide group of its contraction index (laid out [tap][channel in], as the kernel's operand is) in
-    one 32x32 output tile -- what a slab staged half, or a fragment read from the wrong buffer, would do."""
+    one 32x32 output tile -- what a slab staged half, or a fragment read from the wrong buffer, would do; with a sequence
+    of K groups in place of one, all of them (a whole K slice of a split launch).
+    stale = (layer, rows (2, channels in)): that layer reads `rows` where the zero padding behind the last frame should be --
+    what a shorter item of a ragged batch reads when the rows up to the longest item's end were not cleared."""
     x = np.asarray(frames, dtype=np.float64)
     F = x.shape[0]
     for i in range(5):
@@ -167,15 +173,18 @@ def postnet_numpy(orc, blob, frames, spoil=None):
         pad = (k - 1) // 2
         xp = np.zeros((F + 2 * pad, ci))
         xp[pad:pad + F] = x
+        if stale is not None and stale[0] == i:
+            xp[pad + F:] = stale[1]
         s = np.zeros((F, co))
         for j in range(k):
             s += xp[j:j + F] @ w[:, :, j].T
         if spoil is not None and spoil[0] == i:
-            _, tm, tn, kg = spoil
-            j, c0 = (16 * kg) // ci, (16 * kg) % ci
+            _, tm, tn, kgs = spoil
             r0, r1, n0, n1 = 32 * tm, min(32 * tm + 32, F), 32 * tn, min(32 * tn + 32, co)
-            assert r0 < F and n0 < co and j < k, spoil
-            s[r0:r1, n0:n1] -= xp[r0 + j:r1 + j, c0:c0 + 16] @ w[n0:n1, c0:c0 + 16, j].T
+            for kg in (kgs,) if isinstance(kgs, (int, np.integer)) else kgs:
+                j, c0 = (16 * kg) // ci, (16 * kg) % ci
+                assert r0 < F and n0 < co and j < k, spoil
+                s[r0:r1, n0:n1] -= xp[r0 + j:r1 + j, c0:c0 + 16] @ w[n0:n1, c0:c0 + 16, j].T
         s += orc.tensor(blob, p + "conv.bias").astype(np.float64)
         inv = 1.0 / np.sqrt(orc.tensor(blob, p + "bn.running_var").astype(np.float64) + 1e-5)
         s = (s - orc.tensor(blob, p + "bn.running_mean").astype(np.float64)) * inv * orc.tensor(blob, p + "bn.weight").astype(np.float64) \

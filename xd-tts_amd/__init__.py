@@ -123,6 +123,7 @@ SYMBOLS = {
     "xdtts_tacotron2_infer_ids": (_I32, [_VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_tacotron2_infer_batch": (_I32, [_VP, _VP, _VP, _I32, _I32, C.POINTER(InferOpts), _VP, C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_tacotron2_encoder": (_I32, [_VP, _VP, _I32, _VP, _VP]),
+    "xdtts_tacotron2_encoder_batch": (_I32, [_VP, _I32, _VP, _I32, _I32, _VP, _VP]),
     "xdtts_tacotron2_decoder": (_I32, [_VP, _VP, _VP, _I32, _I32, C.POINTER(InferOpts), _VP, _VP, C.POINTER(_SZ)]),
     "xdtts_tacotron2_decoder_step": (_I32, [_VP, _VP, _VP, _I32, _I32, C.POINTER(InferOpts), _U32] + [_VP] * 10),
     "xdtts_tacotron2_decoder_steps": (_I32, [_VP, _I32, _I32, _VP, _VP, _I32, _VP, C.POINTER(InferOpts), _U32, _I32] + [_VP] * 10),
@@ -130,6 +131,7 @@ SYMBOLS = {
     "xdtts_tacotron2_small_batch_engine_state": (_I32, [_VP, C.POINTER(_I32)]),
     "xdtts_tacotron2_engine_reset": (_I32, [_VP]),
     "xdtts_tacotron2_postnet": (_I32, [_VP, _VP, _I32, _VP]),
+    "xdtts_tacotron2_postnet_batch": (_I32, [_VP, _VP, _SZ, _VP, _I32, _I32, _VP]),
     "xdtts_tacotron2_last_timings": (_I32, [_VP, C.POINTER(C.c_float * 4), C.POINTER(_I32)]),
     "xdtts_tacotron2_free": (None, [_VP]),
     "xdtts_tacotron2_sync": (_I32, [_VP]),
@@ -557,6 +559,18 @@ class Tacotron2:
         _check(lib.xdtts_tacotron2_encoder(self._h, _ptr(ids), T, _ptr(memory), _ptr(pmem)))
         return memory, pmem
 
+    BILSTM_ENGINES = {None: -1, "single": 0, "cooperative": 1}
+
+    def encoder_batch(self, ids, engine=None):
+        """encoder.onnx for B chunks at once, the way a batch request runs it: ids (B, T) zero-padded -> memory (B, T, 512),
+        processed_memory (B, T, 128).  engine: None (the handle's), "cooperative" or "single" (the BiLSTM recurrence)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        B, T = ids.shape
+        memory = np.empty((B, T, EMB), dtype=np.float32)
+        pmem = np.empty((B, T, ATT_DIM), dtype=np.float32)
+        _check(lib.xdtts_tacotron2_encoder_batch(self._h, self.BILSTM_ENGINES[engine], _ptr(ids), B, T, _ptr(memory), _ptr(pmem)))
+        return memory, pmem
+
     def decoder(self, memory, pmem, n_valid, opts=None):
         memory = np.ascontiguousarray(memory, dtype=np.float32)
         pmem = np.ascontiguousarray(pmem, dtype=np.float32)
@@ -615,6 +629,23 @@ class Tacotron2:
         out = np.empty((N_MEL, F), dtype=np.float32)
         _check(lib.xdtts_tacotron2_postnet(self._h, _ptr(frames), F, _ptr(out)))
         return out
+
+    def postnet_batch(self, frames_list, per_chunk=False):
+        """postnet.onnx for n chunks through the group loop of a batch request: frames_list[i] is (F_i, 80).  Returns the
+        (80, sum F) matrix with the chunks side by side, or with per_chunk the list of dense (80, F_i) matrices."""
+        n = len(frames_list)
+        F = np.array([np.shape(f)[0] for f in frames_list], dtype=np.int32)
+        stride = int(F.max()) * N_MEL
+        buf = np.zeros((n, stride), dtype=np.float32)
+        for i, f in enumerate(frames_list):
+            buf[i, : F[i] * N_MEL] = np.asarray(f, dtype=np.float32).reshape(-1)
+        total = int(F.sum())
+        out = np.empty(N_MEL * total, dtype=np.float32)
+        _check(lib.xdtts_tacotron2_postnet_batch(self._h, _ptr(buf), stride, _ptr(F), n, 1 if per_chunk else 0, _ptr(out)))
+        if not per_chunk:
+            return out.reshape(N_MEL, total)
+        ends = np.cumsum(F) * N_MEL
+        return [out[e - F[i] * N_MEL:e].reshape(N_MEL, F[i]) for i, e in enumerate(ends)]
 
     def last_timings(self):
         ms = (C.c_float * 4)()

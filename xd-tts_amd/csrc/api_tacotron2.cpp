@@ -225,6 +225,29 @@ xdtts_status xdtts_tacotron2_encoder(xdtts_tacotron2 *h, const int64_t *ids, int
   });
 }
 
+// Parity hook: encoder.onnx for B chunks of T ids through run_encoder(B, T), the call of infer_batch_device, with the BiLSTM
+// engine the caller names.
+xdtts_status xdtts_tacotron2_encoder_batch(xdtts_tacotron2 *h, int32_t engine, const int64_t *ids, int32_t B, int32_t T, float *memory,
+                                           float *processed_memory) {
+  return guard([&] {
+    if (!h || !ids || !memory || !processed_memory) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (engine < -1 || engine > 1) fail(XDTTS_ERR_BAD_ARG, "engine %d out of range (-1 the handle's, 0 single-workgroup, 1 cooperative)", engine);
+    if (B <= 0 || B > 4096) fail(XDTTS_ERR_BAD_ARG, "batch %d out of range", B);
+    if (T <= 0 || T > T_MAX) fail(XDTTS_ERR_BAD_ARG, "window %d out of range (1..%d)", T, T_MAX);
+    for (size_t i = 0; i < (size_t)B * T; ++i)
+      if (ids[i] < 0 || ids[i] >= N_SYMBOLS) fail(XDTTS_ERR_BAD_ARG, "id %lld out of range (0..%d)", (long long)ids[i], N_SYMBOLS - 1);
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIP_CHECK(hipSetDevice(h->device));
+    h->ids.upload(ids, (size_t)B * T, h->stream);
+    std::lock_guard<ChipLock> chip(chip_mutex(h->device));
+    h->run_encoder(B, T, engine);
+    HIP_CHECK(hipMemcpyAsync(memory, h->memory.p, (size_t)B * T * EMB * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(processed_memory, h->pmem.p, (size_t)B * T * ATT_DIM * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->check_encoder_exchange();
+  });
+}
+
 xdtts_status xdtts_tacotron2_decoder(xdtts_tacotron2 *h, const float *memory, const float *processed_memory,
                                      int32_t T, int32_t n_valid, const xdtts_infer_opts *opts, float *frames,
                                      float *gates, size_t *n_frames) {
@@ -480,6 +503,32 @@ xdtts_status xdtts_tacotron2_postnet(xdtts_tacotron2 *h, const float *frames, in
     const long zero = 0;
     h->run_postnet(h->frames.p, 0, &F, &zero, 1, h->mel_dev.p, F);
     HIP_CHECK(hipMemcpyAsync(mel_out, h->mel_dev.p, (size_t)N_MEL * F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+  });
+}
+
+// Parity hook: postnet.onnx for n chunks through postnet_groups, the group loop behind every decode of infer_batch_device.
+xdtts_status xdtts_tacotron2_postnet_batch(xdtts_tacotron2 *h, const float *frames, size_t frame_stride, const int32_t *F, int32_t n,
+                                           int32_t per_chunk, float *out) {
+  return guard([&] {
+    if (!h || !frames || !F || !out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (n <= 0 || n > 4096) fail(XDTTS_ERR_BAD_ARG, "batch %d out of range", n);
+    if (frame_stride == 0 || frame_stride % N_MEL != 0 || frame_stride > ((size_t)1 << 26)) fail(XDTTS_ERR_BAD_ARG, "frame_stride must be a multiple of %d", N_MEL);
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+      if (F[i] <= 0 || (size_t)F[i] * N_MEL > frame_stride) fail(XDTTS_ERR_BAD_ARG, "chunk %d: %d frames do not fit the stride", i, F[i]);
+      total += (size_t)F[i];
+    }
+    if (total > ((size_t)1 << 24)) fail(XDTTS_ERR_BAD_ARG, "%zu frames in all", total);
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIP_CHECK(hipSetDevice(h->device));
+    h->frames.alloc((size_t)n * frame_stride);
+    for (int i = 0; i < n; ++i)  // the rows behind F[i] keep whatever the buffer held, as behind a decode
+      HIP_CHECK(hipMemcpyAsync(h->frames.p + (size_t)i * frame_stride, frames + (size_t)i * frame_stride, (size_t)F[i] * N_MEL * sizeof(float),
+                               hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    const int got = h->postnet_groups(h->frames.p, frame_stride, F, nullptr, n, per_chunk != 0);
+    HIP_CHECK(hipMemcpyAsync(out, h->mel_dev.p, (size_t)N_MEL * got * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));
   });
 }

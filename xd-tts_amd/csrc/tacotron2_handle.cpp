@@ -52,7 +52,7 @@ void xdtts_tacotron2::run_gemm(GemmArgs &g) {
   launch_gemm_nt(g, stream);
 }
 
-void xdtts_tacotron2::run_encoder(int B, int T) {
+void xdtts_tacotron2::run_encoder(int B, int T, int bilstm) {
   const int pad = (ENC_K - 1) / 2, TP = T + 2 * pad;
   const size_t padded = (size_t)B * TP * EMB;
   xpadA.alloc(padded);
@@ -108,10 +108,12 @@ void xdtts_tacotron2::run_encoder(int B, int T) {
   }
   // a demoted encoder probes the cooperative recurrence again by itself (its own counter: the decoder's re-probe does not
   // depend on it, and a batched decode never passes through use_persistent)
-  enc_gate.ensure_probed([] { return true; });
-  enc_gate.tick();
+  if (bilstm < 0) {
+    enc_gate.ensure_probed([] { return true; });
+    enc_gate.tick();
+  }
   bool coop_ran = false;
-  if (enc_gate.usable()) {
+  if (bilstm < 0 ? enc_gate.usable() : bilstm == 1) {
     // groups of four workgroups per direction, at most coop_group of them per launch; from coop_group + 1 chunks on a group
     // takes two chunks (52 chunks on 256 CUs: one launch of 26 two-chunk groups; it was 26 + 26 one-chunk groups)
     const int slots = B > coop_group ? (B + 1) / 2 : B;  // groups needed
@@ -122,6 +124,10 @@ void xdtts_tacotron2::run_encoder(int B, int T) {
                          stream);
       coop_ran = true;
     } catch (const CoopRefused &) {
+      if (bilstm == 1) {
+        (void)hipStreamSynchronize(stream);
+        fail(XDTTS_ERR_HIP, "cooperative encoder BiLSTM not available on this device (cooperative launch refused)");
+      }
       // the runtime refused the cooperative grid (CU masking, a smaller part): the single-workgroup recurrence serves
       // this handle from now on -- the refusal is a property of the device, not a transient
       enc_gate.refuse();
@@ -332,6 +338,33 @@ void xdtts_tacotron2::run_postnet(const float *frames_dev, size_t frame_stride, 
   }
 }
 
+// The post-net behind a decode, and the parity hook's (xdtts_tacotron2_postnet_batch): run_postnet per group of GEMM_RAGGED_MAX slots.
+int xdtts_tacotron2::postnet_groups(const float *frames_dev, size_t frame_stride, const int *Fs, const int *order, int B, bool per_chunk) {
+  std::vector<int> F(B);  // frames per caller index
+  int total = 0;
+  for (int j = 0; j < B; ++j) {
+    F[order ? order[j] : j] = Fs[j];
+    total += Fs[j];
+  }
+  // (In a sequence the vocoder of the PREVIOUS utterance may still be reading mel_dev on its own stream when this runs for the next
+  // one.  DevBuf::alloc only ever grows: the buffer is kept unless this utterance is longer than every one before it, and then the
+  // hipFree inside it synchronises the whole device before the old buffer goes -- correct, at the price of that one overlap.  The
+  // post-net's own writes into a kept buffer are ordered behind the vocoder by the event the frame loop waits for, before_decoder.)
+  mel_dev.alloc((size_t)N_MEL * total);
+  std::vector<long> col0(B), col(B);  // the final mel keeps the caller's chunk order on the time axis (mod.rs:430)
+  long off = 0;
+  for (int b = 0; b < B; ++b) {
+    col0[b] = off;
+    off += F[b];
+  }
+  for (int j = 0; j < B; ++j) col[j] = (per_chunk ? N_MEL : 1) * col0[order ? order[j] : j];
+  for (int b = 0; b < B; b += GEMM_RAGGED_MAX) {
+    const int n = std::min(GEMM_RAGGED_MAX, B - b);
+    run_postnet(frames_dev + (size_t)b * frame_stride, frame_stride, Fs + b, col.data() + b, n, mel_dev.p, total, per_chunk);
+  }
+  return total;
+}
+
 // infer_chunk x B (mod.rs:361-393).  ids_host [B][T] already zero-padded.  Leaves the final mel
 // of chunk b at mel_dev + col_off[b] with row stride F_total; returns per-chunk frame counts.
 // per_chunk: mel_dev receives one dense (80 x F_b) matrix per chunk instead, back to back in the caller's order.
@@ -421,29 +454,11 @@ std::vector<int> xdtts_tacotron2::infer_batch_device(const int64_t *ids_host, co
   int total = 0;
   auto postnet_all = [&](const int *frames_per_slot) {
     HIP_CHECK(hipEventRecord(ev.e[2], stream));
-    total = 0;
     for (int j = 0; j < B; ++j) {
       Fs[j] = frames_per_slot[j];
       F[order[j]] = Fs[j];
-      total += Fs[j];
     }
-    // (In a sequence the vocoder of the PREVIOUS utterance may still be reading mel_dev on its own stream when this runs for the next
-    // one.  DevBuf::alloc only ever grows: the buffer is kept unless this utterance is longer than every one before it, and then the
-    // hipFree inside it synchronises the whole device before the old buffer goes -- correct, at the price of that one overlap.  The
-    // post-net's own writes into a kept buffer are ordered behind the vocoder by the event the frame loop waits for, before_decoder.)
-    mel_dev.alloc((size_t)N_MEL * total);
-    std::vector<long> col0(B), col(B);  // the final mel keeps the caller's chunk order on the time axis (mod.rs:430)
-    long off = 0;
-    for (int b = 0; b < B; ++b) {
-      col0[b] = off;
-      off += F[b];
-    }
-    for (int j = 0; j < B; ++j) col[j] = (per_chunk ? N_MEL : 1) * col0[order[j]];
-    for (int b = 0; b < B; b += GEMM_RAGGED_MAX) {
-      const int n = std::min(GEMM_RAGGED_MAX, B - b);
-      run_postnet(d.frames + (size_t)b * d.max_steps * N_MEL, (size_t)d.max_steps * N_MEL, Fs.data() + b, col.data() + b, n,
-                  mel_dev.p, total, per_chunk);
-    }
+    total = postnet_groups(d.frames, (size_t)d.max_steps * N_MEL, Fs.data(), order.data(), B, per_chunk);
     HIP_CHECK(hipEventRecord(ev.e[3], stream));
   };
   bool postnet_done = false;

@@ -107,12 +107,18 @@ struct xdtts_tacotron2 {
   void init(int dev);
   void run_gemm(xdtts::GemmArgs &g);
   // encoder.onnx (mod.rs:379): ids [B][T] on device -> memory, pmem
-  void run_encoder(int B, int T);
+  // bilstm: -1 = what the handle's gate says (the request path), 1 / 0 = the parity hook's choice: the cooperative recurrence (a
+  // refused launch is an error then) / the single-workgroup one; neither touches the gate
+  void run_encoder(int B, int T, int bilstm = -1);
   void upload_dropout_masks(const xdtts_infer_opts &o, int B, const int *lim);
   // force_batched: -1 = by batch size (the MFMA kernels from BATCH_MFMA_MIN chunks), 0 / 1 = the parity hook's choice
   DecoderBufs decoder_bufs(int B, int T, const float *mem, const float *pm, const xdtts_infer_opts &o, int force_batched = -1);
   void run_postnet(const float *frames_dev, size_t frame_stride, const int *F, const long *col_off, int n, float *out, long ldc,
                    bool dense_items = false);
+  // the post-net of B chunks in groups of at most GEMM_RAGGED_MAX: slot j has Fs[j] frames at frames_dev + j * frame_stride and is the
+  // caller's chunk order[j] (nullptr: j); mel_dev receives the (80 x F_total) matrix in the caller's order, or with per_chunk one dense
+  // (80 x F_b) matrix per chunk back to back.  Returns F_total.
+  int postnet_groups(const float *frames_dev, size_t frame_stride, const int *Fs, const int *order, int B, bool per_chunk);
   std::vector<int> infer_batch_device(const int64_t *ids_host, const int *lens, int B, int T, const xdtts_infer_opts &o,
                                       const int *fixed_per_item, int *F_total, bool per_chunk = false);
   void check_encoder_exchange();
