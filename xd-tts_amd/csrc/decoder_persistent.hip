@@ -36,6 +36,16 @@
 // Only the pieces that depend on the newest vector sit on the critical path (x for the attention LSTM, the
 // softmax for the decoder LSTM); the other column blocks are accumulated per lane while the producers of the
 // next vector are busy, and one DPP wave reduction closes each row.
+// Every all-gather waits for its LAST publisher, so in the lock-step loop a publish is followed by nothing that waits:
+//   * each deferred column block is pinned where the source has it (pin()): left alone, the compiler sank the h_att-column
+//     block of the decoder LSTM behind the energy gather, into the softmax -> h_dec chain of all 256 workgroups;
+//   * no s_waitcnt vmcnt(0) stands between a publish store and the block behind it (loads_settled() at the end of every
+//     gather; tests/test_kernel_isa_persistent_cpu.py counts the FMAs between each publish and the next full wait).
+//     The skewed pair loop keeps the waits it was tuned with: without them its early polls leave earlier still, and it
+//     measured 1.9 % slower (11.05 against 10.85 us per pair step);
+//   * one-chunk kernel: the attention role issues the first poll of the energies, and the projection role the first poll of
+//     the mel rows, from inside the block behind its own publish (EPOLL_AT / MPOLL_AT; the PRE form of gather(), which the
+//     skewed pair loop has for every edge), and the projection role does not fill the layer-1 LDS table it never reads.
 //
 // Every spin is bounded and watches a global error word: a lost workgroup (grid not co-resident)
 // drains the whole launch in microseconds and surfaces as XDTTS_ERR_HIP on the host.
@@ -59,6 +69,12 @@ constexpr int GS = PERSIST_B_MAX;        // chunk stride of the granule arrays: 
 constexpr unsigned P_SPIN_LIMIT = 1u << 21;
 constexpr int PERSIST_LAZY_DEFAULT = 9;  // x 256 clocks: ~0.95 us (6 / 7 / 8 / 9 / 10 -> 8.53 / 8.45 / 8.38 / 8.26 / 8.35 us per 1-chunk step; 0: +1.3 us)
 
+// One-chunk kernel, role workgroups: the first poll of the vector a role gathers next leaves from inside the deferred column
+// block behind its publish, after EPOLL_AT / MPOLL_AT of the block's four parts (attention role: energies; projection role:
+// mel rows); the attention role first sleeps EPOLL_NAP x 256 clocks.  Swept on the headline (profiles/persistent_role_lateness.txt):
+// a poll that leaves too early finds the slowest sibling's store not landed and pays a second round trip -- energies at part 0
+// without the sleep: +0.27 us per step; parts 2..4 with the sleep, and the mel poll at parts 2 or 4, are within the noise of each other.
+constexpr int EPOLL_AT = 2, EPOLL_NAP = 1, MPOLL_AT = 2;
 constexpr int WPAD = TP + 32;            // zero-padded attention-weight window, index t + 15
 static_assert(ATT_RNN == DEC_RNN && P_NCU == 256, "one workgroup per 4 + 4 hidden units");
 
@@ -67,10 +83,16 @@ static_assert(ATT_RNN == DEC_RNN && P_NCU == 256, "one workgroup per 4 + 4 hidde
 // live across the step loop).  A timed-out slot reads as {tag 0, 0.0f}.
 // PRE: the first poll of every granule was issued earlier (pre[i], by the previous phase of the skewed pair loop); a value
 // whose tag is not this step's -- not there yet, or nothing was issued -- is polled as usual.
-template <int N, bool PRE = false>
-__device__ __forceinline__ unsigned gather(const u64 *base, unsigned idx, unsigned stride, unsigned want,
-                                           const bool (&need)[N], float (&out)[N], unsigned (&tag)[N], const PollCtl &err,
-                                           const u64 *pre = nullptr) {
+// gather() ends in loads_settled(), behind the poll loop's last join: the values have all been used, so the wait is free,
+// and it is the form the compiler's waitcnt pass reads -- behind the poll loop's joins it no longer knew that the loads were
+// complete, and put an s_waitcnt vmcnt(0) in front of the first LDS read that reused one of their destination registers.
+// That read stood behind the NEXT publish store, so the role that had just published waited for its write-through store's
+// acknowledgement (stores count in vmcnt on this target) before the deferred column block and its own first poll.
+__device__ __forceinline__ void loads_settled() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // vmcnt(0), nothing else
+template <int N, bool PRE>
+__device__ __forceinline__ unsigned gather_poll(const u64 *base, unsigned idx, unsigned stride, unsigned want,
+                                                const bool (&need)[N], float (&out)[N], unsigned (&tag)[N], const PollCtl &err,
+                                                const u64 *pre) {
   bool done[N];
 #pragma unroll
   for (int i = 0; i < N; ++i) {
@@ -116,6 +138,15 @@ __device__ __forceinline__ unsigned gather(const u64 *base, unsigned idx, unsign
     if (all || give_up(spins, err)) return spins;
   }
 }
+// (SETTLE = false: the skewed pair loop, which keeps the waits it was tuned with -- see ph1)
+template <int N, bool PRE = false, bool SETTLE = true>
+__device__ __forceinline__ unsigned gather(const u64 *base, unsigned idx, unsigned stride, unsigned want,
+                                           const bool (&need)[N], float (&out)[N], unsigned (&tag)[N], const PollCtl &err,
+                                           const u64 *pre = nullptr) {
+  const unsigned spins = gather_poll<N, PRE>(base, idx, stride, want, need, out, tag, err, pre);
+  if (SETTLE) loads_settled();
+  return spins;
+}
 
 // Workgroups that consume a vector only for off-critical-path work start polling it late (n x 256
 // clocks): their polls would otherwise sit in the memory queues the critical consumers wait on.
@@ -134,6 +165,10 @@ __device__ __forceinline__ void straggle(bool me, int s, int at) {
 // Keeps the per-chunk bodies of an unrolled chunk loop in program order: without it the LDS loads
 // of every chunk are hoisted ahead of the first FMA and the live set grows by ~40 VGPRs per chunk.
 __device__ __forceinline__ void chunk_fence() { asm volatile("" ::: "memory"); }
+// Holds a deferred column block where the source has it: its two sums are consumed only a phase later, and without a use in
+// between the compiler sank the block's 32 FMAs per lane behind the next gather -- out of the wait they were meant to fill
+// and onto every workgroup's critical path.
+__device__ __forceinline__ void pin(float &a0, float &a1) { asm volatile("" : "+v"(a0), "+v"(a1)); }
 __device__ __forceinline__ unsigned opaque(unsigned v) {
   asm volatile("" : "+v"(v));
   return v;
@@ -194,6 +229,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
   __shared__ __attribute__((aligned(16))) float smem[persist_lds_floats(PB)];
   const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = d.T;
+  constexpr bool ROLE_REGS = PB == 1;  // one-chunk kernel: the roles' per-step weights in registers, their first polls issued early
   const PollCtl pc{g.err, g.spins > 0 ? (unsigned)g.spins : P_SPIN_LIMIT};
   if (g.fault && c == g.fault - 1) return;  // developer fault injection: this workgroup never shows up
   const unsigned L4 = opaque(4u * (unsigned)lane);
@@ -305,8 +341,9 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
   }
   if (pre) {
     // [in / 4][out][in % 4]: a thread's 40 layer-1 weights are ten conflict-free 16-byte reads (two-chunk kernel; the
-    // one-chunk kernel keeps them in registers)
-    for (int i = tid; i < N_MEL * PRENET; i += PT) s_W0[(((i / PRENET) >> 2) * PRENET + i % PRENET) * 4 + ((i / PRENET) & 3)] = w.pre0T[i];
+    // one-chunk kernel keeps them in registers and never reads s_W0, so it does not fill it: 80 KB of LDS stores per workgroup)
+    if (!ROLE_REGS)
+      for (int i = tid; i < N_MEL * PRENET; i += PT) s_W0[(((i / PRENET) >> 2) * PRENET + i % PRENET) * 4 + ((i / PRENET) & 3)] = w.pre0T[i];
     if (prow_ok) {
       if (lane == 0) s_pb[wave] = w.proj_b[prow];
 #pragma unroll
@@ -318,7 +355,6 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
   // One-chunk kernel: the role's per-step weights move from LDS into the 40 registers the second chunk would need
   // (attention: the two query rows of this wave, 8 float4; prenet: this thread's 40 layer-1 weights) -- the LDS
   // operand reads of these two inner products were ~0.4 us of the step's critical path.
-  constexpr bool ROLE_REGS = PB == 1;
   float rw[ROLE_REGS ? 40 : 1];
   if (ROLE_REGS) {
 #pragma unroll
@@ -425,22 +461,32 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         a0 = dot4(wa[0][k], v, a0);
         a1 = dot4(wa[1][k], v, a1);
       }
+      pin(a0, a1);
       aacc[b][0] = a0;
       aacc[b][1] = a1;
       chunk_fence();
     }
   };
-  auto dec_bulk_h = [&](unsigned L4, bool all) {  // decoder LSTM, columns h_dec(s-1)
+  // poll(): called once AT (an integral_constant, 0..4; -1: never) of a chunk's four column blocks are done -- where a role
+  // issues the first poll of the vector it gathers next
+  auto dec_bulk_h = [&](unsigned L4, bool all, auto AT, auto poll) {  // decoder LSTM, columns h_dec(s-1)
+    constexpr int at = decltype(AT)::value;
 #pragma unroll
     for (int b = 0; b < PB; ++b) {
       if (!all && !s_act[b]) continue;
       float a0 = 0.f, a1 = 0.f;
 #pragma unroll
       for (int k = 6; k < 10; ++k) {
+        if (k - 6 == at) {
+          pin(a0, a1);
+          poll();
+        }
         const float4 v = lds4(s_hdec + b * DEC_RNN + 256 * (k - 6) + L4);
         a0 = dot4(wd[0][k], v, a0);
         a1 = dot4(wd[1][k], v, a1);
       }
+      pin(a0, a1);
+      if (at == 4) poll();
       dacc[b][0] = a0;
       dacc[b][1] = a1;
       chunk_fence();
@@ -481,7 +527,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
     __syncthreads();
   };
   att_bulk(L4, true);
-  dec_bulk_h(L4, true);
+  dec_bulk_h(L4, true, std::integral_constant<int, -1>{}, [] {});
   if (attn) location(tid);
 
 #ifdef XDTTS_PERSIST_PROFILE
@@ -579,7 +625,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         const bool need[1] = {tid < 256};
         float v[1];
         unsigned tg[1];
-        gather<1, true>(g.x, (unsigned)((p * GS + b) * PRENET + i), 0u, want, need, v, tg, pc, pf);
+        gather<1, true, false>(g.x, (unsigned)((p * GS + b) * PRENET + i), 0u, want, need, v, tg, pc, pf);
         if (need[0]) {
           s_x[b * PRENET + i] = v[0];
           if (i == 0) s_act[b] = (tg[0] & ACT_BIT) ? 1 : 0;
@@ -632,7 +678,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         const bool need[2] = {true, true};
         float v[2];
         unsigned tg[2];
-        gather<2, true>(g.hatt, (unsigned)((p * GS + b) * ATT_RNN + tid), PT, want, need, v, tg, pc, pf);
+        gather<2, true, false>(g.hatt, (unsigned)((p * GS + b) * ATT_RNN + tid), PT, want, need, v, tg, pc, pf);
         s_hatt[b * ATT_RNN + TID] = v[0];
         s_hatt[b * ATT_RNN + TID + PT] = v[1];
       }
@@ -691,7 +737,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         const bool need[2] = {t < T, t < T};
         float v[2];
         unsigned tg[2];
-        gather<2, true>(g.ep, (unsigned)(((p * GS + b) * ATTN_CU + j) * EP_LD + t), 4u * EP_LD, want, need, v, tg, pc, pf);
+        gather<2, true, false>(g.ep, (unsigned)(((p * GS + b) * ATTN_CU + j) * EP_LD + t), 4u * EP_LD, want, need, v, tg, pc, pf);
         float e = v[0] + v[1];
         e += dpp_move<0xB1, 0xf>(0.f, e);  // quad_perm:[1,0,3,2]
         e += dpp_move<0x4E, 0xf>(0.f, e);  // quad_perm:[2,3,0,1]
@@ -767,7 +813,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         const bool need[2] = {true, true};
         float v[2];
         unsigned tg[2];
-        gather<2, true>(g.hdec, (unsigned)((p * GS + b) * DEC_RNN + tid), PT, want, need, v, tg, pc, pf);
+        gather<2, true, false>(g.hdec, (unsigned)((p * GS + b) * DEC_RNN + tid), PT, want, need, v, tg, pc, pf);
         s_hdec[b * DEC_RNN + TID] = v[0];
         s_hdec[b * DEC_RNN + TID + PT] = v[1];
       }
@@ -803,7 +849,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         const bool need[1] = {true};
         float v[1];
         unsigned tg[1];
-        gather<1, true>(g.mel, (unsigned)(((p * GS + b) * MEL_GL + tid) * MEL_ST), 0, want, need, v, tg, pc, pf);
+        gather<1, true, false>(g.mel, (unsigned)(((p * GS + b) * MEL_GL + tid) * MEL_ST), 0, want, need, v, tg, pc, pf);
         s_mel[tid] = v[0];
       }
       __syncthreads();
@@ -1016,17 +1062,36 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
       e += dpp_move<0x4E, 0xf>(0.f, e);  // quad_perm:[2,3,0,1]
       if ((tid & 3) == 0 && t < T) publish(g.ep + (unsigned)(((p * GS + rb) * ATTN_CU + rk) * EP_LD + t), want, e);
     }
-    // decoder LSTM: the h_att columns (off the critical path for everyone but the above)
+    // decoder LSTM: the h_att columns (off the critical path for everyone but the above).
+    // One-chunk kernel, attention role: the first poll of the energies it gathers next leaves from inside this block (the
+    // PRE form of the skewed loop) -- the poll's round trip, ~0.45 us even when the data is there, runs under the block
+    // instead of behind it.  Its own slice has just been published; the other seven come from workgroups in step with it.
+    u64 epf[2] = {0ull, 0ull};
+    const bool epoll = ROLE_REGS && attn && act_r;
+    auto issue_ep = [&] {
+      const int t = tid >> 2, j = tid & 3;
+      if (epoll && t < T) {
+        epf[0] = peek(g.ep + (unsigned)((p * GS * ATTN_CU + j) * EP_LD + t));
+        epf[1] = peek(g.ep + (unsigned)((p * GS * ATTN_CU + j + 4) * EP_LD + t));
+      }
+    };
+    if (epoll) lazy_wait(EPOLL_NAP);
 #pragma unroll
     for (int b = 0; b < PB; ++b)
       if (act[b]) {
         float a0 = dacc[b][0], a1 = dacc[b][1];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
+          if (ROLE_REGS && k == EPOLL_AT) {
+            pin(a0, a1);
+            issue_ep();
+          }
           const float4 v = lds4(s_hatt + b * ATT_RNN + 256 * k + L4);
           a0 = dot4(wd[0][k], v, a0);
           a1 = dot4(wd[1][k], v, a1);
         }
+        pin(a0, a1);
+        if (ROLE_REGS && EPOLL_AT == 4) issue_ep();
         dacc[b][0] = a0;
         dacc[b][1] = a1;
         chunk_fence();
@@ -1043,8 +1108,9 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
       for (int i = 0; i < 2 * PB; ++i) need[i] = act[i >> 1] && t < T;
       float v[2 * PB];
       unsigned tg[2 * PB];
-      lazy_wait(attn ? g.efirst : g.clazy);  // the energies cannot arrive before the attention role has run
-      const unsigned np_ = gather<2 * PB>(g.ep, (unsigned)((p * GS * ATTN_CU + j) * EP_LD + t), 4u * EP_LD, want, need, v, tg, pc);
+      // the energies cannot arrive before the attention role has run (which, in the one-chunk kernel, has its first poll in flight)
+      lazy_wait(attn ? (epoll ? 0 : g.efirst) : g.clazy);
+      const unsigned np_ = gather<2 * PB, ROLE_REGS>(g.ep, (unsigned)((p * GS * ATTN_CU + j) * EP_LD + t), 4u * EP_LD, want, need, v, tg, pc, epf);
       PROF_POLLS(2, np_);
 #pragma unroll
       for (int b = 0; b < PB; ++b) {
@@ -1142,7 +1208,13 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
       a = wave_sum(a);
       if (lane == 0) publish(g.mel + (unsigned)(((p * GS + rb) * MEL_GL + prow) * MEL_ST), want, a + s_pb[wave]);
     }
-    dec_bulk_h(L4, false);  // for step s+1
+    // for step s+1.  One-chunk kernel, projection + prenet role: the first poll of the mel rows it gathers in P6 leaves from
+    // inside the block, as the attention role's energy poll does in P2.
+    u64 mpf[1] = {0ull};
+    const bool mpoll = ROLE_REGS && pre && act_r;
+    dec_bulk_h(L4, false, std::integral_constant<int, ROLE_REGS ? MPOLL_AT : -1>{}, [&] {
+      if (mpoll && tid < N_MEL + 1) mpf[0] = peek(g.mel + (unsigned)(((p * GS + rb) * MEL_GL + tid) * MEL_ST));
+    });
     if (attn && act_r) location(tid);
     PROF_MARK(9);  // projection rows + dec bulk + location
     straggle(lag, s, 5);
@@ -1155,9 +1227,10 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
           const bool need[1] = {true};
           float v[1];
           unsigned tg[1];
-          gather<1>(g.mel, (unsigned)(((p * GS + rb) * MEL_GL + tid) * MEL_ST), 0, want, need, v, tg, pc);
+          gather<1, ROLE_REGS>(g.mel, (unsigned)(((p * GS + rb) * MEL_GL + tid) * MEL_ST), 0, want, need, v, tg, pc, mpf);
           s_mel[tid] = v[0];
         }
+        loads_settled();  // (behind the join with the threads that gather nothing: slice 0's frame store below is not waited for)
         __syncthreads();
         PROF_MARK(11);  // prenet role: mel gathered
         const float gate = s_mel[N_MEL];
@@ -1332,7 +1405,7 @@ PersistBufs persist_bufs(unsigned long long *base, int *err, int B) {
   g.slow = 0;
   g.pfirst = 0;  // x 256 clocks (behind the mask hashing; 0 / 1 / 2 / 3 -> 8.44 / 8.33 / 8.71 / 8.70 us per 1-chunk step)
   g.xfirst = 4;
-  g.efirst = 3;  // (with pfirst 0 and lazy 9: 8.38 / 11.39 -> 8.19 / 11.19 us per step, 1 / 2 chunks)
+  g.efirst = 3;  // (with pfirst 0 and lazy 9: 8.38 / 11.39 -> 8.19 / 11.19 us per step, 1 / 2 chunks; since then the one-chunk kernel has EPOLL_AT / EPOLL_NAP in its place)
   g.skew = 1;
   g.both_run = 0;
   g.first = 4;  // x 256 clocks, ~0.4 us: the first polls of a critical consumer cannot succeed earlier (measured: -0.3 us per step)

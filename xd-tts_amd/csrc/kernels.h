@@ -120,7 +120,8 @@ struct PersistBufs {
   int both_run;  // 2-chunk launch without `shrink` whose chunks are both known to run all of its steps (gate-less decode)
   int shrink;  // 2-chunk launch: end as soon as one chunk stops (the host continues with a 1-chunk launch)
   int first;  // delay before a critical consumer's first poll, x 256 clocks (developer knob)
-  int efirst;  // the attention role's first poll of the partial energies (it has just published its own slice)
+  int efirst;  // the attention role's first poll of the partial energies (it has just published its own slice); lock-step pair only:
+               // the one-chunk kernel issues that poll from inside the column block behind the publish (EPOLL_AT, EPOLL_NAP)
   int xfirst;  // the same for the projection role's first poll of x (it has just published its own 16 columns)
   int pfirst;  // the same for the projection role's first poll of h_dec (behind its weight fetch and mask hashing)
   int xlazy, clazy;  // first-poll delay of the x / ctx consumers that are not their producers, x 256 clocks
