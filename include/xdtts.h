@@ -328,7 +328,8 @@ xdtts_status xdtts_griffinlim_step(xdtts_griffinlim *g, const float *S, float *a
 /* ms[0] mel->linear (for the *_prosody and *_contour entries: mel->linear and the prosody stage; with phase_init 1 the SPSI stage as well:
  * everything in front of the loop), ms[1] iterations, ms[2] total of the last call (HIP events).  After
  * xdtts_griffinlim_prosody_linear and xdtts_griffinlim_spsi_phase (and their _batch forms): ms[0] the stage alone, ms[1] the
- * layout change behind it. */
+ * layout change behind it; after xdtts_griffinlim_resample / _resample_batch: ms[0] the stage alone.  With an output rate set
+ * (xdtts_griffinlim_set_output_rate) the resampler falls inside ms[1], as the output normalisation does. */
 xdtts_status xdtts_griffinlim_last_timings(const xdtts_griffinlim *g, float ms[3]);
 
 /* The inverse direction of GriffinLim::infer's conventions: librosa.stft(y, 1024, hop 256, periodic hann, center, reflect)
@@ -515,6 +516,48 @@ xdtts_status xdtts_griffinlim_spsi_phase(xdtts_griffinlim *g, const float *S, si
 /* The ragged form the batch entries run: every output equals the single hook's bit for bit, whatever the mix and order. */
 xdtts_status xdtts_griffinlim_spsi_phase_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
                                                uint32_t *const *turns, float *const *angles);
+
+/* The output rate.  The loop produces 22 050 Hz audio (XDTTS_SAMPLE_RATE, the reference's WAV_SPEC); telephony, WebRTC / Opus
+ * and audio pipelines want 8 .. 48 kHz and beyond.  With the option set, a polyphase windowed-sinc resampler runs on the
+ * device between the final ISTFT and the output normalisation, so the level rules (peak 1, rms target, no sample outside
+ * [-1, 1]) hold for the signal the caller receives.  The definition, exactly:
+ *   R = 22050, Q = the output rate, g = gcd(Q, R), L = Q / g, M = R / g, W = max(L, M), H = 32 W.
+ *   Q is supported iff 8000 <= Q <= 96000 and L <= 640 (8000, 11025, 12000, 16000, 24000, 32000, 44100, 48000, 88200, 96000
+ *   and others); anything else is XDTTS_ERR_BAD_ARG, the message names the rate and the rule.  Q == R is the IDENTITY: it
+ *   launches nothing and every result keeps the bits it has without the option (its plan reads L = M = 1, half_len = 0, one tap
+ *   of 1).
+ *   taps    2 H + 1 of them, k = -H .. H, computed in double and rounded once to fp32:
+ *           h[k] = (L / W) rho sinc(rho k / W) I0(beta sqrt(1 - (k / H)^2)) / I0(beta),  rho = 0.9, beta = 10,
+ *           sinc(x) = sin(pi x) / (pi x): a Kaiser-windowed low-pass at 0.9 of the lower rate's Nyquist, exactly symmetric.
+ *           (fp64 figures for the ten rates above: passband within +-0.0001 dB up to 0.8 of the lower Nyquist, <= -99.7 dB from
+ *           that Nyquist upward, every phase's DC gain within 2e-6 of 1; 129 .. 40 961 taps, 65 .. 177 of them per output sample)
+ *   output  for N input samples N' = ceil(N L / M) samples,
+ *           y[m] = sum over 0 <= n < N with |m M - n L| <= H of x[n] h[m M - n L]
+ *           -- zero extension at both ends and zero phase: y[0] sits on x[0].  (scipy.signal.resample_poly(x, L, M, window =
+ *           h / L) in fp64.)  All index arithmetic is exact integer arithmetic (m M in 64 bits).
+ *   sums    fp32, fused multiply-adds in an order that is a function of (Q, m, N) alone: the ragged batch form returns the
+ *           bits of the single form, whatever the mix and order.  |y - y_fp64| <= (c + 2) 2^-24 sum |h| |x| per sample, c = the
+ *           number of taps that meet it.
+ * Honoured by every entry that delivers a finished utterance: xdtts_griffinlim_infer, _infer_prosody, _infer_contour,
+ * _infer_batch and its prosody and contour forms, xdtts_synthesize_ids, _batch and _sequence with their prosody and contour
+ * forms; *n_samples is N' = the plan's n_out for hop * (F' - 1) in each.  batch == single bit for bit (batch_shape = 4) holds
+ * at every rate.  xdtts_griffinlim_infer_linear (the loop alone), _step and the analysis entries stay at 22 050 Hz.  Not per
+ * utterance inside a batch; no PCM16 / mu-law encoding on the device (xdtts_audio_to_i16 stays on the host).
+ * xdtts_griffinlim_last_timings: the stage falls inside ms[1] (and ms[2]) exactly as the output normalisation does. */
+xdtts_status xdtts_griffinlim_set_output_rate(xdtts_griffinlim *g, int32_t rate);   /* default 22050 */
+xdtts_status xdtts_griffinlim_get_output_rate(const xdtts_griffinlim *g, int32_t *rate);
+/* Host arithmetic, no handle, no device.  _plan: L, M, half_len = H and n_out = N' for n_in samples; any out pointer may be
+ * NULL.  _filter: the library's own fp32 taps, h[-H .. H] (2 H + 1 floats, *n_taps); taps == NULL with cap == 0 asks for the
+ * size alone; a buffer that is too small is XDTTS_ERR_BAD_ARG. */
+xdtts_status xdtts_resample_plan(int32_t rate_out, size_t n_in, int32_t *L, int32_t *M, int32_t *half_len, size_t *n_out);
+xdtts_status xdtts_resample_filter(int32_t rate_out, float *taps, size_t cap, size_t *n_taps);
+/* Parity hooks, the stage alone at rate_out whatever the handle's option: audio (n samples at 22 050 Hz, n < 2^28) -> out, a
+ * caller buffer sized by xdtts_resample_plan; n_out may be NULL.  The ragged form runs all utterances in one launch and
+ * every outs[u] equals the single hook's bit for bit.  Argument errors come back before a device is touched.  Afterwards
+ * xdtts_griffinlim_last_timings ms[0] is the stage alone. */
+xdtts_status xdtts_griffinlim_resample(xdtts_griffinlim *g, const float *audio, size_t n, int32_t rate_out, float *out, size_t *n_out);
+xdtts_status xdtts_griffinlim_resample_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt,
+                                             int32_t rate_out, float *const *outs, size_t *n_out);
 
 void xdtts_griffinlim_free(xdtts_griffinlim *g);
 

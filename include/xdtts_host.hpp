@@ -243,6 +243,42 @@ class GriffinLim {
     check(xdtts_griffinlim_get_opts(g_, &o));
     return o;
   }
+  // The rate of every delivered utterance (xdtts_griffinlim_set_output_rate): 22050 (default, nothing runs) or a supported rate
+  // in 8 .. 96 kHz -- a polyphase resampler on the device behind the loop, in front of the output normalisation.  Hand the same
+  // rate to write_wav.
+  void set_output_rate(int32_t rate) { check(xdtts_griffinlim_set_output_rate(g_, rate)); }
+  int32_t output_rate() const {
+    int32_t rate = 0;
+    check(xdtts_griffinlim_get_output_rate(g_, &rate));
+    return rate;
+  }
+  // ... the stage alone (parity hook, xdtts_griffinlim_resample): audio at 22 050 Hz -> rate_out, whatever the handle's rate
+  std::vector<float> resample(const std::vector<float> &audio, int32_t rate_out) const {
+    size_t n = 0;
+    check(xdtts_resample_plan(rate_out, audio.size(), nullptr, nullptr, nullptr, &n));
+    std::vector<float> out(n ? n : 1);
+    check(xdtts_griffinlim_resample(g_, audio.data(), audio.size(), rate_out, out.data(), &n));
+    out.resize(n);
+    return out;
+  }
+  // ... and the ragged form (xdtts_griffinlim_resample_batch): one launch, the single hook's bits per utterance
+  std::vector<std::vector<float>> resample_batch(const std::vector<std::vector<float>> &audios, int32_t rate_out) const {
+    const size_t n = audios.size();
+    std::vector<std::vector<float>> out(n);
+    std::vector<const float *> ip(n);
+    std::vector<float *> op(n);
+    std::vector<size_t> ns(n), no(n, 0);
+    for (size_t u = 0; u < n; ++u) {
+      check(xdtts_resample_plan(rate_out, audios[u].size(), nullptr, nullptr, nullptr, &no[u]));
+      out[u].resize(no[u] ? no[u] : 1);
+      ip[u] = audios[u].data();
+      op[u] = out[u].data();
+      ns[u] = audios[u].size();
+    }
+    check(xdtts_griffinlim_resample_batch(g_, ip.data(), ns.data(), (int32_t)n, rate_out, op.data(), no.data()));
+    for (size_t u = 0; u < n; ++u) out[u].resize(no[u]);
+    return out;
+  }
   // The inverse direction (xdtts_griffinlim_analyze): audio -> (S (n_bins x F), mel (n_mels x F)) under the handle's conventions,
   // F = audio.size() / 256 + 1
   std::pair<Array2, Array2> analyze(const std::vector<float> &audio, float mel_floor = 1e-5f) const {
@@ -292,6 +328,24 @@ class GriffinLim {
 inline GriffinLim create_griffin_lim(int device_id = XDTTS_DEVICE_DEFAULT) {
   const Array2 mel_basis = create_mel_filter_bank(22050.0f, 1024, 80, 0.0f, 8000.0f);
   return GriffinLim(mel_basis, 1024 - 256, 1.7f, 30, 0.99f, device_id);
+}
+
+// The output-rate stage's host arithmetic (xdtts_resample_plan, xdtts_resample_filter): no handle, no device.
+struct ResamplePlan {
+  int32_t L = 1, M = 1, half_len = 0;
+  size_t n_out = 0;
+};
+inline ResamplePlan resample_plan(int32_t rate_out, size_t n_in = 0) {
+  ResamplePlan p;
+  check(xdtts_resample_plan(rate_out, n_in, &p.L, &p.M, &p.half_len, &p.n_out));
+  return p;
+}
+inline std::vector<float> resample_filter(int32_t rate_out) {  // the library's own fp32 taps h[-H .. H]
+  size_t n = 0;
+  check(xdtts_resample_filter(rate_out, nullptr, 0, &n));
+  std::vector<float> taps(n);
+  check(xdtts_resample_filter(rate_out, taps.data(), taps.size(), &n));
+  return taps;
 }
 
 inline xdtts_prosody default_prosody() {  // rate 1, pitch 1, lifter 30, log_floor 1e-5: the identity

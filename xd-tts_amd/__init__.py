@@ -169,6 +169,12 @@ SYMBOLS = {
     "xdtts_griffinlim_get_phase_init": (_I32, [_VP, C.POINTER(_I32)]),
     "xdtts_griffinlim_spsi_phase": (_I32, [_VP, _VP, _SZ, _VP, _VP]),
     "xdtts_griffinlim_spsi_phase_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
+    "xdtts_griffinlim_set_output_rate": (_I32, [_VP, _I32]),
+    "xdtts_griffinlim_get_output_rate": (_I32, [_VP, C.POINTER(_I32)]),
+    "xdtts_resample_plan": (_I32, [_I32, _SZ, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_SZ)]),
+    "xdtts_resample_filter": (_I32, [_I32, _VP, _SZ, C.POINTER(_SZ)]),
+    "xdtts_griffinlim_resample": (_I32, [_VP, _VP, _SZ, _I32, _VP, C.POINTER(_SZ)]),
+    "xdtts_griffinlim_resample_batch": (_I32, [_VP, _VP, _VP, _I32, _I32, _VP, _VP]),
     "xdtts_griffinlim_free": (None, [_VP]),
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
@@ -857,6 +863,37 @@ class GriffinLim:
             _check(lib.xdtts_griffinlim_spsi_phase_batch(self._h, sp, nf, n, tp, ap))
         return turns, angles
 
+    # -- output rate: 22 050 Hz -> 8 .. 96 kHz behind the loop, in front of the output normalisation ----
+    def set_output_rate(self, rate):
+        """The rate of every delivered utterance (infer, infer_batch, synthesize* and their prosody / contour forms): 22050
+        (default, nothing runs) or a supported rate (resample_plan): a polyphase windowed-sinc stage on the device.  Not honoured
+        by infer_linear, step and the analysis entries."""
+        _check(lib.xdtts_griffinlim_set_output_rate(self._h, int(rate)))
+
+    def get_output_rate(self):
+        rate = C.c_int32()
+        _check(lib.xdtts_griffinlim_get_output_rate(self._h, C.byref(rate)))
+        return rate.value
+
+    def resample(self, audio, rate_out):
+        """The stage alone (parity hook), whatever the handle's rate: audio at 22 050 Hz -> resample_plan(rate_out, len)["n_out"] samples."""
+        return self.resample_batch([audio], rate_out)[0]
+
+    def resample_batch(self, audios, rate_out):
+        """The ragged stage alone (parity hook): one launch for all audios, every result the single hook's bit for bit."""
+        xs = [np.ascontiguousarray(a, dtype=np.float32).ravel() for a in audios]
+        n = len(xs)
+        outs = [np.empty(max(resample_plan(rate_out, x.size)["n_out"], 1), dtype=np.float32) for x in xs]
+        ip = (C.c_void_p * n)(*[x.ctypes.data for x in xs])
+        op = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        ns = (C.c_size_t * n)(*[x.size for x in xs])
+        no = (C.c_size_t * n)()
+        if n == 1:
+            _check(lib.xdtts_griffinlim_resample(self._h, ip[0], ns[0], int(rate_out), op[0], no))
+        else:
+            _check(lib.xdtts_griffinlim_resample_batch(self._h, ip, ns, n, int(rate_out), op, no))
+        return [o[: no[u]] for u, o in enumerate(outs)]
+
     # -- analysis: audio -> magnitude -> mel under the handle's conventions, spectral convergence ----
     def analysis_frames(self, n_samples):
         return int(lib.xdtts_griffinlim_analysis_frames(self._h, int(n_samples)))
@@ -922,6 +959,23 @@ def prosody_contour_table(contour, n_frames):
     c, pitch, gain = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
     _check(lib.xdtts_prosody_contour_table(C.byref(contour), n, _ptr(c), _ptr(pitch), _ptr(gain)))
     return c[:n], pitch[:n], gain[:n]
+
+
+def resample_plan(rate_out, n_in=0):
+    """xdtts_resample_plan (host arithmetic): {"L", "M", "half_len", "n_out"} of the output-rate stage for n_in samples at
+    22 050 Hz; XdttsError (BAD_ARG) for an unsupported rate."""
+    L, M, H, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_size_t()
+    _check(lib.xdtts_resample_plan(int(rate_out), int(n_in), C.byref(L), C.byref(M), C.byref(H), C.byref(n)))
+    return {"L": L.value, "M": M.value, "half_len": H.value, "n_out": n.value}
+
+
+def resample_filter(rate_out):
+    """xdtts_resample_filter: the library's own fp32 taps h[-H .. H] of the output-rate stage (host arithmetic)."""
+    n = C.c_size_t()
+    _check(lib.xdtts_resample_filter(int(rate_out), None, 0, C.byref(n)))
+    taps = np.empty(n.value, dtype=np.float32)
+    _check(lib.xdtts_resample_filter(int(rate_out), _ptr(taps), taps.size, C.byref(n)))
+    return taps
 
 
 def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, contour=None):

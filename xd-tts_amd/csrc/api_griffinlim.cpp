@@ -556,6 +556,123 @@ xdtts_status xdtts_griffinlim_spsi_phase(xdtts_griffinlim *g, const float *S, si
   return xdtts_griffinlim_spsi_phase_batch(g, &S, &n_frames, 1, &turns, &angles);
 }
 
+// ---- output rate: 22 050 Hz -> 8 .. 96 kHz behind the loop, in front of the output normalisation (resample_plan.h, resample.hip) ----
+
+// The rate rule of the entries: the plan of a supported rate, else XDTTS_ERR_BAD_ARG with the rate and the rule.
+static ResamplePlan resample_plan_checked(int32_t rate) {
+  ResamplePlan p;
+  const std::string msg = resample_check(rate, &p);
+  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s (supported: %d .. %d Hz with rate / gcd(rate, %d) <= %d)", msg.c_str(), RESAMPLE_RATE_MIN,
+                         RESAMPLE_RATE_MAX, RESAMPLE_RATE_IN, RESAMPLE_L_MAX);
+  return p;
+}
+
+xdtts_status xdtts_resample_plan(int32_t rate_out, size_t n_in, int32_t *L, int32_t *M, int32_t *half_len, size_t *n_out) {
+  return guard([&] {
+    const ResamplePlan p = resample_plan_checked(rate_out);
+    if (L) *L = p.L;
+    if (M) *M = p.M;
+    if (half_len) *half_len = p.H;
+    if (n_out) *n_out = resample_n_out(p, n_in);
+  });
+}
+
+xdtts_status xdtts_resample_filter(int32_t rate_out, float *taps, size_t cap, size_t *n_taps) {
+  return guard([&] {
+    const ResamplePlan p = resample_plan_checked(rate_out);
+    const size_t n = (size_t)2 * (size_t)p.H + 1;
+    if (n_taps) *n_taps = n;
+    if (!taps && cap == 0) return;  // the size alone
+    if (!taps || cap < n) fail(XDTTS_ERR_BAD_ARG, "rate %d has %zu taps, the buffer holds %zu", rate_out, n, cap);
+    std::vector<float> h;
+    resample_taps(p, h);
+    std::memcpy(taps, h.data(), n * sizeof(float));
+  });
+}
+
+xdtts_status xdtts_griffinlim_set_output_rate(xdtts_griffinlim *g, int32_t rate) {
+  return guard([&] {
+    const ResamplePlan p = resample_plan_checked(rate);  // the rate first: reported without a handle
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->out_rate = rate;
+    g->out_plan = p;
+  });
+}
+
+xdtts_status xdtts_griffinlim_get_output_rate(const xdtts_griffinlim *g, int32_t *rate) {
+  return guard([&] {
+    if (!g || !rate) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    *rate = g->out_rate;
+  });
+}
+
+// What the stage takes in one call: the analysis entries' sample cap per utterance, and 2^31 - 1 output samples in all.
+static constexpr size_t RS_MAX_SAMPLES = (size_t)1 << 28;
+
+// Parity hook of the stage alone, single call and ragged batch: the audios one behind the other on the device, ONE k_resample
+// launch (the single call passes its record by value, the batch uploads the table), and back.  last_timings: ms[0] = the
+// launch alone.  The identity copies and launches nothing.
+xdtts_status xdtts_griffinlim_resample_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt, int32_t rate_out,
+                                             float *const *outs, size_t *n_out) {
+  return guard([&] {
+    for (int u = 0; n_out && u < n_utt; ++u) n_out[u] = 0;
+    const ResamplePlan p = resample_plan_checked(rate_out);
+    if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    if (!g || !audios || !n || !outs) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::vector<ResampleUtt> tab((size_t)n_utt);
+    size_t in_tot = 0, out_tot = 0;
+    int blk = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      if (n[u] >= RS_MAX_SAMPLES) fail(XDTTS_ERR_BAD_ARG, "utterance %d: at most 2^28 - 1 samples, got %zu", u, n[u]);
+      if (n[u] && (!audios[u] || !outs[u])) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null audio", u);
+      const size_t no = resample_n_out(p, n[u]);
+      tab[(size_t)u] = {(long long)in_tot, (long long)out_tot, (int)n[u], (int)no, blk, 0};
+      in_tot += n[u];
+      out_tot += no;
+      if (out_tot > (size_t)0x7fffffff) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^31 - 1 samples at rate %d", rate_out);
+      blk += (int)((no + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK);
+    }
+    if (p.identity) {  // nothing to launch, no device
+      for (int u = 0; u < n_utt; ++u) {
+        if (n[u]) std::memcpy(outs[u], audios[u], n[u] * sizeof(float));
+        if (n_out) n_out[u] = n[u];
+      }
+      return;
+    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    hipStream_t st = g->stream;
+    g->rs_in.alloc(std::max<size_t>(in_tot, 1));
+    g->audio_rs.alloc(std::max<size_t>(out_tot, 1));
+    g->resample_prepare(rate_out);
+    for (int u = 0; u < n_utt; ++u)
+      if (n[u]) HIP_CHECK(hipMemcpyAsync(g->rs_in.p + tab[(size_t)u].src0, audios[u], n[u] * sizeof(float), hipMemcpyHostToDevice, st));
+    if (n_utt > 1) {
+      g->rs_tab_host = tab;
+      g->rs_tab.upload(g->rs_tab_host.data(), g->rs_tab_host.size(), st);
+    }
+    HIP_CHECK(hipEventRecord(g->ev.e[0], st));
+    if (n_utt == 1) {
+      if (n[0]) g->resample_one(g->rs_in.p, n[0], g->audio_rs.p, rate_out);  // (the form the single-utterance entries run)
+    } else {
+      g->resample_rows(g->rs_in.p, g->audio_rs.p, 0, n_utt);
+    }
+    HIP_CHECK(hipEventRecord(g->ev.e[1], st));
+    HIP_CHECK(hipEventRecord(g->ev.e[2], st));
+    for (int u = 0; u < n_utt; ++u)
+      if (tab[(size_t)u].n_out)
+        HIP_CHECK(hipMemcpyAsync(outs[u], g->audio_rs.p + tab[(size_t)u].dst0, (size_t)tab[(size_t)u].n_out * sizeof(float), hipMemcpyDeviceToHost, st));
+    g->finish_timings();  // (drains the stream: the inputs, the table and the outputs)
+    for (int u = 0; n_out && u < n_utt; ++u) n_out[u] = (size_t)tab[(size_t)u].n_out;
+  });
+}
+
+xdtts_status xdtts_griffinlim_resample(xdtts_griffinlim *g, const float *audio, size_t n, int32_t rate_out, float *out, size_t *n_out) {
+  return xdtts_griffinlim_resample_batch(g, &audio, &n, 1, rate_out, &out, n_out);
+}
+
 // ---- analysis: the inverse direction of GriffinLim::infer's conventions (analysis.hip).  No co-resident grid: no chip lock. ----
 
 // What one call takes: the row tiles of the mel GEMM and of the boundary transposes go into a grid dimension of at most 65535

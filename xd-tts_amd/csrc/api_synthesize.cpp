@@ -134,7 +134,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
           h->while_decoding = [&, u, predicted] {
             if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * predicted);
             const size_t Fp = pros ? prosody_frames((size_t)predicted, pros[u].rate) : (size_t)predicted;  // the vocoder's frames, not the mel's
-            if (!audio_host[u].p) audio_host[u] = PinnedGuard((size_t)g->hop * (Fp - 1));
+            if (!audio_host[u].p) audio_host[u] = PinnedGuard(g->delivered((size_t)g->hop * (Fp - 1)));  // (at the handle's output rate)
           };
         for (int i = 0; i < 4; ++i) std::swap(h->ev.e[i], per[u].e[i]);  // (per[u] now holds what the handle had: utterance u - 1's set, or its own)
         h->infer_batch_device(padded.data(), lens.data(), (int)lens.size(), o.max_chunk, o, nullptr, &total[u]);

@@ -182,6 +182,42 @@ void xdtts_griffinlim::spsi_batch(const float *S_dev, const SpsiTables &t, float
               SpsiBufs{spsi_map.p, spsi_comp.p, spsi_entry.p}, ang_out, tprev_out, turns, stream);
 }
 
+// The output-rate stage (resample.hip).  The table is a function of the rate alone: built on the host once per (handle, rate)
+// and kept on the device; the host copy is the upload's source and lives as long as the handle.
+void xdtts_griffinlim::resample_prepare(int rate) {
+  if (rs_table.rate == rate && rs_rows.p) return;
+  HIP_CHECK(hipStreamSynchronize(stream));  // (a launch that reads the table of another rate may be in flight)
+  const std::string msg = resample_check(rate, &rs_plan);
+  if (!msg.empty() || rs_plan.identity) fail(XDTTS_ERR_BAD_ARG, "resample: no table for rate %d", rate);
+  std::vector<float> h;
+  resample_taps(rs_plan, h);
+  rs_table.rate = 0;
+  resample_table(rs_plan, h, rs_table);
+  if (resample_window(rs_table) > RESAMPLE_WINDOW) {  // (never: the rate rule bounds M / L and the entries per phase)
+    rs_table.rate = 0;
+    fail(XDTTS_ERR_BAD_ARG, "resample: rate %d needs a window of %d samples", rate, resample_window(rs_table));
+  }
+  rs_rows.upload(rs_table.rows.data(), rs_table.rows.size(), stream);
+}
+
+size_t xdtts_griffinlim::resample_one(const float *src, size_t n, float *dst, int rate) {
+  resample_prepare(rate);
+  const size_t n_out = resample_n_out(rs_plan, n);
+  if (n_out > (size_t)0x7fffffff) fail(XDTTS_ERR_BAD_ARG, "resample: %zu output samples are more than 2^31 - 1", n_out);
+  const ResampleUtt one{0, 0, (int)n, (int)n_out, 0, 0};
+  launch_resample(src, dst, nullptr, 1, 0, (int)((n_out + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK), one, rs_rows.p, rs_table.L, rs_table.M,
+                  rs_table.Jn, rs_table.T4, stream);
+  return n_out;
+}
+
+void xdtts_griffinlim::resample_rows(const float *src, float *dst, int r0, int count) {
+  if (count <= 0) return;
+  const ResampleUtt &first = rs_tab_host[(size_t)r0], &last = rs_tab_host[(size_t)(r0 + count - 1)];
+  const int nblk = last.blk0 + (last.n_out + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK - first.blk0;
+  launch_resample(src, dst, rs_tab.p + r0, count, first.blk0, nblk, ResampleUtt{}, rs_rows.p, rs_table.L, rs_table.M, rs_table.Jn,
+                  rs_table.T4, stream);
+}
+
 void xdtts_griffinlim::upload_rows(const float *const *S_host, const Rows &rows) {
   for (int u = 0; u < rows.n(); ++u) {
     const size_t r0 = (size_t)rows.row0[(size_t)u] * nb;
@@ -443,31 +479,39 @@ void mel_filter_bank(double sr, int n_fft, int n_mels, double fmin, double fmax,
 }
 
 // "Iterations enqueued" -> "audio on its way to a pinned buffer": phase init + iterations + final ISTFT on the S in place
-// (iterate()), the output normalisation if wanted, ev.e[2], the copy into `host` (taken from the pool here unless the caller
-// brought one) and the engine's error word behind it.  Nothing is waited for.
-static void enqueue_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, bool normalise, PinnedGuard &host) {
-  const size_t N = (size_t)g->hop * (size_t)(b.F - 1);
+// (iterate()), the delivery stages if wanted -- the output rate (resample.hip; nothing at 22050) and then the output
+// normalisation, on the signal the caller receives -- ev.e[2], the copy into `host` (taken from the pool here unless the caller
+// brought one, sized for what is delivered) and the engine's error word behind it.  Nothing is waited for.
+static void enqueue_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, bool deliver, PinnedGuard &host) {
+  size_t N = (size_t)g->hop * (size_t)(b.F - 1);
   g->iterate(b, phase0_dev, iters);
-  if (normalise) launch_gl_output_normalise(g->audio.p, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
+  float *out = g->audio.p;
+  if (deliver && g->out_rate != XDTTS_SAMPLE_RATE && N > 0) {
+    g->audio_rs.alloc(g->delivered(N));
+    N = g->resample_one(g->audio.p, N, g->audio_rs.p, g->out_rate);
+    out = g->audio_rs.p;
+  }
+  if (deliver) launch_gl_output_normalise(out, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
   HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
   if (!host.p) host = PinnedGuard(N);
-  HIP_CHECK(hipMemcpyAsync(host.p, g->audio.p, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+  HIP_CHECK(hipMemcpyAsync(host.p, out, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
   g->fetch_error_word();
 }
 // ... and its counterpart: the wait and the engine's error word.  The persistent engine needs its grid co-resident (the
 // caller holds the chip lock from enqueue_run until here); a timed-out exchange demotes the handle and the same run goes
 // once more, on the launch-per-iteration engine (S, S' and the phase seed are intact until the next enqueue).
-static void collect_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, bool normalise, PinnedGuard &host,
+static void collect_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, bool deliver, PinnedGuard &host,
                         float **audio, size_t *n_samples) {
   g->finish_timings();  // (drains the stream)
   if (g->persistent_failed()) {
     HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));  // time the run that counts
-    enqueue_run(g, b, phase0_dev, iters, normalise, host);
+    enqueue_run(g, b, phase0_dev, iters, deliver, host);  // (the delivery stages again: they read the loop's audio)
     g->finish_timings();
     if (g->persistent_failed()) fail(XDTTS_ERR_HIP, "Griffin-Lim: the fallback engine reported an exchange failure");
   }
+  const size_t N = (size_t)g->hop * (size_t)(b.F - 1);
   *audio = host.release();
-  *n_samples = (size_t)g->hop * (size_t)(b.F - 1);
+  *n_samples = deliver ? g->delivered(N) : N;
 }
 
 // The loop alone on a state the caller has put in place (xdtts_griffinlim_infer_linear), then the audio in a pinned host buffer.
@@ -629,6 +673,25 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     all.S = g->S_pros.p;
   }
   g->audio.alloc(std::max<size_t>(Ntot, 1));
+  // What is delivered: at 22050 the loop's audio where it lies; at another rate the resampled utterances back to back in
+  // audio_rs, and everything behind the loop -- the normaliser's table, the fetch copies, the counts -- works from those.
+  const bool resampled = g->out_rate != XDTTS_SAMPLE_RATE;
+  std::vector<int> rbase, dn((size_t)n_utt);
+  for (int u = 0; u < n_utt; ++u) dn[(size_t)u] = g->hop * (Fu[u] - 1);
+  if (resampled) {
+    size_t Rtot = 0;
+    rbase.resize((size_t)n_utt);
+    for (int u = 0; u < n_utt; ++u) {
+      rbase[(size_t)u] = (int)Rtot;
+      Rtot += g->delivered((size_t)dn[(size_t)u]);
+      if (Rtot > (size_t)0x7fffffff) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^31 - 1 samples at rate %d", g->out_rate);
+      dn[(size_t)u] = (int)(Rtot - (size_t)rbase[(size_t)u]);
+    }
+    g->audio_rs.alloc(std::max<size_t>(Rtot, 1));
+    g->resample_prepare(g->out_rate);
+  }
+  const std::vector<int> &dbase = resampled ? rbase : abase;
+  float *const dbuf = resampled ? g->audio_rs.p : g->audio.p;
   HIP_CHECK(hipStreamSynchronize(st));  // the host vector above
   const float alpha = g->momentum / (1.0f + g->momentum);
   const int norm_mode = g->gopts.output_normalise;
@@ -649,37 +712,48 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
                                            env::int_or(env::GL_BATCH_FORCE, 0));
     std::vector<PinnedGuard> out;  // each utterance straight into the buffer the caller receives
     out.reserve((size_t)n_utt);
-    for (int u = 0; u < n_utt; ++u) out.emplace_back((size_t)g->hop * (size_t)(Fu[u] - 1));
+    for (int u = 0; u < n_utt; ++u) out.emplace_back((size_t)dn[(size_t)u]);
     Drain drain(g->copy_stream);  // no buffer of `out` goes back to the pool while a copy into it may be in flight
-    // Output normalisation (G6): the utterances of one fetch are consecutive rows of `tab` (plan.order), so each fetch is
-    // preceded by ONE two-launch normalisation of exactly its utterances.
+    // The delivery stages.  The utterances of one fetch are consecutive rows of the tables (plan.order), so each fetch is
+    // preceded by ONE resample launch (at a rate other than 22050) and ONE two-launch output normalisation (G6) of exactly
+    // its utterances, in that order: the level rules hold for the signal the caller receives.
     std::vector<int> tab_pos((size_t)n_utt, 0);
-    if (norm_mode) {
+    if (norm_mode || resampled) {
       std::vector<int2> tab;
       tab.reserve((size_t)n_utt);
+      g->rs_tab_host.clear();
+      int blk = 0;
       for (int u : plan.order) {
         tab_pos[(size_t)u] = (int)tab.size();
-        tab.push_back(make_int2(abase[u], g->hop * (Fu[u] - 1)));
+        tab.push_back(make_int2(dbase[(size_t)u], dn[(size_t)u]));
+        if (resampled) {
+          g->rs_tab_host.push_back({(long long)abase[u], (long long)rbase[(size_t)u], g->hop * (Fu[u] - 1), dn[(size_t)u], blk, 0});
+          blk += (dn[(size_t)u] + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK;
+        }
       }
-      g->norm_tab.upload(tab.data(), tab.size(), st);
-      g->norm_parts.alloc((size_t)GLN_SCRATCH * (size_t)n_utt);
+      if (norm_mode) {
+        g->norm_tab.upload(tab.data(), tab.size(), st);
+        g->norm_parts.alloc((size_t)GLN_SCRATCH * (size_t)n_utt);
+      }
+      if (resampled) g->rs_tab.upload(g->rs_tab_host.data(), g->rs_tab_host.size(), st);
       HIP_CHECK(hipStreamSynchronize(st));
     }
     size_t n_ev = 0;
     auto fetch_audio = [&](const std::vector<int> &utts) {  // after the work just enqueued on `st`
+      if (resampled && !utts.empty()) g->resample_rows(g->audio.p, g->audio_rs.p, tab_pos[(size_t)utts[0]], (int)utts.size());
       if (norm_mode && !utts.empty()) {
         int n_max = 0;
-        for (int u : utts) n_max = std::max(n_max, g->hop * (Fu[u] - 1));
+        for (int u : utts) n_max = std::max(n_max, dn[(size_t)u]);
         const int r0 = tab_pos[(size_t)utts[0]];
-        launch_gl_output_normalise(g->audio.p, g->norm_tab.p + r0, (int)utts.size(), 0, n_max, norm_mode, g->gopts.rms_target,
+        launch_gl_output_normalise(dbuf, g->norm_tab.p + r0, (int)utts.size(), 0, n_max, norm_mode, g->gopts.rms_target,
                                    g->norm_parts.p + (size_t)r0 * GLN_SCRATCH, st);
       }
       hipEvent_t e = g->launch_done(n_ev++);
       HIP_CHECK(hipEventRecord(e, st));
       HIP_CHECK(hipStreamWaitEvent(g->copy_stream, e, 0));
       for (int u : utts)
-        HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, g->audio.p + abase[u], sizeof(float) * (size_t)g->hop * (size_t)(Fu[u] - 1),
-                                 hipMemcpyDeviceToHost, g->copy_stream));
+        HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, dbuf + dbase[(size_t)u], sizeof(float) * (size_t)dn[(size_t)u], hipMemcpyDeviceToHost,
+                                 g->copy_stream));
     };
     // the persistent launches, each followed by the fetch of its utterances
     bool used_persistent = false;
@@ -725,7 +799,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     }
     for (int u = 0; u < n_utt; ++u) {
       audios[u] = out[(size_t)u].release();
-      n_samples[u] = (size_t)g->hop * (size_t)(Fu[u] - 1);
+      n_samples[u] = (size_t)dn[(size_t)u];
     }
     return;
   }

@@ -130,6 +130,25 @@ struct xdtts_griffinlim {
   void spsi_tables(const std::vector<int> &Fu, SpsiTables &t);
   void spsi_batch(const float *S_dev, const SpsiTables &t, float2 *ang_out, float2 *tprev_out, unsigned *turns = nullptr);
 
+  // output rate (resample.hip): the stage between the final ISTFT and the output normalisation.  out_rate 22050 = none.
+  int out_rate = XDTTS_SAMPLE_RATE;
+  xdtts::ResamplePlan out_plan;     // of out_rate (the identity by default): set with it
+  xdtts::ResamplePlan rs_plan;      // of the table below (the parity hooks bring their own rate)
+  xdtts::ResampleTable rs_table;    // host copy: the upload's source, kept with the handle
+  DevBuf<float> rs_rows, rs_in, audio_rs;  // the table; the parity hooks' input; the resampled audio (single call and batch)
+  DevBuf<xdtts::ResampleUtt> rs_tab;
+  std::vector<xdtts::ResampleUtt> rs_tab_host;  // the upload's source: stays until the next request of this handle
+  // The table of `rate` (checked by the caller, not the identity) on the device: built and uploaded once per (handle, rate).
+  void resample_prepare(int rate);
+  // One utterance: src[0 .. n) -> dst[0 .. resample_n_out(n)) on the stream; with the table in place nothing but the launch
+  // (the record travels as a kernel argument).  Returns N'.
+  size_t resample_one(const float *src, size_t n, float *dst, int rate);
+  // Ragged: the records of rs_tab_host (uploaded by the caller as rs_tab, behind resample_prepare()) from row r0, `count` of
+  // them, in one launch.
+  void resample_rows(const float *src, float *dst, int r0, int count);
+  // What a request path delivers for n samples of the loop: N' at the handle's rate, n at 22050.
+  size_t delivered(size_t n) const { return xdtts::resample_n_out(out_plan, n); }
+
   ~xdtts_griffinlim();
   GlBufs bufs(int F);
   // The ragged parity hooks: utterance u's magnitude in the boundary layout (nb x F_u), uploaded through `frames` and transposed

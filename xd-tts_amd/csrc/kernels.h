@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "gl_plan.h"
+#include "resample_plan.h"
 #include "weights.h"
 
 namespace xdtts {
@@ -357,5 +358,19 @@ void launch_spsi(const float *S, int F, const SpsiSeg *segs_dev, const SpsiUtt *
                  const SpsiBufs &b, float2 *ang, float2 *tprev, unsigned *turns, hipStream_t s);
 // parity hook: turns / ang [F][nb] -> the boundary layout (nb x F)
 void launch_spsi_export(const unsigned *turns, const float2 *ang, int F, int nb, unsigned *turns_out, float2 *ang_out, hipStream_t s);
+
+// ---- output rate (resample.hip): 22 050 Hz audio -> rate Q behind the loop, polyphase windowed sinc (include/xdtts.h) ---------
+// One utterance of a launch: n samples at x + src0 -> n_out = resample_n_out(n) samples at y + dst0; its workgroups are blk0 ..
+// blk0 + ceil(n_out / RESAMPLE_BLOCK) of the table's numbering (ascending, the utterances back to back).
+struct ResampleUtt {
+  long long src0, dst0;
+  int n, n_out, blk0, pad;
+};
+// nblk workgroups, the first being number blk_base of the table's numbering (a launch may cover a run of consecutive utterances:
+// tab_dev points at the first of them, n_utt counts them).  tab_dev == nullptr: the one utterance `one` (blk0 = 0), nothing
+// is read but the arguments.  rows_dev = ResampleTable::rows on the device.  An output's bits do not depend on what else the
+// launch holds.
+void launch_resample(const float *x, float *y, const ResampleUtt *tab_dev, int n_utt, int blk_base, int nblk, const ResampleUtt &one,
+                     const float *rows_dev, int L, int M, int Jn, int T4, hipStream_t s);
 
 }  // namespace xdtts
