@@ -559,6 +559,62 @@ xdtts_status xdtts_griffinlim_resample(xdtts_griffinlim *g, const float *audio, 
 xdtts_status xdtts_griffinlim_resample_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt,
                                              int32_t rate_out, float *const *outs, size_t *n_out);
 
+/* Loudness-normalised output.  output_normalise levels an utterance by sample peak or rms; what a product ships is an
+ * integrated loudness (ITU-R BS.1770-4 / EBU R128: -16 LUFS for voice assistants, -23 for broadcast) under a true-peak
+ * ceiling.  With a target set, that rule runs on the device at the delivered rate, behind the resampler, IN PLACE OF the
+ * output normalisation; the scaling is one linear gain (no limiter).  The definition, exactly -- Q is the rate of the
+ * delivered signal, 8000 <= Q <= 96000, x its N samples (mono):
+ *   K-weighting  two biquads in cascade (a0 = 1), from the analogue prototypes by the bilinear transform, K = tan(pi f0 / Q):
+ *           high-shelf  f0 = 1681.974450955533 Hz, G = 3.999843853973347 dB, Qf = 0.7071752369554196,
+ *                       Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Qf + K^2,
+ *                       b = [Vh + Vb K/Qf + K^2, 2 (K^2 - Vh), Vh - Vb K/Qf + K^2] / a0,  a = [1, 2 (K^2 - 1) / a0, (1 - K/Qf + K^2) / a0]
+ *           high-pass   f0 = 38.13547087602444 Hz, Qf = 0.5003270373238773, a0 = 1 + K/Qf + K^2,
+ *                       b = [1, -2, 1],  a = [1, 2 (K^2 - 1) / a0, (1 - K/Qf + K^2) / a0]
+ *           (Q = 48000 reproduces the coefficient table of BS.1770.)  Both start from the zero state; y = the filtered signal.
+ *   blocks  h = (Q + 5) / 10 in integer division; block j covers [j h, j h + 4 h), nb = (N - 4 h) / h + 1 if N >= 4 h, else 0;
+ *           z_j = mean of y^2 over block j.
+ *   gates   absolute: z_j > 10^((-70 + 0.691) / 10); relative: z_j > 0.1 mean(z over the absolutely gated blocks);
+ *           Z = mean of z over the blocks that pass both (0 where none does, or nb = 0): mean_square.
+ *           Integrated loudness L = -0.691 + 10 log10 Z, -inf for Z = 0 (the host function below).
+ *   true peak  the largest magnitude over x and three interpolated phases p = 1, 2, 3, n = 0 .. N - 1:
+ *           y[4 n + p] = sum over j = -12 .. 11 of x[n - j] t[4 j + p]  (|4 j + p| < 48, zero extension),
+ *           t[k] = sinc(k / 4) I0(8 sqrt(1 - (k / 48)^2)) / I0(8), in double, rounded once to fp32.
+ *   gain    target T (LUFS), ceiling C (dBTP, NaN = none): gain = 10^((T + 0.691) / 20) / sqrt(Z); if a ceiling is set and
+ *           gain TP > 10^(C / 20), gain = 10^(C / 20) / TP.  Formed in double, applied as ONE fp32 factor.  Z = 0 (too short,
+ *           or silence) leaves the utterance unscaled, as rms 0 does.
+ *   arithmetic  filter state, coefficients and every energy sum fp64 (the high-pass has a double pole at 1 - 0.0025 at 96 kHz);
+ *           the true peak fp32, fused multiply-adds over j ascending: |TP - TP_fp64| <= 26 2^-24 sum |t| |x|.  No atomics, a
+ *           fixed order: the struct is a function of (Q, N, x, T, C) alone, and the ragged batch returns the bits of the
+ *           single call, struct and samples.
+ * A NaN target means off (the default): nothing new is launched and every result keeps its bits.  The target is finite in
+ * [-70, 0], the ceiling in [-20, +6] or NaN; anything else is XDTTS_ERR_BAD_ARG and leaves the setting alone.  Honoured by
+ * every entry that delivers a finished utterance (the list of xdtts_griffinlim_set_output_rate); _infer_linear, _step, the
+ * analysis entries and the resample hooks stay as they are.  In xdtts_griffinlim_last_timings the stage falls inside ms[1]. */
+typedef struct {
+  double mean_square;   /* Z */
+  double true_peak;     /* linear, of the signal as measured (before the gain) */
+  double sample_peak;
+  double gain;          /* applied; 1 where nothing was scaled */
+  int32_t blocks, gated_blocks;   /* nb, and the blocks that passed both gates */
+} xdtts_loudness;
+double xdtts_loudness_lufs(const xdtts_loudness *l);   /* host: -0.691 + 10 log10 Z, -inf for Z = 0 */
+xdtts_status xdtts_griffinlim_set_loudness(xdtts_griffinlim *g, float target_lufs, float ceiling_dbtp);   /* default NaN, NaN */
+xdtts_status xdtts_griffinlim_get_loudness(const xdtts_griffinlim *g, float *target_lufs, float *ceiling_dbtp);
+/* The measurement and applied gain of each utterance of the last delivering call, in the caller's order (they travel back
+ * behind the audio).  *n = their number, 0 without a target; out == NULL with cap == 0 asks for the number alone. */
+xdtts_status xdtts_griffinlim_last_loudness(const xdtts_griffinlim *g, xdtts_loudness *out, size_t cap, size_t *n);
+/* Measurement alone on the caller's audio (1 <= n < 2^28 samples) at any rate in range, whatever the handle's setting:
+ * gain = 1, nothing is scaled.  The ragged form runs all utterances in one set of launches and every out[u] equals the single
+ * call's bit for bit.  Afterwards xdtts_griffinlim_last_timings ms[0] is the stage alone. */
+xdtts_status xdtts_griffinlim_loudness(xdtts_griffinlim *g, const float *audio, size_t n, int32_t rate, xdtts_loudness *out);
+xdtts_status xdtts_griffinlim_loudness_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt,
+                                             int32_t rate, xdtts_loudness *out);
+/* Host arithmetic, no handle, no device.  _plan: h and nb for n samples (either pointer may be NULL).  _filter: coef = the
+ * high-shelf's b0 b1 b2 a1 a2, then the high-pass's.  _true_peak_filter: taps[p - 1][j + 12] = t[4 j + p]. */
+xdtts_status xdtts_loudness_plan(int32_t rate, size_t n, int32_t *hop, size_t *n_blocks);
+xdtts_status xdtts_loudness_filter(int32_t rate, double coef[10]);
+xdtts_status xdtts_true_peak_filter(float taps[3][24]);
+
 void xdtts_griffinlim_free(xdtts_griffinlim *g);
 
 /* ---- XdTts::infer pipeline (src/lib.rs:110-159): mel-gen then vocoder with the mel kept in

@@ -279,6 +279,28 @@ class GriffinLim {
     for (size_t u = 0; u < n; ++u) out[u].resize(no[u]);
     return out;
   }
+  // The level rule of every delivered utterance (xdtts_griffinlim_set_loudness): a BS.1770 target in LUFS under a true-peak
+  // ceiling in dBTP, NaN = off / none; when on it takes the output normalisation's place, at the delivered rate.
+  void set_loudness(float target_lufs, float ceiling_dbtp) { check(xdtts_griffinlim_set_loudness(g_, target_lufs, ceiling_dbtp)); }
+  std::pair<float, float> loudness_setting() const {
+    float t = 0.f, c = 0.f;
+    check(xdtts_griffinlim_get_loudness(g_, &t, &c));
+    return {t, c};
+  }
+  // ... the measurement and applied gain of each utterance of the last delivering call (empty without a target)
+  std::vector<xdtts_loudness> last_loudness() const {
+    size_t n = 0;
+    check(xdtts_griffinlim_last_loudness(g_, nullptr, 0, &n));
+    std::vector<xdtts_loudness> out(n);
+    if (n) check(xdtts_griffinlim_last_loudness(g_, out.data(), out.size(), &n));
+    return out;
+  }
+  // ... and the measurement alone on the caller's audio at `rate` (xdtts_griffinlim_loudness): gain 1, nothing scaled
+  xdtts_loudness loudness(const std::vector<float> &audio, int32_t rate) const {
+    xdtts_loudness l{};
+    check(xdtts_griffinlim_loudness(g_, audio.data(), audio.size(), rate, &l));
+    return l;
+  }
   // The inverse direction (xdtts_griffinlim_analyze): audio -> (S (n_bins x F), mel (n_mels x F)) under the handle's conventions,
   // F = audio.size() / 256 + 1
   std::pair<Array2, Array2> analyze(const std::vector<float> &audio, float mel_floor = 1e-5f) const {

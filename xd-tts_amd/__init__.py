@@ -86,6 +86,21 @@ class ProsodyContour(C.Structure):
             self.log_floor = log_floor
 
 
+class Loudness(C.Structure):
+    """xdtts_loudness: the BS.1770 measurement of one utterance and the gain that was applied.  .lufs is the integrated
+    loudness (-inf where no block passed the gates)."""
+
+    _fields_ = [("mean_square", C.c_double), ("true_peak", C.c_double), ("sample_peak", C.c_double), ("gain", C.c_double),
+                ("blocks", C.c_int32), ("gated_blocks", C.c_int32)]
+
+    @property
+    def lufs(self):
+        return float(lib.xdtts_loudness_lufs(C.byref(self)))
+
+    def astuple(self):
+        return (self.mean_square, self.true_peak, self.sample_peak, self.gain, self.blocks, self.gated_blocks)
+
+
 class InferOpts(C.Structure):
     _fields_ = [
         ("gate_threshold", C.c_float),
@@ -175,6 +190,15 @@ SYMBOLS = {
     "xdtts_resample_filter": (_I32, [_I32, _VP, _SZ, C.POINTER(_SZ)]),
     "xdtts_griffinlim_resample": (_I32, [_VP, _VP, _SZ, _I32, _VP, C.POINTER(_SZ)]),
     "xdtts_griffinlim_resample_batch": (_I32, [_VP, _VP, _VP, _I32, _I32, _VP, _VP]),
+    "xdtts_loudness_lufs": (C.c_double, [C.POINTER(Loudness)]),
+    "xdtts_griffinlim_set_loudness": (_I32, [_VP, _F, _F]),
+    "xdtts_griffinlim_get_loudness": (_I32, [_VP, _PF, _PF]),
+    "xdtts_griffinlim_last_loudness": (_I32, [_VP, _VP, _SZ, C.POINTER(_SZ)]),
+    "xdtts_griffinlim_loudness": (_I32, [_VP, _VP, _SZ, _I32, _VP]),
+    "xdtts_griffinlim_loudness_batch": (_I32, [_VP, _VP, _VP, _I32, _I32, _VP]),
+    "xdtts_loudness_plan": (_I32, [_I32, _SZ, C.POINTER(_I32), C.POINTER(_SZ)]),
+    "xdtts_loudness_filter": (_I32, [_I32, _VP]),
+    "xdtts_true_peak_filter": (_I32, [_VP]),
     "xdtts_griffinlim_free": (None, [_VP]),
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
@@ -894,6 +918,45 @@ class GriffinLim:
             _check(lib.xdtts_griffinlim_resample_batch(self._h, ip, ns, n, int(rate_out), op, no))
         return [o[: no[u]] for u, o in enumerate(outs)]
 
+    # -- loudness: BS.1770 integrated loudness under a true-peak ceiling, behind the resampler ----
+    def set_loudness(self, target_lufs=None, ceiling_dbtp=None):
+        """The level rule of every delivered utterance: a target in LUFS ([-70, 0]; None / NaN = off, the default) under a
+        true-peak ceiling in dBTP ([-20, 6]; None / NaN = none).  When on it takes output_normalise's place, at the delivered
+        rate; last_loudness() then has the measurement and the gain of each utterance."""
+        t = float("nan") if target_lufs is None else float(target_lufs)
+        c = float("nan") if ceiling_dbtp is None else float(ceiling_dbtp)
+        _check(lib.xdtts_griffinlim_set_loudness(self._h, t, c))
+
+    def get_loudness(self):
+        t, c = C.c_float(), C.c_float()
+        _check(lib.xdtts_griffinlim_get_loudness(self._h, C.byref(t), C.byref(c)))
+        return t.value, c.value
+
+    def last_loudness(self):
+        """[Loudness] of the last delivering call, in the caller's order; [] without a target."""
+        n = C.c_size_t()
+        _check(lib.xdtts_griffinlim_last_loudness(self._h, None, 0, C.byref(n)))
+        out = (Loudness * max(n.value, 1))()
+        _check(lib.xdtts_griffinlim_last_loudness(self._h, out, n.value, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
+    def loudness(self, audio, rate):
+        """The measurement alone on `audio` at `rate` (8000 .. 96000), whatever the handle's setting: a Loudness with gain 1."""
+        return self.loudness_batch([audio], rate)[0]
+
+    def loudness_batch(self, audios, rate):
+        """The ragged measurement: one set of launches for all audios, every struct the single call's bit for bit."""
+        xs = [np.ascontiguousarray(a, dtype=np.float32).ravel() for a in audios]
+        n = len(xs)
+        out = (Loudness * max(n, 1))()
+        ip = (C.c_void_p * max(n, 1))(*[x.ctypes.data for x in xs])
+        ns = (C.c_size_t * max(n, 1))(*[x.size for x in xs])
+        if n == 1:
+            _check(lib.xdtts_griffinlim_loudness(self._h, ip[0], ns[0], int(rate), out))
+        else:
+            _check(lib.xdtts_griffinlim_loudness_batch(self._h, ip, ns, n, int(rate), out))
+        return [out[i] for i in range(n)]
+
     # -- analysis: audio -> magnitude -> mel under the handle's conventions, spectral convergence ----
     def analysis_frames(self, n_samples):
         return int(lib.xdtts_griffinlim_analysis_frames(self._h, int(n_samples)))
@@ -976,6 +1039,28 @@ def resample_filter(rate_out):
     taps = np.empty(n.value, dtype=np.float32)
     _check(lib.xdtts_resample_filter(int(rate_out), _ptr(taps), taps.size, C.byref(n)))
     return taps
+
+
+def loudness_plan(rate, n=0):
+    """xdtts_loudness_plan (host arithmetic): {"hop", "n_blocks"} of the loudness stage for n samples at `rate`."""
+    h, nb = C.c_int32(), C.c_size_t()
+    _check(lib.xdtts_loudness_plan(int(rate), int(n), C.byref(h), C.byref(nb)))
+    return {"hop": h.value, "n_blocks": nb.value}
+
+
+def loudness_filter(rate):
+    """xdtts_loudness_filter: the K-weighting at `rate` as ((b_shelf, a_shelf), (b_highpass, a_highpass)), fp64, a0 = 1."""
+    c = np.zeros(10, dtype=np.float64)
+    _check(lib.xdtts_loudness_filter(int(rate), _ptr(c)))
+    one = np.ones(1)
+    return (c[0:3].copy(), np.concatenate([one, c[3:5]])), (c[5:8].copy(), np.concatenate([one, c[8:10]]))
+
+
+def true_peak_filter():
+    """xdtts_true_peak_filter: the library's own fp32 taps, [3][24]: taps[p - 1][j + 12] = t[4 j + p]."""
+    t = np.zeros((3, 24), dtype=np.float32)
+    _check(lib.xdtts_true_peak_filter(_ptr(t)))
+    return t
 
 
 def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, contour=None):

@@ -673,6 +673,120 @@ xdtts_status xdtts_griffinlim_resample(xdtts_griffinlim *g, const float *audio, 
   return xdtts_griffinlim_resample_batch(g, &audio, &n, 1, rate_out, &out, n_out);
 }
 
+// ---- loudness: BS.1770 integrated loudness under a true-peak ceiling, behind the resampler (loudness_plan.h, loudness.hip) ----
+
+static void loudness_rate_checked(int32_t rate) {
+  const std::string msg = loudness_check(rate);
+  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+}
+
+double xdtts_loudness_lufs(const xdtts_loudness *l) { return l ? loudness_lufs(l->mean_square) : -INFINITY; }
+
+xdtts_status xdtts_loudness_plan(int32_t rate, size_t n, int32_t *hop, size_t *n_blocks) {
+  return guard([&] {
+    loudness_rate_checked(rate);
+    if (hop) *hop = loudness_hop(rate);
+    if (n_blocks) *n_blocks = loudness_blocks(rate, n);
+  });
+}
+
+xdtts_status xdtts_loudness_filter(int32_t rate, double coef[10]) {
+  return guard([&] {
+    loudness_rate_checked(rate);
+    if (!coef) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    loudness_coef(rate, coef);
+  });
+}
+
+xdtts_status xdtts_true_peak_filter(float taps[3][24]) {
+  return guard([&] {
+    if (!taps) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    static_assert(LOUD_TP_PHASES == 3 && LOUD_TP_TAPS == 24, "the header's array type");
+    loudness_true_peak_taps(taps);
+  });
+}
+
+xdtts_status xdtts_griffinlim_set_loudness(xdtts_griffinlim *g, float target_lufs, float ceiling_dbtp) {
+  return guard([&] {
+    const std::string msg = loudness_target_check(target_lufs, ceiling_dbtp);  // the values first: reported without a handle
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->loud_target = target_lufs;
+    g->loud_ceiling = ceiling_dbtp;
+  });
+}
+
+xdtts_status xdtts_griffinlim_get_loudness(const xdtts_griffinlim *g, float *target_lufs, float *ceiling_dbtp) {
+  return guard([&] {
+    if (!g || !target_lufs || !ceiling_dbtp) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    *target_lufs = g->loud_target;
+    *ceiling_dbtp = g->loud_ceiling;
+  });
+}
+
+xdtts_status xdtts_griffinlim_last_loudness(const xdtts_griffinlim *g, xdtts_loudness *out, size_t cap, size_t *n) {
+  return guard([&] {
+    if (n) *n = 0;
+    if (!g || !n) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    *n = g->last_loud.size();
+    if (!out && cap == 0) return;  // the count alone
+    if (!out || cap < g->last_loud.size()) fail(XDTTS_ERR_BAD_ARG, "the last call delivered %zu utterances, the buffer holds %zu", g->last_loud.size(), cap);
+    if (!g->last_loud.empty()) std::memcpy(out, g->last_loud.data(), g->last_loud.size() * sizeof(xdtts_loudness));
+  });
+}
+
+// Measurement hook of the stage alone, single call and ragged batch: the audios one behind the other on the device, the four
+// launches of launch_loudness_measure (the single call passes its record by value, the batch uploads the table), and the
+// structs back.  No target, no scaling: gain = 1.  last_timings: ms[0] = the stage alone.
+xdtts_status xdtts_griffinlim_loudness_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt, int32_t rate,
+                                             xdtts_loudness *out) {
+  return guard([&] {
+    loudness_rate_checked(rate);
+    if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    if (!g || !audios || !n || !out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::vector<LoudUtt> tab((size_t)n_utt);
+    size_t tot = 0, grp = 0, seg = 0, sb = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      if (n[u] == 0 || n[u] >= RS_MAX_SAMPLES) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need 1 .. 2^28 - 1 samples, got %zu", u, n[u]);
+      if (!audios[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null audio", u);
+      tab[(size_t)u] = {(long long)tot, (int)n[u], (int)grp, (int)seg, (int)sb};
+      tot += n[u];
+      grp += loudness_groups(n[u]);
+      seg += loudness_segments(n[u]);
+      sb += loudness_sub_blocks(rate, n[u]);
+      if (tot > (size_t)0x7fffffff) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^31 - 1 samples");
+    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    hipStream_t st = g->stream;
+    g->rs_in.alloc(tot);
+    g->loudness_prepare(rate);
+    g->loudness_bufs(grp, (size_t)n_utt);
+    for (int u = 0; u < n_utt; ++u)
+      HIP_CHECK(hipMemcpyAsync(g->rs_in.p + tab[(size_t)u].src0, audios[u], n[u] * sizeof(float), hipMemcpyHostToDevice, st));
+    if (n_utt > 1) {
+      g->loud_tab_host = tab;
+      g->loud_tab.upload(g->loud_tab_host.data(), g->loud_tab_host.size(), st);
+    }
+    HIP_CHECK(hipEventRecord(g->ev.e[0], st));
+    if (n_utt == 1) g->loudness_one(g->rs_in.p, n[0], rate, false);  // (the form the single-utterance entries run)
+    else g->loudness_rows(g->rs_in.p, 0, n_utt, rate, false);
+    HIP_CHECK(hipEventRecord(g->ev.e[1], st));
+    HIP_CHECK(hipEventRecord(g->ev.e[2], st));
+    g->loudness_fetch(0, n_utt, st);
+    g->finish_timings();  // (drains the stream: the inputs, the table and the structs)
+    static_assert(sizeof(xdtts_loudness) == sizeof(LoudResult), "LoudResult is xdtts_loudness");
+    std::memcpy(out, g->loud_host, (size_t)n_utt * sizeof(xdtts_loudness));
+  });
+}
+
+xdtts_status xdtts_griffinlim_loudness(xdtts_griffinlim *g, const float *audio, size_t n, int32_t rate, xdtts_loudness *out) {
+  return xdtts_griffinlim_loudness_batch(g, &audio, &n, 1, rate, out);
+}
+
 // ---- analysis: the inverse direction of GriffinLim::infer's conventions (analysis.hip).  No co-resident grid: no chip lock. ----
 
 // What one call takes: the row tiles of the mel GEMM and of the boundary transposes go into a grid dimension of at most 65535

@@ -84,6 +84,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
     std::lock_guard<std::mutex> lk(h->mu);
     std::lock_guard<std::mutex> lk2(g->mu);
     std::lock_guard<ChipLock> chip(chip_mutex(h->device));  // the whole sequence: co-resident launches of two streams are in flight
+    g->last_loud.clear();  // (gl_collect appends utterance by utterance)
     const xdtts_infer_opts o = resolve_opts(opts);
     struct Hook {  // (the hook never outlives this call, whatever throws)
       xdtts_tacotron2 *h;

@@ -25,6 +25,7 @@ const Var table[N_VARS] = {
     {"XDTTS_GEMM_SPLIT_TILE", Kind::form, When::process},
     {"XDTTS_GL_BATCH_FORCE", Kind::form, When::request},
     {"XDTTS_PROSODY_BATCH", Kind::form, When::request},     // =loop: the batch parity hook runs one k_prosody launch per utterance
+    {"XDTTS_LOUD", Kind::form, When::request},              // =fp32: the loudness stage's recurrences in fp32 (what fp64 costs)
     // test hooks: a lost or a slow workgroup, a short spin budget
     {"XDTTS_ATT_SPINS", Kind::hook, When::request},
     {"XDTTS_ATT_FAULT", Kind::hook, When::request},

@@ -9,7 +9,7 @@ namespace env {
 enum Id {
   DEVICE, CHIP_LOCK_DIR, DECODER, GL, COOP,                                  // product
   ATT_FUSED, NO_EARLY, NO_TAIL, NO_CTXFOLD, NO_SKEW, P8,                     // engine forms (the tests compare them)
-  GEMM_TILE, GEMM_SPLITK, GEMM_SPLIT_TILE, GL_BATCH_FORCE, PROSODY_BATCH,
+  GEMM_TILE, GEMM_SPLITK, GEMM_SPLIT_TILE, GL_BATCH_FORCE, PROSODY_BATCH, LOUD,
   ATT_SPINS, ATT_FAULT, ATT_SLOW, TAIL_FAULT,                                // test hooks of the lost / slow workgroup paths
   PERSIST_SPINS, PERSIST_FAULT, PERSIST_SLOW, ENC_SPINS, ENC_FAULT, GL_SPINS, GL_SLOW,
   PERSIST_PROFILE, GL_PROFILE,                                               // output paths of the `make prof` build

@@ -13,6 +13,7 @@ xdtts_griffinlim::~xdtts_griffinlim() {
   for (hipEvent_t e : copy_ev) (void)hipEventDestroy(e);
   if (copy_stream) (void)hipStreamDestroy(copy_stream);
   if (host_err) (void)hipHostFree(host_err);
+  if (loud_host) (void)hipHostFree(loud_host);
   if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -216,6 +217,67 @@ void xdtts_griffinlim::resample_rows(const float *src, float *dst, int r0, int c
   const int nblk = last.blk0 + (last.n_out + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK - first.blk0;
   launch_resample(src, dst, rs_tab.p + r0, count, first.blk0, nblk, ResampleUtt{}, rs_rows.p, rs_table.L, rs_table.M, rs_table.Jn,
                   rs_table.T4, stream);
+}
+
+// The loudness stage (loudness.hip).  The table is a function of the rate alone: built on the host once per (handle, rate) and
+// kept on the device; the host copy is the upload's source and lives as long as the handle.
+void xdtts_griffinlim::loudness_prepare(int rate) {
+  if (loud_table_host.rate == rate && loud_table.p) return;
+  HIP_CHECK(hipStreamSynchronize(stream));  // (a launch that reads the table of another rate may be in flight)
+  const std::string msg = loudness_check(rate);
+  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  loud_table_host.rate = 0;
+  loudness_table(rate, loud_table_host);
+  loud_table.upload(&loud_table_host, 1, stream);
+}
+
+LoudBufs xdtts_griffinlim::loudness_bufs(size_t groups, size_t n_utt) {
+  groups = std::max<size_t>(groups, 1);
+  n_utt = std::max<size_t>(n_utt, 1);
+  const size_t segs = groups * LOUD_LANES;
+  if (segs > loud_excl.n / 4 || n_utt > loud_res.n) HIP_CHECK(hipStreamSynchronize(stream));  // (growing frees what a launch may read)
+  loud_excl.alloc(segs * 4);
+  loud_agg.alloc(groups * 4);
+  loud_gin.alloc(groups * 4);
+  loud_part.alloc(segs * 2);
+  loud_sub.alloc(groups * 3 + n_utt);  // (h >= 800: at most three sub-blocks begin inside a group of 2048, one more per utterance)
+  loud_peaks.alloc(groups);
+  loud_res.alloc(n_utt);
+  if (n_utt > loud_host_n) {
+    if (loud_host) HIP_CHECK(hipHostFree(loud_host));
+    loud_host = nullptr;
+    loud_host_n = 0;
+    HIP_CHECK(hipHostMalloc((void **)&loud_host, n_utt * sizeof(LoudResult), hipHostMallocDefault));
+    loud_host_n = n_utt;
+  }
+  return LoudBufs{loud_excl.p, loud_agg.p, loud_gin.p, loud_part.p, loud_sub.p, loud_peaks.p};
+}
+
+void xdtts_griffinlim::loudness_one(float *x, size_t n, int rate, bool scale) {
+  if (n == 0 || n >= ((size_t)1 << 28)) fail(XDTTS_ERR_BAD_ARG, "loudness: need 1 .. 2^28 - 1 samples, got %zu", n);
+  loudness_prepare(rate);
+  const int groups = (int)loudness_groups(n);
+  const LoudBufs b = loudness_bufs((size_t)groups, 1);
+  const LoudUtt one{0, (int)n, 0, 0, 0};
+  const bool on = scale && loudness_on();
+  launch_loudness_measure(x, nullptr, 1, 0, groups, one, loud_table.p, b, loud_res.p, rate, on ? loudness_target_lin(loud_target) : 0.0,
+                          on ? loudness_ceiling_lin(loud_ceiling) : 0.0, stream);
+  if (on) launch_loudness_scale(x, nullptr, 1, 0, groups, one, loud_res.p, stream);
+}
+
+void xdtts_griffinlim::loudness_rows(float *x, int r0, int count, int rate, bool scale) {
+  if (count <= 0) return;
+  const LoudUtt &first = loud_tab_host[(size_t)r0], &last = loud_tab_host[(size_t)(r0 + count - 1)];
+  const int groups = last.grp0 + (int)loudness_groups((size_t)last.n) - first.grp0;
+  const LoudBufs b{loud_excl.p, loud_agg.p, loud_gin.p, loud_part.p, loud_sub.p, loud_peaks.p};
+  const bool on = scale && loudness_on();
+  launch_loudness_measure(x, loud_tab.p + r0, count, first.grp0, groups, LoudUtt{}, loud_table.p, b, loud_res.p + r0, rate,
+                          on ? loudness_target_lin(loud_target) : 0.0, on ? loudness_ceiling_lin(loud_ceiling) : 0.0, stream);
+  if (on) launch_loudness_scale(x, loud_tab.p + r0, count, first.grp0, groups, LoudUtt{}, loud_res.p + r0, stream);
+}
+
+void xdtts_griffinlim::loudness_fetch(int r0, int count, hipStream_t s) {
+  HIP_CHECK(hipMemcpyAsync(loud_host + r0, loud_res.p + r0, (size_t)count * sizeof(LoudResult), hipMemcpyDeviceToHost, s));
 }
 
 void xdtts_griffinlim::upload_rows(const float *const *S_host, const Rows &rows) {
@@ -491,10 +553,13 @@ static void enqueue_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
     N = g->resample_one(g->audio.p, N, g->audio_rs.p, g->out_rate);
     out = g->audio_rs.p;
   }
-  if (deliver) launch_gl_output_normalise(out, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
+  const bool loud = deliver && g->loudness_on() && N > 0;  // the loudness rule takes the output normalisation's place
+  if (loud) g->loudness_one(out, N, g->out_rate, true);
+  else if (deliver) launch_gl_output_normalise(out, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
   HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
   if (!host.p) host = PinnedGuard(N);
   HIP_CHECK(hipMemcpyAsync(host.p, out, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+  if (loud) g->loudness_fetch(0, 1, g->stream);  // the measurement and the gain travel back behind the audio
   g->fetch_error_word();
 }
 // ... and its counterpart: the wait and the engine's error word.  The persistent engine needs its grid co-resident (the
@@ -510,6 +575,12 @@ static void collect_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
     if (g->persistent_failed()) fail(XDTTS_ERR_HIP, "Griffin-Lim: the fallback engine reported an exchange failure");
   }
   const size_t N = (size_t)g->hop * (size_t)(b.F - 1);
+  if (deliver && g->loudness_on() && N > 0) {
+    xdtts_loudness l;
+    static_assert(sizeof l == sizeof(LoudResult), "LoudResult is xdtts_loudness");
+    std::memcpy(&l, g->loud_host, sizeof l);
+    g->last_loud.push_back(l);
+  }
   *audio = host.release();
   *n_samples = deliver ? g->delivered(N) : N;
 }
@@ -519,6 +590,7 @@ void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *pha
                           bool normalise) {
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
   g->probe_tick();
+  g->last_loud.clear();
   PinnedGuard host;
   enqueue_run(g, b, phase0_dev, iters, normalise, host);
   collect_run(g, b, phase0_dev, iters, normalise, host, audio, n_samples);
@@ -556,6 +628,7 @@ void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, si
 
 void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const ProsodyArg &p, float **audio, size_t *n_samples) {
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
+  g->last_loud.clear();
   PinnedGuard host;
   gl_enqueue_from_device_mel(g, mel_dev_ptr, F, host, p);
   gl_collect(g, F, host, audio, n_samples, p);
@@ -694,7 +767,16 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
   float *const dbuf = resampled ? g->audio_rs.p : g->audio.p;
   HIP_CHECK(hipStreamSynchronize(st));  // the host vector above
   const float alpha = g->momentum / (1.0f + g->momentum);
-  const int norm_mode = g->gopts.output_normalise;
+  // With a loudness target the loudness stage (loudness.hip) takes the output normalisation's place, on the same rows.
+  const bool loud = g->loudness_on();
+  const int norm_mode = loud ? 0 : g->gopts.output_normalise;
+  g->last_loud.clear();
+  if (loud) {
+    size_t groups = 0;
+    for (int u = 0; u < n_utt; ++u) groups += loudness_groups((size_t)dn[(size_t)u]);
+    g->loudness_prepare(g->out_rate);
+    g->loudness_bufs(groups, (size_t)n_utt);
+  }
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
   g->probe_tick();
   for (int attempt = 0;; ++attempt) {
@@ -718,14 +800,22 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     // preceded by ONE resample launch (at a rate other than 22050) and ONE two-launch output normalisation (G6) of exactly
     // its utterances, in that order: the level rules hold for the signal the caller receives.
     std::vector<int> tab_pos((size_t)n_utt, 0);
-    if (norm_mode || resampled) {
+    if (norm_mode || resampled || loud) {
       std::vector<int2> tab;
       tab.reserve((size_t)n_utt);
       g->rs_tab_host.clear();
-      int blk = 0;
+      g->loud_tab_host.clear();
+      int blk = 0, grp = 0, seg = 0, sb = 0;
       for (int u : plan.order) {
         tab_pos[(size_t)u] = (int)tab.size();
         tab.push_back(make_int2(dbase[(size_t)u], dn[(size_t)u]));
+        if (loud) {
+          const size_t n = (size_t)dn[(size_t)u];
+          g->loud_tab_host.push_back({(long long)dbase[(size_t)u], dn[(size_t)u], grp, seg, sb});
+          grp += (int)loudness_groups(n);
+          seg += (int)loudness_segments(n);
+          sb += (int)loudness_sub_blocks(g->out_rate, n);
+        }
         if (resampled) {
           g->rs_tab_host.push_back({(long long)abase[u], (long long)rbase[(size_t)u], g->hop * (Fu[u] - 1), dn[(size_t)u], blk, 0});
           blk += (dn[(size_t)u] + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK;
@@ -736,6 +826,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
         g->norm_parts.alloc((size_t)GLN_SCRATCH * (size_t)n_utt);
       }
       if (resampled) g->rs_tab.upload(g->rs_tab_host.data(), g->rs_tab_host.size(), st);
+      if (loud) g->loud_tab.upload(g->loud_tab_host.data(), g->loud_tab_host.size(), st);
       HIP_CHECK(hipStreamSynchronize(st));
     }
     size_t n_ev = 0;
@@ -748,12 +839,14 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
         launch_gl_output_normalise(dbuf, g->norm_tab.p + r0, (int)utts.size(), 0, n_max, norm_mode, g->gopts.rms_target,
                                    g->norm_parts.p + (size_t)r0 * GLN_SCRATCH, st);
       }
+      if (loud && !utts.empty()) g->loudness_rows(dbuf, tab_pos[(size_t)utts[0]], (int)utts.size(), g->out_rate, true);
       hipEvent_t e = g->launch_done(n_ev++);
       HIP_CHECK(hipEventRecord(e, st));
       HIP_CHECK(hipStreamWaitEvent(g->copy_stream, e, 0));
       for (int u : utts)
         HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, dbuf + dbase[(size_t)u], sizeof(float) * (size_t)dn[(size_t)u], hipMemcpyDeviceToHost,
                                  g->copy_stream));
+      if (loud && !utts.empty()) g->loudness_fetch(tab_pos[(size_t)utts[0]], (int)utts.size(), g->copy_stream);
     };
     // the persistent launches, each followed by the fetch of its utterances
     bool used_persistent = false;
@@ -800,6 +893,11 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     for (int u = 0; u < n_utt; ++u) {
       audios[u] = out[(size_t)u].release();
       n_samples[u] = (size_t)dn[(size_t)u];
+      if (loud) {
+        xdtts_loudness l;
+        std::memcpy(&l, g->loud_host + tab_pos[(size_t)u], sizeof l);
+        g->last_loud.push_back(l);
+      }
     }
     return;
   }

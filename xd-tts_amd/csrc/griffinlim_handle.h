@@ -149,6 +149,33 @@ struct xdtts_griffinlim {
   // What a request path delivers for n samples of the loop: N' at the handle's rate, n at 22050.
   size_t delivered(size_t n) const { return xdtts::resample_n_out(out_plan, n); }
 
+  // loudness (loudness.hip): with a target set, the stage that takes the output normalisation's place behind the resampler --
+  // BS.1770 integrated loudness and true peak of the delivered signal, then one linear gain.  NaN target = off (the default).
+  float loud_target = NAN, loud_ceiling = NAN;
+  bool loudness_on() const { return !std::isnan(loud_target); }
+  xdtts::LoudnessTable loud_table_host{};   // the upload's source, kept with the handle; rate 0 = none yet
+  DevBuf<xdtts::LoudnessTable> loud_table;
+  DevBuf<double> loud_excl, loud_agg, loud_gin, loud_part, loud_sub;  // the scan's scratch (kernels.h: LoudBufs)
+  DevBuf<float2> loud_peaks;
+  DevBuf<xdtts::LoudResult> loud_res;       // one per utterance of a request
+  DevBuf<xdtts::LoudUtt> loud_tab;
+  std::vector<xdtts::LoudUtt> loud_tab_host;  // the upload's source: stays until the next request of this handle
+  xdtts::LoudResult *loud_host = nullptr;   // pinned: the structs travel back behind the audio
+  size_t loud_host_n = 0;
+  std::vector<xdtts_loudness> last_loud;    // xdtts_griffinlim_last_loudness: of the last delivering call, in the caller's order
+  // The coefficients, matrix powers and taps of `rate` on the device: built and uploaded once per (handle, rate).
+  void loudness_prepare(int rate);
+  // Scratch for `groups` workgroups in all (every array is sized from it) and `n_utt` results, device and pinned host.
+  xdtts::LoudBufs loudness_bufs(size_t groups, size_t n_utt);
+  // One utterance, x[0 .. n) at `rate`, on the stream: the measurement into loud_res[0] and, with scale, the gain of the
+  // handle's target applied in place.  Nothing is uploaded (the record travels as a kernel argument).
+  void loudness_one(float *x, size_t n, int rate, bool scale);
+  // Ragged: records loud_tab_host[r0 .. r0 + count) (uploaded by the caller as loud_tab, behind loudness_prepare() and
+  // loudness_bufs()), results into loud_res[r0 ..].
+  void loudness_rows(float *x, int r0, int count, int rate, bool scale);
+  // loud_res[r0 .. r0 + count) -> loud_host, on `s`
+  void loudness_fetch(int r0, int count, hipStream_t s);
+
   ~xdtts_griffinlim();
   GlBufs bufs(int F);
   // The ragged parity hooks: utterance u's magnitude in the boundary layout (nb x F_u), uploaded through `frames` and transposed

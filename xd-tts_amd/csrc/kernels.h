@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "gl_plan.h"
+#include "loudness_plan.h"
 #include "resample_plan.h"
 #include "weights.h"
 
@@ -372,5 +373,37 @@ struct ResampleUtt {
 // launch holds.
 void launch_resample(const float *x, float *y, const ResampleUtt *tab_dev, int n_utt, int blk_base, int nblk, const ResampleUtt &one,
                      const float *rows_dev, int L, int M, int Jn, int T4, hipStream_t s);
+
+// ---- loudness (loudness.hip): BS.1770 integrated loudness and true peak of the delivered signal, and the gain to a target ----
+// One utterance of a launch: n samples at x + src0.  Its workgroups (LOUD_GROUP samples each) are grp0 .. of the table's
+// numbering, its segments (LOUD_SEG samples) seg0 .., its 100 ms sub-blocks sb0 .. -- ascending, the utterances back to back;
+// those three also index the scratch arrays below.
+struct LoudUtt {
+  long long src0;
+  int n, grp0, seg0, sb0;
+};
+struct LoudResult {  // == xdtts_loudness (include/xdtts.h)
+  double mean_square, true_peak, sample_peak, gain;
+  int blocks, gated;
+};
+struct LoudBufs {
+  double *excl;   // [segments][4]  a segment's state on entry, had its group started from zero
+  double *agg;    // [groups][4]    a group's final state from zero
+  double *gin;    // [groups][4]    a group's true state on entry
+  double *part;   // [segments][2]  sum of y^2 inside the first / the second sub-block a segment touches
+  double *sub;    // [sub-blocks]   sum of y^2 per 100 ms
+  float2 *peaks;  // [groups]       (true peak, sample peak)
+};
+// The measurement of `count` utterances (records tab_dev[0 .. count), or `one` by value where tab_dev is null: the single call
+// uploads nothing) in four launches: local runs + true peak, the carry, the energy runs, the gates.  res[u] receives utterance
+// u's struct; tgt = 0 measures only (gain 1), else the gain rule of loudness_plan.h with tgt and ceil.  n_groups = the
+// utterances' groups in all, the first being group grp_base.  No atomics, a fixed order everywhere: res[u] is a function of
+// (rate, n, the utterance's samples, tgt, ceil) alone.
+void launch_loudness_measure(const float *x, const LoudUtt *tab_dev, int count, int grp_base, int n_groups, const LoudUtt &one,
+                             const LoudnessTable *table_dev, const LoudBufs &b, LoudResult *res, int rate, double tgt, double ceil,
+                             hipStream_t s);
+// x[i] *= (float)res[u].gain over the same utterances, one launch
+void launch_loudness_scale(float *x, const LoudUtt *tab_dev, int count, int grp_base, int n_groups, const LoudUtt &one,
+                           const LoudResult *res, hipStream_t s);
 
 }  // namespace xdtts
