@@ -542,7 +542,7 @@ xdtts_status xdtts_griffinlim_spsi_phase_batch(xdtts_griffinlim *g, const float 
  * _infer_batch and its prosody and contour forms, xdtts_synthesize_ids, _batch and _sequence with their prosody and contour
  * forms; *n_samples is N' = the plan's n_out for hop * (F' - 1) in each.  batch == single bit for bit (batch_shape = 4) holds
  * at every rate.  xdtts_griffinlim_infer_linear (the loop alone), _step and the analysis entries stay at 22 050 Hz.  Not per
- * utterance inside a batch; no PCM16 / mu-law encoding on the device (xdtts_audio_to_i16 stays on the host).
+ * utterance inside a batch.  (PCM16 / mu-law / A-law on the device and the joined stream: xdtts_synthesize_document below.)
  * xdtts_griffinlim_last_timings: the stage falls inside ms[1] (and ms[2]) exactly as the output normalisation does. */
 xdtts_status xdtts_griffinlim_set_output_rate(xdtts_griffinlim *g, int32_t rate);   /* default 22050 */
 xdtts_status xdtts_griffinlim_get_output_rate(const xdtts_griffinlim *g, int32_t *rate);
@@ -614,6 +614,68 @@ xdtts_status xdtts_griffinlim_loudness_batch(xdtts_griffinlim *g, const float *c
 xdtts_status xdtts_loudness_plan(int32_t rate, size_t n, int32_t *hop, size_t *n_blocks);
 xdtts_status xdtts_loudness_filter(int32_t rate, double coef[10]);
 xdtts_status xdtts_true_peak_filter(float taps[3][24]);
+
+/* Document output: the utterances of a sequence joined with their <break> silences into ONE stream, faded at their edges,
+ * levelled by one programme gain and encoded, on the device -- the output stage of XdTts::generate_audio (src/lib.rs:60-108:
+ * every piece written as i16, the silences between them, one PCM stream).  The last stage of the delivery chain: rate ->
+ * level -> join + sample format.  The definition, exactly:
+ *   layout  utterances of n[u] >= 0 samples, u = 0 .. U - 1, 1 <= U <= 4096; gaps gap[0 .. U] in samples at the delivered rate,
+ *           gap[0] in front of the first utterance, gap[u + 1] behind utterance u (gaps == NULL: all zero; the host gets the
+ *           lengths from xdtts_silence_samples).  offset[u] = gap[0] + sum over v < u of (n[v] + gap[v + 1]);
+ *           total = offset[U - 1] + n[U - 1] + gap[U], 1 <= total < 2^28.  Gap samples are exact zeros: fp32 +0.0f, PCM16 0,
+ *           mu-law 0xFF, A-law 0xD5.
+ *   sample i of utterance u, stream position k = offset[u] + i, in this order; every product is rounded to fp32 on its own
+ *   (nothing is fused across the steps):
+ *   1 fade    f = min(fade, n[u] / 2) in integer division; T[j] = 0.5 - 0.5 cos(pi (j + 0.5) / fade), j < fade, in double on
+ *             the host, rounded once to fp32.  i < f: x <- fl(x T[i]); n[u] - 1 - i < f: x <- fl(x T[n[u] - 1 - i]) (the two
+ *             exclude each other).  An utterance shorter than 2 fade uses the first f entries only: continuous, the window
+ *             just stays below 1.
+ *   2 gain    programme level only: x <- fl(x gain), the one fp32 factor below.
+ *   3 format 0  x.
+ *   4 format 1  v = fl(x 32767.0f).  Without dither q = the Rust cast `v as i16` (truncating toward zero, saturating, NaN -> 0:
+ *             the bits of xdtts_audio_to_i16).  With dither d = u(2 k) - u(2 k + 1) (exact in fp32), u(i) = the library's
+ *             counter-based uniform of (dither_seed, stream number 0x57AEA401, i): 24 bits in [0, 1); v <- fl(v + d),
+ *             q = floor(fl(v + 0.5f)) saturated to [-32768, 32767], NaN -> 0.  The dither is a function of the ABSOLUTE
+ *             stream position k: an utterance moved by a gap gets other dither, a stream cut in two does not repeat it.
+ *   5 formats 2, 3  from the undithered q of step 4 in sign-magnitude form (the symmetric form of G.711 itself):
+ *             a = min(|q|, 32767), neg = q < 0.
+ *             mu-law  m = min(a >> 2, 8158) + 33, e = floor(log2 m) - 5 (0 .. 7), mant = (m >> (e + 1)) & 15,
+ *                     byte = 0xFF ^ ((neg ? 0x80 : 0) | e << 4 | mant)
+ *             A-law   a13 = a >> 3; a13 < 32: e = 0, mant = a13 >> 1; else e = floor(log2 a13) - 4, mant = (a13 >> e) & 15;
+ *                     byte = ((neg ? 0 : 0x80) | e << 4 | mant) ^ 0x55
+ *             (for q >= 0 the bytes of the common table-driven encoders; for q < 0 the exact mirror, enc(-q) = enc(q) ^ 0x80.)
+ *   programme level (level = 1)  BS.1770 is a programme measurement: the utterances enter unlevelled (no output
+ *             normalisation, no loudness stage of their own), the stream is formed in fp32 with fades and gaps, measured ONCE as
+ *             a single signal of `total` samples at the delivered rate, and the gain rule above (target, ceiling, no gated
+ *             block -> 1) gives one factor for every sample.  Needs a target on the handle (xdtts_griffinlim_set_loudness), else
+ *             XDTTS_ERR_BAD_ARG; xdtts_griffinlim_last_loudness then returns exactly ONE struct.
+ * Out of scope: a document built from xdtts_synthesize_batch; a rate or a format per utterance; noise-shaped dither; dither
+ * for G.711; WAV container writing for the 8-bit formats (xdtts_wav_write stays PCM16). */
+typedef struct {
+  int32_t  format;       /* 0 fp32, 1 PCM16 (little-endian int16), 2 G.711 mu-law, 3 G.711 A-law (one byte a sample) */
+  int32_t  dither;       /* 0 none: the reference's cast, 1 TPDF; format 1 only, else XDTTS_ERR_BAD_ARG */
+  uint32_t dither_seed;
+  int32_t  level;        /* 0 each utterance as the handle delivers it, 1 programme: ONE gain for the whole stream */
+  int32_t  fade;         /* samples per utterance edge at the delivered rate, 0 .. 4800; 0 = none */
+} xdtts_stream_opts;     /* default {1, 0, 0, 0, 0} */
+/* Host arithmetic, no handle, no device.  _sample_bytes: 4, 2, 1, 1; 0 for an unknown format.  _plan: offsets[0 .. n_utt) and
+ * *total (either may be NULL) by the layout rule, checked term by term before anything is added.  _fade_table: w[0 .. fade).
+ * _encode_sample: steps 3 to 5 for ONE sample x (behind fade and gain) at stream position k, into out[0 .. sample_bytes). */
+void xdtts_stream_opts_default(xdtts_stream_opts *o);
+size_t xdtts_stream_sample_bytes(int32_t format);
+xdtts_status xdtts_stream_plan(const size_t *n, int32_t n_utt, const size_t *gaps, size_t *offsets, size_t *total);
+xdtts_status xdtts_stream_fade_table(int32_t fade, float *w);
+xdtts_status xdtts_stream_encode_sample(float x, int32_t format, int32_t dither, uint32_t seed, size_t k, void *out);
+/* The stage alone on the caller's audio, in one k_stream_join launch (level 1: the fp32 stream is formed and measured first):
+ * the parity hook, and an entry for a host that holds batch outputs.  audios[u] may be NULL where n[u] == 0; out takes
+ * total * sample_bytes bytes (cap_bytes is checked against it), offsets [n_utt] and total may be NULL.  rate matters to
+ * programme level only (the range of xdtts_griffinlim_loudness).  o == NULL: the default.  Argument errors come back before a
+ * device is touched, and the message names the field and the index.  Afterwards xdtts_griffinlim_last_timings ms[0] is the
+ * stage alone.  (The hook stages utterance u at a device address with the 16-byte phase of audios[u] + offset[u], so a caller
+ * reaches the 128-bit and the scalar load route of the kernel from the host.) */
+xdtts_status xdtts_griffinlim_join(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt,
+                                   const size_t *gaps, int32_t rate, const xdtts_stream_opts *o,
+                                   void *out, size_t cap_bytes, size_t *offsets, size_t *total);
 
 void xdtts_griffinlim_free(xdtts_griffinlim *g);
 
@@ -689,6 +751,22 @@ xdtts_status xdtts_synthesize_sequence_prosody(xdtts_tacotron2 *h, xdtts_griffin
                                                int32_t n_utt, const xdtts_infer_opts *opts,
                                                const xdtts_prosody *p /* [n_utt] */, float **mels, size_t *n_frames,
                                                float **audios, size_t *n_samples);
+/* XdTts::generate_audio (src/lib.rs:60-108): a text cut at its <break>s, the pieces synthesised one after the other, ONE
+ * stream out (the definition above xdtts_stream_opts).  The utterances run exactly as xdtts_synthesize_sequence (p == NULL) or
+ * xdtts_synthesize_sequence_prosody runs them, but each utterance's delivered audio STAYS IN HBM: where the sequence copies
+ * it to the host, the document copies it device-to-device to its place in a staging buffer.  At level 0 each utterance's
+ * level stage runs as in the sequence, at level 1 it is skipped.  Behind the last vocoder: the level-1 measurement if asked
+ * for, ONE k_stream_join launch, ONE copy of total * sample_bytes bytes to the host.  gaps [n_utt + 1] (NULL: none) and
+ * o->fade are in samples of the handle's output rate, which applies as in every delivering entry.  *stream is released with
+ * xdtts_free; mels (may be NULL) / n_frames as in the sequence; offsets [n_utt] may be NULL.  On an error nothing is
+ * returned. */
+xdtts_status xdtts_synthesize_document(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids,
+                                       const size_t *n_ids, const size_t *const *splits, const size_t *n_splits,
+                                       int32_t n_utt, const xdtts_infer_opts *opts,
+                                       const xdtts_prosody *p /* [n_utt] or NULL */,
+                                       const size_t *gaps, const xdtts_stream_opts *o,
+                                       float **mels, size_t *n_frames,
+                                       void **stream, size_t *offsets, size_t *total);
 
 /* ---- host-side front of Tacotron2::infer (stays on the CPU side of the FFI) ---------------- */
 /* generate_id_list -- src/tacotron2/mod.rs:90-122: 148 symbols; token text of an id. */

@@ -582,6 +582,70 @@ inline std::vector<std::pair<Array2, std::vector<float>>> infer_sequence(const T
   return out;
 }
 
+// XdTts::generate_audio (src/lib.rs:60-108): a text cut at its <break>s -- `pieces` one after the other, breaks[u] seconds of
+// silence BEHIND piece u (src/lib.rs:162-176; breaks may be shorter than pieces: the rest is 0) -- as ONE stream in the sample
+// format of `stream` (default PCM16, the reference's i16 writer), joined and encoded on the device (xdtts_synthesize_document).
+// The bytes of the stream: int16 little endian for format 1, one byte a sample for G.711, float for format 0.
+struct Document {
+  std::vector<unsigned char> bytes;
+  std::vector<size_t> offsets;  // of each piece, in samples
+  size_t total = 0;             // samples
+  xdtts_stream_opts opts;
+  std::vector<Array2> mels;
+};
+inline Document generate_audio(const Tacotron2 &model, const GriffinLim &vocoder, const std::vector<std::vector<Unit>> &pieces,
+                               const std::vector<double> &breaks = {}, const xdtts_stream_opts *stream = nullptr,
+                               const xdtts_infer_opts *opts = nullptr, const std::vector<xdtts_prosody> *prosody = nullptr) {
+  if (prosody && prosody->size() != pieces.size()) throw std::runtime_error("xdtts: one prosody per piece");
+  xdtts_infer_opts o;
+  xdtts_infer_opts_default(&o);
+  if (opts) o = *opts;
+  Document doc;
+  xdtts_stream_opts_default(&doc.opts);
+  if (stream) doc.opts = *stream;
+  const size_t n_utt = pieces.size();
+  std::vector<std::vector<int64_t>> ids(n_utt);
+  std::vector<std::vector<size_t>> splits(n_utt);
+  std::vector<const int64_t *> ids_p(n_utt);
+  std::vector<const size_t *> sp_p(n_utt);
+  std::vector<size_t> n_ids(n_utt), n_sp(n_utt), gaps(n_utt + 1, 0);
+  int32_t rate = XDTTS_SAMPLE_RATE;
+  check(xdtts_griffinlim_get_output_rate(vocoder.raw(), &rate));
+  for (size_t u = 0; u < n_utt; ++u) {
+    for (const Unit &x : pieces[u]) {
+      const int64_t id = xdtts_unit_id(x.token.c_str(), x.is_character ? 1 : 0);
+      if (id >= 0) ids[u].push_back(id);  // units with no id are dropped, mod.rs:403-406
+    }
+    splits[u].resize(ids[u].size() + 2);
+    size_t n = 0;
+    check(xdtts_find_splits(ids[u].data(), ids[u].size(), (size_t)o.max_chunk, splits[u].data(), splits[u].size(), &n));
+    splits[u].resize(n);
+    ids_p[u] = ids[u].data();
+    n_ids[u] = ids[u].size();
+    sp_p[u] = splits[u].data();
+    n_sp[u] = n;
+    if (u < breaks.size()) gaps[u + 1] = xdtts_silence_samples(breaks[u], (uint32_t)rate);
+  }
+  std::vector<float *> mels(n_utt, nullptr);
+  std::vector<size_t> nf(n_utt, 0);
+  doc.offsets.assign(n_utt, 0);
+  void *out = nullptr;
+  check(xdtts_synthesize_document(model.raw(), vocoder.raw(), ids_p.data(), n_ids.data(), sp_p.data(), n_sp.data(), (int32_t)n_utt, &o,
+                                  prosody ? prosody->data() : nullptr, gaps.data(), &doc.opts, mels.data(), nf.data(), &out,
+                                  doc.offsets.data(), &doc.total));
+  const unsigned char *b = static_cast<const unsigned char *>(out);
+  doc.bytes.assign(b, b + doc.total * xdtts_stream_sample_bytes(doc.opts.format));
+  xdtts_free(out);
+  doc.mels.resize(n_utt);
+  for (size_t i = 0; i < n_utt; ++i) {
+    doc.mels[i].rows = 80;
+    doc.mels[i].cols = nf[i];
+    doc.mels[i].data.assign(mels[i], mels[i] + 80 * nf[i]);
+    xdtts_free(mels[i]);
+  }
+  return doc;
+}
+
 // XdTts::infer's output stage (src/lib.rs:145-157): RTF, `(sample * i16::MAX as f32) as i16`,
 // mono 22050 Hz 16-bit WAV (WAV_SPEC, src/lib.rs:25-30).
 inline std::vector<int16_t> to_i16(const std::vector<float> &audio) {

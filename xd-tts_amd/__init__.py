@@ -101,6 +101,25 @@ class Loudness(C.Structure):
         return (self.mean_square, self.true_peak, self.sample_peak, self.gain, self.blocks, self.gated_blocks)
 
 
+STREAM_F32, STREAM_PCM16, STREAM_ULAW, STREAM_ALAW = 0, 1, 2, 3
+_STREAM_DTYPE = {STREAM_F32: np.float32, STREAM_PCM16: np.dtype("<i2"), STREAM_ULAW: np.uint8, STREAM_ALAW: np.uint8}
+
+
+class StreamOpts(C.Structure):
+    """xdtts_stream_opts: how a joined sequence leaves the device.  format 0 fp32, 1 PCM16, 2 G.711 mu-law, 3 A-law; dither 1 =
+    TPDF (PCM16 only) seeded by dither_seed and the absolute stream position; level 1 = programme (ONE BS.1770 gain for the
+    whole stream, needs set_loudness); fade = samples per utterance edge at the delivered rate (0 .. 4800)."""
+
+    _fields_ = [("format", C.c_int32), ("dither", C.c_int32), ("dither_seed", C.c_uint32), ("level", C.c_int32), ("fade", C.c_int32)]
+
+    def __init__(self, format=None, dither=None, dither_seed=None, level=None, fade=None):
+        super().__init__()
+        lib.xdtts_stream_opts_default(C.byref(self))
+        for k, v in (("format", format), ("dither", dither), ("dither_seed", dither_seed), ("level", level), ("fade", fade)):
+            if v is not None:
+                setattr(self, k, int(v))
+
+
 class InferOpts(C.Structure):
     _fields_ = [
         ("gate_threshold", C.c_float),
@@ -196,6 +215,14 @@ SYMBOLS = {
     "xdtts_griffinlim_last_loudness": (_I32, [_VP, _VP, _SZ, C.POINTER(_SZ)]),
     "xdtts_griffinlim_loudness": (_I32, [_VP, _VP, _SZ, _I32, _VP]),
     "xdtts_griffinlim_loudness_batch": (_I32, [_VP, _VP, _VP, _I32, _I32, _VP]),
+    "xdtts_stream_opts_default": (None, [C.POINTER(StreamOpts)]),
+    "xdtts_stream_sample_bytes": (_SZ, [_I32]),
+    "xdtts_stream_plan": (_I32, [_VP, _I32, _VP, _VP, C.POINTER(_SZ)]),
+    "xdtts_stream_fade_table": (_I32, [_I32, _VP]),
+    "xdtts_stream_encode_sample": (_I32, [_F, _I32, _I32, _U32, _SZ, _VP]),
+    "xdtts_griffinlim_join": (_I32, [_VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(StreamOpts), _VP, _SZ, _VP, C.POINTER(_SZ)]),
+    "xdtts_synthesize_document": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, C.POINTER(StreamOpts), _VP, _VP,
+                                         C.POINTER(_VP), _VP, C.POINTER(_SZ)]),
     "xdtts_loudness_plan": (_I32, [_I32, _SZ, C.POINTER(_I32), C.POINTER(_SZ)]),
     "xdtts_loudness_filter": (_I32, [_I32, _VP]),
     "xdtts_true_peak_filter": (_I32, [_VP]),
@@ -957,6 +984,27 @@ class GriffinLim:
             _check(lib.xdtts_griffinlim_loudness_batch(self._h, ip, ns, n, int(rate), out))
         return [out[i] for i in range(n)]
 
+    # -- stream: a sequence joined with its gaps, faded, levelled and encoded on the device ----
+    def join(self, audios, gaps=None, rate=SAMPLE_RATE, opts=None, guard=0):
+        """xdtts_griffinlim_join: the stage alone on the caller's audios (fp32, each read where it lies: a view's address decides
+        the kernel's load route).  gaps = n + 1 lengths in samples, or None.  Returns (stream, offsets): stream is float32 /
+        int16 / uint8 by opts.format.  guard= extra bytes behind the stream, filled with 0xA5 and returned with it (the tests'
+        guard band)."""
+        xs = [np.ascontiguousarray(a, dtype=np.float32).ravel() for a in audios]
+        n = len(xs)
+        o = opts if opts is not None else StreamOpts()
+        ns = (C.c_size_t * max(n, 1))(*[x.size for x in xs])
+        ip = (C.c_void_p * max(n, 1))(*[(x.ctypes.data if x.size else None) for x in xs])
+        gp = None if gaps is None else (C.c_size_t * (n + 1))(*[int(v) for v in gaps])
+        offs, tot = (C.c_size_t * max(n, 1))(), C.c_size_t()
+        _check(lib.xdtts_stream_plan(ns, n, gp, offs, C.byref(tot)))
+        sb = int(lib.xdtts_stream_sample_bytes(o.format))
+        raw = np.full(tot.value * sb + int(guard), 0xA5, dtype=np.uint8)
+        _check(lib.xdtts_griffinlim_join(self._h, ip, ns, n, gp, int(rate), C.byref(o), _ptr(raw), tot.value * sb, offs, C.byref(tot)))
+        out = raw[: tot.value * sb].view(_STREAM_DTYPE[o.format])
+        offsets = [int(offs[u]) for u in range(n)]
+        return (out, offsets, raw[tot.value * sb:]) if guard else (out, offsets)
+
     # -- analysis: audio -> magnitude -> mel under the handle's conventions, spectral convergence ----
     def analysis_frames(self, n_samples):
         return int(lib.xdtts_griffinlim_analysis_frames(self._h, int(n_samples)))
@@ -1061,6 +1109,60 @@ def true_peak_filter():
     t = np.zeros((3, 24), dtype=np.float32)
     _check(lib.xdtts_true_peak_filter(_ptr(t)))
     return t
+
+
+def stream_sample_bytes(format):
+    return int(lib.xdtts_stream_sample_bytes(int(format)))
+
+
+def stream_plan(n, gaps=None):
+    """xdtts_stream_plan (host arithmetic): (offsets, total) of utterances of n[u] samples joined with gaps[0 .. len(n)]."""
+    U = len(n)
+    ns = (C.c_size_t * max(U, 1))(*[int(v) for v in n])
+    gp = None if gaps is None else (C.c_size_t * (U + 1))(*[int(v) for v in gaps])
+    offs, tot = (C.c_size_t * max(U, 1))(), C.c_size_t()
+    _check(lib.xdtts_stream_plan(ns, U, gp, offs, C.byref(tot)))
+    return [int(offs[u]) for u in range(U)], int(tot.value)
+
+
+def stream_fade_table(fade):
+    """xdtts_stream_fade_table: T[j] = 0.5 - 0.5 cos(pi (j + 0.5) / fade) as the library's own fp32 values."""
+    w = np.zeros(int(fade), dtype=np.float32)
+    _check(lib.xdtts_stream_fade_table(int(fade), _ptr(w) if w.size else None))
+    return w
+
+
+def stream_encode_sample(x, format, dither=0, seed=0, k=0):
+    """xdtts_stream_encode_sample: one sample behind fade and gain at stream position k -> its fp32 / int16 / uint8 value."""
+    out = np.zeros(4, dtype=np.uint8)
+    _check(lib.xdtts_stream_encode_sample(float(x), int(format), int(dither), int(seed), int(k), _ptr(out)))
+    return out[: stream_sample_bytes(format)].view(_STREAM_DTYPE[int(format)])[0]
+
+
+def synthesize_document(tacotron2, vocoder, ids_list, gaps=None, stream_opts=None, splits_list=None, opts=None, want_mels=True, prosody=None):
+    """XdTts::generate_audio (src/lib.rs:60-108): the utterances run as synthesize_sequence runs them, their audio stays on the
+    device and leaves as ONE stream -- joined with the gaps (n + 1 lengths in samples at the vocoder's output rate), faded,
+    levelled and encoded as stream_opts says (xdtts_synthesize_document).  Returns (mels or None, stream, offsets)."""
+    n = len(ids_list)
+    idv = [np.ascontiguousarray(x, dtype=np.int64) for x in ids_list]
+    spv = [None if (splits_list is None or splits_list[u] is None) else np.ascontiguousarray(splits_list[u], dtype=np.uintp) for u in range(n)]
+    ids_p = (C.c_void_p * n)(*[x.ctypes.data for x in idv])
+    n_ids = (C.c_size_t * n)(*[x.size for x in idv])
+    sp_p = (C.c_void_p * n)(*[(None if s is None else s.ctypes.data) for s in spv])
+    n_sp = (C.c_size_t * n)(*[(0 if s is None else s.size) for s in spv])
+    o = stream_opts if stream_opts is not None else StreamOpts()
+    gp = None if gaps is None else (C.c_size_t * (n + 1))(*[int(v) for v in gaps])
+    mels = (_PF * n)() if want_mels else None
+    nf, offs = (C.c_size_t * n)(), (C.c_size_t * n)()
+    stream, tot = C.c_void_p(), C.c_size_t()
+    _check(lib.xdtts_synthesize_document(tacotron2._h, vocoder._h, ids_p, n_ids, sp_p, n_sp, n, C.byref(opts) if opts else None,
+                                         None if prosody is None else _prosody_array(prosody, n), gp, C.byref(o), mels, nf,
+                                         C.byref(stream), offs, C.byref(tot)))
+    nbytes = tot.value * stream_sample_bytes(o.format)
+    words = _take(C.cast(stream, _PF), (nbytes + 3) // 4, ((nbytes + 3) // 4,))  # (the pool's buffer, released with the last view)
+    out = words.view(np.uint8)[:nbytes].view(_STREAM_DTYPE[o.format])
+    out_m = [_take(mels[u], N_MEL * nf[u], (N_MEL, nf[u])) for u in range(n)] if want_mels else None
+    return out_m, out, [int(offs[u]) for u in range(n)]
 
 
 def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, contour=None):

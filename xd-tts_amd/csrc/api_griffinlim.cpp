@@ -787,6 +787,96 @@ xdtts_status xdtts_griffinlim_loudness(xdtts_griffinlim *g, const float *audio, 
   return xdtts_griffinlim_loudness_batch(g, &audio, &n, 1, rate, out);
 }
 
+// ---- stream: the sequence joined with its gaps, faded, levelled, encoded (stream_plan.h, stream.hip) ----------------------------
+
+static_assert(sizeof(xdtts_stream_opts) == sizeof(StreamOpts) && offsetof(xdtts_stream_opts, fade) == offsetof(StreamOpts, fade),
+              "xdtts_stream_opts and StreamOpts share one layout");
+
+void xdtts_stream_opts_default(xdtts_stream_opts *o) {
+  if (!o) return;
+  const StreamOpts d = stream_opts_default();
+  std::memcpy(o, &d, sizeof d);
+}
+
+size_t xdtts_stream_sample_bytes(int32_t format) { return (size_t)stream_sample_bytes(format); }
+
+xdtts_status xdtts_stream_plan(const size_t *n, int32_t n_utt, const size_t *gaps, size_t *offsets, size_t *total) {
+  return guard([&] {
+    const std::string msg = stream_plan(n, n_utt, gaps, offsets, total);
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  });
+}
+
+xdtts_status xdtts_stream_fade_table(int32_t fade, float *w) {
+  return guard([&] {
+    if (fade < 0 || fade > STREAM_FADE_MAX) fail(XDTTS_ERR_BAD_ARG, "stream: fade %d is not in [0, %d]", fade, STREAM_FADE_MAX);
+    if (fade > 0 && !w) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    stream_fade_table(fade, w);
+  });
+}
+
+xdtts_status xdtts_stream_encode_sample(float x, int32_t format, int32_t dither, uint32_t seed, size_t k, void *out) {
+  return guard([&] {
+    const std::string msg = stream_opts_check(StreamOpts{format, dither, seed, 0, 0});
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+    if (k >= STREAM_TOTAL_MAX) fail(XDTTS_ERR_BAD_ARG, "stream: position %zu is not below 2^28", k);
+    if (!out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    const uint32_t b = stream_encode(x, format, dither, seed, (uint32_t)k);
+    std::memcpy(out, &b, (size_t)stream_sample_bytes(format));  // (little endian: the low bytes)
+  });
+}
+
+xdtts_status xdtts_griffinlim_join(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt, const size_t *gaps,
+                                   int32_t rate, const xdtts_stream_opts *o, void *out, size_t cap_bytes, size_t *offsets, size_t *total) {
+  return guard([&] {
+    if (total) *total = 0;
+    const StreamOpts so = stream_opts_checked(o);
+    if (so.level == 1) loudness_rate_checked(rate);
+    std::vector<size_t> off((size_t)std::max(0, std::min(n_utt, STREAM_UTT_MAX)));
+    size_t tot = 0;
+    const std::string msg = stream_plan(n, n_utt, gaps, off.data(), &tot);
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+    if (!audios || !out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    for (int u = 0; u < n_utt; ++u)
+      if (n[u] && !audios[u]) fail(XDTTS_ERR_BAD_ARG, "audios[%d] is null with n[%d] = %zu", u, u, n[u]);
+    const size_t bytes = tot * (size_t)stream_sample_bytes(so.format);
+    if (cap_bytes < bytes) fail(XDTTS_ERR_BAD_ARG, "cap_bytes %zu: the stream has %zu samples = %zu bytes", cap_bytes, tot, bytes);
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (so.level == 1 && !g->loudness_on()) fail(XDTTS_ERR_BAD_ARG, "stream: level 1 (programme) needs a loudness target on the handle");
+    HIP_CHECK(hipSetDevice(g->device));
+    hipStream_t st = g->stream;
+    HIP_CHECK(hipStreamSynchronize(st));
+    g->last_loud.clear();
+    // utterance u at a multiple of four floats plus the 16-byte phase of (its host address + its offset): an interior pack of
+    // the kernel then reads at the phase of the caller's buffer
+    g->st_tab_host.clear();
+    size_t at = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      const size_t phase = ((reinterpret_cast<uintptr_t>(audios[u]) / sizeof(float)) + off[(size_t)u]) & 3u;
+      const size_t src0 = ((at + 3) & ~(size_t)3) + phase;
+      g->st_tab_host.push_back(StreamUtt{(long long)src0, (uint32_t)off[(size_t)u], (int32_t)n[u]});
+      at = src0 + n[u];
+    }
+    g->st_used = 0;
+    g->stream_reserve(std::max<size_t>(at, 1));
+    for (int u = 0; u < n_utt; ++u)
+      if (n[u]) HIP_CHECK(hipMemcpyAsync(g->st_src.p + g->st_tab_host[(size_t)u].src0, audios[u], n[u] * sizeof(float), hipMemcpyHostToDevice, st));
+    g->stream_join(tot, so, rate, g->ev.e[0]);
+    HIP_CHECK(hipEventRecord(g->ev.e[1], st));
+    HIP_CHECK(hipEventRecord(g->ev.e[2], st));
+    HIP_CHECK(hipMemcpyAsync(out, g->st_out.p, bytes, hipMemcpyDeviceToHost, st));
+    g->finish_timings();  // (drains the stream: the inputs, the tables, the stream and the struct)
+    if (so.level == 1) {
+      xdtts_loudness l;
+      std::memcpy(&l, g->loud_host, sizeof l);
+      g->last_loud.push_back(l);
+    }
+    for (int u = 0; offsets && u < n_utt; ++u) offsets[u] = off[(size_t)u];
+    if (total) *total = tot;
+  });
+}
+
 // ---- analysis: the inverse direction of GriffinLim::infer's conventions (analysis.hip).  No co-resident grid: no chip lock. ----
 
 // What one call takes: the row tiles of the mel GEMM and of the boundary transposes go into a grid dimension of at most 65535

@@ -69,9 +69,60 @@ static xdtts_status check_prosody_array(const xdtts_prosody *p, int32_t n_utt, f
 // collects u's audio while u + 1 decodes.  Same bits as xdtts_synthesize_ids called once per utterance.
 // (pros == null: xdtts_synthesize_sequence; else one prosody per utterance, fields checked by the caller: utterance u's vocoder
 // half runs the single-utterance stage, the bits of xdtts_synthesize_ids_prosody)
+// (doc: xdtts_synthesize_document -- the same run, but each utterance's delivered audio stays in HBM: doc->place() names its
+// place in the handle's staging buffer in front of the vocoder's enqueue, audios[u] stays null, and doc->finish() runs the
+// stream stage behind the last vocoder, under the locks of the run.)
+struct DocRun {
+  xdtts_griffinlim *g;
+  StreamOpts o;
+  const size_t *gaps;  // [n_utt + 1] or null
+  int n_utt;
+  size_t at = 0, src_at = 0;  // the stream position behind what has been placed; the floats of the staging buffer in use
+  std::vector<size_t> off, n;
+  PinnedGuard out;
+  size_t total = 0;
+  size_t gap(int u) const { return gaps ? gaps[u] : 0; }
+  // utterance u (the next one) delivers N samples: its record, room in the staging buffer, the sink.  g->stream is idle.
+  void place(int u, size_t N) {
+    if (u == 0) {
+      g->st_tab_host.clear();
+      g->st_used = 0;
+      at = gap(0);
+    }
+    if (at + N >= STREAM_TOTAL_MAX || at + N + gap(u + 1) >= STREAM_TOTAL_MAX)
+      fail(XDTTS_ERR_BAD_ARG, "stream: utterance %d (%zu samples) and gaps[%d] take the stream to 2^28 samples or more", u, N, u + 1);
+    const size_t src0 = ((src_at + 3) & ~(size_t)3) + (at & 3u);  // (an interior pack of the kernel then reads aligned 128 bits)
+    g->stream_reserve(src0 + N + 4);
+    g->st_tab_host.push_back(StreamUtt{(long long)src0, (uint32_t)at, (int32_t)N});
+    off.push_back(at);
+    n.push_back(N);
+    src_at = src0 + N;
+    g->st_used = src_at;
+    at += N + gap(u + 1);
+    g->sink.dst = g->st_src.p + src0;
+    g->sink.unlevelled = o.level == 1;
+  }
+  // behind the last collect: the level-1 measurement if asked for, ONE k_stream_join launch, ONE copy to the host
+  void finish() {
+    g->sink = xdtts_griffinlim::StreamSink();
+    total = at;
+    if (total == 0) fail(XDTTS_ERR_BAD_ARG, "stream: total is 0 samples");
+    const size_t bytes = total * (size_t)stream_sample_bytes(o.format);
+    g->stream_join(total, o, g->out_rate);
+    out = PinnedGuard((bytes + 3) / 4);
+    HIP_CHECK(hipMemcpyAsync(out.p, g->st_out.p, bytes, hipMemcpyDeviceToHost, g->stream));
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+    if (o.level == 1) {
+      xdtts_loudness l;
+      std::memcpy(&l, g->loud_host, sizeof l);
+      g->last_loud.push_back(l);
+    }
+  }
+};
 static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
                                         const size_t *const *splits, const size_t *n_splits, int32_t n_utt, const xdtts_infer_opts *opts,
-                                        const xdtts_prosody *pros, float **mels, size_t *n_frames, float **audios, size_t *n_samples) {
+                                        const xdtts_prosody *pros, float **mels, size_t *n_frames, float **audios, size_t *n_samples,
+                                        DocRun *doc = nullptr) {
   return guard([&] {
     if (!h || !g || !ids || !n_ids || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "null argument / no utterance");
     if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
@@ -88,11 +139,15 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
     const xdtts_infer_opts o = resolve_opts(opts);
     struct Hook {  // (the hook never outlives this call, whatever throws)
       xdtts_tacotron2 *h;
+      xdtts_griffinlim *g;
       ~Hook() {
         h->before_decoder = nullptr;
         h->while_decoding = nullptr;
+        g->sink = xdtts_griffinlim::StreamSink();
       }
-    } unhook{h};
+    } unhook{h, g};
+    if (doc && doc->o.level == 1 && !g->loudness_on())
+      fail(XDTTS_ERR_BAD_ARG, "stream: level 1 (programme) needs a loudness target on the handle");
     std::vector<PinnedGuard> mel_host(n_utt), audio_host(n_utt);
     std::vector<int> total(n_utt, 0);
     std::vector<float *> audio_out(n_utt, nullptr);
@@ -135,7 +190,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
           h->while_decoding = [&, u, predicted] {
             if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * predicted);
             const size_t Fp = pros ? prosody_frames((size_t)predicted, pros[u].rate) : (size_t)predicted;  // the vocoder's frames, not the mel's
-            if (!audio_host[u].p) audio_host[u] = PinnedGuard(g->delivered((size_t)g->hop * (Fp - 1)));  // (at the handle's output rate)
+            if (!doc && !audio_host[u].p) audio_host[u] = PinnedGuard(g->delivered((size_t)g->hop * (Fp - 1)));  // (at the handle's output rate)
           };
         for (int i = 0; i < 4; ++i) std::swap(h->ev.e[i], per[u].e[i]);  // (per[u] now holds what the handle had: utterance u - 1's set, or its own)
         h->infer_batch_device(padded.data(), lens.data(), (int)lens.size(), o.max_chunk, o, nullptr, &total[u]);
@@ -153,10 +208,12 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
         if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * total[u]);
         HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));  // the vocoder reads the mel behind the post-net
         HIP_CHECK(hipMemcpyAsync(mel_host[u].p, h->mel_dev.p, (size_t)N_MEL * total[u] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (doc) doc->place(u, g->delivered((size_t)g->hop * ((pros ? prosody_frames((size_t)total[u], pros[u].rate) : (size_t)total[u]) - 1)));
         gl_enqueue_from_device_mel(g, h->mel_dev.p, total[u], audio_host[u], pros ? &pros[u] : nullptr);
       }
       gl_collect(g, total[n_utt - 1], audio_host[n_utt - 1], &audio_out[n_utt - 1], &n_samples[n_utt - 1], pros ? &pros[n_utt - 1] : nullptr);
       add_gl();
+      if (doc) doc->finish();
       h->finish_timings();  // (stream sync: every mel has landed; last_ms = the last utterance's phases)
       float hsum[4] = {h->last_ms[0], h->last_ms[1], h->last_ms[2], h->last_ms[3]};
       for (int u = 1; u < n_utt; ++u) {  // utterance u - 1's events sit in per[u]
@@ -306,6 +363,46 @@ xdtts_status xdtts_synthesize_sequence_prosody(xdtts_tacotron2 *h, xdtts_griffin
   const xdtts_status st = check_prosody_array(p, n_utt, mels, n_frames, audios, n_samples);
   if (st != XDTTS_OK) return st;
   return synthesize_sequence(h, g, ids, n_ids, splits, n_splits, n_utt, opts, p, mels, n_frames, audios, n_samples);
+}
+
+// XdTts::generate_audio (src/lib.rs:60-108): the sequence, its audio kept in HBM, joined and encoded on the device
+xdtts_status xdtts_synthesize_document(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
+                                       const size_t *const *splits, const size_t *n_splits, int32_t n_utt, const xdtts_infer_opts *opts,
+                                       const xdtts_prosody *p, const size_t *gaps, const xdtts_stream_opts *o, float **mels, size_t *n_frames,
+                                       void **stream, size_t *offsets, size_t *total) {
+  DocRun doc{};
+  std::vector<float *> audios;
+  std::vector<size_t> n_samples;
+  xdtts_status st = guard([&] {  // the options, the count and the gaps: before a handle is looked at
+    if (stream) *stream = nullptr;
+    if (total) *total = 0;
+    doc.o = stream_opts_checked(o);
+    if (n_utt < 1 || n_utt > STREAM_UTT_MAX) fail(XDTTS_ERR_BAD_ARG, "stream: n_utt %d is not in [1, %d]", n_utt, STREAM_UTT_MAX);
+    if (!stream || !total || !n_frames) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    size_t sum = 0;
+    for (int u = 0; gaps && u <= n_utt; ++u) {
+      if (gaps[u] >= STREAM_TOTAL_MAX || sum + gaps[u] >= STREAM_TOTAL_MAX)
+        fail(XDTTS_ERR_BAD_ARG, "stream: gaps[%d] = %zu takes the stream to 2^28 samples or more", u, gaps[u]);
+      sum += gaps[u];
+    }
+    if (p) prosody_check_array(p, n_utt);
+    for (int u = 0; u < n_utt; ++u) {
+      if (mels) mels[u] = nullptr;
+      n_frames[u] = 0;
+    }
+    audios.assign((size_t)n_utt, nullptr);
+    n_samples.assign((size_t)n_utt, 0);
+  });
+  if (st != XDTTS_OK) return st;
+  doc.g = g;
+  doc.gaps = gaps;
+  doc.n_utt = n_utt;
+  st = synthesize_sequence(h, g, ids, n_ids, splits, n_splits, n_utt, opts, p, mels, n_frames, audios.data(), n_samples.data(), &doc);
+  if (st != XDTTS_OK) return st;
+  for (int u = 0; offsets && u < n_utt; ++u) offsets[u] = doc.off[(size_t)u];
+  *total = doc.total;
+  *stream = doc.out.release();
+  return XDTTS_OK;
 }
 
 xdtts_status xdtts_synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,

@@ -14,6 +14,7 @@
 
 #include "../../include/xdtts.h"
 #include "env.h"
+#include "rng.h"
 
 namespace xdtts {
 
@@ -122,21 +123,7 @@ struct CoopRefused {};
     HIP_CHECK(ce_);                                           \
   } while (0)
 
-// ---- counter-based RNG (specification shared with oracle/, implemented independently) ----
-__host__ __device__ inline uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352dU;
-  x ^= x >> 15;
-  x *= 0x846ca68bU;
-  x ^= x >> 16;
-  return x;
-}
-__host__ __device__ inline uint32_t rng_u32(uint32_t seed, uint32_t stream, uint32_t idx) {
-  return mix32(mix32(mix32(seed ^ 0x9E3779B9U) + stream) + idx);
-}
-__host__ __device__ inline float rng_uniform(uint32_t seed, uint32_t stream, uint32_t idx) {
-  return (float)(rng_u32(seed, stream, idx) >> 8) * (1.0f / 16777216.0f);
-}
+// ---- counter-based RNG: rng.h (mix32, rng_u32, rng_uniform) ----
 
 // ---- device memory helper -------------------------------------------------------------------
 template <class T>

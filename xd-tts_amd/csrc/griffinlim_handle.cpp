@@ -280,6 +280,58 @@ void xdtts_griffinlim::loudness_fetch(int r0, int count, hipStream_t s) {
   HIP_CHECK(hipMemcpyAsync(loud_host + r0, loud_res.p + r0, (size_t)count * sizeof(LoudResult), hipMemcpyDeviceToHost, s));
 }
 
+// The stream stage (stream.hip).
+void xdtts_griffinlim::stream_reserve(size_t floats) {
+  if (floats <= st_src.n) return;
+  DevBuf<float> grown;
+  grown.alloc(std::max(floats, 2 * st_src.n));
+  if (st_used) HIP_CHECK(hipMemcpyAsync(grown.p, st_src.p, st_used * sizeof(float), hipMemcpyDeviceToDevice, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  std::swap(grown.p, st_src.p);
+  std::swap(grown.n, st_src.n);
+}
+
+void xdtts_griffinlim::stream_join(size_t total, const StreamOpts &o, int rate, hipEvent_t begin) {
+  const int n_utt = (int)st_tab_host.size();
+  st_tab.upload(st_tab_host.data(), st_tab_host.size(), stream);
+  if (o.fade > 0) {
+    st_fade_host.resize((size_t)o.fade);
+    stream_fade_table(o.fade, st_fade_host.data());
+    st_fade.upload(st_fade_host.data(), st_fade_host.size(), stream);
+  }
+  st_out.alloc(total * (size_t)stream_sample_bytes(o.format));
+  if (o.level == 1) {
+    loudness_prepare(rate);
+    loudness_bufs(loudness_groups(total), 1);
+    st_f32.alloc(total);
+  }
+  if (begin) HIP_CHECK(hipEventRecord(begin, stream));
+  StreamJob job{};
+  job.src = st_src.p;
+  job.tab = st_tab.p;
+  job.fade_tab = o.fade > 0 ? st_fade.p : nullptr;
+  job.n_utt = n_utt;
+  job.total = (uint32_t)total;
+  job.format = o.format;
+  job.dither = o.dither;
+  job.seed = o.dither_seed;
+  job.fade = o.fade;
+  if (o.level == 1) {
+    const int groups = (int)loudness_groups(total);
+    const LoudBufs b = loudness_bufs((size_t)groups, 1);  // (sized above: nothing grows here)
+    StreamJob form = job;  // the stream as level 0 / format 0 delivers it: what the programme measurement is defined on
+    form.format = STREAM_F32;
+    form.dither = 0;
+    launch_stream_join(form, st_f32.p, stream);
+    const LoudUtt one{0, (int)total, 0, 0, 0};
+    launch_loudness_measure(st_f32.p, nullptr, 1, 0, groups, one, loud_table.p, b, loud_res.p, rate, loudness_target_lin(loud_target),
+                            loudness_ceiling_lin(loud_ceiling), stream);
+    job.gain = &loud_res.p->gain;
+  }
+  launch_stream_join(job, st_out.p, stream);
+  if (o.level == 1) loudness_fetch(0, 1, stream);
+}
+
 void xdtts_griffinlim::upload_rows(const float *const *S_host, const Rows &rows) {
   for (int u = 0; u < rows.n(); ++u) {
     const size_t r0 = (size_t)rows.row0[(size_t)u] * nb;
@@ -553,12 +605,17 @@ static void enqueue_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
     N = g->resample_one(g->audio.p, N, g->audio_rs.p, g->out_rate);
     out = g->audio_rs.p;
   }
-  const bool loud = deliver && g->loudness_on() && N > 0;  // the loudness rule takes the output normalisation's place
+  const bool level = deliver && !(g->sink.dst && g->sink.unlevelled);  // (a document at programme level takes the utterance unlevelled)
+  const bool loud = level && g->loudness_on() && N > 0;  // the loudness rule takes the output normalisation's place
   if (loud) g->loudness_one(out, N, g->out_rate, true);
-  else if (deliver) launch_gl_output_normalise(out, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
+  else if (level) launch_gl_output_normalise(out, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
   HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
-  if (!host.p) host = PinnedGuard(N);
-  HIP_CHECK(hipMemcpyAsync(host.p, out, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+  if (deliver && g->sink.dst) {  // a document run: the utterance stays in HBM, at its place in the staging buffer
+    HIP_CHECK(hipMemcpyAsync(g->sink.dst, out, N * sizeof(float), hipMemcpyDeviceToDevice, g->stream));
+  } else {
+    if (!host.p) host = PinnedGuard(N);
+    HIP_CHECK(hipMemcpyAsync(host.p, out, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+  }
   if (loud) g->loudness_fetch(0, 1, g->stream);  // the measurement and the gain travel back behind the audio
   g->fetch_error_word();
 }
@@ -575,7 +632,7 @@ static void collect_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
     if (g->persistent_failed()) fail(XDTTS_ERR_HIP, "Griffin-Lim: the fallback engine reported an exchange failure");
   }
   const size_t N = (size_t)g->hop * (size_t)(b.F - 1);
-  if (deliver && g->loudness_on() && N > 0) {
+  if (deliver && g->loudness_on() && N > 0 && !(g->sink.dst && g->sink.unlevelled)) {
     xdtts_loudness l;
     static_assert(sizeof l == sizeof(LoudResult), "LoudResult is xdtts_loudness");
     std::memcpy(&l, g->loud_host, sizeof l);

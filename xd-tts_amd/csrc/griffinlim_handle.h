@@ -31,6 +31,14 @@ struct ProsodyArg {
   bool identity(int u) const { return contour ? contour[u].identity : (!uniform || prosody_is_identity(uniform[u])); }
   int frames(int u, int F) const { return contour ? contour[u].Fout : (uniform ? (int)prosody_frames((size_t)F, uniform[u].rate) : F); }  // F'
 };
+// The options of a stream request (stream_plan.h, which knows no status codes), before a handle is looked at; null = the default
+inline StreamOpts stream_opts_checked(const xdtts_stream_opts *o) {
+  StreamOpts s = stream_opts_default();
+  if (o) std::memcpy(&s, o, sizeof s);
+  const std::string msg = stream_opts_check(s);
+  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  return s;
+}
 // Rows::add (gl_plan.h, which knows no status codes) inside a request: past the cap it fails with XDTTS_ERR_BAD_ARG and the text
 inline void rows_add(Rows &r, size_t rows, size_t cap, const char *too_large) {
   try {
@@ -175,6 +183,30 @@ struct xdtts_griffinlim {
   void loudness_rows(float *x, int r0, int count, int rate, bool scale);
   // loud_res[r0 .. r0 + count) -> loud_host, on `s`
   void loudness_fetch(int r0, int count, hipStream_t s);
+
+  // stream (stream.hip): the utterances of a sequence joined with their gaps, faded, levelled and encoded -- the stage behind
+  // everything above (xdtts_griffinlim_join, xdtts_synthesize_document).
+  DevBuf<float> st_src, st_f32, st_fade;      // the utterances' fp32 staging; the programme level's fp32 stream; the fade table
+  DevBuf<unsigned char> st_out;               // the encoded stream
+  DevBuf<xdtts::StreamUtt> st_tab;
+  std::vector<xdtts::StreamUtt> st_tab_host;  // the uploads' sources: they stay until the next stream request of this handle,
+  std::vector<float> st_fade_host;            // which starts behind a drained stream
+  size_t st_used = 0;                         // floats of st_src that hold utterances of the request in flight
+  // Where a document run delivers an utterance: enqueue_run copies to dst on the device instead of to a pinned host buffer (one
+  // stream-ordered operation in the place of one; a demoted engine's retry writes the same place again), and with
+  // `unlevelled` runs neither the loudness stage nor the output normalisation (programme level: one gain for the stream).
+  struct StreamSink {
+    float *dst = nullptr;
+    bool unlevelled = false;
+  } sink;
+  // st_src with room for `floats` in all; what it holds (st_used floats) survives the growth.  Stream idle.
+  void stream_reserve(size_t floats);
+  // The stage on the stream, from st_tab_host (src0 into st_src) -> st_out (total * sample_bytes bytes): the table and the fade
+  // table go up, then at level 0 ONE k_stream_join launch; at level 1 the fp32 stream is formed first (format 0, no gain),
+  // measured once by the loudness kernels at `rate`, and the encode launch reads the gain from loud_res[0] on the device --
+  // the struct travels back behind it (loud_host[0]).  Checked arguments.
+  // (begin: recorded behind the uploads, in front of the first launch)
+  void stream_join(size_t total, const xdtts::StreamOpts &o, int rate, hipEvent_t begin = nullptr);
 
   ~xdtts_griffinlim();
   GlBufs bufs(int F);

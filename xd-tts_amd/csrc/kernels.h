@@ -4,6 +4,7 @@
 #include "gl_plan.h"
 #include "loudness_plan.h"
 #include "resample_plan.h"
+#include "stream_plan.h"
 #include "weights.h"
 
 namespace xdtts {
@@ -405,5 +406,11 @@ void launch_loudness_measure(const float *x, const LoudUtt *tab_dev, int count, 
 // x[i] *= (float)res[u].gain over the same utterances, one launch
 void launch_loudness_scale(float *x, const LoudUtt *tab_dev, int count, int grp_base, int n_groups, const LoudUtt &one,
                            const LoudResult *res, hipStream_t s);
+
+// ---- stream (stream.hip): utterances joined with their gaps into one stream, faded, levelled, encoded (include/xdtts.h) -------
+// ONE launch of k_stream_join: job.tab[0 .. n_utt) on the device, ascending off (stream_plan.h: StreamUtt), the utterances'
+// samples at job.src + src0; out = total * sample_bytes bytes, 16-byte aligned -- nothing at or behind that is written.
+// job.gain (device memory) is read by the kernel: the measurement that writes it is ordered in front on the stream.
+void launch_stream_join(const StreamJob &job, void *out, hipStream_t s);
 
 }  // namespace xdtts
