@@ -562,7 +562,8 @@ xdtts_status xdtts_griffinlim_resample_batch(xdtts_griffinlim *g, const float *c
 /* Loudness-normalised output.  output_normalise levels an utterance by sample peak or rms; what a product ships is an
  * integrated loudness (ITU-R BS.1770-4 / EBU R128: -16 LUFS for voice assistants, -23 for broadcast) under a true-peak
  * ceiling.  With a target set, that rule runs on the device at the delivered rate, behind the resampler, IN PLACE OF the
- * output normalisation; the scaling is one linear gain (no limiter).  The definition, exactly -- Q is the rate of the
+ * output normalisation; the scaling is one linear gain, or, with a limiter set (xdtts_griffinlim_set_limiter below), the
+ * uncapped gain under a look-ahead true-peak limiter.  The definition, exactly -- Q is the rate of the
  * delivered signal, 8000 <= Q <= 96000, x its N samples (mono):
  *   K-weighting  two biquads in cascade (a0 = 1), from the analogue prototypes by the bilinear transform, K = tan(pi f0 / Q):
  *           high-shelf  f0 = 1681.974450955533 Hz, G = 3.999843853973347 dB, Qf = 0.7071752369554196,
@@ -614,6 +615,61 @@ xdtts_status xdtts_griffinlim_loudness_batch(xdtts_griffinlim *g, const float *c
 xdtts_status xdtts_loudness_plan(int32_t rate, size_t n, int32_t *hop, size_t *n_blocks);
 xdtts_status xdtts_loudness_filter(int32_t rate, double coef[10]);
 xdtts_status xdtts_true_peak_filter(float taps[3][24]);
+
+/* Look-ahead true-peak limiter behind the loudness stage.  The one-gain rule above keeps a ceiling by lowering the WHOLE
+ * utterance: where the ceiling binds, the delivered loudness stays below the target.  With a limiter set, the measurement's
+ * gain is formed WITHOUT the ceiling (g0 = 10^((T + 0.691) / 20) / sqrt(Z)) and the ceiling is kept by a gain that dips only
+ * around the peaks.  The definition, exactly -- x the N fp32 samples at rate Q, g0 a double, c = 10^(C / 20) a double > 0,
+ * lookahead_us an integer in [500, 10000]:
+ *   half width  H = max(12, (Q lookahead_us + 500000) / 1000000) in 64-bit integer division (960 at 96 kHz and 10 ms).
+ *   peak envelope  y[4 n + p] as in the true peak above (the taps of xdtts_true_peak_filter, fp32 fmaf chains over j ascending,
+ *           zero extension); Y[n] = max over p of |y[4 n + p]|, Y[-1] = 0; e[n] = max(|x[n]|, Y[n], Y[n - 1]): a peak between
+ *           two samples belongs to both of them.
+ *   needed gain  G = (float) g0; a[n] = fl(G e[n]); r[n] = 1 unless a[n] > (float) c, then
+ *           r[n] = (float)((double)(float) c / (double) a[n]); r = 1 outside [0, N).
+ *   hold    m[n] = min r[n - H .. n + H].
+ *   smoothing  d[n] = fl(1 - m[n]); w[j] = (0.5 + 0.5 cos(pi j / (H + 1))) / (H + 1), j = -H .. H, in double on the host, rounded
+ *           once to fp32 (the exact weights sum to 1); s[n] = fl(1 - sum over j of w[j] d[n + j]), one fmaf chain from 0 over j
+ *           ascending.  An all-zero d gives s = 1 exactly.
+ *   gain    g[n] = min(s[n], r[n]) (every m[n + j] <= r[n], so s <= r in exact arithmetic; the min covers rounding);
+ *           out[n] = fl(x[n] fl(G g[n])).  Symmetric (offline): no latency, attack = release = H samples.  Where g = 1 the
+ *           sample has the bits of the one-gain scaling by G.
+ *   engaged  if and only if a limiter, a target and a ceiling are set, Z > 0 and g0 TP > c (doubles of the measurement);
+ *           otherwise every sample is fl(x G) -- the scaling above by the uncapped gain.
+ * With the limiter on, xdtts_loudness.gain is g0, the static gain that was applied; the struct keeps its layout, and the
+ * stats below travel back behind it.  Decided on the device, without a host synchronisation; the ragged batch returns the bits
+ * of the single call.  At programme level (xdtts_stream_opts.level = 1) the stage runs once over the formed fp32 stream, and
+ * the encode reads the limited stream; gaps stay the exact zeros.  0 = off (the default): nothing new is launched and every
+ * result keeps its bits.  A value outside 0 and [500, 10000] is XDTTS_ERR_BAD_ARG and leaves the setting alone.
+ * Out of scope: make-up gain or iteration toward the target, a compressor, separate attack and release; the values delivered
+ * for non-finite samples are not specified. */
+typedef struct {
+  float   min_gain;     /* the smallest g; 1 where nothing was limited */
+  int32_t half_width;   /* H */
+  int32_t engaged;      /* 1 where the stage ran, 0 where every sample is fl(x G) */
+  int64_t limited;      /* samples with g < 1 */
+} xdtts_limiter_stats;
+xdtts_status xdtts_griffinlim_set_limiter(xdtts_griffinlim *g, int32_t lookahead_us);   /* default 0 */
+xdtts_status xdtts_griffinlim_get_limiter(const xdtts_griffinlim *g, int32_t *lookahead_us);
+/* The stats of each utterance of the last delivering call, shaped like xdtts_griffinlim_last_loudness; *n = 0 unless a
+ * target, a ceiling and a limiter are set (without a ceiling there is nothing to keep: nothing new is launched). */
+xdtts_status xdtts_griffinlim_last_limiter(const xdtts_griffinlim *g, xdtts_limiter_stats *out, size_t cap, size_t *n);
+/* The stage alone on the caller's audio (1 <= n < 2^28 samples, 8000 <= rate <= 96000, gain0 finite and >= 0, ceiling_lin
+ * finite and > 0), whatever the handle's settings: the `engaged` rule is not applied, the stage always runs.  The parity hook:
+ * out (n floats) and stats equal xdtts_limiter_reference bit for bit, and every outs[u] of the ragged form equals the single
+ * call's.  Argument errors come back before a device is touched.  Afterwards xdtts_griffinlim_last_timings ms[0] is the stage
+ * alone. */
+xdtts_status xdtts_griffinlim_limit(xdtts_griffinlim *g, const float *audio, size_t n, int32_t rate, double gain0, double ceiling_lin,
+                                    int32_t lookahead_us, float *out, xdtts_limiter_stats *stats);
+xdtts_status xdtts_griffinlim_limit_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt, int32_t rate,
+                                          double gain0, double ceiling_lin, int32_t lookahead_us, float *const *outs,
+                                          xdtts_limiter_stats *stats);
+/* Host arithmetic, no handle, no device.  _plan: H and the tile (outputs per workgroup); either pointer may be NULL.  _window:
+ * w[0 .. 2 H] = w[-H .. H].  _reference: the definition evaluated sample by sample in plain C++ (stats may be NULL). */
+xdtts_status xdtts_limiter_plan(int32_t rate, int32_t lookahead_us, int32_t *half_width, int32_t *tile);
+xdtts_status xdtts_limiter_window(int32_t rate, int32_t lookahead_us, float *w);
+xdtts_status xdtts_limiter_reference(const float *audio, size_t n, int32_t rate, double gain0, double ceiling_lin, int32_t lookahead_us,
+                                     float *out, xdtts_limiter_stats *stats);
 
 /* Document output: the utterances of a sequence joined with their <break> silences into ONE stream, faded at their edges,
  * levelled by one programme gain and encoded, on the device -- the output stage of XdTts::generate_audio (src/lib.rs:60-108:

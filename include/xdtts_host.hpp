@@ -301,6 +301,31 @@ class GriffinLim {
     check(xdtts_griffinlim_loudness(g_, audio.data(), audio.size(), rate, &l));
     return l;
   }
+  // A look-ahead true-peak limiter beside the target and the ceiling (xdtts_griffinlim_set_limiter): 500 .. 10000 microseconds,
+  // 0 = off.  The gain is then formed without the ceiling and the limiter keeps it around the peaks only.
+  void set_limiter(int32_t lookahead_us) { check(xdtts_griffinlim_set_limiter(g_, lookahead_us)); }
+  int32_t limiter_setting() const {
+    int32_t us = 0;
+    check(xdtts_griffinlim_get_limiter(g_, &us));
+    return us;
+  }
+  // ... the stats of each utterance of the last delivering call (empty unless a target, a ceiling and a limiter are set)
+  std::vector<xdtts_limiter_stats> last_limiter() const {
+    size_t n = 0;
+    check(xdtts_griffinlim_last_limiter(g_, nullptr, 0, &n));
+    std::vector<xdtts_limiter_stats> out(n);
+    if (n) check(xdtts_griffinlim_last_limiter(g_, out.data(), out.size(), &n));
+    return out;
+  }
+  // ... and the stage alone on the caller's audio (xdtts_griffinlim_limit): always engaged, the bits of xdtts_limiter_reference
+  std::vector<float> limit(const std::vector<float> &audio, int32_t rate, double gain0, double ceiling_lin, int32_t lookahead_us,
+                           xdtts_limiter_stats *stats = nullptr) const {
+    std::vector<float> out(audio.size());
+    xdtts_limiter_stats st{};
+    check(xdtts_griffinlim_limit(g_, audio.data(), audio.size(), rate, gain0, ceiling_lin, lookahead_us, out.data(), &st));
+    if (stats) *stats = st;
+    return out;
+  }
   // The inverse direction (xdtts_griffinlim_analyze): audio -> (S (n_bins x F), mel (n_mels x F)) under the handle's conventions,
   // F = audio.size() / 256 + 1
   std::pair<Array2, Array2> analyze(const std::vector<float> &audio, float mel_floor = 1e-5f) const {

@@ -12,6 +12,7 @@ run gate_rig_check.py         python tools/gate_rig_check.py
 run gemm_bench.py             python tools/gemm_bench.py 200 2
 run gl_check.py               python tools/gl_check.py
 run loudness_check.py         python tools/loudness_check.py
+run limiter_check.py          python tools/limiter_check.py
 run document_check.py         python tools/document_check.py 2
 run gl_hash.py                python tools/gl_hash.py
 run gl_tf_sweep.py            python tools/gl_tf_sweep.py

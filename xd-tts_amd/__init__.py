@@ -101,6 +101,15 @@ class Loudness(C.Structure):
         return (self.mean_square, self.true_peak, self.sample_peak, self.gain, self.blocks, self.gated_blocks)
 
 
+class LimiterStats(C.Structure):
+    """xdtts_limiter_stats: what the look-ahead limiter did to one utterance."""
+
+    _fields_ = [("min_gain", C.c_float), ("half_width", C.c_int32), ("engaged", C.c_int32), ("limited", C.c_int64)]
+
+    def astuple(self):
+        return (self.min_gain, self.half_width, self.engaged, self.limited)
+
+
 STREAM_F32, STREAM_PCM16, STREAM_ULAW, STREAM_ALAW = 0, 1, 2, 3
 _STREAM_DTYPE = {STREAM_F32: np.float32, STREAM_PCM16: np.dtype("<i2"), STREAM_ULAW: np.uint8, STREAM_ALAW: np.uint8}
 
@@ -226,6 +235,14 @@ SYMBOLS = {
     "xdtts_loudness_plan": (_I32, [_I32, _SZ, C.POINTER(_I32), C.POINTER(_SZ)]),
     "xdtts_loudness_filter": (_I32, [_I32, _VP]),
     "xdtts_true_peak_filter": (_I32, [_VP]),
+    "xdtts_griffinlim_set_limiter": (_I32, [_VP, _I32]),
+    "xdtts_griffinlim_get_limiter": (_I32, [_VP, C.POINTER(_I32)]),
+    "xdtts_griffinlim_last_limiter": (_I32, [_VP, _VP, _SZ, C.POINTER(_SZ)]),
+    "xdtts_griffinlim_limit": (_I32, [_VP, _VP, _SZ, _I32, C.c_double, C.c_double, _I32, _VP, _VP]),
+    "xdtts_griffinlim_limit_batch": (_I32, [_VP, _VP, _VP, _I32, _I32, C.c_double, C.c_double, _I32, _VP, _VP]),
+    "xdtts_limiter_plan": (_I32, [_I32, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
+    "xdtts_limiter_window": (_I32, [_I32, _I32, _VP]),
+    "xdtts_limiter_reference": (_I32, [_VP, _SZ, _I32, C.c_double, C.c_double, _I32, _VP, _VP]),
     "xdtts_griffinlim_free": (None, [_VP]),
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
@@ -984,6 +1001,48 @@ class GriffinLim:
             _check(lib.xdtts_griffinlim_loudness_batch(self._h, ip, ns, n, int(rate), out))
         return [out[i] for i in range(n)]
 
+    # -- limiter: look-ahead true-peak limiter where the loudness stage scaled ----
+    def set_limiter(self, lookahead_us=0):
+        """With a target and a ceiling set (set_loudness): the gain is formed without the ceiling and a look-ahead limiter of
+        `lookahead_us` microseconds (500 .. 10000; 0 / None = off, the default) keeps the ceiling around the peaks only.
+        last_limiter() then has the stats of each utterance; last_loudness()[u].gain is the static gain."""
+        _check(lib.xdtts_griffinlim_set_limiter(self._h, int(lookahead_us or 0)))
+
+    def get_limiter(self):
+        v = C.c_int32()
+        _check(lib.xdtts_griffinlim_get_limiter(self._h, C.byref(v)))
+        return v.value
+
+    def last_limiter(self):
+        """[LimiterStats] of the last delivering call, in the caller's order; [] unless a target, a ceiling and a limiter are set."""
+        n = C.c_size_t()
+        _check(lib.xdtts_griffinlim_last_limiter(self._h, None, 0, C.byref(n)))
+        out = (LimiterStats * max(n.value, 1))()
+        _check(lib.xdtts_griffinlim_last_limiter(self._h, out, n.value, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
+    def limit(self, audio, rate, gain0, ceiling_lin, lookahead_us):
+        """The stage alone on `audio`, whatever the handle's settings: (out, LimiterStats), the bits of limiter_reference()."""
+        outs, stats = self.limit_batch([audio], rate, gain0, ceiling_lin, lookahead_us)
+        return outs[0], stats[0]
+
+    def limit_batch(self, audios, rate, gain0, ceiling_lin, lookahead_us):
+        """The ragged stage: one set of launches for all audios, every output and struct the single call's bit for bit."""
+        xs = [np.ascontiguousarray(a, dtype=np.float32).ravel() for a in audios]
+        n = len(xs)
+        outs = [np.empty(x.size, dtype=np.float32) for x in xs]
+        stats = (LimiterStats * max(n, 1))()
+        ip = (C.c_void_p * max(n, 1))(*[x.ctypes.data for x in xs])
+        op = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        ns = (C.c_size_t * max(n, 1))(*[x.size for x in xs])
+        if n == 1:
+            _check(lib.xdtts_griffinlim_limit(self._h, ip[0], ns[0], int(rate), float(gain0), float(ceiling_lin), int(lookahead_us),
+                                              op[0], stats))
+        else:
+            _check(lib.xdtts_griffinlim_limit_batch(self._h, ip, ns, n, int(rate), float(gain0), float(ceiling_lin),
+                                                    int(lookahead_us), op, stats))
+        return outs, [stats[i] for i in range(n)]
+
     # -- stream: a sequence joined with its gaps, faded, levelled and encoded on the device ----
     def join(self, audios, gaps=None, rate=SAMPLE_RATE, opts=None, guard=0):
         """xdtts_griffinlim_join: the stage alone on the caller's audios (fp32, each read where it lies: a view's address decides
@@ -1109,6 +1168,30 @@ def true_peak_filter():
     t = np.zeros((3, 24), dtype=np.float32)
     _check(lib.xdtts_true_peak_filter(_ptr(t)))
     return t
+
+
+def limiter_plan(rate, lookahead_us):
+    """xdtts_limiter_plan (host arithmetic): {"half_width", "tile"} of the limiter at `rate` with `lookahead_us` microseconds."""
+    h, t = C.c_int32(), C.c_int32()
+    _check(lib.xdtts_limiter_plan(int(rate), int(lookahead_us), C.byref(h), C.byref(t)))
+    return {"half_width": h.value, "tile": t.value}
+
+
+def limiter_window(rate, lookahead_us):
+    """xdtts_limiter_window: the library's own fp32 smoothing weights w[-H .. H]."""
+    w = np.zeros(2 * limiter_plan(rate, lookahead_us)["half_width"] + 1, dtype=np.float32)
+    _check(lib.xdtts_limiter_window(int(rate), int(lookahead_us), _ptr(w)))
+    return w
+
+
+def limiter_reference(audio, rate, gain0, ceiling_lin, lookahead_us):
+    """xdtts_limiter_reference: the definition sample by sample in plain C++ on the host: (out, LimiterStats)."""
+    x = np.ascontiguousarray(audio, dtype=np.float32).ravel()
+    out = np.empty(x.size, dtype=np.float32)
+    st = LimiterStats()
+    _check(lib.xdtts_limiter_reference(_ptr(x) if x.size else None, x.size, int(rate), float(gain0), float(ceiling_lin), int(lookahead_us),
+                                       _ptr(out) if x.size else None, C.byref(st)))
+    return out, st
 
 
 def stream_sample_bytes(format):

@@ -787,6 +787,123 @@ xdtts_status xdtts_griffinlim_loudness(xdtts_griffinlim *g, const float *audio, 
   return xdtts_griffinlim_loudness_batch(g, &audio, &n, 1, rate, out);
 }
 
+// ---- limiter: look-ahead true-peak limiter where the loudness stage scaled (limiter_plan.h, limiter.hip) ------------------------
+
+static_assert(sizeof(xdtts_limiter_stats) == sizeof(LimiterStats) && offsetof(xdtts_limiter_stats, limited) == offsetof(LimiterStats, limited),
+              "xdtts_limiter_stats and LimiterStats share one layout");
+
+xdtts_status xdtts_limiter_plan(int32_t rate, int32_t lookahead_us, int32_t *half_width, int32_t *tile) {
+  return guard([&] {
+    const std::string msg = limiter_check(rate, lookahead_us);
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+    if (half_width) *half_width = limiter_half_width(rate, lookahead_us);
+    if (tile) *tile = LIM_TILE;
+  });
+}
+
+xdtts_status xdtts_limiter_window(int32_t rate, int32_t lookahead_us, float *w) {
+  return guard([&] {
+    const std::string msg = limiter_check(rate, lookahead_us);
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+    if (!w) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    limiter_window(limiter_half_width(rate, lookahead_us), w);
+  });
+}
+
+xdtts_status xdtts_limiter_reference(const float *audio, size_t n, int32_t rate, double gain0, double ceiling_lin, int32_t lookahead_us,
+                                     float *out, xdtts_limiter_stats *stats) {
+  return guard([&] {
+    const std::string msg = limiter_args_check(rate, lookahead_us, n, gain0, ceiling_lin);
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+    if (!audio || !out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    const LimiterStats st = limiter_reference(audio, n, rate, lookahead_us, gain0, ceiling_lin, out);
+    if (stats) std::memcpy(stats, &st, sizeof st);
+  });
+}
+
+xdtts_status xdtts_griffinlim_set_limiter(xdtts_griffinlim *g, int32_t lookahead_us) {
+  return guard([&] {
+    const std::string msg = limiter_setting_check(lookahead_us);  // the value first: reported without a handle
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->lim_us = lookahead_us;
+  });
+}
+
+xdtts_status xdtts_griffinlim_get_limiter(const xdtts_griffinlim *g, int32_t *lookahead_us) {
+  return guard([&] {
+    if (!g || !lookahead_us) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    *lookahead_us = g->lim_us;
+  });
+}
+
+xdtts_status xdtts_griffinlim_last_limiter(const xdtts_griffinlim *g, xdtts_limiter_stats *out, size_t cap, size_t *n) {
+  return guard([&] {
+    if (n) *n = 0;
+    if (!g || !n) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    *n = g->last_lim.size();
+    if (!out && cap == 0) return;  // the count alone
+    if (!out || cap < g->last_lim.size()) fail(XDTTS_ERR_BAD_ARG, "the last call delivered %zu utterances, the buffer holds %zu", g->last_lim.size(), cap);
+    if (!g->last_lim.empty()) std::memcpy(out, g->last_lim.data(), g->last_lim.size() * sizeof(xdtts_limiter_stats));
+  });
+}
+
+// The stage alone, single call and ragged batch: the audios one behind the other on the device, the two launches of
+// launch_limit (the single call passes its record by value, the batch uploads the table), the outputs and the stats back.
+// Always engaged, g0 = gain0.  last_timings: ms[0] = the stage alone.
+xdtts_status xdtts_griffinlim_limit_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt, int32_t rate,
+                                          double gain0, double ceiling_lin, int32_t lookahead_us, float *const *outs,
+                                          xdtts_limiter_stats *stats) {
+  return guard([&] {
+    if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    if (!n) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::vector<LimUtt> tab((size_t)n_utt);
+    size_t tot = 0, tile = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      const std::string msg = limiter_args_check(rate, lookahead_us, n[u], gain0, ceiling_lin);
+      if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "utterance %d: %s", u, msg.c_str());
+      tab[(size_t)u] = {(long long)tot, (long long)tot, (int)n[u], (int)tile};
+      tot += n[u];
+      tile += limiter_tiles(n[u]);
+      if (tot > (size_t)0x7fffffff) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^31 - 1 samples");
+    }
+    if (!g || !audios || !outs || !stats) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    for (int u = 0; u < n_utt; ++u)
+      if (!audios[u] || !outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null audio / out", u);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    hipStream_t st = g->stream;
+    g->rs_in.alloc(tot);
+    g->limiter_prepare(rate, lookahead_us);
+    g->limiter_bufs(tot, (size_t)n_utt);
+    for (int u = 0; u < n_utt; ++u)
+      HIP_CHECK(hipMemcpyAsync(g->rs_in.p + tab[(size_t)u].src0, audios[u], n[u] * sizeof(float), hipMemcpyHostToDevice, st));
+    if (n_utt > 1) {
+      g->lim_tab_host = tab;
+      g->lim_tab.upload(g->lim_tab_host.data(), g->lim_tab_host.size(), st);
+    }
+    const LimJob job = g->limiter_job(false, 0, gain0, ceiling_lin);
+    HIP_CHECK(hipEventRecord(g->ev.e[0], st));
+    if (n_utt == 1) g->limit_one(g->rs_in.p, n[0], job);  // (the form the single-utterance entries run)
+    else g->limit_rows(g->rs_in.p, 0, n_utt, job);
+    HIP_CHECK(hipEventRecord(g->ev.e[1], st));
+    HIP_CHECK(hipEventRecord(g->ev.e[2], st));
+    for (int u = 0; u < n_utt; ++u)
+      HIP_CHECK(hipMemcpyAsync(outs[u], g->lim_out.p + tab[(size_t)u].dst0, n[u] * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(g->lim_host, g->lim_stats.p, (size_t)n_utt * sizeof(LimiterStats), hipMemcpyDeviceToHost, st));
+    g->finish_timings();  // (drains the stream: the inputs, the table, the outputs and the stats)
+    std::memcpy(stats, g->lim_host, (size_t)n_utt * sizeof(xdtts_limiter_stats));
+  });
+}
+
+xdtts_status xdtts_griffinlim_limit(xdtts_griffinlim *g, const float *audio, size_t n, int32_t rate, double gain0, double ceiling_lin,
+                                    int32_t lookahead_us, float *out, xdtts_limiter_stats *stats) {
+  return xdtts_griffinlim_limit_batch(g, &audio, &n, 1, rate, gain0, ceiling_lin, lookahead_us, &out, stats);
+}
+
 // ---- stream: the sequence joined with its gaps, faded, levelled, encoded (stream_plan.h, stream.hip) ----------------------------
 
 static_assert(sizeof(xdtts_stream_opts) == sizeof(StreamOpts) && offsetof(xdtts_stream_opts, fade) == offsetof(StreamOpts, fade),
@@ -847,7 +964,7 @@ xdtts_status xdtts_griffinlim_join(xdtts_griffinlim *g, const float *const *audi
     HIP_CHECK(hipSetDevice(g->device));
     hipStream_t st = g->stream;
     HIP_CHECK(hipStreamSynchronize(st));
-    g->last_loud.clear();
+    g->clear_last();
     // utterance u at a multiple of four floats plus the 16-byte phase of (its host address + its offset): an interior pack of
     // the kernel then reads at the phase of the caller's buffer
     g->st_tab_host.clear();
@@ -867,11 +984,7 @@ xdtts_status xdtts_griffinlim_join(xdtts_griffinlim *g, const float *const *audi
     HIP_CHECK(hipEventRecord(g->ev.e[2], st));
     HIP_CHECK(hipMemcpyAsync(out, g->st_out.p, bytes, hipMemcpyDeviceToHost, st));
     g->finish_timings();  // (drains the stream: the inputs, the tables, the stream and the struct)
-    if (so.level == 1) {
-      xdtts_loudness l;
-      std::memcpy(&l, g->loud_host, sizeof l);
-      g->last_loud.push_back(l);
-    }
+    if (so.level == 1) g->push_last(0);
     for (int u = 0; offsets && u < n_utt; ++u) offsets[u] = off[(size_t)u];
     if (total) *total = tot;
   });

@@ -112,11 +112,7 @@ struct DocRun {
     out = PinnedGuard((bytes + 3) / 4);
     HIP_CHECK(hipMemcpyAsync(out.p, g->st_out.p, bytes, hipMemcpyDeviceToHost, g->stream));
     HIP_CHECK(hipStreamSynchronize(g->stream));
-    if (o.level == 1) {
-      xdtts_loudness l;
-      std::memcpy(&l, g->loud_host, sizeof l);
-      g->last_loud.push_back(l);
-    }
+    if (o.level == 1) g->push_last(0);
   }
 };
 static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
@@ -135,7 +131,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
     std::lock_guard<std::mutex> lk(h->mu);
     std::lock_guard<std::mutex> lk2(g->mu);
     std::lock_guard<ChipLock> chip(chip_mutex(h->device));  // the whole sequence: co-resident launches of two streams are in flight
-    g->last_loud.clear();  // (gl_collect appends utterance by utterance)
+    g->clear_last();  // (gl_collect appends utterance by utterance)
     const xdtts_infer_opts o = resolve_opts(opts);
     struct Hook {  // (the hook never outlives this call, whatever throws)
       xdtts_tacotron2 *h;

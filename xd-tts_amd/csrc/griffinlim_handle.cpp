@@ -14,6 +14,7 @@ xdtts_griffinlim::~xdtts_griffinlim() {
   if (copy_stream) (void)hipStreamDestroy(copy_stream);
   if (host_err) (void)hipHostFree(host_err);
   if (loud_host) (void)hipHostFree(loud_host);
+  if (lim_host) (void)hipHostFree(lim_host);
   if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -253,31 +254,115 @@ LoudBufs xdtts_griffinlim::loudness_bufs(size_t groups, size_t n_utt) {
   return LoudBufs{loud_excl.p, loud_agg.p, loud_gin.p, loud_part.p, loud_sub.p, loud_peaks.p};
 }
 
-void xdtts_griffinlim::loudness_one(float *x, size_t n, int rate, bool scale) {
+float *xdtts_griffinlim::loudness_one(float *x, size_t n, int rate, bool scale) {
   if (n == 0 || n >= ((size_t)1 << 28)) fail(XDTTS_ERR_BAD_ARG, "loudness: need 1 .. 2^28 - 1 samples, got %zu", n);
   loudness_prepare(rate);
   const int groups = (int)loudness_groups(n);
   const LoudBufs b = loudness_bufs((size_t)groups, 1);
   const LoudUtt one{0, (int)n, 0, 0, 0};
-  const bool on = scale && loudness_on();
+  const bool on = scale && loudness_on(), lim = on && limiter_on();
+  lim_ran = lim;
+  if (lim) {  // (in front of the launches: growing a buffer drains the stream)
+    limiter_prepare(rate, lim_us);
+    limiter_bufs(n, 1);
+  }
   launch_loudness_measure(x, nullptr, 1, 0, groups, one, loud_table.p, b, loud_res.p, rate, on ? loudness_target_lin(loud_target) : 0.0,
-                          on ? loudness_ceiling_lin(loud_ceiling) : 0.0, stream);
+                          on && !lim ? loudness_ceiling_lin(loud_ceiling) : 0.0, stream);
+  if (lim) {
+    limit_one(x, n, limiter_job(true, 0, 0.0, loudness_ceiling_lin(loud_ceiling)));
+    return lim_out.p;
+  }
   if (on) launch_loudness_scale(x, nullptr, 1, 0, groups, one, loud_res.p, stream);
+  return x;
 }
 
-void xdtts_griffinlim::loudness_rows(float *x, int r0, int count, int rate, bool scale) {
-  if (count <= 0) return;
+float *xdtts_griffinlim::loudness_rows(float *x, int r0, int count, int rate, bool scale) {
+  if (count <= 0) return x;
   const LoudUtt &first = loud_tab_host[(size_t)r0], &last = loud_tab_host[(size_t)(r0 + count - 1)];
   const int groups = last.grp0 + (int)loudness_groups((size_t)last.n) - first.grp0;
   const LoudBufs b{loud_excl.p, loud_agg.p, loud_gin.p, loud_part.p, loud_sub.p, loud_peaks.p};
-  const bool on = scale && loudness_on();
+  const bool on = scale && loudness_on(), lim = on && limiter_on();
+  lim_ran = lim;
   launch_loudness_measure(x, loud_tab.p + r0, count, first.grp0, groups, LoudUtt{}, loud_table.p, b, loud_res.p + r0, rate,
-                          on ? loudness_target_lin(loud_target) : 0.0, on ? loudness_ceiling_lin(loud_ceiling) : 0.0, stream);
+                          on ? loudness_target_lin(loud_target) : 0.0, on && !lim ? loudness_ceiling_lin(loud_ceiling) : 0.0, stream);
+  if (lim) {
+    limit_rows(x, r0, count, limiter_job(true, r0, 0.0, loudness_ceiling_lin(loud_ceiling)));
+    return lim_out.p;
+  }
   if (on) launch_loudness_scale(x, loud_tab.p + r0, count, first.grp0, groups, LoudUtt{}, loud_res.p + r0, stream);
+  return x;
 }
 
 void xdtts_griffinlim::loudness_fetch(int r0, int count, hipStream_t s) {
   HIP_CHECK(hipMemcpyAsync(loud_host + r0, loud_res.p + r0, (size_t)count * sizeof(LoudResult), hipMemcpyDeviceToHost, s));
+  if (lim_ran)
+    HIP_CHECK(hipMemcpyAsync(lim_host + r0, lim_stats.p + r0, (size_t)count * sizeof(LimiterStats), hipMemcpyDeviceToHost, s));
+}
+
+void xdtts_griffinlim::push_last(size_t r) {
+  xdtts_loudness l;
+  static_assert(sizeof l == sizeof(LoudResult), "LoudResult is xdtts_loudness");
+  std::memcpy(&l, loud_host + r, sizeof l);
+  last_loud.push_back(l);
+  if (lim_ran) {
+    xdtts_limiter_stats st;
+    static_assert(sizeof st == sizeof(LimiterStats), "LimiterStats is xdtts_limiter_stats");
+    std::memcpy(&st, lim_host + r, sizeof st);
+    last_lim.push_back(st);
+  }
+}
+
+// The limiter (limiter.hip).  The window is a function of H alone: built on the host when H changes and kept on the device.
+void xdtts_griffinlim::limiter_prepare(int rate, int lookahead_us) {
+  const std::string msg = limiter_check(rate, lookahead_us);
+  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  loudness_prepare(rate);  // (the taps)
+  const int H = limiter_half_width(rate, lookahead_us);
+  if (H == lim_H && lim_win.p) return;
+  HIP_CHECK(hipStreamSynchronize(stream));  // (a launch that reads another window may be in flight)
+  lim_H = 0;
+  lim_win_host.resize((size_t)(2 * H + 1));
+  limiter_window(H, lim_win_host.data());
+  lim_win.upload(lim_win_host.data(), lim_win_host.size(), stream);
+  lim_H = H;
+}
+
+void xdtts_griffinlim::limiter_bufs(size_t floats, size_t n_utt) {
+  floats = std::max<size_t>(floats, 1);
+  n_utt = std::max<size_t>(n_utt, 1);
+  if (floats > lim_out.n || n_utt > lim_stats.n) HIP_CHECK(hipStreamSynchronize(stream));  // (growing frees what a launch may touch)
+  lim_out.alloc(floats);
+  lim_stats.alloc(n_utt);
+  if (n_utt > lim_host_n) {
+    if (lim_host) HIP_CHECK(hipHostFree(lim_host));
+    lim_host = nullptr;
+    lim_host_n = 0;
+    HIP_CHECK(hipHostMalloc((void **)&lim_host, n_utt * sizeof(LimiterStats), hipHostMallocDefault));
+    lim_host_n = n_utt;
+  }
+}
+
+LimJob xdtts_griffinlim::limiter_job(bool res_from_loudness, int r0, double gain0, double ceil) const {
+  LimJob j{};
+  j.taps = &loud_table.p->taps[0][0];
+  j.win = lim_win.p;
+  j.res = res_from_loudness ? loud_res.p + r0 : nullptr;
+  j.gain0 = gain0;
+  j.ceil = ceil;
+  j.H = lim_H;
+  return j;
+}
+
+void xdtts_griffinlim::limit_one(const float *x, size_t n, const LimJob &job) {
+  const LimUtt one{0, 0, (int)n, 0};
+  launch_limit(x, lim_out.p, nullptr, 1, 0, (int)limiter_tiles(n), one, job, lim_stats.p, stream);
+}
+
+void xdtts_griffinlim::limit_rows(const float *x, int r0, int count, const LimJob &job) {
+  if (count <= 0) return;
+  const LimUtt &first = lim_tab_host[(size_t)r0], &last = lim_tab_host[(size_t)(r0 + count - 1)];
+  const int tiles = last.tile0 + (int)limiter_tiles((size_t)last.n) - first.tile0;
+  launch_limit(x, lim_out.p, lim_tab.p + r0, count, first.tile0, tiles, LimUtt{}, job, lim_stats.p + r0, stream);
 }
 
 // The stream stage (stream.hip).
@@ -300,10 +385,19 @@ void xdtts_griffinlim::stream_join(size_t total, const StreamOpts &o, int rate, 
     st_fade.upload(st_fade_host.data(), st_fade_host.size(), stream);
   }
   st_out.alloc(total * (size_t)stream_sample_bytes(o.format));
+  const bool lim = o.level == 1 && limiter_on();
+  lim_ran = lim;
   if (o.level == 1) {
     loudness_prepare(rate);
     loudness_bufs(loudness_groups(total), 1);
     st_f32.alloc(total);
+  }
+  if (lim) {  // the encode then reads the limited stream: the same offsets, the utterances where they lie in it
+    limiter_prepare(rate, lim_us);
+    limiter_bufs(total, 1);
+    st_lim_tab_host = st_tab_host;
+    for (StreamUtt &r : st_lim_tab_host) r.src0 = (long long)r.off;
+    st_lim_tab.upload(st_lim_tab_host.data(), st_lim_tab_host.size(), stream);
   }
   if (begin) HIP_CHECK(hipEventRecord(begin, stream));
   StreamJob job{};
@@ -325,8 +419,16 @@ void xdtts_griffinlim::stream_join(size_t total, const StreamOpts &o, int rate, 
     launch_stream_join(form, st_f32.p, stream);
     const LoudUtt one{0, (int)total, 0, 0, 0};
     launch_loudness_measure(st_f32.p, nullptr, 1, 0, groups, one, loud_table.p, b, loud_res.p, rate, loudness_target_lin(loud_target),
-                            loudness_ceiling_lin(loud_ceiling), stream);
+                            lim ? 0.0 : loudness_ceiling_lin(loud_ceiling), stream);
     job.gain = &loud_res.p->gain;
+    if (lim) {  // fade and gain are in the limited stream already; gaps stay the encoder's constants
+      limit_one(st_f32.p, total, limiter_job(true, 0, 0.0, loudness_ceiling_lin(loud_ceiling)));
+      job.src = lim_out.p;
+      job.tab = st_lim_tab.p;
+      job.fade_tab = nullptr;
+      job.fade = 0;
+      job.gain = nullptr;
+    }
   }
   launch_stream_join(job, st_out.p, stream);
   if (o.level == 1) loudness_fetch(0, 1, stream);
@@ -607,7 +709,7 @@ static void enqueue_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
   }
   const bool level = deliver && !(g->sink.dst && g->sink.unlevelled);  // (a document at programme level takes the utterance unlevelled)
   const bool loud = level && g->loudness_on() && N > 0;  // the loudness rule takes the output normalisation's place
-  if (loud) g->loudness_one(out, N, g->out_rate, true);
+  if (loud) out = g->loudness_one(out, N, g->out_rate, true);  // (the limiter works out of place)
   else if (level) launch_gl_output_normalise(out, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
   HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
   if (deliver && g->sink.dst) {  // a document run: the utterance stays in HBM, at its place in the staging buffer
@@ -632,12 +734,7 @@ static void collect_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
     if (g->persistent_failed()) fail(XDTTS_ERR_HIP, "Griffin-Lim: the fallback engine reported an exchange failure");
   }
   const size_t N = (size_t)g->hop * (size_t)(b.F - 1);
-  if (deliver && g->loudness_on() && N > 0 && !(g->sink.dst && g->sink.unlevelled)) {
-    xdtts_loudness l;
-    static_assert(sizeof l == sizeof(LoudResult), "LoudResult is xdtts_loudness");
-    std::memcpy(&l, g->loud_host, sizeof l);
-    g->last_loud.push_back(l);
-  }
+  if (deliver && g->loudness_on() && N > 0 && !(g->sink.dst && g->sink.unlevelled)) g->push_last(0);
   *audio = host.release();
   *n_samples = deliver ? g->delivered(N) : N;
 }
@@ -647,7 +744,7 @@ void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *pha
                           bool normalise) {
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
   g->probe_tick();
-  g->last_loud.clear();
+  g->clear_last();
   PinnedGuard host;
   enqueue_run(g, b, phase0_dev, iters, normalise, host);
   collect_run(g, b, phase0_dev, iters, normalise, host, audio, n_samples);
@@ -685,7 +782,7 @@ void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, si
 
 void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const ProsodyArg &p, float **audio, size_t *n_samples) {
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
-  g->last_loud.clear();
+  g->clear_last();
   PinnedGuard host;
   gl_enqueue_from_device_mel(g, mel_dev_ptr, F, host, p);
   gl_collect(g, F, host, audio, n_samples, p);
@@ -827,12 +924,20 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
   // With a loudness target the loudness stage (loudness.hip) takes the output normalisation's place, on the same rows.
   const bool loud = g->loudness_on();
   const int norm_mode = loud ? 0 : g->gopts.output_normalise;
-  g->last_loud.clear();
+  g->clear_last();
+  const bool limited = loud && g->limiter_on();  // k_limit where k_loud_scale ran: out of place, the rows at the same offsets
   if (loud) {
-    size_t groups = 0;
-    for (int u = 0; u < n_utt; ++u) groups += loudness_groups((size_t)dn[(size_t)u]);
+    size_t groups = 0, dtot = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      groups += loudness_groups((size_t)dn[(size_t)u]);
+      dtot = std::max(dtot, (size_t)dbase[(size_t)u] + (size_t)dn[(size_t)u]);
+    }
     g->loudness_prepare(g->out_rate);
     g->loudness_bufs(groups, (size_t)n_utt);
+    if (limited) {
+      g->limiter_prepare(g->out_rate, g->lim_us);
+      g->limiter_bufs(dtot, (size_t)n_utt);
+    }
   }
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
   g->probe_tick();
@@ -862,7 +967,8 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
       tab.reserve((size_t)n_utt);
       g->rs_tab_host.clear();
       g->loud_tab_host.clear();
-      int blk = 0, grp = 0, seg = 0, sb = 0;
+      g->lim_tab_host.clear();
+      int blk = 0, grp = 0, seg = 0, sb = 0, tile = 0;
       for (int u : plan.order) {
         tab_pos[(size_t)u] = (int)tab.size();
         tab.push_back(make_int2(dbase[(size_t)u], dn[(size_t)u]));
@@ -872,6 +978,10 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
           grp += (int)loudness_groups(n);
           seg += (int)loudness_segments(n);
           sb += (int)loudness_sub_blocks(g->out_rate, n);
+          if (limited) {
+            g->lim_tab_host.push_back({(long long)dbase[(size_t)u], (long long)dbase[(size_t)u], dn[(size_t)u], tile});
+            tile += (int)limiter_tiles(n);
+          }
         }
         if (resampled) {
           g->rs_tab_host.push_back({(long long)abase[u], (long long)rbase[(size_t)u], g->hop * (Fu[u] - 1), dn[(size_t)u], blk, 0});
@@ -884,6 +994,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
       }
       if (resampled) g->rs_tab.upload(g->rs_tab_host.data(), g->rs_tab_host.size(), st);
       if (loud) g->loud_tab.upload(g->loud_tab_host.data(), g->loud_tab_host.size(), st);
+      if (limited) g->lim_tab.upload(g->lim_tab_host.data(), g->lim_tab_host.size(), st);
       HIP_CHECK(hipStreamSynchronize(st));
     }
     size_t n_ev = 0;
@@ -896,12 +1007,13 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
         launch_gl_output_normalise(dbuf, g->norm_tab.p + r0, (int)utts.size(), 0, n_max, norm_mode, g->gopts.rms_target,
                                    g->norm_parts.p + (size_t)r0 * GLN_SCRATCH, st);
       }
-      if (loud && !utts.empty()) g->loudness_rows(dbuf, tab_pos[(size_t)utts[0]], (int)utts.size(), g->out_rate, true);
+      const float *src = dbuf;  // where the delivered rows lie
+      if (loud && !utts.empty()) src = g->loudness_rows(dbuf, tab_pos[(size_t)utts[0]], (int)utts.size(), g->out_rate, true);
       hipEvent_t e = g->launch_done(n_ev++);
       HIP_CHECK(hipEventRecord(e, st));
       HIP_CHECK(hipStreamWaitEvent(g->copy_stream, e, 0));
       for (int u : utts)
-        HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, dbuf + dbase[(size_t)u], sizeof(float) * (size_t)dn[(size_t)u], hipMemcpyDeviceToHost,
+        HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, src + dbase[(size_t)u], sizeof(float) * (size_t)dn[(size_t)u], hipMemcpyDeviceToHost,
                                  g->copy_stream));
       if (loud && !utts.empty()) g->loudness_fetch(tab_pos[(size_t)utts[0]], (int)utts.size(), g->copy_stream);
     };
@@ -950,11 +1062,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     for (int u = 0; u < n_utt; ++u) {
       audios[u] = out[(size_t)u].release();
       n_samples[u] = (size_t)dn[(size_t)u];
-      if (loud) {
-        xdtts_loudness l;
-        std::memcpy(&l, g->loud_host + tab_pos[(size_t)u], sizeof l);
-        g->last_loud.push_back(l);
-      }
+      if (loud) g->push_last((size_t)tab_pos[(size_t)u]);
     }
     return;
   }

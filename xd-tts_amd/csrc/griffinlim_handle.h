@@ -177,18 +177,52 @@ struct xdtts_griffinlim {
   xdtts::LoudBufs loudness_bufs(size_t groups, size_t n_utt);
   // One utterance, x[0 .. n) at `rate`, on the stream: the measurement into loud_res[0] and, with scale, the gain of the
   // handle's target applied in place.  Nothing is uploaded (the record travels as a kernel argument).
-  void loudness_one(float *x, size_t n, int rate, bool scale);
+  // Returns where the delivered signal lies: x, or -- where the limiter ran -- lim_out.p (out of place, the same offsets).
+  float *loudness_one(float *x, size_t n, int rate, bool scale);
   // Ragged: records loud_tab_host[r0 .. r0 + count) (uploaded by the caller as loud_tab, behind loudness_prepare() and
-  // loudness_bufs()), results into loud_res[r0 ..].
-  void loudness_rows(float *x, int r0, int count, int rate, bool scale);
-  // loud_res[r0 .. r0 + count) -> loud_host, on `s`
+  // loudness_bufs()), results into loud_res[r0 ..].  With the limiter: lim_tab_host / lim_tab likewise, behind limiter_prepare()
+  // and limiter_bufs(); returns as loudness_one (src0 = dst0 in the records).
+  float *loudness_rows(float *x, int r0, int count, int rate, bool scale);
+  // loud_res[r0 .. r0 + count) -> loud_host (and, with the limiter, lim_stats -> lim_host), on `s`
   void loudness_fetch(int r0, int count, hipStream_t s);
+
+  // limiter (limiter.hip): with a look-ahead set beside a target AND a ceiling, the measurement forms the gain without the
+  // ceiling and k_limit takes k_loud_scale's place, out of place into lim_out.  0 = off (the default).
+  int lim_us = 0;
+  bool limiter_on() const { return lim_us != 0 && loudness_on() && !std::isnan(loud_ceiling); }
+  bool lim_ran = false;                       // the last loudness_one / _rows / stream_join launched k_limit: stats travel back
+  int lim_H = 0;                              // the half width whose window is on the device; 0 = none yet
+  std::vector<float> lim_win_host;            // the upload's source, kept with the handle
+  DevBuf<float> lim_win, lim_out;
+  DevBuf<xdtts::LimiterStats> lim_stats;      // one per utterance of a request
+  DevBuf<xdtts::LimUtt> lim_tab;
+  std::vector<xdtts::LimUtt> lim_tab_host;    // the upload's source: stays until the next request of this handle
+  xdtts::LimiterStats *lim_host = nullptr;    // pinned: the stats travel back behind the loudness structs
+  size_t lim_host_n = 0;
+  std::vector<xdtts_limiter_stats> last_lim;  // xdtts_griffinlim_last_limiter: of the last delivering call, in the caller's order
+  // The window of H(rate, lookahead_us) on the device (built and uploaded when H changes) and the loudness table's taps.
+  void limiter_prepare(int rate, int lookahead_us);
+  // lim_out with room for `floats`, stats for n_utt utterances, device and pinned host.
+  void limiter_bufs(size_t floats, size_t n_utt);
+  // the job of the handle's settings reading loud_res + r0 (res_from_loudness), or of the stage alone with (gain0, ceil)
+  xdtts::LimJob limiter_job(bool res_from_loudness, int r0, double gain0, double ceil) const;
+  // One utterance x[0 .. n) -> lim_out[0 .. n), stats into lim_stats[0]; nothing is uploaded.
+  void limit_one(const float *x, size_t n, const xdtts::LimJob &job);
+  // Ragged: records lim_tab_host[r0 .. r0 + count) (uploaded by the caller as lim_tab), stats into lim_stats[r0 ..].
+  void limit_rows(const float *x, int r0, int count, const xdtts::LimJob &job);
+  void clear_last() {
+    last_loud.clear();
+    last_lim.clear();
+  }
+  // the structs of record r of the last fetch -> last_loud (and last_lim where the limiter ran)
+  void push_last(size_t r);
 
   // stream (stream.hip): the utterances of a sequence joined with their gaps, faded, levelled and encoded -- the stage behind
   // everything above (xdtts_griffinlim_join, xdtts_synthesize_document).
   DevBuf<float> st_src, st_f32, st_fade;      // the utterances' fp32 staging; the programme level's fp32 stream; the fade table
   DevBuf<unsigned char> st_out;               // the encoded stream
-  DevBuf<xdtts::StreamUtt> st_tab;
+  DevBuf<xdtts::StreamUtt> st_tab, st_lim_tab;  // st_lim_tab: the same records with sources in the limited stream (programme level)
+  std::vector<xdtts::StreamUtt> st_lim_tab_host;
   std::vector<xdtts::StreamUtt> st_tab_host;  // the uploads' sources: they stay until the next stream request of this handle,
   std::vector<float> st_fade_host;            // which starts behind a drained stream
   size_t st_used = 0;                         // floats of st_src that hold utterances of the request in flight

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "gl_plan.h"
+#include "limiter_plan.h"
 #include "loudness_plan.h"
 #include "resample_plan.h"
 #include "stream_plan.h"
@@ -406,6 +407,27 @@ void launch_loudness_measure(const float *x, const LoudUtt *tab_dev, int count, 
 // x[i] *= (float)res[u].gain over the same utterances, one launch
 void launch_loudness_scale(float *x, const LoudUtt *tab_dev, int count, int grp_base, int n_groups, const LoudUtt &one,
                            const LoudResult *res, hipStream_t s);
+
+// ---- limiter (limiter.hip): look-ahead true-peak limiter where the loudness stage scaled (include/xdtts.h, limiter_plan.h) ------
+// One utterance of a launch: n samples at x + src0 -> n samples at out + dst0 (out of place).  Its workgroups (LIM_TILE outputs
+// each) are tile0 .. of the table's numbering, ascending, the utterances back to back.
+struct LimUtt {
+  long long src0, dst0;
+  int n, tile0;
+};
+struct LimJob {
+  const float *taps;       // LoudnessTable::taps on the device
+  const float *win;        // the 2 H + 1 weights of limiter_window on the device
+  const LoudResult *res;   // per utterance: the kernel reads Z, TP and the gain g0 there and decides `engaged`; null: the
+  double gain0;            //   stage alone -- always engaged, g0 = gain0
+  double ceil;             // the linear ceiling c
+  int H;
+};
+// Two launches: the stats' initial values (min_gain 1, H, engaged, 0), then k_limit over n_tiles workgroups, the first being
+// tile tile_base of the table's numbering (tab_dev == nullptr: the one utterance `one`).  stats[u] / job.res[u] belong to
+// record u.  Integer and float-bits atomics on the stats only: out and stats are functions of (the utterance, job) alone.
+void launch_limit(const float *x, float *out, const LimUtt *tab_dev, int count, int tile_base, int n_tiles, const LimUtt &one,
+                  const LimJob &job, LimiterStats *stats, hipStream_t s);
 
 // ---- stream (stream.hip): utterances joined with their gaps into one stream, faded, levelled, encoded (include/xdtts.h) -------
 // ONE launch of k_stream_join: job.tab[0 .. n_utt) on the device, ascending off (stream_plan.h: StreamUtt), the utterances'
