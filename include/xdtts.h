@@ -447,8 +447,9 @@ xdtts_status xdtts_griffinlim_prosody_linear_batch(xdtts_griffinlim *g, const fl
  * by one from xdtts_prosody_frames (at most one for F in {2, 3, 5, 37, 48, 800, 16384} and ten rates; e.g. F = 3, r = 0.8).  A
  * rate-1 contour maps frame j to frame j exactly: c[m] = 65536 m.  The identity contour launches nothing and returns the bits
  * of the plain entries; an identity utterance inside a mixed batch is copied.  Batch == single, bit for bit: one kernel serves both.
- * Out of scope: the sequence entries (a caller loops over xdtts_synthesize_ids_contour); absolute-Hz and semitone targets (the
- * host converts them to factors); positions in seconds or phonemes (these need alignments). */
+ * Out of scope: the sequence entries (a caller loops over xdtts_synthesize_ids_contour); semitone targets (the host converts
+ * them to factors; absolute-Hz targets and the pitch range are xdtts_pitch_target, below); positions in seconds or phonemes
+ * (these need alignments). */
 typedef struct { float pos, rate, pitch, gain; } xdtts_prosody_point;   /* 16 bytes */
 typedef struct {
   const xdtts_prosody_point *points;   /* host memory, read during the call only */
@@ -480,6 +481,112 @@ xdtts_status xdtts_griffinlim_infer_contour(xdtts_griffinlim *g, const float *me
 xdtts_status xdtts_griffinlim_infer_batch_contour(xdtts_griffinlim *g, const float *const *mels, size_t n_mels,
                                                   const size_t *n_frames, int32_t n_utt, const xdtts_prosody_contour *c /* [n_utt] */,
                                                   float **audios, size_t *n_samples);
+
+/* Pitch tracking on the device, and pitch TARGETS: what SSML <prosody pitch="180Hz"> and <prosody range="..."> ask for.  Both
+ * need the utterance's own F0 -- per frame and its median -- which xdtts_prosody and the contours, working with factors, never
+ * measure.  The tracker reads the magnitude S [F][513] that mel -> linear leaves (or an analysed one), forms each frame's real
+ * cepstrum exactly as xdtts_prosody does, and takes the pitch period from its peak; a second kernel smooths, selects the median
+ * and turns a target into one pitch factor per frame, multiplied on the device into the pitch array of a contour table -- no
+ * round trip to the host between mel -> linear and the loop.
+ * Options xdtts_f0_opts {fmin, fmax, threshold, octave_bias, log_floor}, default {60, 400, 0.2, 0.9, 1e-5}.  Rules: every field
+ * finite; 50 <= fmin < fmax <= 1000; threshold >= 0; octave_bias in (0, 1]; log_floor > 0.  Quefrency range, host arithmetic in
+ * double: q_lo = ceil(22050 / fmax), q_hi = floor(22050 / fmin); q_lo < q_hi is required (the rules give 22 <= q_lo, q_hi <= 441).
+ * Anything else is XDTTS_ERR_BAD_ARG, found before a device is touched; the message names the field.  o == NULL: the default.
+ * Per frame (device, fp32), m = S[t][0 .. 512]:
+ *   L[k]   = logf(fmaxf(m[k], log_floor))                            (a NaN cell becomes log_floor)
+ *   c      = the real cepstrum of L exactly as xdtts_prosody forms it (1024-point transform of the even extension, / 1024)
+ *   top    = max c[n], q_lo <= n <= q_hi                             (NaN compares false)
+ *   n*     = the LOWEST n in [q_lo, q_hi] with c[n] >= octave_bias * top, c[n] >= c[n-1] and c[n] >= c[n+1]; if top <= 0 or no
+ *            n qualifies: the lowest n with c[n] == top; if none (all NaN): q_lo
+ *   p      = the parabolic offset of SPSI (below, "offset") on (c[n*-1], c[n*], c[n*+1]), clamped to [-0.5, 0.5]
+ *   raw[t] = 22050.0f / ((float)n* + p);  strength[t] = c[n*];  voiced[t] = strength[t] >= threshold   (NaN: unvoiced)
+ * The lowest qualifying local maximum, not the plain argmax, keeps a rahmonic (the peak at twice the period) from being taken
+ * for the period; octave_bias = 1 is the plain argmax.
+ * Per utterance (device; comparisons and selections only, hence exact -- a raw value is a positive float, whose order is the
+ * order of its bit pattern):
+ *   f0[t] = voiced[t] ? the LOWER median of {raw[u] : |u - t| <= 2, 0 <= u < F, voiced[u]} : 0    (index (n - 1) / 2 of the sorted)
+ *   stats : n_frames, n_voiced, median_hz = the lower median of the voiced f0[t] (0 if none), min_hz, max_hz over them (0 if none)
+ * Target xdtts_pitch_target {mode, value, range}, default {0, 1, 1}: mode 0 none, 1 `value` in Hz in [50, 1000], 2 `value` a
+ * factor in [0.5, 2]; range in [0, 4]: 1 leaves the intonation, 0 flattens it to the median, 2 doubles every excursion in
+ * log-frequency.  The IDENTITY is range == 1 with mode 0, or with mode 2 and value == 1: it launches nothing and returns the
+ * bits of the entry without a target (xdtts_griffinlim_last_f0 then reports n = 0).
+ *   base     = mode 1: value / median_hz;  mode 2: value;  mode 0: 1           (n_voiced == 0: base = 1 and every ratio is 1)
+ *   ratio[t] = voiced[t] ? exp2(log2(base) + (range - 1) * (log2(f0[t]) - log2(median_hz))) : base
+ *   ratio[t] = fminf(fmaxf(ratio[t], 0.5f), 2.0f);  stats.n_clamped counts the frames the clamp changed;  stats.base_ratio = base
+ * Every operation is rounded to fp32 on its own (nothing is fused); log2 and exp2 are the CORRECTLY ROUNDED fp32 functions
+ * (taken in double and rounded once, on the device as in xdtts_f0_track_reference), so host and device agree.  The new pitch
+ * of frame t is f0[t] ratio[t] = T (f0[t] / median)^range with T = base median.
+ * Application: ratio is multiplied, on the device, into the per-frame pitch array of a contour table, the product clamped to
+ * [0.5, 2] again, and k_prosody_contour runs as for a contour.  Without a caller's contour the table is the rate-1 one (c[m] =
+ * 65536 m, pitch 1, gain 1, F' = F, lifter 30, log_floor 1e-5); with one, rate and gain are the contour's and pitch_m =
+ * clamp(contour pitch_m * ratio[m]).  F' depends on the rate alone: the host knows every size before anything is enqueued.
+ * An utterance under a target that is not the identity takes what a contour that is not the identity takes, 2 <= F <= 16384;
+ * the tracker alone takes 1 <= F <= 16384 per utterance.  Batch == single, bit for bit: a frame needs nothing of its
+ * neighbours, and one workgroup owns an utterance's selection.
+ * Limits: through mel -> linear (pinv of the 80 mel bands) a 90 Hz voice gives a strength near 0.1 -- the bands no longer
+ * resolve its harmonics -- and 70 Hz is lost; on an analysed magnitude (xdtts_griffinlim_f0_audio) the range holds.  Audio
+ * that came out of the Griffin-Lim loop carries a weaker peak than its source (about 0.15 against 0.4 for a synthetic voice
+ * after 30 iterations, beside 0.14 for white noise): its period is tracked all the same, so give such audio a lower threshold.
+ * Out of scope: the sequence and document entries; targets in semitones (the host converts them to a factor, mode 2); voices
+ * whose harmonics the mel bands do not resolve. */
+typedef struct { float fmin, fmax, threshold, octave_bias, log_floor; } xdtts_f0_opts;      /* 20 bytes */
+typedef struct { int32_t mode; float value, range; } xdtts_pitch_target;                    /* 12 bytes */
+typedef struct {
+  int32_t n_frames, n_voiced, n_clamped;
+  float   median_hz, min_hz, max_hz, base_ratio;
+} xdtts_f0_stats;                                                                            /* 28 bytes */
+void xdtts_f0_opts_default(xdtts_f0_opts *o);
+void xdtts_pitch_target_default(xdtts_pitch_target *t);
+/* Host arithmetic, no handle, no device.  _plan: the rules and the quefrency range (either pointer may be NULL).
+ * _track_reference: the utterance stage from given raw / strength arrays (n_frames >= 1 entries each; a voiced raw value must
+ * be positive) -- f0_out, ratio_out (n_frames each) and stats may each be NULL; t == NULL: the default target. */
+xdtts_status xdtts_f0_plan(const xdtts_f0_opts *o, int32_t *q_lo, int32_t *q_hi);
+xdtts_status xdtts_f0_track_reference(const float *raw, const float *strength, size_t n_frames, const xdtts_f0_opts *o,
+                                      const xdtts_pitch_target *t, float *f0_out, float *ratio_out, xdtts_f0_stats *stats);
+/* The tracker alone on the caller's magnitude S (n_bins x F, as everywhere at the boundary): raw_out, strength_out, f0_out
+ * (F floats each) and stats may each be NULL.  The ragged form runs ONE k_f0_frames launch over all rows and one k_f0_track
+ * workgroup per utterance; each output equals the single call's bit for bit.  last_timings: ms[0] = k_f0_frames, ms[1] =
+ * k_f0_track, ms[2] = both. */
+xdtts_status xdtts_griffinlim_f0_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_f0_opts *o,
+                                        float *raw_out, float *strength_out, float *f0_out, xdtts_f0_stats *stats);
+xdtts_status xdtts_griffinlim_f0_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
+                                              const xdtts_f0_opts *o, float *const *raw_outs, float *const *strength_outs,
+                                              float *const *f0_outs, xdtts_f0_stats *stats /* [n_utt] or NULL */);
+/* ... from a mel (the handle's mel -> linear, then the stage), and from audio (k_stft_mag of the analysis entries, then the
+ * stage; the outputs hold xdtts_griffinlim_analysis_frames(n_samples) entries). */
+xdtts_status xdtts_griffinlim_f0(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames, const xdtts_f0_opts *o,
+                                 float *raw_out, float *strength_out, float *f0_out, xdtts_f0_stats *stats);
+xdtts_status xdtts_griffinlim_f0_audio(xdtts_griffinlim *g, const float *audio, size_t n_samples, const xdtts_f0_opts *o,
+                                       float *raw_out, float *strength_out, float *f0_out, xdtts_f0_stats *stats);
+/* Parity hooks of the application: tracker, ratios, table and k_prosody_contour on the caller's magnitude.  c (c[u]) may be
+ * NULL: no contour.  S_out (n_bins x F', F' = xdtts_prosody_contour_frames of the contour, F without one), ratio_out (F floats)
+ * and stats may each be NULL.  An utterance whose target and contour are both the identity is copied, its ratios are 1. */
+xdtts_status xdtts_griffinlim_pitch_target_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_f0_opts *o,
+                                                  const xdtts_pitch_target *t, const xdtts_prosody_contour *c, float *S_out,
+                                                  float *ratio_out, xdtts_f0_stats *stats);
+xdtts_status xdtts_griffinlim_pitch_target_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames,
+                                                        int32_t n_utt, const xdtts_f0_opts *o, const xdtts_pitch_target *t /* [n_utt] */,
+                                                        const xdtts_prosody_contour *const *c /* [n_utt] or NULL */,
+                                                        float *const *S_outs, float *const *ratio_outs,
+                                                        xdtts_f0_stats *stats /* [n_utt] or NULL */);
+/* xdtts_griffinlim_infer / _infer_batch with the tracker and the target between mel -> linear and the contour stage: both
+ * kernels go onto the handle's stream, the stats travel to a pinned buffer by a copy on the same stream and are collected by
+ * the call's final synchronisation (no extra host wait); last_timings ms[0] covers everything in front of the loop.  The batch
+ * form takes one target per utterance, one `o` per call and contours that may be NULL per utterance (c == NULL: none at all); it
+ * follows the array rules above xdtts_griffinlim_infer_batch_prosody, and with opts.batch_shape = 4 audios[u] is the single
+ * call's, bit for bit.  A retry on the fallback engine recomputes from the intact S. */
+xdtts_status xdtts_griffinlim_infer_pitch_target(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
+                                                 const xdtts_f0_opts *o, const xdtts_pitch_target *t, const xdtts_prosody_contour *c,
+                                                 float **audio, size_t *n_samples);
+xdtts_status xdtts_griffinlim_infer_batch_pitch_target(xdtts_griffinlim *g, const float *const *mels, size_t n_mels,
+                                                       const size_t *n_frames, int32_t n_utt, const xdtts_f0_opts *o,
+                                                       const xdtts_pitch_target *t /* [n_utt] */,
+                                                       const xdtts_prosody_contour *const *c /* [n_utt] or NULL */,
+                                                       float **audios, size_t *n_samples);
+/* The stats of each utterance of the last call that ran the tracker (a target entry, a hook or a tracker entry), in the caller's
+ * order, shaped like xdtts_griffinlim_last_loudness; every delivering call clears them first, so *n = 0 after one that ran
+ * no tracker (a plain entry, or targets that were all the identity). */
+xdtts_status xdtts_griffinlim_last_f0(const xdtts_griffinlim *g, xdtts_f0_stats *out, size_t cap, size_t *n);
 
 /* The initial phase of the loop.  Mode 0 (the default, the crate's behaviour) draws it from the seeded random stream; mode 1
  * computes it from the magnitude by Single Pass Spectrogram Inversion (Beauregard, Harish, Wyse 2015), which lowers the
@@ -787,6 +894,24 @@ xdtts_status xdtts_synthesize_batch_contour(xdtts_tacotron2 *h, xdtts_griffinlim
                                             const xdtts_infer_opts *opts, const int32_t *fixed_steps_per_item,
                                             const xdtts_prosody_contour *c /* [n_utt] */, float **mels, size_t *n_frames,
                                             float **audios, size_t *n_samples);
+/* xdtts_synthesize_ids and xdtts_synthesize_batch with a pitch target (xdtts_pitch_target, above; o == NULL: the default
+ * options; c, or an element of it, may be NULL: no contour): the mel is the plain entry's, bit for bit, the audio goes through
+ * the tracker, the target and the contour stage.  The frame count is known only behind the decoder, so the rule on it (2 ..
+ * 16384 under a target that is not the identity) is reported then, before anything of the vocoder is enqueued.  Results equal
+ * the mel entries followed by xdtts_griffinlim_infer_pitch_target / _infer_batch_pitch_target bit for bit;
+ * xdtts_griffinlim_last_f0 returns the stats. */
+xdtts_status xdtts_synthesize_ids_pitch_target(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
+                                               const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts,
+                                               const xdtts_f0_opts *o, const xdtts_pitch_target *t,
+                                               const xdtts_prosody_contour *c, float **mel, size_t *n_frames, float **audio,
+                                               size_t *n_samples);
+xdtts_status xdtts_synthesize_batch_pitch_target(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids,
+                                                 const int32_t *lens, int32_t B, int32_t t_stride,
+                                                 const int32_t *utt_chunks, int32_t n_utt,
+                                                 const xdtts_infer_opts *opts, const int32_t *fixed_steps_per_item,
+                                                 const xdtts_f0_opts *o, const xdtts_pitch_target *t /* [n_utt] */,
+                                                 const xdtts_prosody_contour *const *c /* [n_utt] or NULL */, float **mels,
+                                                 size_t *n_frames, float **audios, size_t *n_samples);
 
 /* XdTts::infer (src/lib.rs:110-159) for a SEQUENCE of n_utt utterances, each decoded alone (batch 1) exactly as
  * xdtts_synthesize_ids does it -- what a loop over src/lib.rs:122-141 does -- with the vocoder of utterance u overlapped with the

@@ -236,6 +236,118 @@ class GriffinLim {
     }
     return out;
   }
+  // Pitch tracking on the device and pitch targets (xdtts_f0_opts, xdtts_pitch_target: an absolute median pitch in Hz and / or a
+  // scaled pitch range, what SSML pitch="180Hz" and range= ask for).  The tracker alone, from a
+  // magnitude (xdtts_griffinlim_f0_linear), a mel (xdtts_griffinlim_f0) or audio at 22 050 Hz (xdtts_griffinlim_f0_audio);
+  // o == nullptr: the default options.
+  struct F0Track {
+    std::vector<float> raw, strength, f0;  // per frame: raw F0 in Hz, the cepstral peak, the smoothed F0 (0 = unvoiced)
+    xdtts_f0_stats stats{};
+  };
+  F0Track f0_linear(const Array2 &S, const xdtts_f0_opts *o = nullptr) const {
+    F0Track t{std::vector<float>(S.cols), std::vector<float>(S.cols), std::vector<float>(S.cols)};
+    check(xdtts_griffinlim_f0_linear(g_, S.data.data(), S.cols, o, t.raw.data(), t.strength.data(), t.f0.data(), &t.stats));
+    return t;
+  }
+  std::vector<F0Track> f0_linear_batch(const std::vector<Array2> &S, const xdtts_f0_opts *o = nullptr) const {
+    const size_t n = S.size();
+    std::vector<F0Track> out(n);
+    std::vector<const float *> sp(n);
+    std::vector<float *> rp(n), tp(n), fp(n);
+    std::vector<size_t> nf(n);
+    std::vector<xdtts_f0_stats> st(n);
+    for (size_t u = 0; u < n; ++u) {
+      out[u] = F0Track{std::vector<float>(S[u].cols), std::vector<float>(S[u].cols), std::vector<float>(S[u].cols)};
+      sp[u] = S[u].data.data();
+      rp[u] = out[u].raw.data();
+      tp[u] = out[u].strength.data();
+      fp[u] = out[u].f0.data();
+      nf[u] = S[u].cols;
+    }
+    check(xdtts_griffinlim_f0_linear_batch(g_, sp.data(), nf.data(), (int32_t)n, o, rp.data(), tp.data(), fp.data(), st.data()));
+    for (size_t u = 0; u < n; ++u) out[u].stats = st[u];
+    return out;
+  }
+  F0Track f0(const Array2 &mel, const xdtts_f0_opts *o = nullptr) const {
+    F0Track t{std::vector<float>(mel.cols), std::vector<float>(mel.cols), std::vector<float>(mel.cols)};
+    check(xdtts_griffinlim_f0(g_, mel.data.data(), mel.rows, mel.cols, o, t.raw.data(), t.strength.data(), t.f0.data(), &t.stats));
+    return t;
+  }
+  F0Track f0_audio(const std::vector<float> &audio, const xdtts_f0_opts *o = nullptr) const {
+    const size_t F = xdtts_griffinlim_analysis_frames(g_, audio.size());
+    F0Track t{std::vector<float>(F), std::vector<float>(F), std::vector<float>(F)};
+    check(xdtts_griffinlim_f0_audio(g_, audio.data(), audio.size(), o, t.raw.data(), t.strength.data(), t.f0.data(), &t.stats));
+    return t;
+  }
+  // ... infer() with the tracker, the target and the contour stage between mel -> linear and the loop
+  // (xdtts_griffinlim_infer_pitch_target; c == nullptr: no contour), and for several utterances (one target each, contours that
+  // may be null: xdtts_griffinlim_infer_batch_pitch_target).  last_f0() then returns the stats.
+  std::vector<float> infer(const Array2 &mel, const xdtts_pitch_target &t, const xdtts_prosody_contour *c = nullptr,
+                           const xdtts_f0_opts *o = nullptr) const {
+    float *audio = nullptr;
+    size_t n = 0;
+    check(xdtts_griffinlim_infer_pitch_target(g_, mel.data.data(), mel.rows, mel.cols, o, &t, c, &audio, &n));
+    std::vector<float> out(audio, audio + n);
+    xdtts_free(audio);
+    return out;
+  }
+  std::vector<std::vector<float>> infer_batch(const std::vector<Array2> &mels, const std::vector<xdtts_pitch_target> &t,
+                                              const std::vector<const xdtts_prosody_contour *> *c = nullptr,
+                                              const xdtts_f0_opts *o = nullptr) const {
+    const size_t n = mels.size();
+    if (t.size() != n || (c && c->size() != n)) throw std::runtime_error("xdtts: one pitch target (and contour pointer) per utterance");
+    std::vector<const float *> mp(n);
+    std::vector<size_t> nf(n), ns(n, 0);
+    std::vector<float *> audios(n, nullptr);
+    for (size_t u = 0; u < n; ++u) {
+      mp[u] = mels[u].data.data();
+      nf[u] = mels[u].cols;
+    }
+    check(xdtts_griffinlim_infer_batch_pitch_target(g_, mp.data(), n ? mels[0].rows : 0, nf.data(), (int32_t)n, o, t.data(),
+                                                    c ? c->data() : nullptr, audios.data(), ns.data()));
+    std::vector<std::vector<float>> out(n);
+    for (size_t u = 0; u < n; ++u) {
+      out[u].assign(audios[u], audios[u] + ns[u]);
+      xdtts_free(audios[u]);
+    }
+    return out;
+  }
+  // ... the application alone (parity hooks: xdtts_griffinlim_pitch_target_linear and its ragged form): S' and the ratios
+  std::pair<Array2, std::vector<float>> pitch_target_linear(const Array2 &S, const xdtts_pitch_target &t, const xdtts_prosody_contour *c = nullptr,
+                                                            const xdtts_f0_opts *o = nullptr, xdtts_f0_stats *stats = nullptr) const {
+    const size_t Fp = c ? xdtts_prosody_contour_frames(c, S.cols) : S.cols;
+    std::pair<Array2, std::vector<float>> out{Array2{n_bins_, Fp, std::vector<float>(n_bins_ * (Fp ? Fp : 1))}, std::vector<float>(S.cols)};
+    check(xdtts_griffinlim_pitch_target_linear(g_, S.data.data(), S.cols, o, &t, c, out.first.data.data(), out.second.data(), stats));
+    return out;
+  }
+  std::vector<Array2> pitch_target_linear_batch(const std::vector<Array2> &S, const std::vector<xdtts_pitch_target> &t,
+                                                const std::vector<const xdtts_prosody_contour *> *c = nullptr,
+                                                const xdtts_f0_opts *o = nullptr) const {
+    const size_t n = S.size();
+    if (t.size() != n || (c && c->size() != n)) throw std::runtime_error("xdtts: one pitch target (and contour pointer) per utterance");
+    std::vector<Array2> out(n);
+    std::vector<const float *> sp(n);
+    std::vector<float *> op(n);
+    std::vector<size_t> nf(n);
+    for (size_t u = 0; u < n; ++u) {
+      const size_t Fp = c && (*c)[u] ? xdtts_prosody_contour_frames((*c)[u], S[u].cols) : S[u].cols;
+      out[u] = Array2{n_bins_, Fp, std::vector<float>(n_bins_ * (Fp ? Fp : 1))};
+      sp[u] = S[u].data.data();
+      op[u] = out[u].data.data();
+      nf[u] = S[u].cols;
+    }
+    check(xdtts_griffinlim_pitch_target_linear_batch(g_, sp.data(), nf.data(), (int32_t)n, o, t.data(), c ? c->data() : nullptr, op.data(),
+                                                     nullptr, nullptr));
+    return out;
+  }
+  // The stats of the last call that ran the tracker, one per utterance (xdtts_griffinlim_last_f0)
+  std::vector<xdtts_f0_stats> last_f0() const {
+    size_t n = 0;
+    check(xdtts_griffinlim_last_f0(g_, nullptr, 0, &n));
+    std::vector<xdtts_f0_stats> out(n);
+    if (n) check(xdtts_griffinlim_last_f0(g_, out.data(), out.size(), &n));
+    return out;
+  }
   // The conventions of the crate's mel->linear step as switches (xdtts_griffinlim_opts)
   void set_opts(const xdtts_griffinlim_opts &o) { check(xdtts_griffinlim_set_opts(g_, &o)); }
   xdtts_griffinlim_opts opts() const {
@@ -487,16 +599,76 @@ inline std::pair<Array2, std::vector<float>> infer_contour(const Tacotron2 &mode
   return out;
 }
 
+// ... and with a pitch target (xdtts_synthesize_ids_pitch_target): the utterance's own F0 is tracked on the device and its median
+// moved to an absolute pitch and / or its range scaled; contour: null or a contour to combine with; f0: null = the default options.
+inline xdtts_f0_opts f0_opts_default() {
+  xdtts_f0_opts o;
+  xdtts_f0_opts_default(&o);
+  return o;
+}
+inline xdtts_pitch_target pitch_target_default() {
+  xdtts_pitch_target t;
+  xdtts_pitch_target_default(&t);
+  return t;
+}
+inline std::pair<int, int> f0_plan(const xdtts_f0_opts *o = nullptr) {  // (q_lo, q_hi) -- xdtts_f0_plan
+  int32_t lo = 0, hi = 0;
+  check(xdtts_f0_plan(o, &lo, &hi));
+  return {lo, hi};
+}
+// The utterance stage on the host (xdtts_f0_track_reference): raw / strength -> (f0, ratio), stats if wanted
+inline std::pair<std::vector<float>, std::vector<float>> f0_track_reference(const std::vector<float> &raw, const std::vector<float> &strength,
+                                                                             const xdtts_pitch_target *t = nullptr, const xdtts_f0_opts *o = nullptr,
+                                                                             xdtts_f0_stats *stats = nullptr) {
+  if (raw.size() != strength.size()) throw std::runtime_error("xdtts: raw and strength have one length");
+  std::pair<std::vector<float>, std::vector<float>> out{std::vector<float>(raw.size()), std::vector<float>(raw.size())};
+  check(xdtts_f0_track_reference(raw.data(), strength.data(), raw.size(), o, t, out.first.data(), out.second.data(), stats));
+  return out;
+}
+inline std::pair<Array2, std::vector<float>> infer_pitch_target(const Tacotron2 &model, const GriffinLim &vocoder, const std::vector<Unit> &units,
+                                                                 const xdtts_pitch_target &target, const ProsodyContour *contour = nullptr,
+                                                                 const xdtts_f0_opts *f0 = nullptr, const xdtts_infer_opts *opts = nullptr) {
+  xdtts_infer_opts o;
+  xdtts_infer_opts_default(&o);
+  if (opts) o = *opts;
+  std::vector<int64_t> ids;
+  for (const Unit &u : units) {
+    const int64_t id = xdtts_unit_id(u.token.c_str(), u.is_character ? 1 : 0);
+    if (id >= 0) ids.push_back(id);
+  }
+  std::vector<size_t> splits(ids.size() + 2);
+  size_t n_splits = 0;
+  check(xdtts_find_splits(ids.data(), ids.size(), (size_t)o.max_chunk, splits.data(), splits.size(), &n_splits));
+  float *mel = nullptr, *audio = nullptr;
+  size_t nf = 0, ns = 0;
+  xdtts_prosody_contour c;
+  if (contour) c = contour->c();
+  check(xdtts_synthesize_ids_pitch_target(model.raw(), vocoder.raw(), ids.data(), ids.size(), splits.data(), n_splits, &o, f0, &target,
+                                          contour ? &c : nullptr, &mel, &nf, &audio, &ns));
+  std::pair<Array2, std::vector<float>> out;
+  out.first.rows = 80;
+  out.first.cols = nf;
+  out.first.data.assign(mel, mel + 80 * nf);
+  out.second.assign(audio, audio + ns);
+  xdtts_free(mel);
+  xdtts_free(audio);
+  return out;
+}
+
 // XdTts::infer (src/lib.rs:110-159) for several utterances in one call (xdtts_synthesize_batch): units -> ids
 // (units with no id are dropped, mod.rs:403-406), find_splits per utterance (mod.rs:399,412-414), all chunks in one
 // lock-step batch, the mel kept in HBM between mel-gen and vocoder.  Returns (mel, audio) per utterance.
 // (prosody: null, or one per text -- xdtts_synthesize_batch_prosody: the mels stay Tacotron2's own, the audios are the modified ones;
-// contour: null, or one per text -- xdtts_synthesize_batch_contour; not both)
+// contour: null, or one per text -- xdtts_synthesize_batch_contour; not both.  target: null, or one pitch target per text --
+// xdtts_synthesize_batch_pitch_target, alone or with `contour`; f0: its tracker options, null = the default)
 inline std::vector<std::pair<Array2, std::vector<float>>> infer_many(const Tacotron2 &model, const GriffinLim &vocoder,
                                                                        const std::vector<std::vector<Unit>> &texts,
                                                                        const xdtts_infer_opts *opts = nullptr,
                                                                        const std::vector<xdtts_prosody> *prosody = nullptr,
-                                                                       const std::vector<ProsodyContour> *contour = nullptr) {
+                                                                       const std::vector<ProsodyContour> *contour = nullptr,
+                                                                       const std::vector<xdtts_pitch_target> *target = nullptr,
+                                                                       const xdtts_f0_opts *f0 = nullptr) {
+  if (target && (target->size() != texts.size() || prosody)) throw std::runtime_error("xdtts: one pitch target per text, and no uniform prosody beside it");
   if (prosody && prosody->size() != texts.size()) throw std::runtime_error("xdtts: one prosody per text");
   if (contour && contour->size() != texts.size()) throw std::runtime_error("xdtts: one contour per text");
   if (prosody && contour) throw std::runtime_error("xdtts: a prosody or a contour per text, not both");
@@ -533,7 +705,17 @@ inline std::vector<std::pair<Array2, std::vector<float>>> infer_many(const Tacot
   const size_t n_utt = texts.size();
   std::vector<float *> mels(n_utt, nullptr), audios(n_utt, nullptr);
   std::vector<size_t> nf(n_utt, 0), ns(n_utt, 0);
-  if (contour) {
+  if (target) {
+    std::vector<xdtts_prosody_contour> cs;
+    std::vector<const xdtts_prosody_contour *> cp;
+    if (contour) {
+      for (const ProsodyContour &c : *contour) cs.push_back(c.c());
+      for (const xdtts_prosody_contour &c : cs) cp.push_back(&c);
+    }
+    check(xdtts_synthesize_batch_pitch_target(model.raw(), vocoder.raw(), ids.data(), lens.data(), (int32_t)lens.size(), (int32_t)T, utt_chunks.data(),
+                                              (int32_t)n_utt, &o, nullptr, f0, target->data(), contour ? cp.data() : nullptr, mels.data(), nf.data(),
+                                              audios.data(), ns.data()));
+  } else if (contour) {
     std::vector<xdtts_prosody_contour> cs;
     for (const ProsodyContour &c : *contour) cs.push_back(c.c());
     check(xdtts_synthesize_batch_contour(model.raw(), vocoder.raw(), ids.data(), lens.data(), (int32_t)lens.size(), (int32_t)T, utt_chunks.data(),

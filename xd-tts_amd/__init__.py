@@ -86,6 +86,61 @@ class ProsodyContour(C.Structure):
             self.log_floor = log_floor
 
 
+class F0Opts(C.Structure):
+    """xdtts_f0_opts: the pitch tracker's search range in Hz (50 <= fmin < fmax <= 1000), the voicing threshold on the cepstral
+    peak (>= 0), octave_bias in (0, 1] (1 = the plain argmax; lower prefers the first peak over a rahmonic) and log_floor > 0.
+    F0Opts() holds the library's defaults (60, 400, 0.2, 0.9, 1e-5); keywords override fields."""
+
+    _fields_ = [("fmin", C.c_float), ("fmax", C.c_float), ("threshold", C.c_float), ("octave_bias", C.c_float), ("log_floor", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib.xdtts_f0_opts_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+PITCH_NONE, PITCH_HZ, PITCH_FACTOR = 0, 1, 2
+
+
+class PitchTarget(C.Structure):
+    """xdtts_pitch_target: mode 0 none, 1 `value` an absolute median pitch in Hz (50 .. 1000), 2 `value` a factor (0.5 .. 2);
+    range in [0, 4] scales every frame's excursion from the median in log-frequency (1 leaves it, 0 flattens, 2 doubles).
+    PitchTarget() is the identity {0, 1, 1}; PitchTarget(hz=180), PitchTarget(factor=1.1, range=0.5)."""
+
+    _fields_ = [("mode", C.c_int32), ("value", C.c_float), ("range", C.c_float)]
+
+    def __init__(self, hz=None, factor=None, range=None, mode=None, value=None):
+        super().__init__()
+        lib.xdtts_pitch_target_default(C.byref(self))
+        if hz is not None and factor is not None:
+            raise ValueError("pass hz= or factor=, not both")
+        if hz is not None:
+            self.mode, self.value = PITCH_HZ, hz
+        if factor is not None:
+            self.mode, self.value = PITCH_FACTOR, factor
+        if mode is not None:
+            self.mode = mode
+        if value is not None:
+            self.value = value
+        if range is not None:
+            self.range = range
+
+
+class F0Stats(C.Structure):
+    """xdtts_f0_stats: what the tracker found in one utterance, and what a target did with it."""
+
+    _fields_ = [("n_frames", C.c_int32), ("n_voiced", C.c_int32), ("n_clamped", C.c_int32), ("median_hz", C.c_float), ("min_hz", C.c_float),
+                ("max_hz", C.c_float), ("base_ratio", C.c_float)]
+
+    def astuple(self):
+        return (self.n_frames, self.n_voiced, self.n_clamped, self.median_hz, self.min_hz, self.max_hz, self.base_ratio)
+
+    def bits(self):
+        """The struct's bytes: what `bit for bit` compares (a float's NaN or -0 included)."""
+        return bytes(self)
+
+
 class Loudness(C.Structure):
     """xdtts_loudness: the BS.1770 measurement of one utterance and the gain that was applied.  .lufs is the integrated
     loudness (-inf where no block passed the gates)."""
@@ -208,6 +263,19 @@ SYMBOLS = {
     "xdtts_griffinlim_contour_linear_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP, _VP]),
     "xdtts_griffinlim_infer_contour": (_I32, [_VP, _VP, _SZ, _SZ, C.POINTER(ProsodyContour), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_griffinlim_infer_batch_contour": (_I32, [_VP, _VP, _SZ, _VP, _I32, _VP, _VP, _VP]),
+    "xdtts_f0_opts_default": (None, [C.POINTER(F0Opts)]),
+    "xdtts_pitch_target_default": (None, [C.POINTER(PitchTarget)]),
+    "xdtts_f0_plan": (_I32, [C.POINTER(F0Opts), C.POINTER(_I32), C.POINTER(_I32)]),
+    "xdtts_f0_track_reference": (_I32, [_VP, _VP, _SZ, C.POINTER(F0Opts), C.POINTER(PitchTarget), _VP, _VP, C.POINTER(F0Stats)]),
+    "xdtts_griffinlim_f0_linear": (_I32, [_VP, _VP, _SZ, C.POINTER(F0Opts), _VP, _VP, _VP, C.POINTER(F0Stats)]),
+    "xdtts_griffinlim_f0_linear_batch": (_I32, [_VP, _VP, _VP, _I32, C.POINTER(F0Opts), _VP, _VP, _VP, _VP]),
+    "xdtts_griffinlim_f0": (_I32, [_VP, _VP, _SZ, _SZ, C.POINTER(F0Opts), _VP, _VP, _VP, C.POINTER(F0Stats)]),
+    "xdtts_griffinlim_f0_audio": (_I32, [_VP, _VP, _SZ, C.POINTER(F0Opts), _VP, _VP, _VP, C.POINTER(F0Stats)]),
+    "xdtts_griffinlim_pitch_target_linear": (_I32, [_VP, _VP, _SZ, C.POINTER(F0Opts), C.POINTER(PitchTarget), C.POINTER(ProsodyContour), _VP, _VP, C.POINTER(F0Stats)]),
+    "xdtts_griffinlim_pitch_target_linear_batch": (_I32, [_VP, _VP, _VP, _I32, C.POINTER(F0Opts), _VP, _VP, _VP, _VP, _VP]),
+    "xdtts_griffinlim_infer_pitch_target": (_I32, [_VP, _VP, _SZ, _SZ, C.POINTER(F0Opts), C.POINTER(PitchTarget), C.POINTER(ProsodyContour), C.POINTER(_PF), C.POINTER(_SZ)]),
+    "xdtts_griffinlim_infer_batch_pitch_target": (_I32, [_VP, _VP, _SZ, _VP, _I32, C.POINTER(F0Opts), _VP, _VP, _VP, _VP]),
+    "xdtts_griffinlim_last_f0": (_I32, [_VP, _VP, _SZ, C.POINTER(_SZ)]),
     "xdtts_griffinlim_set_phase_init": (_I32, [_VP, _I32]),
     "xdtts_griffinlim_get_phase_init": (_I32, [_VP, C.POINTER(_I32)]),
     "xdtts_griffinlim_spsi_phase": (_I32, [_VP, _VP, _SZ, _VP, _VP]),
@@ -248,6 +316,8 @@ SYMBOLS = {
     "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_contour": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(ProsodyContour), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_batch_contour": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "xdtts_synthesize_ids_pitch_target": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(F0Opts), C.POINTER(PitchTarget), C.POINTER(ProsodyContour), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
+    "xdtts_synthesize_batch_pitch_target": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, C.POINTER(F0Opts), _VP, _VP, _VP, _VP, _VP, _VP]),
     "xdtts_synthesize_batch": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP]),
     "xdtts_synthesize_sequence": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP]),
     "xdtts_synthesize_batch_prosody": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP, _VP]),
@@ -343,6 +413,28 @@ def _contour_array(contour, n):
         arr[u].points, arr[u].n_points, arr[u].lifter, arr[u].log_floor = c.points, c.n_points, c.lifter, c.log_floor
     arr._keep = cs  # the point arrays
     return arr
+
+
+def _target_arrays(targets, contours, n):
+    """n PitchTarget (and n ProsodyContour or None each, or None for none at all) -> the C arrays the target entries take:
+    xdtts_pitch_target[n] and an array of n contour pointers.  The third value keeps the contours alive."""
+    ts = list(targets)
+    if len(ts) != n:
+        raise ValueError("target= takes one PitchTarget per utterance: %d for %d utterances" % (len(ts), n))
+    ta = (PitchTarget * n)()
+    for u, t in enumerate(ts):
+        ta[u].mode, ta[u].value, ta[u].range = t.mode, t.value, t.range
+    if contours is None:
+        return ta, None, None
+    cs = list(contours)
+    if len(cs) != n:
+        raise ValueError("contour= takes one ProsodyContour (or None) per utterance: %d for %d utterances" % (len(cs), n))
+    ca = (C.c_void_p * n)(*[(None if c is None else C.addressof(c)) for c in cs])
+    return ta, ca, cs
+
+
+def _opt_ref(x):
+    return None if x is None else C.byref(x)
 
 
 def _one_of(prosody, contour):
@@ -897,6 +989,104 @@ class GriffinLim:
         _check(lib.xdtts_griffinlim_infer_contour(self._h, _ptr(mel), mel.shape[0], mel.shape[1], C.byref(contour), C.byref(audio), C.byref(n)))
         return _take(audio, n.value, (n.value,))
 
+    # -- pitch tracker and pitch targets: F0 per frame on the device, absolute-Hz targets and the pitch range ----
+    def _f0_outs(self, Fs):
+        n = len(Fs)
+        raw, strength, f0 = ([np.empty(F, dtype=np.float32) for F in Fs] for _ in range(3))
+        stats = (F0Stats * n)()
+        return raw, strength, f0, stats
+
+    def f0_linear_batch(self, S_list, opts=None):
+        """The tracker alone on magnitudes S_u (n_bins, F_u), one k_f0_frames launch over all of them: (raw, strength, f0, stats),
+        a list of one entry per utterance each -- raw F0 in Hz and the cepstral peak per frame, the smoothed F0 (0 = unvoiced),
+        and an F0Stats."""
+        Ss = [np.ascontiguousarray(S, dtype=np.float32) for S in S_list]
+        n = len(Ss)
+        raw, strength, f0, stats = self._f0_outs([S.shape[1] for S in Ss])
+        sp = (C.c_void_p * n)(*[S.ctypes.data for S in Ss])
+        nf = (C.c_size_t * n)(*[S.shape[1] for S in Ss])
+        ptrs = [(C.c_void_p * n)(*[a.ctypes.data for a in arrs]) for arrs in (raw, strength, f0)]
+        _check(lib.xdtts_griffinlim_f0_linear_batch(self._h, sp, nf, n, _opt_ref(opts), ptrs[0], ptrs[1], ptrs[2], stats))
+        return raw, strength, f0, list(stats)
+
+    def f0_linear(self, S, opts=None):
+        """The tracker alone on one magnitude S (n_bins, F): (raw, strength, f0, stats)."""
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        raw, strength, f0, stats = self._f0_outs([S.shape[1]])
+        _check(lib.xdtts_griffinlim_f0_linear(self._h, _ptr(S), S.shape[1], _opt_ref(opts), _ptr(raw[0]), _ptr(strength[0]), _ptr(f0[0]), C.byref(stats[0])))
+        return raw[0], strength[0], f0[0], stats[0]
+
+    def f0(self, mel, opts=None):
+        """The tracker on a mel (n_mels, F) through the handle's mel -> linear: (raw, strength, f0, stats)."""
+        mel = np.ascontiguousarray(mel, dtype=np.float32)
+        raw, strength, f0, stats = self._f0_outs([mel.shape[1]])
+        _check(lib.xdtts_griffinlim_f0(self._h, _ptr(mel), mel.shape[0], mel.shape[1], _opt_ref(opts), _ptr(raw[0]), _ptr(strength[0]), _ptr(f0[0]), C.byref(stats[0])))
+        return raw[0], strength[0], f0[0], stats[0]
+
+    def f0_audio(self, audio, opts=None):
+        """The tracker on audio at 22 050 Hz (the analysis entries' STFT magnitude, then the stage): (raw, strength, f0, stats),
+        analysis_frames(len(audio)) entries each."""
+        audio = np.ascontiguousarray(audio, dtype=np.float32)
+        raw, strength, f0, stats = self._f0_outs([audio.size // 256 + 1])
+        _check(lib.xdtts_griffinlim_f0_audio(self._h, _ptr(audio), audio.size, _opt_ref(opts), _ptr(raw[0]), _ptr(strength[0]), _ptr(f0[0]), C.byref(stats[0])))
+        return raw[0], strength[0], f0[0], stats[0]
+
+    def pitch_target_linear_batch(self, S_list, targets, contours=None, opts=None):
+        """The application alone (parity hook): magnitudes S_u (n_bins, F_u), one PitchTarget each and contours that may be None
+        -> (list of S'_u (n_bins, F'_u), list of ratio_u (F_u), list of F0Stats)."""
+        Ss = [np.ascontiguousarray(S, dtype=np.float32) for S in S_list]
+        n = len(Ss)
+        ta, ca, keep = _target_arrays(targets, contours, n)
+        Fp = [S.shape[1] if (keep is None or keep[u] is None) else prosody_contour_frames(keep[u], S.shape[1]) for u, S in enumerate(Ss)]
+        outs = [np.empty((self.n_bins, max(f, 1)), dtype=np.float32) for f in Fp]
+        ratios = [np.empty(S.shape[1], dtype=np.float32) for S in Ss]
+        stats = (F0Stats * n)()
+        sp = (C.c_void_p * n)(*[S.ctypes.data for S in Ss])
+        op = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        rp = (C.c_void_p * n)(*[r.ctypes.data for r in ratios])
+        nf = (C.c_size_t * n)(*[S.shape[1] for S in Ss])
+        _check(lib.xdtts_griffinlim_pitch_target_linear_batch(self._h, sp, nf, n, _opt_ref(opts), ta, ca, op, rp, stats))
+        return outs, ratios, list(stats)
+
+    def pitch_target_linear(self, S, target, contour=None, opts=None):
+        """The application alone on one magnitude: (S' (n_bins, F'), ratio (F), stats)."""
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        Fp = S.shape[1] if contour is None else prosody_contour_frames(contour, S.shape[1])
+        out = np.empty((self.n_bins, max(Fp, 1)), dtype=np.float32)
+        ratio = np.empty(S.shape[1], dtype=np.float32)
+        stats = F0Stats()
+        _check(lib.xdtts_griffinlim_pitch_target_linear(self._h, _ptr(S), S.shape[1], _opt_ref(opts), C.byref(target), _opt_ref(contour), _ptr(out), _ptr(ratio), C.byref(stats)))
+        return out, ratio, stats
+
+    def infer_pitch_target(self, mel, target, contour=None, opts=None):
+        """infer() with the tracker, the target and the contour stage behind mel -> linear; last_f0() then holds the stats."""
+        mel = np.ascontiguousarray(mel, dtype=np.float32)
+        audio, n = _PF(), C.c_size_t()
+        _check(lib.xdtts_griffinlim_infer_pitch_target(self._h, _ptr(mel), mel.shape[0], mel.shape[1], _opt_ref(opts), C.byref(target), _opt_ref(contour), C.byref(audio), C.byref(n)))
+        return _take(audio, n.value, (n.value,))
+
+    def infer_batch_pitch_target(self, mels, targets, contours=None, opts=None):
+        """infer_batch() with one PitchTarget per utterance (and contours that may be None)."""
+        ms = [np.ascontiguousarray(m, dtype=np.float32) for m in mels]
+        n = len(ms)
+        ta, ca, keep = _target_arrays(targets, contours, n)
+        ptrs = (C.c_void_p * n)(*[m.ctypes.data for m in ms])
+        nf = (C.c_size_t * n)(*[m.shape[1] for m in ms])
+        audios, ns = (_PF * n)(), (C.c_size_t * n)()
+        _check(lib.xdtts_griffinlim_infer_batch_pitch_target(self._h, ptrs, ms[0].shape[0], nf, n, _opt_ref(opts), ta, ca, audios, ns))
+        return [_take(audios[u], ns[u], (ns[u],)) for u in range(n)]
+
+    def last_f0(self):
+        """The F0Stats of each utterance of the last call that ran the tracker, in the caller's order ([] after a delivering call
+        that ran none)."""
+        n = C.c_size_t()
+        _check(lib.xdtts_griffinlim_last_f0(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return []
+        out = (F0Stats * n.value)()
+        _check(lib.xdtts_griffinlim_last_f0(self._h, out, n.value, C.byref(n)))
+        return list(out)
+
     # -- initial phase: the seeded random stream (0) or Single Pass Spectrogram Inversion (1) ----
     def set_phase_init(self, mode):
         """0: the seeded random stream (default), 1: SPSI on the magnitude that enters the loop; honoured by every entry
@@ -1123,6 +1313,24 @@ def prosody_contour_frames(contour, n_frames):
     return int(lib.xdtts_prosody_contour_frames(C.byref(contour), int(n_frames)))
 
 
+def f0_plan(opts=None):
+    """xdtts_f0_plan: (q_lo, q_hi), the quefrency range of the options (host arithmetic); raises on a bad field."""
+    lo, hi = C.c_int32(), C.c_int32()
+    _check(lib.xdtts_f0_plan(_opt_ref(opts), C.byref(lo), C.byref(hi)))
+    return lo.value, hi.value
+
+
+def f0_track_reference(raw, strength, opts=None, target=None):
+    """xdtts_f0_track_reference: the utterance stage on the host from raw / strength arrays -> (f0, ratio, F0Stats)."""
+    raw = np.ascontiguousarray(raw, dtype=np.float32)
+    strength = np.ascontiguousarray(strength, dtype=np.float32)
+    if raw.shape != strength.shape or raw.ndim != 1:
+        raise ValueError("raw and strength are two vectors of one length")
+    f0, ratio, stats = np.empty(raw.size, dtype=np.float32), np.empty(raw.size, dtype=np.float32), F0Stats()
+    _check(lib.xdtts_f0_track_reference(_ptr(raw), _ptr(strength), raw.size, _opt_ref(opts), _opt_ref(target), _ptr(f0), _ptr(ratio), C.byref(stats)))
+    return f0, ratio, stats
+
+
 def prosody_contour_table(contour, n_frames):
     """xdtts_prosody_contour_table: (c uint32, pitch float32, gain float32), n_frames entries each -- the table the device reads."""
     n = int(n_frames)
@@ -1248,17 +1456,23 @@ def synthesize_document(tacotron2, vocoder, ids_list, gaps=None, stream_opts=Non
     return out_m, out, [int(offs[u]) for u in range(n)]
 
 
-def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, contour=None):
+def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, contour=None, target=None, f0_opts=None):
     """XdTts::infer (src/lib.rs:110-159): mel-gen then vocoder, mel kept in HBM in between.  prosody= (a Prosody) changes rate
     and pitch in the vocoder (xdtts_synthesize_ids_prosody): the mel returned is Tacotron2's own, the audio the modified one.
-    contour= (a ProsodyContour) does so with values that vary inside the utterance (xdtts_synthesize_ids_contour)."""
+    contour= (a ProsodyContour) does so with values that vary inside the utterance (xdtts_synthesize_ids_contour).  target= (a
+    PitchTarget, with contour= or alone; f0_opts= an F0Opts) tracks the utterance's F0 on the device and moves its median to an
+    absolute pitch and / or scales its range (xdtts_synthesize_ids_pitch_target); vocoder.last_f0() then holds the stats."""
     _one_of(prosody, contour)
+    if target is not None and prosody is not None:
+        raise ValueError("target= goes with contour=, not with prosody=")
     ids = np.ascontiguousarray(ids, dtype=np.int64)
     sp = None if splits is None else np.ascontiguousarray(splits, dtype=np.uintp)
     mel, nf, audio, ns = _PF(), C.c_size_t(), _PF(), C.c_size_t()
     head = (tacotron2._h, vocoder._h, _ptr(ids), ids.size, None if sp is None else _ptr(sp), 0 if sp is None else sp.size, C.byref(opts) if opts else None)
     tail = (C.byref(mel), C.byref(nf), C.byref(audio), C.byref(ns))
-    if contour is not None:
+    if target is not None:
+        _check(lib.xdtts_synthesize_ids_pitch_target(*head, _opt_ref(f0_opts), C.byref(target), _opt_ref(contour), *tail))
+    elif contour is not None:
         _check(lib.xdtts_synthesize_ids_contour(*head, C.byref(contour), *tail))
     elif prosody is None:
         _check(lib.xdtts_synthesize_ids(*head, *tail))
@@ -1267,15 +1481,19 @@ def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, co
     return _take(mel, N_MEL * nf.value, (N_MEL, nf.value)), _take(audio, ns.value, (ns.value,))
 
 
-def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_steps=None, want_mels=True, prosody=None, contour=None):
+def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_steps=None, want_mels=True, prosody=None, contour=None,
+                     target=None, f0_opts=None):
     """XdTts::infer (src/lib.rs:110-159) for several utterances in one call: `utterance_chunks[u]` is the
     list of <=window-id chunks of utterance u (find_splits + the trailing split, mod.rs:399,412-414);
     `fixed_steps`, if given, holds one frame count per chunk in the same nested shape.  All chunks decode
     in one lock-step batch and the vocoder batch reads the concatenated mel in HBM.  Returns
     (mels or None, audios), one entry per utterance.  prosody= (a list of one Prosody per utterance): the mels stay Tacotron2's
     own, the audios go through the rate / pitch stage (xdtts_synthesize_batch_prosody); contour= (a list of one ProsodyContour per
-    utterance) likewise with the contour stage (xdtts_synthesize_batch_contour)."""
+    utterance) likewise with the contour stage (xdtts_synthesize_batch_contour).  target= (a list of one PitchTarget per
+    utterance; contour= may then hold None entries) runs the pitch tracker and the targets (xdtts_synthesize_batch_pitch_target)."""
     _one_of(prosody, contour)
+    if target is not None and prosody is not None:
+        raise ValueError("target= goes with contour=, not with prosody=")
     chunks = [c for u in utterance_chunks for c in u]
     B, n_utt = len(chunks), len(utterance_chunks)
     lens = np.array([len(x) for x in chunks], dtype=np.int32)
@@ -1289,7 +1507,10 @@ def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_step
     audios = (_PF * n_utt)()
     nf, ns = (C.c_size_t * n_utt)(), (C.c_size_t * n_utt)()
     head = (tacotron2._h, vocoder._h, _ptr(ids), _ptr(lens), B, stride, _ptr(uc), n_utt, C.byref(opts) if opts else None, None if fs is None else _ptr(fs))
-    if contour is not None:
+    if target is not None:
+        ta, ca, _keep = _target_arrays(target, contour, n_utt)
+        _check(lib.xdtts_synthesize_batch_pitch_target(*head, _opt_ref(f0_opts), ta, ca, mels, nf, audios, ns))
+    elif contour is not None:
         _check(lib.xdtts_synthesize_batch_contour(*head, _contour_array(contour, n_utt), mels, nf, audios, ns))
     elif prosody is None:
         _check(lib.xdtts_synthesize_batch(*head, mels, nf, audios, ns))

@@ -12,9 +12,12 @@ using namespace xdtts;
 // the utterances' frames are concatenated, mel -> linear is one GEMM over all of them, and the persistent
 // kernel takes as many utterances per launch as fit one workgroup per CU.  Every utterance's audio is bit-identical to what
 // xdtts_griffinlim_infer returns for it alone.  (pros == cont == null: xdtts_griffinlim_infer_batch; else one prosody or one
-// contour per utterance, its fields checked by the caller)
+// contour per utterance, its fields checked by the caller; job: a pitch-target request -- checked options, one checked target
+// per utterance and contours that may be null, which take the place of pros / cont)
 static xdtts_status infer_batch(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames, int32_t n_utt,
-                                const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **audios, size_t *n_samples) {
+                                const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **audios, size_t *n_samples,
+                                const F0Job *job = nullptr, const xdtts_pitch_target *tg = nullptr,
+                                const xdtts_prosody_contour *const *tc = nullptr) {
   return guard([&] {
     if (!g || !mels || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "bad argument");
     if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
@@ -31,6 +34,8 @@ static xdtts_status infer_batch(xdtts_griffinlim *g, const float *const *mels, s
       }
       rows_add(rows, n_frames[u], (size_t)1 << 24, "batch too large");
     }
+    TargetPlan plan;
+    if (job) target_plan(*job, tg, tc, n_utt, n_frames, plan);
     const size_t Ftot = rows.total;
     std::lock_guard<std::mutex> lk(g->mu);
     HIP_CHECK(hipSetDevice(g->device));
@@ -41,7 +46,8 @@ static xdtts_status infer_batch(xdtts_griffinlim *g, const float *const *mels, s
         std::memcpy(mel_all.p + m * Ftot + rows.row0[u], mels[u] + m * n_frames[u], sizeof(float) * n_frames[u]);
     g->mel_in.upload(mel_all.p, (size_t)n_mels * Ftot, g->stream);
     HIP_CHECK(hipStreamSynchronize(g->stream));  // the staging buffer goes back to the pool
-    gl_batch_from_device(g, g->mel_in.p, rows.F, audios, n_samples, cont ? ProsodyArg(tabs.data()) : ProsodyArg(pros));
+    gl_batch_from_device(g, g->mel_in.p, rows.F, audios, n_samples, job ? plan.arg() : (cont ? ProsodyArg(tabs.data()) : ProsodyArg(pros)));
+    if (job && plan.active) g->f0_collect();
   });
 }
 
@@ -485,6 +491,248 @@ xdtts_status xdtts_griffinlim_infer_batch_contour(xdtts_griffinlim *g, const flo
   });
   if (st != XDTTS_OK) return st;
   return infer_batch(g, mels, n_mels, n_frames, n_utt, nullptr, c, audios, n_samples);
+}
+
+// ---- pitch tracker and pitch targets (f0_plan.h, f0.hip: k_f0_frames, k_f0_track) ----------------------------------------------
+
+void xdtts_f0_opts_default(xdtts_f0_opts *o) {
+  if (!o) return;
+  const F0Opts d = f0_opts_default();
+  std::memcpy(o, &d, sizeof d);
+}
+
+void xdtts_pitch_target_default(xdtts_pitch_target *t) {
+  if (!t) return;
+  const PitchTarget d = pitch_target_default();
+  std::memcpy(t, &d, sizeof d);
+}
+
+xdtts_status xdtts_f0_plan(const xdtts_f0_opts *o, int32_t *q_lo, int32_t *q_hi) {
+  return guard([&] {
+    if (q_lo) *q_lo = 0;
+    if (q_hi) *q_hi = 0;
+    const F0Job j = f0_job_checked(o);
+    if (q_lo) *q_lo = j.q_lo;
+    if (q_hi) *q_hi = j.q_hi;
+  });
+}
+
+xdtts_status xdtts_f0_track_reference(const float *raw, const float *strength, size_t n_frames, const xdtts_f0_opts *o,
+                                      const xdtts_pitch_target *t, float *f0_out, float *ratio_out, xdtts_f0_stats *stats) {
+  return guard([&] {
+    const F0Job j = f0_job_checked(o);
+    xdtts_pitch_target td;
+    xdtts_pitch_target_default(&td);
+    pitch_target_check_array(t ? t : &td, 1);
+    if (!raw || !strength) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (n_frames < 1 || n_frames > F0_MAX_ROWS) fail(XDTTS_ERR_BAD_ARG, "f0 reference: need 1 .. 2^20 frames, got %zu", n_frames);
+    PitchTarget pt;
+    std::memcpy(&pt, t ? t : &td, sizeof pt);
+    F0Stats st;
+    f0_track_reference(raw, strength, n_frames, j.opts, pt, f0_out, ratio_out, &st);
+    if (stats) std::memcpy(stats, &st, sizeof st);
+  });
+}
+
+xdtts_status xdtts_griffinlim_last_f0(const xdtts_griffinlim *g, xdtts_f0_stats *out, size_t cap, size_t *n) {
+  return guard([&] {
+    if (n) *n = 0;
+    if (!g || !n) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    *n = g->last_f0.size();
+    if (!out && cap == 0) return;  // the count alone
+    if (!out || cap < g->last_f0.size()) fail(XDTTS_ERR_BAD_ARG, "the last call tracked %zu utterances, the buffer holds %zu", g->last_f0.size(), cap);
+    if (!g->last_f0.empty()) std::memcpy(out, g->last_f0.data(), g->last_f0.size() * sizeof(xdtts_f0_stats));
+  });
+}
+
+// The tracker's results of the rows `rows` to the host (any array, and any element of one, may be null), the wait, the stats.
+// Behind f0_launch() on g->stream; ev.e[0 .. 2] recorded by the caller.
+static void f0_fetch(xdtts_griffinlim *g, const Rows &rows, float *const *raw_outs, float *const *strength_outs, float *const *f0_outs,
+                     float *const *ratio_outs, xdtts_f0_stats *stats) {
+  for (int u = 0; u < rows.n(); ++u) {
+    const size_t r0 = (size_t)rows.row0[(size_t)u], nbytes = (size_t)rows.F[(size_t)u] * sizeof(float);
+    if (raw_outs && raw_outs[u]) HIP_CHECK(hipMemcpyAsync(raw_outs[u], g->f0_raw.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
+    if (strength_outs && strength_outs[u]) HIP_CHECK(hipMemcpyAsync(strength_outs[u], g->f0_strength.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
+    if (f0_outs && f0_outs[u]) HIP_CHECK(hipMemcpyAsync(f0_outs[u], g->f0_val.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
+    if (ratio_outs && ratio_outs[u]) HIP_CHECK(hipMemcpyAsync(ratio_outs[u], g->f0_ratio.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
+  }
+  g->finish_timings();  // (drains the stream)
+  g->clear_last();
+  g->f0_collect();
+  if (stats && !g->last_f0.empty()) std::memcpy(stats, g->last_f0.data(), g->last_f0.size() * sizeof(xdtts_f0_stats));
+}
+
+// The tracker alone on S_dev [rows.total][nb]: no target, no table.  ms[0] = k_f0_frames, ms[1] = k_f0_track.
+static void f0_run(xdtts_griffinlim *g, const float *S_dev, const Rows &rows, const F0Job &job, float *const *raw_outs,
+                   float *const *strength_outs, float *const *f0_outs, xdtts_f0_stats *stats) {
+  std::vector<F0Utt> utts;
+  for (int u = 0; u < rows.n(); ++u) utts.push_back({rows.row0[(size_t)u], rows.F[(size_t)u], -1, 0, 1.0f, 1.0f});
+  g->f0_prepare(utts);
+  HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+  g->f0_launch(S_dev, job, nullptr, 0, g->ev.e[1]);
+  HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+  f0_fetch(g, rows, raw_outs, strength_outs, f0_outs, nullptr, stats);
+}
+
+static void f0_rows_checked(Rows &rows, const size_t *n_frames, int n_utt) {
+  for (int u = 0; u < n_utt; ++u) {
+    if (n_frames[u] < 1 || n_frames[u] > F0_MAX_FRAMES) fail(XDTTS_ERR_BAD_ARG, "utterance %d: the pitch tracker takes 1 .. %zu frames, got %zu", u, F0_MAX_FRAMES, n_frames[u]);
+    rows_add(rows, n_frames[u], F0_MAX_ROWS, "batch too large: more than 2^20 frames");
+  }
+}
+
+xdtts_status xdtts_griffinlim_f0_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
+                                              const xdtts_f0_opts *o, float *const *raw_outs, float *const *strength_outs,
+                                              float *const *f0_outs, xdtts_f0_stats *stats) {
+  return guard([&] {
+    const F0Job job = f0_job_checked(o);
+    if (n_utt < 1) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    if (!S || !n_frames) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    Rows rows;
+    for (int u = 0; u < n_utt; ++u)
+      if (!S[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
+    f0_rows_checked(rows, n_frames, n_utt);
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    g->bufs((int)rows.total);
+    g->upload_rows(S, rows);
+    f0_run(g, g->S.p, rows, job, raw_outs, strength_outs, f0_outs, stats);
+  });
+}
+
+xdtts_status xdtts_griffinlim_f0_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_f0_opts *o,
+                                        float *raw_out, float *strength_out, float *f0_out, xdtts_f0_stats *stats) {
+  return xdtts_griffinlim_f0_linear_batch(g, &S, &n_frames, 1, o, &raw_out, &strength_out, &f0_out, stats);
+}
+
+xdtts_status xdtts_griffinlim_f0(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames, const xdtts_f0_opts *o,
+                                 float *raw_out, float *strength_out, float *f0_out, xdtts_f0_stats *stats) {
+  return guard([&] {
+    const F0Job job = f0_job_checked(o);
+    if (!g || !mel) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
+    Rows rows;
+    f0_rows_checked(rows, &n_frames, 1);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    g->bufs((int)n_frames);
+    g->mel_in.upload(mel, n_mels * n_frames, g->stream);
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+    g->mel_to_linear(g->mel_in.p, (int)n_frames);
+    f0_run(g, g->S.p, rows, job, &raw_out, &strength_out, &f0_out, stats);
+  });
+}
+
+xdtts_status xdtts_griffinlim_f0_audio(xdtts_griffinlim *g, const float *audio, size_t n_samples, const xdtts_f0_opts *o,
+                                       float *raw_out, float *strength_out, float *f0_out, xdtts_f0_stats *stats) {
+  return guard([&] {
+    const F0Job job = f0_job_checked(o);
+    if (!g || !audio) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if (n_samples == 0 || n_samples >= ((size_t)1 << 28)) fail(XDTTS_ERR_BAD_ARG, "need 1 .. 2^28 - 1 samples, got %zu", n_samples);
+    const size_t F = n_samples / (size_t)g->hop + 1;
+    Rows rows;
+    f0_rows_checked(rows, &F, 1);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    gl_analysis_enqueue(g, &audio, &n_samples, rows, false);
+    f0_run(g, g->an_S.p, rows, job, &raw_out, &strength_out, &f0_out, stats);
+  });
+}
+
+// Parity hook of the application: the magnitudes one behind the other on the device, the tables (with the pitches kept a second
+// time), k_f0_frames, k_f0_track -- which writes the tables' pitches -- and k_prosody_contour, and back.  The hook always runs
+// the tracker: under identity targets the ratios are 1 and the utterances are copied.  ms[0] = k_f0_frames, ms[1] = the rest.
+xdtts_status xdtts_griffinlim_pitch_target_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames,
+                                                        int32_t n_utt, const xdtts_f0_opts *o, const xdtts_pitch_target *t,
+                                                        const xdtts_prosody_contour *const *c, float *const *S_outs,
+                                                        float *const *ratio_outs, xdtts_f0_stats *stats) {
+  return guard([&] {
+    const F0Job job = f0_job_checked(o);
+    pitch_target_check_array(t, n_utt);
+    if (!S || !n_frames) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    for (int u = 0; u < n_utt; ++u) {
+      if (!S[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
+      if (c && c[u]) contour_check_at(c[u], u, std::max<size_t>(n_frames[u], 2));  // the fields first
+    }
+    Rows in, out;
+    f0_rows_checked(in, n_frames, n_utt);
+    TargetPlan plan;
+    target_plan(job, t, c, n_utt, n_frames, plan);
+    for (int u = 0; u < n_utt; ++u) rows_add(out, (size_t)plan.tabs[(size_t)u].Fout, (size_t)1 << 24, "batch too large");
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    const size_t nb = (size_t)g->nb;
+    g->bufs((int)std::max(in.total, out.total));
+    g->upload_rows(S, in);
+    g->contour_upload(plan.tabs.data(), n_utt, true);
+    g->f0_prepare_contour(plan.job);
+    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+    g->f0_launch(g->S.p, plan.job, g->contour_ftab.p, g->contour_n_tab, g->ev.e[1]);
+    g->contour_launch();
+    for (int u = 0; u < n_utt; ++u) {
+      if (!S_outs || !S_outs[u]) continue;
+      const size_t r0 = (size_t)out.row0[(size_t)u] * nb;
+      launch_transpose(g->S_pros.p + r0, g->frames.p + r0, out.F[(size_t)u], g->nb, g->stream);
+    }
+    HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+    for (int u = 0; u < n_utt; ++u) {
+      if (!S_outs || !S_outs[u]) continue;
+      const size_t r0 = (size_t)out.row0[(size_t)u] * nb;
+      HIP_CHECK(hipMemcpyAsync(S_outs[u], g->frames.p + r0, (size_t)out.F[(size_t)u] * nb * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    }
+    f0_fetch(g, in, nullptr, nullptr, nullptr, ratio_outs, stats);
+  });
+}
+
+xdtts_status xdtts_griffinlim_pitch_target_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_f0_opts *o,
+                                                  const xdtts_pitch_target *t, const xdtts_prosody_contour *c, float *S_out,
+                                                  float *ratio_out, xdtts_f0_stats *stats) {
+  return xdtts_griffinlim_pitch_target_linear_batch(g, &S, &n_frames, 1, o, t, c ? &c : nullptr, &S_out, &ratio_out, stats);
+}
+
+xdtts_status xdtts_griffinlim_infer_pitch_target(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
+                                                 const xdtts_f0_opts *o, const xdtts_pitch_target *t, const xdtts_prosody_contour *c,
+                                                 float **audio, size_t *n_samples) {
+  return guard([&] {
+    if (audio) *audio = nullptr;
+    if (n_samples) *n_samples = 0;
+    const F0Job job = f0_job_checked(o);  // the fields first: reported without a handle
+    pitch_target_check_array(t, 1);
+    if (c) contour_check(c, std::max<size_t>(n_frames, 2));
+    if (!g || !mel || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    if ((int)n_mels != g->n_mels) fail(XDTTS_ERR_BAD_ARG, "mel has %zu rows, basis has %d", n_mels, g->n_mels);
+    if (n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "need at least 2 frames, got %zu", n_frames);
+    TargetPlan plan;
+    target_plan(job, t, c ? &c : nullptr, 1, &n_frames, plan);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    g->mel_in.upload(mel, n_mels * n_frames, g->stream);
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+    gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, plan.arg(), audio, n_samples);
+    if (plan.active) g->f0_collect();
+  });
+}
+
+xdtts_status xdtts_griffinlim_infer_batch_pitch_target(xdtts_griffinlim *g, const float *const *mels, size_t n_mels,
+                                                       const size_t *n_frames, int32_t n_utt, const xdtts_f0_opts *o,
+                                                       const xdtts_pitch_target *t, const xdtts_prosody_contour *const *c,
+                                                       float **audios, size_t *n_samples) {
+  F0Job job;
+  xdtts_status st = guard([&] {
+    for (int u = 0; u < n_utt; ++u) {
+      if (audios) audios[u] = nullptr;
+      if (n_samples) n_samples[u] = 0;
+    }
+    job = f0_job_checked(o);
+    pitch_target_check_array(t, n_utt);
+    for (int u = 0; c && u < n_utt; ++u)
+      if (c[u]) contour_check_at(c[u], u, 2);
+  });
+  if (st != XDTTS_OK) return st;
+  return infer_batch(g, mels, n_mels, n_frames, n_utt, nullptr, nullptr, audios, n_samples, &job, t, c);
 }
 
 // ---- initial phase: the seeded random stream (0) or Single Pass Spectrogram Inversion (1; phase_spsi.hip) ---------------------

@@ -12,7 +12,8 @@ using namespace xdtts;
 // (pros == cont == null: xdtts_synthesize_ids; else the prosody stage between mel -> linear and the loop, fields checked by the caller)
 static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n, const size_t *splits,
                                    size_t n_splits, const xdtts_infer_opts *opts, const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **mel,
-                                   size_t *n_frames, float **audio, size_t *n_samples) {
+                                   size_t *n_frames, float **audio, size_t *n_samples, const F0Job *job = nullptr,
+                                   const xdtts_pitch_target *tg = nullptr, const xdtts_prosody_contour *const *tc = nullptr) {
   return guard([&] {
     if (!h || !g || !mel || !n_frames || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
@@ -40,7 +41,11 @@ static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, cons
       contour_check(cont, (size_t)total);
       contour_table(*cont, (size_t)total, tab);
     }
-    gl_run_from_device_mel(g, h->mel_dev.p, total, cont ? ProsodyArg(&tab) : ProsodyArg(pros), audio, n_samples);
+    TargetPlan plan;  // (a pitch-target request: checked options and target, a contour that may be null)
+    const size_t total_frames = (size_t)total;
+    if (job) target_plan(*job, tg, tc, 1, &total_frames, plan);
+    gl_run_from_device_mel(g, h->mel_dev.p, total, job ? plan.arg() : (cont ? ProsodyArg(&tab) : ProsodyArg(pros)), audio, n_samples);
+    if (job && plan.active) g->f0_collect();
     h->finish_timings();  // (stream sync: the mel has landed)
     *mel = mel_host.release();
     *n_frames = (size_t)total;
@@ -247,7 +252,8 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
 static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
                                      int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
                                      const int32_t *fixed_steps_per_item, const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **mels, size_t *n_frames,
-                                     float **audios, size_t *n_samples) {
+                                     float **audios, size_t *n_samples, const F0Job *job = nullptr, const xdtts_pitch_target *tg = nullptr,
+                                     const xdtts_prosody_contour *const *tc = nullptr) {
   return guard([&] {
     if (!h || !g || !ids || !lens || !utt_chunks || !n_frames || !audios || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
@@ -281,6 +287,11 @@ static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, co
         contour_table(cont[u], (size_t)Fu[u], tabs[(size_t)u]);
       }
     }
+    TargetPlan plan;  // (a pitch-target request: checked options and targets, contours that may be null)
+    if (job) {
+      const std::vector<size_t> Fz(Fu.begin(), Fu.end());
+      target_plan(*job, tg, tc, n_utt, Fz.data(), plan);
+    }
     // the vocoder stream reads the mel behind the post-net (event 3 of infer_batch_device); the host copies of the
     // mel follow on the mel-gen stream and overlap the vocoder
     HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));
@@ -294,7 +305,8 @@ static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, co
                                    sizeof(float) * (size_t)Fu[u], N_MEL, hipMemcpyDeviceToHost, h->stream));
       }
     }
-    gl_batch_from_device(g, h->mel_dev.p, Fu, audios, n_samples, cont ? ProsodyArg(tabs.data()) : ProsodyArg(pros));
+    gl_batch_from_device(g, h->mel_dev.p, Fu, audios, n_samples, job ? plan.arg() : (cont ? ProsodyArg(tabs.data()) : ProsodyArg(pros)));
+    if (job && plan.active) g->f0_collect();
     try {
       h->finish_timings();  // (stream sync: the mel copies have landed)
     } catch (...) {  // the caller gets either every buffer of the call or none
@@ -434,6 +446,46 @@ xdtts_status xdtts_synthesize_batch_contour(xdtts_tacotron2 *h, xdtts_griffinlim
   });
   if (st != XDTTS_OK) return st;
   return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, nullptr, c, mels, n_frames, audios, n_samples);
+}
+
+// ... with a pitch target (xdtts_pitch_target): tracker, target and contour stage behind mel -> linear; the table is built once
+// the frame count is known
+xdtts_status xdtts_synthesize_ids_pitch_target(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
+                                               const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts,
+                                               const xdtts_f0_opts *o, const xdtts_pitch_target *t, const xdtts_prosody_contour *c,
+                                               float **mel, size_t *n_frames, float **audio, size_t *n_samples) {
+  F0Job job;
+  xdtts_status st = guard([&] {  // the fields, before a device is touched
+    job = f0_job_checked(o);
+    pitch_target_check_array(t, 1);
+    if (c) contour_check(c, 2);
+  });
+  if (st != XDTTS_OK) return st;
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, nullptr, nullptr, mel, n_frames, audio, n_samples, &job, t, c ? &c : nullptr);
+}
+
+// ... one target per utterance, contours that may be null
+xdtts_status xdtts_synthesize_batch_pitch_target(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
+                                                 int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
+                                                 const int32_t *fixed_steps_per_item, const xdtts_f0_opts *o, const xdtts_pitch_target *t,
+                                                 const xdtts_prosody_contour *const *c, float **mels, size_t *n_frames, float **audios,
+                                                 size_t *n_samples) {
+  F0Job job;
+  const xdtts_status st = guard([&] {
+    for (int u = 0; u < n_utt; ++u) {
+      if (mels) mels[u] = nullptr;
+      if (audios) audios[u] = nullptr;
+      if (n_frames) n_frames[u] = 0;
+      if (n_samples) n_samples[u] = 0;
+    }
+    job = f0_job_checked(o);
+    pitch_target_check_array(t, n_utt);
+    for (int u = 0; c && u < n_utt; ++u)
+      if (c[u]) contour_check_at(c[u], u, 2);
+  });
+  if (st != XDTTS_OK) return st;
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, nullptr, nullptr, mels, n_frames, audios, n_samples,
+                          &job, t, c);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@ xdtts_griffinlim::~xdtts_griffinlim() {
   if (host_err) (void)hipHostFree(host_err);
   if (loud_host) (void)hipHostFree(loud_host);
   if (lim_host) (void)hipHostFree(lim_host);
+  if (f0_host) (void)hipHostFree(f0_host);
   if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -112,7 +113,11 @@ void xdtts_griffinlim::mel_to_linear(const float *mel_dev_ptr, int F) {
 int xdtts_griffinlim::prosody(const ProsodyArg &arg, int F) {
   if (arg.identity(0)) return F;
   if (arg.contour) {
-    const int Fp = contour_upload(arg.contour, 1);
+    const int Fp = contour_upload(arg.contour, 1, arg.f0 != nullptr);
+    if (arg.f0) {  // the tracker and the target write the table's pitches in front of the stage that reads them
+      f0_prepare_contour(*arg.f0);
+      f0_launch(S.p, *arg.f0, contour_ftab.p, contour_n_tab);
+    }
     contour_launch();
     return Fp;
   }
@@ -123,7 +128,7 @@ int xdtts_griffinlim::prosody(const ProsodyArg &arg, int F) {
   return Fp;
 }
 
-int xdtts_griffinlim::contour_upload(const ContourTable *tabs, int n_utt) {
+int xdtts_griffinlim::contour_upload(const ContourTable *tabs, int n_utt, bool keep_pitch) {
   contour_utts_host.clear();
   int src = 0, dst = 0, ntab = 0;
   for (int u = 0; u < n_utt; ++u) {
@@ -135,7 +140,7 @@ int xdtts_griffinlim::contour_upload(const ContourTable *tabs, int n_utt) {
   }
   contour_n_tab = ntab;
   contour_rows = dst;
-  contour_ftab_host.assign((size_t)3 * std::max(ntab, 1), 0u);
+  contour_ftab_host.assign((size_t)(keep_pitch ? 4 : 3) * std::max(ntab, 1), 0u);
   for (int u = 0; u < n_utt; ++u) {
     const ContourTable &t = tabs[u];
     const size_t at = (size_t)contour_utts_host[(size_t)u].tab0, n = t.c.size();
@@ -143,6 +148,7 @@ int xdtts_griffinlim::contour_upload(const ContourTable *tabs, int n_utt) {
     std::memcpy(&contour_ftab_host[at], t.c.data(), n * sizeof(unsigned));
     std::memcpy(&contour_ftab_host[(size_t)ntab + at], t.pitch.data(), n * sizeof(float));
     std::memcpy(&contour_ftab_host[(size_t)2 * ntab + at], t.gain.data(), n * sizeof(float));
+    if (keep_pitch) std::memcpy(&contour_ftab_host[(size_t)3 * ntab + at], t.pitch.data(), n * sizeof(float));
   }
   contour_utts.upload(contour_utts_host.data(), contour_utts_host.size(), stream);
   contour_ftab.upload(contour_ftab_host.data(), contour_ftab_host.size(), stream);
@@ -152,6 +158,53 @@ int xdtts_griffinlim::contour_upload(const ContourTable *tabs, int n_utt) {
 
 void xdtts_griffinlim::contour_launch() {
   launch_prosody_contour(S.p, S_pros.p, contour_utts.p, (int)contour_utts_host.size(), contour_ftab.p, contour_n_tab, contour_rows, tw.p, stream);
+}
+
+// The pitch tracker (f0.hip).  Buffers grow with the request and stay; a growth happens behind a drained stream (every request
+// path starts there).
+void xdtts_griffinlim::f0_prepare(const std::vector<F0Utt> &utts) {
+  f0_utts_host = utts;
+  int rows = 0;
+  for (const F0Utt &u : utts) rows = std::max(rows, u.row0 + u.F);
+  f0_rows = rows;
+  const size_t n = (size_t)std::max(rows, 1), n_utt = std::max<size_t>(utts.size(), 1);
+  f0_raw.alloc(n);
+  f0_strength.alloc(n);
+  f0_val.alloc(n);
+  f0_ratio.alloc(n);
+  f0_stats.alloc(n_utt);
+  if (n_utt > f0_host_n) {
+    if (f0_host) HIP_CHECK(hipHostFree(f0_host));
+    f0_host = nullptr;
+    f0_host_n = 0;
+    HIP_CHECK(hipHostMalloc((void **)&f0_host, n_utt * sizeof(F0Stats), hipHostMallocDefault));
+    f0_host_n = n_utt;
+  }
+  f0_utts.upload(f0_utts_host.data(), f0_utts_host.size(), stream);
+}
+
+void xdtts_griffinlim::f0_prepare_contour(const F0Job &job) {
+  std::vector<F0Utt> utts;
+  for (size_t u = 0; u < contour_utts_host.size(); ++u) {
+    const ContourUtt &c = contour_utts_host[u];
+    const PitchTarget &t = job.targets[u];
+    utts.push_back({c.src0, c.F, c.identity ? -1 : c.tab0, t.mode, t.value, t.range});
+  }
+  f0_prepare(utts);
+}
+
+void xdtts_griffinlim::f0_launch(const float *S_dev, const F0Job &job, unsigned *ftab, int n_tab, hipEvent_t between) {
+  const int n_utt = (int)f0_utts_host.size();
+  launch_f0_frames(S_dev, f0_rows, job.opts, job.q_lo, job.q_hi, tw.p, f0_raw.p, f0_strength.p, stream);
+  if (between) HIP_CHECK(hipEventRecord(between, stream));
+  launch_f0_track(f0_raw.p, f0_strength.p, f0_utts.p, n_utt, job.opts.threshold, f0_val.p, f0_ratio.p, f0_stats.p, ftab, n_tab, stream);
+  HIP_CHECK(hipMemcpyAsync(f0_host, f0_stats.p, (size_t)n_utt * sizeof(F0Stats), hipMemcpyDeviceToHost, stream));
+}
+
+void xdtts_griffinlim::f0_collect() {
+  static_assert(sizeof(xdtts_f0_stats) == sizeof(F0Stats), "F0Stats is xdtts_f0_stats");
+  last_f0.resize(f0_utts_host.size());
+  if (!last_f0.empty()) std::memcpy(last_f0.data(), f0_host, last_f0.size() * sizeof(F0Stats));
 }
 
 // The initial phase by SPSI (phase_spsi.hip) on a magnitude in place.  Scratch grows with the request and stays.
@@ -811,6 +864,62 @@ void prosody_check(const xdtts_prosody *p, size_t n_frames) {
 
 static_assert(sizeof(xdtts_prosody_point) == sizeof(ContourPoint) && offsetof(xdtts_prosody_point, gain) == offsetof(ContourPoint, gain),
               "xdtts_prosody_point and ContourPoint share one layout");
+F0Job f0_job_checked(const xdtts_f0_opts *o) {
+  static_assert(sizeof(xdtts_f0_opts) == sizeof(F0Opts) && sizeof(xdtts_pitch_target) == sizeof(PitchTarget), "the layouts of f0_plan.h");
+  F0Job j;
+  j.opts = f0_opts_default();
+  if (o) std::memcpy(&j.opts, o, sizeof j.opts);
+  const std::string msg = f0_opts_check(j.opts);
+  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  f0_quefrency(j.opts, &j.q_lo, &j.q_hi);
+  return j;
+}
+
+void pitch_target_check_array(const xdtts_pitch_target *t, int n_utt) {
+  if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+  if (!t) fail(XDTTS_ERR_BAD_ARG, "null pitch target");
+  for (int u = 0; u < n_utt; ++u) {
+    PitchTarget p;
+    std::memcpy(&p, &t[u], sizeof p);
+    const std::string msg = pitch_target_check(p);
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "utterance %d: %s", u, msg.c_str());
+  }
+}
+
+void target_plan(const F0Job &job, const xdtts_pitch_target *t, const xdtts_prosody_contour *const *c, int n_utt, const size_t *n_frames,
+                 TargetPlan &p) {
+  p.job = job;
+  p.targets.resize((size_t)n_utt);
+  p.tabs.assign((size_t)n_utt, ContourTable());
+  p.active = p.any_contour = false;
+  for (int u = 0; u < n_utt; ++u) {
+    std::memcpy(&p.targets[(size_t)u], &t[u], sizeof(PitchTarget));
+    p.active = p.active || !pitch_target_is_identity(p.targets[(size_t)u]);
+    p.any_contour = p.any_contour || (c && c[u]);
+  }
+  for (int u = 0; u < n_utt; ++u) {
+    const size_t F = n_frames[u];
+    ContourTable &tab = p.tabs[(size_t)u];
+    if (c && c[u]) {
+      contour_check_at(c[u], u, F);
+      contour_table(*c[u], F, tab);
+    } else {
+      tab.F = tab.Fout = (int)F;  // (the identity: no table)
+    }
+    if (p.active && (F < 1 || F > F0_MAX_FRAMES)) fail(XDTTS_ERR_BAD_ARG, "utterance %d: the pitch tracker takes 1 .. %zu frames, got %zu", u, F0_MAX_FRAMES, F);
+    if (pitch_target_is_identity(p.targets[(size_t)u])) continue;
+    if (F < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: a pitch target that is not the identity takes 2 .. %zu frames, got %zu", u, F0_MAX_FRAMES, F);
+    if (tab.identity) {  // the rate-1 table: c[m] = 65536 m, pitch 1, gain 1, F' = F
+      tab.identity = false;
+      tab.c.resize(F);
+      for (size_t m = 0; m < F; ++m) tab.c[m] = (uint32_t)(65536u * m);
+      tab.pitch.assign(F, 1.0f);
+      tab.gain.assign(F, 1.0f);
+    }
+  }
+  p.job.targets = p.targets.data();
+}
+
 static const ContourPoint *contour_points(const xdtts_prosody_contour &c) { return reinterpret_cast<const ContourPoint *>(c.points); }
 
 void contour_check(const xdtts_prosody_contour *c, size_t n_frames) {
@@ -894,7 +1003,10 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
   GlBufs all = g->bufs((int)std::max(in.total, rows.total));
   all.F = (int)rows.total;
   if (staged) {
-    if (contour) g->contour_upload(pros.contour, n_utt);  // (its rows are `in` and `rows`: the utterances back to back)
+    if (contour) {
+      g->contour_upload(pros.contour, n_utt, pros.f0 != nullptr);  // (its rows are `in` and `rows`: the utterances back to back)
+      if (pros.f0) g->f0_prepare_contour(*pros.f0);
+    }
     else g->pros_tab.upload(ptab.data(), ptab.size(), st);
     g->S_pros.alloc(rows.total * (size_t)g->nb);
     all.S = g->S_pros.p;
@@ -945,8 +1057,10 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     // mel -> linear, the ragged stages, the initial phase: all from the mel, so a retry starts from an intact S / S'
     HIP_CHECK(hipEventRecord(g->ev.e[0], st));
     g->mel_to_linear(mel_dev_all, (int)in.total);
-    if (contour) g->contour_launch();
-    else if (staged) launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)rows.total, g->tw.p, st);
+    if (contour) {
+      if (pros.f0) g->f0_launch(g->S.p, *pros.f0, g->contour_ftab.p, g->contour_n_tab);  // (from the intact S: a retry writes the same pitches)
+      g->contour_launch();
+    } else if (staged) launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)rows.total, g->tw.p, st);
     if (use_spsi) g->spsi_batch(all.S, spsi_tab, all.ang, all.tprev);
     HIP_CHECK(hipEventRecord(g->ev.e[1], st));
     if (!use_spsi) launch_gl_phase_init_batch(all, g->seed, g->frame_local.p, st);

@@ -20,17 +20,42 @@ void contour_table(const xdtts_prosody_contour &c, size_t n_frames, ContourTable
 // What a request path puts between mel -> linear and the loop, as ONE argument: nothing, a uniform prosody (checked by the
 // caller), or the table of a contour (built by the caller once the frame count is known).  The single-utterance path reads
 // element 0, the batch path one element per utterance.
+// With a pitch target (f0_plan.h) the tables are a TargetPlan's and `f0` is its job: the tracker and the target run on S in
+// front of the contour stage and multiply their ratios into the tables' pitches on the device.
+struct F0Job {
+  F0Opts opts;
+  int q_lo = 0, q_hi = 0;
+  const PitchTarget *targets = nullptr;  // one per utterance
+};
 struct ProsodyArg {
   const xdtts_prosody *uniform = nullptr;
   const ContourTable *contour = nullptr;
+  const F0Job *f0 = nullptr;  // (with `contour` only)
   ProsodyArg() = default;
   ProsodyArg(std::nullptr_t) {}
   ProsodyArg(const xdtts_prosody *p) : uniform(p) {}
-  ProsodyArg(const ContourTable *t) : contour(t) {}
+  ProsodyArg(const ContourTable *t, const F0Job *j = nullptr) : contour(t), f0(j) {}
   explicit operator bool() const { return uniform || contour; }
   bool identity(int u) const { return contour ? contour[u].identity : (!uniform || prosody_is_identity(uniform[u])); }
   int frames(int u, int F) const { return contour ? contour[u].Fout : (uniform ? (int)prosody_frames((size_t)F, uniform[u].rate) : F); }  // F'
 };
+// xdtts_f0_opts / xdtts_pitch_target on top of f0_plan.h, which knows no status codes: the checked options (null = the default)
+// with their quefrency range, and the targets of n_utt utterances; both fail with XDTTS_ERR_BAD_ARG and need no handle.
+F0Job f0_job_checked(const xdtts_f0_opts *o);
+void pitch_target_check_array(const xdtts_pitch_target *t, int n_utt);
+// What a target request runs on, built once the frame counts are known (checked options and targets): the contour tables --
+// the caller's, or the rate-1 table where an utterance under a target that is not the identity has no contour of its own (its
+// identity flag is off: the stage reads the pitches the device writes) -- and the job.  active = some target is not the
+// identity; without it arg() is the request of the contours alone (or nothing: the bits of the plain entry).
+struct TargetPlan {
+  F0Job job;
+  std::vector<PitchTarget> targets;
+  std::vector<ContourTable> tabs;
+  bool active = false, any_contour = false;
+  ProsodyArg arg() const { return active ? ProsodyArg(tabs.data(), &job) : (any_contour ? ProsodyArg(tabs.data()) : ProsodyArg()); }
+};
+void target_plan(const F0Job &job, const xdtts_pitch_target *t, const xdtts_prosody_contour *const *c, int n_utt, const size_t *n_frames,
+                 TargetPlan &p);
 // The options of a stream request (stream_plan.h, which knows no status codes), before a handle is looked at; null = the default
 inline StreamOpts stream_opts_checked(const xdtts_stream_opts *o) {
   StreamOpts s = stream_opts_default();
@@ -116,8 +141,25 @@ struct xdtts_griffinlim {
   int contour_n_tab = 0, contour_rows = 0;  // entries per array of the frame table; sum of F'
   // Uploads (on the stream) the records and tables of n_utt utterances lying back to back in S (rows F_u) and S_pros (rows
   // F'_u, allocated here); returns sum F'.  contour_launch() then runs the stage, any number of times (a retry).
-  int contour_upload(const xdtts::ContourTable *tabs, int n_utt);
+  // (keep_pitch: a fourth array behind the three, the pitches once more -- what k_f0_track multiplies its ratios into `pitch` from)
+  int contour_upload(const xdtts::ContourTable *tabs, int n_utt, bool keep_pitch = false);
   void contour_launch();
+  // pitch tracker and pitch targets (f0.hip): raw / strength / f0 / ratio of the rows of a request, the per-utterance records
+  // and stats.  f0_prepare() sizes the buffers and uploads the records (on the stream; the host vector stays until the next
+  // tracker request of this handle); f0_launch() runs k_f0_frames on S_dev [rows][nb] and k_f0_track and sends the stats to
+  // the pinned buffer, any number of times (a retry).  ftab: the contour table whose pitches take the ratios, or null.
+  DevBuf<float> f0_raw, f0_strength, f0_val, f0_ratio;
+  DevBuf<xdtts::F0Stats> f0_stats;
+  DevBuf<xdtts::F0Utt> f0_utts;
+  std::vector<xdtts::F0Utt> f0_utts_host;
+  xdtts::F0Stats *f0_host = nullptr;  // pinned
+  size_t f0_host_n = 0;
+  int f0_rows = 0;
+  std::vector<xdtts_f0_stats> last_f0;  // xdtts_griffinlim_last_f0
+  void f0_prepare(const std::vector<xdtts::F0Utt> &utts);
+  void f0_prepare_contour(const xdtts::F0Job &job);  // ... from the records contour_upload() has just built
+  void f0_launch(const float *S_dev, const xdtts::F0Job &job, unsigned *ftab, int n_tab, hipEvent_t between = nullptr);
+  void f0_collect();  // behind a drained stream: the pinned stats -> last_f0
 
   // initial phase (phase_spsi.hip): 0 = the seeded random stream, 1 = SPSI on the magnitude that enters the loop
   int phase_init = 0;
@@ -213,6 +255,7 @@ struct xdtts_griffinlim {
   void clear_last() {
     last_loud.clear();
     last_lim.clear();
+    last_f0.clear();
   }
   // the structs of record r of the last fetch -> last_loud (and last_lim where the limiter ran)
   void push_last(size_t r);

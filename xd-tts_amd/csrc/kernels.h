@@ -1,6 +1,7 @@
 // kernels.h -- host-side launch interface of the HIP kernels (gfx950).
 #pragma once
 #include "common.h"
+#include "f0_plan.h"
 #include "gl_plan.h"
 #include "limiter_plan.h"
 #include "loudness_plan.h"
@@ -333,6 +334,23 @@ struct ContourUtt {
 };
 void launch_prosody_contour(const float *S, float *Sout, const ContourUtt *utt, int n_utt, const unsigned *ftab, int n_tab, int Fout_all,
                             const float2 *tw, hipStream_t s);
+
+// ---- pitch tracker (f0.hip): F0 per frame from the magnitude's cepstrum, the utterance's median, pitch targets (include/xdtts.h) ----
+// raw[t], strength[t] for every row t < rows of S [rows][513] (the utterances of a batch back to back: a frame needs nothing of
+// its neighbours); o, q_lo, q_hi: checked options and their quefrency range (f0_plan.h).  One launch.
+void launch_f0_frames(const float *S, int rows, const F0Opts &o, int q_lo, int q_hi, const float2 *tw, float *raw, float *strength,
+                      hipStream_t s);
+// One utterance of launch_f0_track: rows row0 .. row0 + F (1 <= F <= F0_MAX_FRAMES) of raw / strength / f0 / ratio; tab0 = its entry
+// in the contour frame table whose pitch slice takes the ratios, -1 = none; the fields of its xdtts_pitch_target.
+struct F0Utt {
+  int row0, F, tab0, mode;
+  float value, range;
+};
+// One workgroup per utterance: f0, ratio (rows as raw), stats[u], and for tab0 >= 0 the table's pitches
+// ftab[n_tab + tab0 + t] = clamp(ftab[3 n_tab + tab0 + t] * ratio[t]) -- ftab = the table of launch_prosody_contour with a
+// FOURTH array behind the three it reads: the pitches before the target.  ftab may be null where no utterance has a table.
+void launch_f0_track(const float *raw, const float *strength, const F0Utt *utts_dev, int n_utt, float threshold, float *f0, float *ratio,
+                     F0Stats *stats, unsigned *ftab, int n_tab, hipStream_t s);
 
 // ---- initial phase by Single Pass Spectrogram Inversion (phase_spsi.hip; phase_init mode 1, include/xdtts.h) -----------------
 // The recurrence over the frames runs as a scan over segments of SPSI_L consecutive frames of one utterance: the dependent
