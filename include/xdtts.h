@@ -624,6 +624,54 @@ xdtts_status xdtts_griffinlim_spsi_phase(xdtts_griffinlim *g, const float *S, si
 xdtts_status xdtts_griffinlim_spsi_phase_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
                                                uint32_t *const *turns, float *const *angles);
 
+/* Voice timbre: vocal-tract length and breathiness -- the two voice effects TTS services put beside <prosody>.  Prosody changes
+ * how a sentence is spoken; timbre changes who seems to speak it: a deeper or lighter voice, a second speaker in a dialogue, a
+ * whispered aside, from the one checkpoint.  The cepstral split of xdtts_prosody separates a frame's harmonics from its
+ * envelope; prosody moves the harmonics under a fixed envelope, this stage does the reverse.
+ *   vtl    in [0.5, 2]: the vocal tract is `vtl` times as long.  The ENVELOPE is resampled on the frequency axis, a formant at
+ *          bin b moves to b / vtl; the harmonics are not warped, so F0 stays.
+ *   breath in [0, 1]: the harmonics give way to a noise magnitude under the same formants; 1 is a whisper.
+ *   seed   of the noise; lifter in [1, 255] and log_floor > 0 as in xdtts_prosody.
+ * The setting is the IDENTITY when vtl == 1 && breath == 0 (the default): the stage then launches nothing and allocates
+ * nothing, and every entry returns the bits it returns without it.  The definition, exactly, for frame j (the index inside its
+ * own utterance) of the magnitude S that would enter the loop, k = 0 .. 512:
+ *   L[k]  = ln(max(S[j][k], log_floor))
+ *   c     = the real cepstrum of L exactly as xdtts_prosody forms it (1024-point transform of the even extension, / 1024)
+ *   E     = the transform of c with c[n] = 0 for lifter < n < 1024 - lifter          (the envelope)
+ *   R     = L - E                                                                    (the harmonics)
+ *   p     = k * vtl;   E'[k] = p <= 512 ? (1 - a) E[q] + a E[min(q + 1, 512)]  (q = floor p, a = p - q)  :  E[512]
+ *   n     = rng_u32(seed, 0x71B8, j * 513 + k) >> 9;   v = (2 n + 1) * 2^-24         (exact in fp32, 0 < v < 1)
+ *   N     = 0.5 * ln(-ln v) + 0.28860784          (log of a Rayleigh magnitude, shifted by gamma / 2 to zero mean)
+ *   R'[k] = breath == 0 ? R[k] : (1 - breath) * R[k] + breath * N
+ *   S'[j][k] = exp(E'[k] + R'[k])
+ * The noise depends on (seed, j, k) alone: not on the handle's phase seed, not on where the utterance lies in a batch.
+ * Place: behind the prosody / contour / pitch-target stage (the pitch tracker sees the unmodified voice) and in front of the
+ * initial phase (with phase_init 1, SPSI runs on S'); out of place, so S and the prosody stage's output stay intact.
+ * Timbre is a SETTING OF THE HANDLE -- the voice of that handle -- like the output rate, the loudness target and the initial
+ * phase.  Every entry that runs mel -> linear itself honours it: xdtts_griffinlim_infer, _infer_prosody, _infer_contour,
+ * _infer_pitch_target and their _batch forms, xdtts_synthesize_ids / _batch / _sequence / _document with all their prosody,
+ * contour and pitch-target forms; xdtts_griffinlim_last_timings ms[0] then covers the stage.  xdtts_griffinlim_infer_linear
+ * runs the loop on a caller's magnitude and does NOT honour it (such a caller composes with xdtts_griffinlim_timbre_linear);
+ * neither do the _prosody_linear, _contour_linear and _pitch_target_linear hooks nor the analysis entries.  One setting holds
+ * for every utterance of a batch, sequence or document call; a two-voice dialogue uses two handles and xdtts_griffinlim_join.
+ * Argument rules, checked before a handle is looked at (XDTTS_ERR_BAD_ARG, the message names the field): vtl finite and in
+ * [0.5, 2], breath finite and in [0, 1], lifter in [1, 255], log_floor finite and > 0; a request of the stage alone holds 1 ..
+ * 2^20 frames (no time interpolation: one frame is enough).  A failed set leaves the setting as it was. */
+typedef struct { float vtl, breath; uint32_t seed; int32_t lifter; float log_floor; } xdtts_timbre;  /* 20 bytes */
+void xdtts_timbre_default(xdtts_timbre *t); /* 1, 0, 1, 30, 1e-5 */
+xdtts_status xdtts_griffinlim_set_timbre(xdtts_griffinlim *g, const xdtts_timbre *t);   /* NULL = the default (off) */
+xdtts_status xdtts_griffinlim_get_timbre(xdtts_griffinlim *g, xdtts_timbre *t);
+/* Parity hook, the stage alone, whatever the handle's setting: S (n_bins x F, C order, as xdtts_griffinlim_mel_to_linear
+ * returns it), F >= 1 -> S_out (n_bins x F).  The identity returns S's bits and touches no device. */
+xdtts_status xdtts_griffinlim_timbre_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_timbre *t, float *S_out);
+/* The ragged form the batch entries run, one setting PER UTTERANCE (the delivering entries pass the handle's to all): every
+ * S_outs[u] equals the single hook's for S[u] alone bit for bit, whatever the mix and the order; a bad element's message names
+ * the utterance. */
+xdtts_status xdtts_griffinlim_timbre_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
+                                                  const xdtts_timbre *t /* [n_utt] */, float *const *S_outs);
+/* Host arithmetic, no handle, no device: n of cell (frame, bin) above. */
+uint32_t xdtts_timbre_noise_bits(uint32_t seed, uint32_t frame, uint32_t bin);
+
 /* The output rate.  The loop produces 22 050 Hz audio (XDTTS_SAMPLE_RATE, the reference's WAV_SPEC); telephony, WebRTC / Opus
  * and audio pipelines want 8 .. 48 kHz and beyond.  With the option set, a polyphase windowed-sinc resampler runs on the
  * device between the final ISTFT and the output normalisation, so the level rules (peak 1, rms target, no sample outside

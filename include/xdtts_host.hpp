@@ -438,6 +438,43 @@ class GriffinLim {
     if (stats) *stats = st;
     return out;
   }
+  // The voice of this handle (xdtts_griffinlim_set_timbre): vocal-tract length and breathiness on the magnitude behind the prosody
+  // stage.  The default is the identity, which launches nothing; every entry that runs mel -> linear itself honours the setting.
+  static xdtts_timbre default_timbre() {
+    xdtts_timbre t{};
+    xdtts_timbre_default(&t);
+    return t;
+  }
+  void set_timbre(const xdtts_timbre &t) { check(xdtts_griffinlim_set_timbre(g_, &t)); }
+  void clear_timbre() { check(xdtts_griffinlim_set_timbre(g_, nullptr)); }
+  xdtts_timbre timbre_setting() const {
+    xdtts_timbre t{};
+    check(xdtts_griffinlim_get_timbre(g_, &t));
+    return t;
+  }
+  // ... and the stage alone on the caller's magnitude (xdtts_griffinlim_timbre_linear), whatever the setting: S (n_bins x F) -> S'
+  Array2 timbre_linear(const Array2 &S, const xdtts_timbre &t) const {
+    Array2 out{S.rows, S.cols, std::vector<float>(S.data.size())};
+    check(xdtts_griffinlim_timbre_linear(g_, S.data.data(), S.cols, &t, out.data.data()));
+    return out;
+  }
+  // ... for several magnitudes in one launch, one setting each (xdtts_griffinlim_timbre_linear_batch): the single call's bits
+  std::vector<Array2> timbre_linear_batch(const std::vector<Array2> &S, const std::vector<xdtts_timbre> &t) const {
+    const size_t n = S.size();
+    if (t.size() != n) throw std::runtime_error("xdtts: one timbre per utterance");
+    std::vector<Array2> out(n);
+    std::vector<const float *> in(n);
+    std::vector<float *> op(n);
+    std::vector<size_t> nf(n);
+    for (size_t u = 0; u < n; ++u) {
+      out[u] = Array2{S[u].rows, S[u].cols, std::vector<float>(S[u].data.size())};
+      in[u] = S[u].data.data();
+      op[u] = out[u].data.data();
+      nf[u] = S[u].cols;
+    }
+    check(xdtts_griffinlim_timbre_linear_batch(g_, in.data(), nf.data(), (int32_t)n, t.data(), op.data()));
+    return out;
+  }
   // The inverse direction (xdtts_griffinlim_analyze): audio -> (S (n_bins x F), mel (n_mels x F)) under the handle's conventions,
   // F = audio.size() / 256 + 1
   std::pair<Array2, Array2> analyze(const std::vector<float> &audio, float mel_floor = 1e-5f) const {

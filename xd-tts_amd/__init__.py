@@ -57,6 +57,24 @@ class Prosody(C.Structure):
             setattr(self, k, v)
 
 
+class Timbre(C.Structure):
+    """xdtts_timbre: the voice of a vocoder handle, applied to the magnitude behind the prosody stage and in front of the initial
+    phase.  vtl in [0.5, 2] (> 1: a longer vocal tract, formants move down, F0 stays), breath in [0, 1] (1: a whisper), seed of
+    the breath noise, lifter in [1, 255], log_floor > 0.  Timbre() holds the library's defaults (1, 0, 1, 30, 1e-5), i.e. the
+    identity; keywords override fields."""
+
+    _fields_ = [("vtl", C.c_float), ("breath", C.c_float), ("seed", C.c_uint32), ("lifter", C.c_int32), ("log_floor", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib.xdtts_timbre_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def astuple(self):
+        return (self.vtl, self.breath, self.seed, self.lifter, self.log_floor)
+
+
 class ProsodyPoint(C.Structure):
     """xdtts_prosody_point: (pos, rate, pitch, gain), pos a fraction of the utterance's duration in [0, 1]."""
 
@@ -280,6 +298,12 @@ SYMBOLS = {
     "xdtts_griffinlim_get_phase_init": (_I32, [_VP, C.POINTER(_I32)]),
     "xdtts_griffinlim_spsi_phase": (_I32, [_VP, _VP, _SZ, _VP, _VP]),
     "xdtts_griffinlim_spsi_phase_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
+    "xdtts_timbre_default": (None, [C.POINTER(Timbre)]),
+    "xdtts_timbre_noise_bits": (_U32, [_U32, _U32, _U32]),
+    "xdtts_griffinlim_set_timbre": (_I32, [_VP, C.POINTER(Timbre)]),
+    "xdtts_griffinlim_get_timbre": (_I32, [_VP, C.POINTER(Timbre)]),
+    "xdtts_griffinlim_timbre_linear": (_I32, [_VP, _VP, _SZ, C.POINTER(Timbre), _VP]),
+    "xdtts_griffinlim_timbre_linear_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
     "xdtts_griffinlim_set_output_rate": (_I32, [_VP, _I32]),
     "xdtts_griffinlim_get_output_rate": (_I32, [_VP, C.POINTER(_I32)]),
     "xdtts_resample_plan": (_I32, [_I32, _SZ, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_SZ)]),
@@ -1191,6 +1215,42 @@ class GriffinLim:
             _check(lib.xdtts_griffinlim_loudness_batch(self._h, ip, ns, n, int(rate), out))
         return [out[i] for i in range(n)]
 
+    # -- timbre: vocal-tract length and breathiness, the voice of this handle ----
+    def set_timbre(self, timbre=None):
+        """The handle's voice from now on: a Timbre, or None for the default (the identity: nothing is launched).  Honoured by
+        every entry that runs mel -> linear itself (infer*, synthesize*); infer_linear and the *_linear hooks do not."""
+        _check(lib.xdtts_griffinlim_set_timbre(self._h, _opt_ref(timbre)))
+
+    def get_timbre(self):
+        t = Timbre()
+        _check(lib.xdtts_griffinlim_get_timbre(self._h, C.byref(t)))
+        return t
+
+    def timbre_linear(self, S, timbre):
+        """The timbre stage alone (parity hook), whatever the handle's setting: S (n_bins, F) -> S' (n_bins, F)."""
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        out = np.empty_like(S)
+        _check(lib.xdtts_griffinlim_timbre_linear(self._h, _ptr(S), S.shape[1], C.byref(timbre), _ptr(out)))
+        return out
+
+    def timbre_linear_batch(self, S_list, timbre_list):
+        """The ragged stage alone (parity hook): a list of S_u (n_bins, F_u) and one Timbre each -> the list of S'_u, one
+        k_timbre launch for all of them."""
+        Ss = [np.ascontiguousarray(S, dtype=np.float32) for S in S_list]
+        n = len(Ss)
+        ts = list(timbre_list)
+        if len(ts) != n:
+            raise ValueError("timbre_linear_batch takes one Timbre per utterance: %d for %d utterances" % (len(ts), n))
+        ta = (Timbre * max(n, 1))()
+        for u, t in enumerate(ts):
+            ta[u].vtl, ta[u].breath, ta[u].seed, ta[u].lifter, ta[u].log_floor = t.vtl, t.breath, t.seed, t.lifter, t.log_floor
+        outs = [np.empty_like(S) for S in Ss]
+        sp = (C.c_void_p * max(n, 1))(*[S.ctypes.data for S in Ss])
+        op = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        nf = (C.c_size_t * max(n, 1))(*[S.shape[1] for S in Ss])
+        _check(lib.xdtts_griffinlim_timbre_linear_batch(self._h, sp, nf, n, ta, op))
+        return outs
+
     # -- limiter: look-ahead true-peak limiter where the loudness stage scaled ----
     def set_limiter(self, lookahead_us=0):
         """With a target and a ceiling set (set_loudness): the gain is formed without the ceiling and a look-ahead limiter of
@@ -1400,6 +1460,11 @@ def limiter_reference(audio, rate, gain0, ceiling_lin, lookahead_us):
     _check(lib.xdtts_limiter_reference(_ptr(x) if x.size else None, x.size, int(rate), float(gain0), float(ceiling_lin), int(lookahead_us),
                                        _ptr(out) if x.size else None, C.byref(st)))
     return out, st
+
+
+def timbre_noise_bits(seed, frame, bin):
+    """n of the timbre stage's breath noise at cell (frame, bin): 23 bits, a function of (seed, frame, bin) alone.  Host arithmetic."""
+    return int(lib.xdtts_timbre_noise_bits(int(seed) & 0xFFFFFFFF, int(frame), int(bin)))
 
 
 def stream_sample_bytes(format):

@@ -804,6 +804,92 @@ xdtts_status xdtts_griffinlim_spsi_phase(xdtts_griffinlim *g, const float *S, si
   return xdtts_griffinlim_spsi_phase_batch(g, &S, &n_frames, 1, &turns, &angles);
 }
 
+// ---- timbre: vocal-tract length and breathiness, the voice of a handle (timbre_plan.h, timbre.hip) --------------------------------
+
+void xdtts_timbre_default(xdtts_timbre *t) {
+  if (!t) return;
+  const Timbre d = timbre_default();
+  std::memcpy(t, &d, sizeof d);
+}
+
+uint32_t xdtts_timbre_noise_bits(uint32_t seed, uint32_t frame, uint32_t bin) { return timbre_noise_bits(seed, frame, bin); }
+
+xdtts_status xdtts_griffinlim_set_timbre(xdtts_griffinlim *g, const xdtts_timbre *t) {
+  return guard([&] {
+    const Timbre s = timbre_checked(t);  // (the fields before the handle; a failure leaves the setting as it was)
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->timbre = s;
+  });
+}
+
+xdtts_status xdtts_griffinlim_get_timbre(xdtts_griffinlim *g, xdtts_timbre *t) {
+  return guard([&] {
+    if (!g || !t) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    std::memcpy(t, &g->timbre, sizeof g->timbre);
+  });
+}
+
+// Parity hook of the stage alone: the utterances' magnitudes one behind the other on the device, ONE k_timbre launch -- with
+// the table for several utterances, with the record as a kernel argument for one (the form the single-utterance entries run)
+// -- and back.  A request of identities alone touches no device.  last_timings: ms[0] = the stage alone, ms[1] = the layout change.
+xdtts_status xdtts_griffinlim_timbre_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
+                                                  const xdtts_timbre *t, float *const *S_outs) {
+  return guard([&] {
+    if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    if (!t) fail(XDTTS_ERR_BAD_ARG, "null timbre");
+    std::vector<Timbre> ts((size_t)n_utt);
+    bool any = false;
+    for (int u = 0; u < n_utt; ++u) {
+      std::string msg;
+      std::memcpy(&ts[(size_t)u], &t[u], sizeof(Timbre));
+      msg = timbre_check(ts[(size_t)u]);
+      if (msg.empty() && n_frames) msg = timbre_frames_check(n_frames[u]);
+      if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "utterance %d: %s", u, msg.c_str());
+      any = any || !timbre_is_identity(ts[(size_t)u]);
+    }
+    if (!g || !S || !n_frames || !S_outs) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    Rows rows;
+    for (int u = 0; u < n_utt; ++u) {
+      if (!S[u] || !S_outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
+      rows_add(rows, n_frames[u], (size_t)1 << 24, "batch too large");
+    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    const size_t nb = (size_t)g->nb;
+    if (!any) {  // the identity: S's bits, nothing launched, nothing allocated
+      for (int u = 0; u < n_utt; ++u)
+        if (S_outs[u] != S[u]) std::memmove(S_outs[u], S[u], n_frames[u] * nb * sizeof(float));
+      return;
+    }
+    HIP_CHECK(hipSetDevice(g->device));
+    g->bufs((int)rows.total);  // (frames: the boundary-layout staging of both directions)
+    g->S_timbre.alloc(rows.total * nb);
+    g->timbre_tab_host.clear();
+    for (int u = 0; u < n_utt; ++u) g->timbre_tab_host.push_back(timbre_utt(rows.row0[(size_t)u], rows.row0[(size_t)u], rows.F[(size_t)u], ts[(size_t)u]));
+    if (n_utt > 1) g->timbre_tab.upload(g->timbre_tab_host.data(), g->timbre_tab_host.size(), g->stream);
+    g->upload_rows(S, rows);
+    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+    if (n_utt == 1) g->timbre_one(g->S.p, rows.F[0], ts[0]);
+    else g->timbre_rows(g->S.p, (int)rows.total);
+    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
+    for (int u = 0; u < n_utt; ++u) {
+      const size_t r0 = (size_t)rows.row0[(size_t)u] * nb;
+      launch_transpose(g->S_timbre.p + r0, g->frames.p + r0, rows.F[(size_t)u], g->nb, g->stream);
+    }
+    HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+    for (int u = 0; u < n_utt; ++u) {
+      const size_t r0 = (size_t)rows.row0[(size_t)u] * nb;
+      HIP_CHECK(hipMemcpyAsync(S_outs[u], g->frames.p + r0, (size_t)rows.F[(size_t)u] * nb * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    }
+    g->finish_timings();  // (drains the stream: the table and the outputs)
+  });
+}
+
+xdtts_status xdtts_griffinlim_timbre_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_timbre *t, float *S_out) {
+  return xdtts_griffinlim_timbre_linear_batch(g, &S, &n_frames, 1, t, &S_out);
+}
+
 // ---- output rate: 22 050 Hz -> 8 .. 96 kHz behind the loop, in front of the output normalisation (resample_plan.h, resample.hip) ----
 
 // The rate rule of the entries: the plan of a supported rate, else XDTTS_ERR_BAD_ARG with the rate and the rule.

@@ -160,6 +160,14 @@ void xdtts_griffinlim::contour_launch() {
   launch_prosody_contour(S.p, S_pros.p, contour_utts.p, (int)contour_utts_host.size(), contour_ftab.p, contour_n_tab, contour_rows, tw.p, stream);
 }
 
+// The timbre stage (timbre.hip) on a magnitude in place, out of place into S_timbre.
+void xdtts_griffinlim::timbre_one(const float *S_in, int F, const Timbre &t) {
+  launch_timbre(S_in, S_timbre.p, nullptr, 1, timbre_utt(0, 0, F, t), F, tw.p, stream);
+}
+void xdtts_griffinlim::timbre_rows(const float *S_in, int rows_all) {
+  launch_timbre(S_in, S_timbre.p, timbre_tab.p, (int)timbre_tab_host.size(), TimbreUtt{}, rows_all, tw.p, stream);
+}
+
 // The pitch tracker (f0.hip).  Buffers grow with the request and stay; a growth happens behind a drained stream (every request
 // path starts there).
 void xdtts_griffinlim::f0_prepare(const std::vector<F0Utt> &utts) {
@@ -808,6 +816,7 @@ static GlBufs request_bufs(xdtts_griffinlim *g, int F, const ProsodyArg &p) {
   const int Fp = p.frames(0, F);
   GlBufs b = g->bufs(std::max(F, Fp));  // (before mel -> linear: growing S would drop its contents; in gl_collect nothing grows)
   b.F = Fp;
+  if (g->timbre_on()) g->S_timbre.alloc((size_t)Fp * g->nb);  // (the identity allocates nothing)
   return b;
 }
 // GriffinLim::infer (G1..G6) from a mel in HBM, in two halves for a caller that overlaps the vocoder with other work
@@ -823,6 +832,10 @@ void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, i
     g->prosody(p, F);
     b.S = g->prosody_S(p);
   }
+  if (g->timbre_on()) {  // the handle's voice: behind the prosody stage (the tracker saw the unmodified voice), in front of the phase
+    g->timbre_one(b.S, b.F, g->timbre);
+    b.S = g->S_timbre.p;
+  }
   HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
   g->probe_tick();
   enqueue_run(g, b, nullptr, g->iters, true, host);  // (the sequence hands in a buffer it took from the pool while the frame loop ran)
@@ -830,6 +843,7 @@ void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, i
 void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const ProsodyArg &p) {
   GlBufs b = request_bufs(g, F, p);
   if (p) b.S = g->prosody_S(p);
+  if (g->timbre_on()) b.S = g->S_timbre.p;  // (intact: a demoted engine's retry runs on it again)
   collect_run(g, b, nullptr, g->iters, true, host, audio, n_samples);
 }
 
@@ -1011,6 +1025,16 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     g->S_pros.alloc(rows.total * (size_t)g->nb);
     all.S = g->S_pros.p;
   }
+  // The handle's timbre: one setting for every utterance, the ragged stage on the rows behind the prosody stage (src0 = dst0).
+  const bool timbre = g->timbre_on();
+  const float *const S_staged = all.S;  // what the timbre stage reads: S, or S_pros
+  if (timbre) {
+    g->timbre_tab_host.clear();
+    for (int u = 0; u < n_utt; ++u) g->timbre_tab_host.push_back(timbre_utt(fbase[u], fbase[u], Fu[u], g->timbre));
+    g->timbre_tab.upload(g->timbre_tab_host.data(), g->timbre_tab_host.size(), st);
+    g->S_timbre.alloc(rows.total * (size_t)g->nb);
+    all.S = g->S_timbre.p;
+  }
   g->audio.alloc(std::max<size_t>(Ntot, 1));
   // What is delivered: at 22050 the loop's audio where it lies; at another rate the resampled utterances back to back in
   // audio_rs, and everything behind the loop -- the normaliser's table, the fetch copies, the counts -- works from those.
@@ -1061,6 +1085,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
       if (pros.f0) g->f0_launch(g->S.p, *pros.f0, g->contour_ftab.p, g->contour_n_tab);  // (from the intact S: a retry writes the same pitches)
       g->contour_launch();
     } else if (staged) launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)rows.total, g->tw.p, st);
+    if (timbre) g->timbre_rows(S_staged, (int)rows.total);  // (out of place: a retry finds S and S_pros intact)
     if (use_spsi) g->spsi_batch(all.S, spsi_tab, all.ang, all.tprev);
     HIP_CHECK(hipEventRecord(g->ev.e[1], st));
     if (!use_spsi) launch_gl_phase_init_batch(all, g->seed, g->frame_local.p, st);

@@ -64,6 +64,19 @@ inline StreamOpts stream_opts_checked(const xdtts_stream_opts *o) {
   if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
   return s;
 }
+// xdtts_timbre (include/xdtts.h) on top of timbre_plan.h, which knows no status codes: the checked setting (null = the default,
+// the identity), before a handle is looked at; and the record of one utterance of the stage.
+inline Timbre timbre_checked(const xdtts_timbre *t) {
+  static_assert(sizeof(xdtts_timbre) == sizeof(Timbre) && sizeof(Timbre) == 20, "Timbre is xdtts_timbre");
+  Timbre s = timbre_default();
+  if (t) std::memcpy(&s, t, sizeof s);
+  const std::string msg = timbre_check(s);
+  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  return s;
+}
+inline TimbreUtt timbre_utt(int src0, int dst0, int F, const Timbre &t) {
+  return TimbreUtt{src0, dst0, F, t.vtl, t.breath, t.seed, t.lifter, t.log_floor};
+}
 // Rows::add (gl_plan.h, which knows no status codes) inside a request: past the cap it fails with XDTTS_ERR_BAD_ARG and the text
 inline void rows_add(Rows &r, size_t rows, size_t cap, const char *too_large) {
   try {
@@ -160,6 +173,21 @@ struct xdtts_griffinlim {
   void f0_prepare_contour(const xdtts::F0Job &job);  // ... from the records contour_upload() has just built
   void f0_launch(const float *S_dev, const xdtts::F0Job &job, unsigned *ftab, int n_tab, hipEvent_t between = nullptr);
   void f0_collect();  // behind a drained stream: the pinned stats -> last_f0
+
+  // timbre (timbre.hip): the voice of this handle -- vocal-tract length and breathiness on the magnitude that would enter the
+  // loop (S, or S_pros behind a prosody stage), out of place into S_timbre [F'][nb]; S and S_pros stay as their stages left them.
+  // The identity (the default) launches and allocates nothing.  The table of the ragged form and its host vector, the upload's
+  // source, stay until the next request of this handle, which every path starts behind a drained stream.
+  xdtts::Timbre timbre = xdtts::timbre_default();
+  bool timbre_on() const { return !xdtts::timbre_is_identity(timbre); }
+  DevBuf<float> S_timbre;
+  DevBuf<xdtts::TimbreUtt> timbre_tab;
+  std::vector<xdtts::TimbreUtt> timbre_tab_host;
+  // One utterance: S_in [F][nb] -> S_timbre (allocated by the caller) under t, one launch on the stream, nothing uploaded.
+  void timbre_one(const float *S_in, int F, const xdtts::Timbre &t);
+  // Ragged: the records of timbre_tab_host (uploaded by the caller as timbre_tab), rows_all rows, one launch; any number of
+  // times (a retry).
+  void timbre_rows(const float *S_in, int rows_all);
 
   // initial phase (phase_spsi.hip): 0 = the seeded random stream, 1 = SPSI on the magnitude that enters the loop
   int phase_init = 0;

@@ -7,6 +7,7 @@
 #include "loudness_plan.h"
 #include "resample_plan.h"
 #include "stream_plan.h"
+#include "timbre_plan.h"
 #include "weights.h"
 
 namespace xdtts {
@@ -334,6 +335,23 @@ struct ContourUtt {
 };
 void launch_prosody_contour(const float *S, float *Sout, const ContourUtt *utt, int n_utt, const unsigned *ftab, int n_tab, int Fout_all,
                             const float2 *tw, hipStream_t s);
+
+// ---- timbre (timbre.hip): vocal-tract length and breathiness on the magnitude, behind prosody and in front of the initial phase ----
+// S -> Sout, out of place, the same frame counts: utterance u's F rows start at row src0 of S and at row dst0 of Sout (dst0
+// ascending, back to back; rows_all = the sum of F); per frame the ENVELOPE of the prosody stage's cepstral split is resampled by
+// vtl on the frequency axis and the fine structure fades by `breath` into a noise of (seed, frame inside the utterance, bin)
+// (include/xdtts.h, timbre_plan.h).  An utterance with vtl == 1 and breath == 0 is copied.  tab (device memory, n_utt records),
+// or nullptr: n_utt = 1 and the record is `one`, a kernel argument -- nothing is uploaded.  One launch of one kernel either
+// way; a row has the same bits in both forms.
+struct TimbreUtt {
+  int src0, dst0, F;
+  float vtl, breath;
+  uint32_t seed;
+  int lifter;
+  float log_floor;
+};
+void launch_timbre(const float *S, float *Sout, const TimbreUtt *tab, int n_utt, const TimbreUtt &one, int rows_all, const float2 *tw,
+                   hipStream_t s);
 
 // ---- pitch tracker (f0.hip): F0 per frame from the magnitude's cepstrum, the utterance's median, pitch targets (include/xdtts.h) ----
 // raw[t], strength[t] for every row t < rows of S [rows][513] (the utterances of a batch back to back: a frame needs nothing of

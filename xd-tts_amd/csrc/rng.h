@@ -1,7 +1,8 @@
 // rng.h -- the counter-based RNG (specification shared with oracle/, implemented independently).  Plain C++ with the HIP
 // qualifiers only under hipcc: common.h brings it to the library, stream_plan.h to the host drivers that build with plain g++.
 // Stream numbers in use: 0x47 the vocoder's initial phase, 0x1000 + ... the prenet dropout, the small row indices of the
-// synthetic weights, 0x57AEA401 the TPDF dither of the stream stage (stream_plan.h).
+// synthetic weights, 0x57AEA401 the TPDF dither of the stream stage (stream_plan.h), 0x71B8 the breath noise of the timbre
+// stage (timbre_plan.h).
 #pragma once
 #include <cstdint>
 
