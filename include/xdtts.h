@@ -796,7 +796,8 @@ xdtts_status xdtts_true_peak_filter(float taps[3][24]);
  * of the single call.  At programme level (xdtts_stream_opts.level = 1) the stage runs once over the formed fp32 stream, and
  * the encode reads the limited stream; gaps stay the exact zeros.  0 = off (the default): nothing new is launched and every
  * result keeps its bits.  A value outside 0 and [500, 10000] is XDTTS_ERR_BAD_ARG and leaves the setting alone.
- * Out of scope: make-up gain or iteration toward the target, a compressor, separate attack and release; the values delivered
+ * Out of scope: make-up gain or iteration toward the target, separate attack and release (the compressor below has both, in
+ * front of the level stage); the values delivered
  * for non-finite samples are not specified. */
 typedef struct {
   float   min_gain;     /* the smallest g; 1 where nothing was limited */
@@ -825,6 +826,87 @@ xdtts_status xdtts_limiter_plan(int32_t rate, int32_t lookahead_us, int32_t *hal
 xdtts_status xdtts_limiter_window(int32_t rate, int32_t lookahead_us, float *w);
 xdtts_status xdtts_limiter_reference(const float *audio, size_t n, int32_t rate, double gain0, double ceiling_lin, int32_t lookahead_us,
                                      float *out, xdtts_limiter_stats *stats);
+
+/* Dynamic range compressor in FRONT of the level stage (<amazon:effect name="drc">).  The stage runs on a finished utterance
+ * behind the resampler, at the delivered rate, and in front of whichever level stage is configured -- the output
+ * normalisation, the loudness target, the limiter -- so an rms or LUFS target still holds for what the caller receives.
+ * Nothing has to be causal: in the place of an attack / release follower (a state-dependent recurrence) the gain is driven by a
+ * TENT ENVELOPE in the log domain -- each sample's level spreads backwards with the attack slope and forwards with the release
+ * slope, and the envelope is the maximum over all tents: two max-plus scans over integers, associative, order-free, exact.
+ * The definition, exactly -- x the n fp32 samples at rate Q, c the settings:
+ *   level   a[n] = |x[n]|; l[n] = lvl(a[n]), an int32 in units of 2^-16 octaves: for a normal float 2^e (1 + f), f in [0, 1),
+ *           lvl = 65536 e + (int32) fl(65536 p + 0.5) with p = fl(f q(f)), q the degree-8 polynomial of compressor_plan.h
+ *           (COMP_LOG2_Q; |f q(f) - log2(1 + f)| <= 4e-8 in exact arithmetic) by Horner's rule in fmaf from the highest
+ *           coefficient; zeros and denormals have lvl = L_FLOOR = -127 * 65536.  lvl(1) = 0; no finite float's level exceeds
+ *           128 * 65536, so every sum below fits 32 bits inside a tile and 64 bits anywhere.
+ *   reference level  P = lvl(max a[n]): thresholds are in dB under the utterance's own sample peak (the level of Griffin-Lim
+ *           output in front of the level stage is arbitrary).  A maximum does not depend on the order, so P is exact however
+ *           it is reduced.  max a = 0: not engaged, the utterance is delivered unchanged.
+ *   slopes  host integers, log10(2) = 0.30102999566398119521, doubles, each step one operation in the order written,
+ *           round(v) = floor(v + 0.5):  oct10 = 10 / (20 log10 2);
+ *           alpha = clamp(round(65536 oct10 / (attack_ms Q / 1000)), 1, 2^18), rho likewise from release_ms;
+ *           T = round(threshold_db (65536 / (20 log10 2))), W = round(knee_db (65536 / (20 log10 2))).
+ *           attack_ms: the time in which the gain ramps across 10 dB in front of a loud onset; release_ms: behind it.
+ *   envelope  V[n] = max( max over k <= n of (l[k] - (n - k) rho), max over k >= n of (l[k] - (k - n) alpha) ), exact in
+ *           integers; serially E[n] = max(l[n], E[n - 1] - rho), its mirror image with alpha, V the larger of the two.
+ *   gain    s = (float)(1 / ratio - 1) <= 0, o = V[n] - (P + T) (int32).  In integers: 2 o <= -W: r = 0;  2 |o| < W:
+ *           h = fl((float) o + (float)(W / 2)), r = fl(fl(h h) kq) with kq = (float)(s / (2 W)) formed in double;  otherwise
+ *           r = fl(s (float) o).  g = min(1, exp2(r / 65536)): r / 65536 = i + f with i = floor, 2^f = fmaf(f, q(f), 1), q of
+ *           degree 5 (COMP_EXP2_Q; |1 + f q(f) - 2^f| <= 3e-8), times 2^i through the exponent bits, 0 below -126 octaves.
+ *           out[n] = fl(x[n] fl(g mk)), mk = (float) 10^(makeup_db / 20).  Where r = 0, g = 1 exactly: untouched stretches
+ *           are fl(x mk), and with makeup_db = 0 they are the input's bits.
+ *   stats   peak = max a; max_over = the largest o; compressed = the number of samples with r < 0; engaged.  Integer maxima
+ *           and sums: independent of the order of arrival.  Not engaged (or the identity): all four are 0.
+ * Settings: threshold_db in [-60, 0] (dB re peak), ratio in [1, 20], knee_db in [0, 24], attack_ms in [0.1, 100], release_ms in
+ * [1, 2000], makeup_db in [0, 24], all finite; anything else is XDTTS_ERR_BAD_ARG before a device is touched, the message
+ * names the field.  ratio == 1 with makeup_db == 0 is the identity: nothing is launched and every bit is kept.  Decided on the
+ * device (P, engaged) without a host synchronisation; the ragged batch returns the bits of the single call, and the device the
+ * bits of xdtts_compressor_reference.  Honoured by every entry that delivers an utterance: the single calls, both halves of a
+ * sequence, the batch, a demoted engine's retry, and the pieces of xdtts_synthesize_document (each piece on its own, also at
+ * programme level).  Off (the default): nothing new is launched and every result keeps its bits.
+ * Out of scope: a compressor over the joined document stream, settings per utterance inside a batch, a downward expander or
+ * gate, multiband, RMS- or LUFS-relative thresholds; the values delivered for non-finite samples are not specified. */
+typedef struct {
+  float threshold_db;   /* dB relative to the utterance's sample peak, [-60, 0] */
+  float ratio;          /* [1, 20] */
+  float knee_db;        /* full width of the soft knee, [0, 24] */
+  float attack_ms;      /* [0.1, 100] */
+  float release_ms;     /* [1, 2000] */
+  float makeup_db;      /* [0, 24] */
+} xdtts_compressor;
+typedef struct {
+  float   peak;         /* max |x| of the utterance in front of the stage; 0 where not engaged */
+  int32_t max_over;     /* the largest o = V - (P + T), Q16 octaves */
+  int32_t engaged;      /* 1 where the stage ran */
+  int64_t compressed;   /* samples with r < 0 */
+} xdtts_compressor_stats;
+void xdtts_compressor_default(xdtts_compressor *c);   /* the identity: {0, 1, 0, 5, 100, 0} */
+/* which = 0: the default; 1: "drc" {-24, 3, 6, 5, 100, 0} -- the level stage behind supplies the make-up.  Else BAD_ARG. */
+xdtts_status xdtts_compressor_preset(int32_t which, xdtts_compressor *out);
+/* c == NULL switches the stage off (the default).  The fields are looked at before the handle. */
+xdtts_status xdtts_griffinlim_set_compressor(xdtts_griffinlim *g, const xdtts_compressor *c);
+/* *on = 1 and *c = the setting, or *on = 0 and *c = the default; either pointer may be NULL */
+xdtts_status xdtts_griffinlim_get_compressor(const xdtts_griffinlim *g, xdtts_compressor *c, int32_t *on);
+/* The stats of each utterance of the last delivering call, shaped like xdtts_griffinlim_last_limiter; *n = 0 unless a
+ * compressor other than the identity is set. */
+xdtts_status xdtts_griffinlim_last_compressor(const xdtts_griffinlim *g, xdtts_compressor_stats *out, size_t cap, size_t *n);
+/* The stage alone on the caller's audio (1 <= n < 2^28 samples, 8000 <= rate <= 96000), whatever the handle's settings.  The
+ * parity hook: out (n floats) and stats equal xdtts_compressor_reference bit for bit, and every outs[u] of the ragged form
+ * equals the single call's.  Argument errors come back before a device is touched.  Afterwards xdtts_griffinlim_last_timings
+ * ms[0] is the stage alone. */
+xdtts_status xdtts_griffinlim_compress(xdtts_griffinlim *g, const float *audio, size_t n, int32_t rate, const xdtts_compressor *c,
+                                       float *out, xdtts_compressor_stats *stats);
+xdtts_status xdtts_griffinlim_compress_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt, int32_t rate,
+                                             const xdtts_compressor *c, float *const *outs, xdtts_compressor_stats *stats);
+/* Host arithmetic, no handle, no device.  _plan: the host integers and the tile (samples per workgroup); any pointer may be
+ * NULL.  _level: l[0 .. n) = lvl(|audio|).  _envelope: V[0 .. n).  _reference: the definition evaluated sample by sample in
+ * the serial form in plain C++ (stats may be NULL). */
+xdtts_status xdtts_compressor_plan(int32_t rate, const xdtts_compressor *c, int32_t *alpha, int32_t *rho, int32_t *T, int32_t *W,
+                                   int32_t *tile);
+xdtts_status xdtts_compressor_level(const float *audio, size_t n, int32_t *l);
+xdtts_status xdtts_compressor_envelope(const float *audio, size_t n, int32_t rate, const xdtts_compressor *c, int32_t *V);
+xdtts_status xdtts_compressor_reference(const float *audio, size_t n, int32_t rate, const xdtts_compressor *c, float *out,
+                                        xdtts_compressor_stats *stats);
 
 /* Document output: the utterances of a sequence joined with their <break> silences into ONE stream, faded at their edges,
  * levelled by one programme gain and encoded, on the device -- the output stage of XdTts::generate_audio (src/lib.rs:60-108:

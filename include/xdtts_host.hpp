@@ -438,6 +438,37 @@ class GriffinLim {
     if (stats) *stats = st;
     return out;
   }
+  // A dynamic range compressor in front of the level stage (xdtts_griffinlim_set_compressor): nullptr = off, the default;
+  // compressor_preset(1) is "drc".  It runs behind the output rate and in front of the normalisation / loudness target / limiter.
+  static xdtts_compressor compressor_preset(int32_t which) {
+    xdtts_compressor c{};
+    check(xdtts_compressor_preset(which, &c));
+    return c;
+  }
+  void set_compressor(const xdtts_compressor *c) { check(xdtts_griffinlim_set_compressor(g_, c)); }
+  // ... the setting, and whether the stage is on
+  bool compressor_setting(xdtts_compressor *c) const {
+    int32_t on = 0;
+    check(xdtts_griffinlim_get_compressor(g_, c, &on));
+    return on != 0;
+  }
+  // ... the stats of each utterance of the last delivering call (empty unless a compressor other than the identity is set)
+  std::vector<xdtts_compressor_stats> last_compressor() const {
+    size_t n = 0;
+    check(xdtts_griffinlim_last_compressor(g_, nullptr, 0, &n));
+    std::vector<xdtts_compressor_stats> out(n);
+    if (n) check(xdtts_griffinlim_last_compressor(g_, out.data(), out.size(), &n));
+    return out;
+  }
+  // ... and the stage alone on the caller's audio (xdtts_griffinlim_compress): the bits of xdtts_compressor_reference
+  std::vector<float> compress(const std::vector<float> &audio, int32_t rate, const xdtts_compressor &c,
+                              xdtts_compressor_stats *stats = nullptr) const {
+    std::vector<float> out(audio.size());
+    xdtts_compressor_stats st{};
+    check(xdtts_griffinlim_compress(g_, audio.data(), audio.size(), rate, &c, out.data(), &st));
+    if (stats) *stats = st;
+    return out;
+  }
   // The voice of this handle (xdtts_griffinlim_set_timbre): vocal-tract length and breathiness on the magnitude behind the prosody
   // stage.  The default is the identity, which launches nothing; every entry that runs mel -> linear itself honours the setting.
   static xdtts_timbre default_timbre() {

@@ -13,6 +13,7 @@ run gemm_bench.py             python tools/gemm_bench.py 200 2
 run gl_check.py               python tools/gl_check.py
 run loudness_check.py         python tools/loudness_check.py
 run limiter_check.py          python tools/limiter_check.py
+run compressor_check.py       python tools/compressor_check.py
 run timbre_check.py           python tools/timbre_check.py
 run document_check.py         python tools/document_check.py 2
 run gl_hash.py                python tools/gl_hash.py

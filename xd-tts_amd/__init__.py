@@ -183,6 +183,34 @@ class LimiterStats(C.Structure):
         return (self.min_gain, self.half_width, self.engaged, self.limited)
 
 
+class Compressor(C.Structure):
+    """xdtts_compressor: the dynamic range compressor in front of the level stage.  threshold_db in [-60, 0] (dB under the
+    utterance's own sample peak), ratio in [1, 20], knee_db in [0, 24], attack_ms in [0.1, 100], release_ms in [1, 2000],
+    makeup_db in [0, 24].  Compressor() holds the library's defaults (0, 1, 0, 5, 100, 0), i.e. the identity; keywords override
+    fields; compressor_preset(1) is "drc"."""
+
+    _fields_ = [("threshold_db", C.c_float), ("ratio", C.c_float), ("knee_db", C.c_float), ("attack_ms", C.c_float), ("release_ms", C.c_float),
+                ("makeup_db", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib.xdtts_compressor_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def astuple(self):
+        return (self.threshold_db, self.ratio, self.knee_db, self.attack_ms, self.release_ms, self.makeup_db)
+
+
+class CompressorStats(C.Structure):
+    """xdtts_compressor_stats: what the compressor did to one utterance."""
+
+    _fields_ = [("peak", C.c_float), ("max_over", C.c_int32), ("engaged", C.c_int32), ("compressed", C.c_int64)]
+
+    def astuple(self):
+        return (self.peak, self.max_over, self.engaged, self.compressed)
+
+
 STREAM_F32, STREAM_PCM16, STREAM_ULAW, STREAM_ALAW = 0, 1, 2, 3
 _STREAM_DTYPE = {STREAM_F32: np.float32, STREAM_PCM16: np.dtype("<i2"), STREAM_ULAW: np.uint8, STREAM_ALAW: np.uint8}
 
@@ -335,6 +363,17 @@ SYMBOLS = {
     "xdtts_limiter_plan": (_I32, [_I32, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "xdtts_limiter_window": (_I32, [_I32, _I32, _VP]),
     "xdtts_limiter_reference": (_I32, [_VP, _SZ, _I32, C.c_double, C.c_double, _I32, _VP, _VP]),
+    "xdtts_compressor_default": (None, [_VP]),
+    "xdtts_compressor_preset": (_I32, [_I32, _VP]),
+    "xdtts_griffinlim_set_compressor": (_I32, [_VP, _VP]),
+    "xdtts_griffinlim_get_compressor": (_I32, [_VP, _VP, C.POINTER(_I32)]),
+    "xdtts_griffinlim_last_compressor": (_I32, [_VP, _VP, _SZ, C.POINTER(_SZ)]),
+    "xdtts_griffinlim_compress": (_I32, [_VP, _VP, _SZ, _I32, _VP, _VP, _VP]),
+    "xdtts_griffinlim_compress_batch": (_I32, [_VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
+    "xdtts_compressor_plan": (_I32, [_I32, _VP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "xdtts_compressor_level": (_I32, [_VP, _SZ, _VP]),
+    "xdtts_compressor_envelope": (_I32, [_VP, _SZ, _I32, _VP, _VP]),
+    "xdtts_compressor_reference": (_I32, [_VP, _SZ, _I32, _VP, _VP, _VP]),
     "xdtts_griffinlim_free": (None, [_VP]),
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
@@ -1293,6 +1332,47 @@ class GriffinLim:
                                                     int(lookahead_us), op, stats))
         return outs, [stats[i] for i in range(n)]
 
+    # -- compressor: tent-envelope dynamic range compressor in front of the level stage ----
+    def set_compressor(self, compressor=None):
+        """The handle's compressor from now on: a Compressor, or None for off (the default).  It runs behind the output rate and
+        in front of the output normalisation / loudness target / limiter, on every entry that delivers an utterance;
+        last_compressor() then has the stats of each utterance.  The identity (ratio 1, makeup 0) launches nothing."""
+        _check(lib.xdtts_griffinlim_set_compressor(self._h, _opt_ref(compressor)))
+
+    def get_compressor(self):
+        """The Compressor that is set, or None where the stage is off."""
+        c, on = Compressor(), C.c_int32()
+        _check(lib.xdtts_griffinlim_get_compressor(self._h, C.byref(c), C.byref(on)))
+        return c if on.value else None
+
+    def last_compressor(self):
+        """[CompressorStats] of the last delivering call, in the caller's order; [] unless a compressor other than the identity is set."""
+        n = C.c_size_t()
+        _check(lib.xdtts_griffinlim_last_compressor(self._h, None, 0, C.byref(n)))
+        out = (CompressorStats * max(n.value, 1))()
+        _check(lib.xdtts_griffinlim_last_compressor(self._h, out, n.value, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
+    def compress(self, audio, rate, compressor):
+        """The stage alone on `audio`, whatever the handle's settings: (out, CompressorStats), the bits of compressor_reference()."""
+        outs, stats = self.compress_batch([audio], rate, compressor)
+        return outs[0], stats[0]
+
+    def compress_batch(self, audios, rate, compressor):
+        """The ragged stage: one set of launches for all audios, every output and struct the single call's bit for bit."""
+        xs = [np.ascontiguousarray(a, dtype=np.float32).ravel() for a in audios]
+        n = len(xs)
+        outs = [np.empty(x.size, dtype=np.float32) for x in xs]
+        stats = (CompressorStats * max(n, 1))()
+        ip = (C.c_void_p * max(n, 1))(*[x.ctypes.data for x in xs])
+        op = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        ns = (C.c_size_t * max(n, 1))(*[x.size for x in xs])
+        if n == 1:
+            _check(lib.xdtts_griffinlim_compress(self._h, ip[0], ns[0], int(rate), C.byref(compressor), op[0], stats))
+        else:
+            _check(lib.xdtts_griffinlim_compress_batch(self._h, ip, ns, n, int(rate), C.byref(compressor), op, stats))
+        return outs, [stats[i] for i in range(n)]
+
     # -- stream: a sequence joined with its gaps, faded, levelled and encoded on the device ----
     def join(self, audios, gaps=None, rate=SAMPLE_RATE, opts=None, guard=0):
         """xdtts_griffinlim_join: the stage alone on the caller's audios (fp32, each read where it lies: a view's address decides
@@ -1459,6 +1539,47 @@ def limiter_reference(audio, rate, gain0, ceiling_lin, lookahead_us):
     st = LimiterStats()
     _check(lib.xdtts_limiter_reference(_ptr(x) if x.size else None, x.size, int(rate), float(gain0), float(ceiling_lin), int(lookahead_us),
                                        _ptr(out) if x.size else None, C.byref(st)))
+    return out, st
+
+
+def compressor_preset(which):
+    """xdtts_compressor_preset: 0 the default (the identity), 1 "drc" (-24 dB, 3:1, knee 6 dB, 5 ms / 100 ms, no make-up)."""
+    c = Compressor()
+    _check(lib.xdtts_compressor_preset(int(which), C.byref(c)))
+    return c
+
+
+def compressor_plan(rate, compressor):
+    """xdtts_compressor_plan (host arithmetic): {"alpha", "rho", "T", "W", "tile"} -- slopes per sample, threshold and knee, all in
+    2^-16 octaves, and the samples per workgroup."""
+    v = [C.c_int32() for _ in range(5)]
+    _check(lib.xdtts_compressor_plan(int(rate), C.byref(compressor), *[C.byref(x) for x in v]))
+    return dict(zip(("alpha", "rho", "T", "W", "tile"), (x.value for x in v)))
+
+
+def compressor_level(audio):
+    """xdtts_compressor_level: the library's own lvl(|audio|), int32 in 2^-16 octaves (host arithmetic)."""
+    x = np.ascontiguousarray(audio, dtype=np.float32).ravel()
+    l = np.zeros(x.size, dtype=np.int32)
+    _check(lib.xdtts_compressor_level(_ptr(x) if x.size else None, x.size, _ptr(l) if x.size else None))
+    return l
+
+
+def compressor_envelope(audio, rate, compressor):
+    """xdtts_compressor_envelope: the integer envelope V of the definition (host arithmetic, the serial form)."""
+    x = np.ascontiguousarray(audio, dtype=np.float32).ravel()
+    V = np.zeros(x.size, dtype=np.int32)
+    _check(lib.xdtts_compressor_envelope(_ptr(x) if x.size else None, x.size, int(rate), C.byref(compressor), _ptr(V) if x.size else None))
+    return V
+
+
+def compressor_reference(audio, rate, compressor):
+    """xdtts_compressor_reference: the definition sample by sample in plain C++ on the host: (out, CompressorStats)."""
+    x = np.ascontiguousarray(audio, dtype=np.float32).ravel()
+    out = np.empty(x.size, dtype=np.float32)
+    st = CompressorStats()
+    _check(lib.xdtts_compressor_reference(_ptr(x) if x.size else None, x.size, int(rate), C.byref(compressor), _ptr(out) if x.size else None,
+                                          C.byref(st)))
     return out, st
 
 

@@ -1238,6 +1238,178 @@ xdtts_status xdtts_griffinlim_limit(xdtts_griffinlim *g, const float *audio, siz
   return xdtts_griffinlim_limit_batch(g, &audio, &n, 1, rate, gain0, ceiling_lin, lookahead_us, &out, stats);
 }
 
+// ---- compressor: tent-envelope dynamic range compressor in front of the level stage (compressor_plan.h, compressor.hip) --------
+
+static_assert(sizeof(xdtts_compressor) == sizeof(Compressor) && offsetof(xdtts_compressor, makeup_db) == offsetof(Compressor, makeup_db),
+              "xdtts_compressor and Compressor share one layout");
+static_assert(sizeof(xdtts_compressor_stats) == sizeof(CompressorStats) &&
+                  offsetof(xdtts_compressor_stats, compressed) == offsetof(CompressorStats, compressed),
+              "xdtts_compressor_stats and CompressorStats share one layout");
+
+// the checked setting (null is an error here: the entries that take "off" look at the pointer first)
+static Compressor compressor_checked(const xdtts_compressor *c) {
+  if (!c) fail(XDTTS_ERR_BAD_ARG, "compressor: null settings");
+  Compressor s;
+  std::memcpy(&s, c, sizeof s);
+  const std::string msg = compressor_check(s);
+  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  return s;
+}
+
+void xdtts_compressor_default(xdtts_compressor *c) {
+  if (!c) return;
+  const Compressor d = compressor_default();
+  std::memcpy(c, &d, sizeof d);
+}
+
+xdtts_status xdtts_compressor_preset(int32_t which, xdtts_compressor *out) {
+  return guard([&] {
+    if (!out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    Compressor p;
+    if (!compressor_preset(which, &p)) fail(XDTTS_ERR_BAD_ARG, "compressor: preset %d is not 0 (default) or 1 (drc)", which);
+    std::memcpy(out, &p, sizeof p);
+  });
+}
+
+xdtts_status xdtts_compressor_plan(int32_t rate, const xdtts_compressor *c, int32_t *alpha, int32_t *rho, int32_t *T, int32_t *W,
+                                   int32_t *tile) {
+  return guard([&] {
+    const Compressor s = compressor_checked(c);
+    const std::string msg = compressor_rate_check(rate);
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+    const CompPlan p = compressor_plan(s, rate);
+    if (alpha) *alpha = p.alpha;
+    if (rho) *rho = p.rho;
+    if (T) *T = p.T;
+    if (W) *W = p.W;
+    if (tile) *tile = COMP_TILE;
+  });
+}
+
+xdtts_status xdtts_compressor_level(const float *audio, size_t n, int32_t *l) {
+  return guard([&] {
+    if (n >= COMP_MAX_SAMPLES) fail(XDTTS_ERR_BAD_ARG, "compressor: need at most 2^28 - 1 samples, got %zu", n);
+    if (n && (!audio || !l)) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    compressor_level(audio, n, l);
+  });
+}
+
+xdtts_status xdtts_compressor_envelope(const float *audio, size_t n, int32_t rate, const xdtts_compressor *c, int32_t *V) {
+  return guard([&] {
+    const Compressor s = compressor_checked(c);
+    const std::string msg = compressor_args_check(s, rate, n);
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+    if (!audio || !V) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    const CompPlan p = compressor_plan(s, rate);
+    std::vector<int32_t> l(n);
+    compressor_level(audio, n, l.data());
+    compressor_envelope_from_level(l.data(), n, p.alpha, p.rho, V);
+  });
+}
+
+xdtts_status xdtts_compressor_reference(const float *audio, size_t n, int32_t rate, const xdtts_compressor *c, float *out,
+                                        xdtts_compressor_stats *stats) {
+  return guard([&] {
+    const Compressor s = compressor_checked(c);
+    const std::string msg = compressor_args_check(s, rate, n);
+    if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+    if (!audio || !out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    const CompressorStats st = compressor_reference(audio, n, rate, s, out);
+    if (stats) std::memcpy(stats, &st, sizeof st);
+  });
+}
+
+xdtts_status xdtts_griffinlim_set_compressor(xdtts_griffinlim *g, const xdtts_compressor *c) {
+  return guard([&] {
+    Compressor s = compressor_default();
+    if (c) s = compressor_checked(c);  // the fields first: reported without a handle
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->comp = s;
+    g->comp_set = c != nullptr;
+  });
+}
+
+xdtts_status xdtts_griffinlim_get_compressor(const xdtts_griffinlim *g, xdtts_compressor *c, int32_t *on) {
+  return guard([&] {
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (c) std::memcpy(c, &g->comp, sizeof g->comp);
+    if (on) *on = g->comp_set ? 1 : 0;
+  });
+}
+
+xdtts_status xdtts_griffinlim_last_compressor(const xdtts_griffinlim *g, xdtts_compressor_stats *out, size_t cap, size_t *n) {
+  return guard([&] {
+    if (n) *n = 0;
+    if (!g || !n) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    *n = g->last_comp.size();
+    if (!out && cap == 0) return;  // the count alone
+    if (!out || cap < g->last_comp.size()) fail(XDTTS_ERR_BAD_ARG, "the last call delivered %zu utterances, the buffer holds %zu", g->last_comp.size(), cap);
+    if (!g->last_comp.empty()) std::memcpy(out, g->last_comp.data(), g->last_comp.size() * sizeof(xdtts_compressor_stats));
+  });
+}
+
+// The stage alone, single call and ragged batch: the audios one behind the other on the device, the three launches of
+// launch_compress in place (the single call passes its record by value, the batch uploads the table), the outputs and the
+// stats back.  The identity touches no device: the inputs' bits, stats of zeros.  last_timings: ms[0] = the stage alone.
+xdtts_status xdtts_griffinlim_compress_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt, int32_t rate,
+                                             const xdtts_compressor *c, float *const *outs, xdtts_compressor_stats *stats) {
+  return guard([&] {
+    const Compressor s = compressor_checked(c);
+    if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    if (!n) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::vector<CompUtt> tab((size_t)n_utt);
+    size_t tot = 0, tile = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      const std::string msg = compressor_args_check(s, rate, n[u]);
+      if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "utterance %d: %s", u, msg.c_str());
+      tab[(size_t)u] = {(long long)tot, (long long)tot, (int)n[u], (int)tile};  // (back to back, as the batch's rows lie)
+      tot += n[u];
+      tile += compressor_tiles(n[u]);
+      if (tot > (size_t)0x7fffffff) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^31 - 1 samples");
+    }
+    if (!g || !audios || !outs || !stats) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    for (int u = 0; u < n_utt; ++u)
+      if (!audios[u] || !outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null audio / out", u);
+    if (compressor_is_identity(s)) {
+      for (int u = 0; u < n_utt; ++u) {
+        if (outs[u] != audios[u]) std::memmove(outs[u], audios[u], n[u] * sizeof(float));
+        stats[u] = xdtts_compressor_stats{0.0f, 0, 0, 0};
+      }
+      return;
+    }
+    const CompPlan plan = compressor_plan(s, rate);
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    hipStream_t st = g->stream;
+    g->rs_in.alloc(tot);
+    g->compressor_bufs(tile, (size_t)n_utt);
+    for (int u = 0; u < n_utt; ++u)
+      HIP_CHECK(hipMemcpyAsync(g->rs_in.p + tab[(size_t)u].src0, audios[u], n[u] * sizeof(float), hipMemcpyHostToDevice, st));
+    if (n_utt > 1) {
+      g->comp_tab_host = tab;
+      g->comp_tab.upload(g->comp_tab_host.data(), g->comp_tab_host.size(), st);
+    }
+    HIP_CHECK(hipEventRecord(g->ev.e[0], st));
+    if (n_utt == 1) g->compress_one(g->rs_in.p, g->rs_in.p, n[0], plan);  // (the form the single-utterance entries run)
+    else g->compress_rows(g->rs_in.p, g->rs_in.p, 0, n_utt, plan);
+    HIP_CHECK(hipEventRecord(g->ev.e[1], st));
+    HIP_CHECK(hipEventRecord(g->ev.e[2], st));
+    for (int u = 0; u < n_utt; ++u)
+      HIP_CHECK(hipMemcpyAsync(outs[u], g->rs_in.p + tab[(size_t)u].dst0, n[u] * sizeof(float), hipMemcpyDeviceToHost, st));
+    g->compressor_fetch(0, n_utt, st);
+    g->finish_timings();  // (drains the stream: the inputs, the table, the outputs and the stats)
+    std::memcpy(stats, g->comp_host, (size_t)n_utt * sizeof(xdtts_compressor_stats));
+  });
+}
+
+xdtts_status xdtts_griffinlim_compress(xdtts_griffinlim *g, const float *audio, size_t n, int32_t rate, const xdtts_compressor *c,
+                                       float *out, xdtts_compressor_stats *stats) {
+  return xdtts_griffinlim_compress_batch(g, &audio, &n, 1, rate, c, &out, stats);
+}
+
 // ---- stream: the sequence joined with its gaps, faded, levelled, encoded (stream_plan.h, stream.hip) ----------------------------
 
 static_assert(sizeof(xdtts_stream_opts) == sizeof(StreamOpts) && offsetof(xdtts_stream_opts, fade) == offsetof(StreamOpts, fade),

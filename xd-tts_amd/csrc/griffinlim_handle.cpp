@@ -15,6 +15,7 @@ xdtts_griffinlim::~xdtts_griffinlim() {
   if (host_err) (void)hipHostFree(host_err);
   if (loud_host) (void)hipHostFree(loud_host);
   if (lim_host) (void)hipHostFree(lim_host);
+  if (comp_host) (void)hipHostFree(comp_host);
   if (f0_host) (void)hipHostFree(f0_host);
   if (stream) (void)hipStreamDestroy(stream);
 }
@@ -426,6 +427,45 @@ void xdtts_griffinlim::limit_rows(const float *x, int r0, int count, const LimJo
   launch_limit(x, lim_out.p, lim_tab.p + r0, count, first.tile0, tiles, LimUtt{}, job, lim_stats.p + r0, stream);
 }
 
+// The compressor (compressor.hip).
+void xdtts_griffinlim::compressor_bufs(size_t tiles, size_t n_utt) {
+  tiles = std::max<size_t>(tiles, 1);
+  n_utt = std::max<size_t>(n_utt, 1);
+  if (tiles > comp_agg.n || n_utt > comp_stats.n) HIP_CHECK(hipStreamSynchronize(stream));  // (growing frees what a launch may touch)
+  comp_agg.alloc(tiles);
+  comp_stats.alloc(n_utt);
+  if (n_utt > comp_host_n) {
+    if (comp_host) HIP_CHECK(hipHostFree(comp_host));
+    comp_host = nullptr;
+    comp_host_n = 0;
+    HIP_CHECK(hipHostMalloc((void **)&comp_host, n_utt * sizeof(CompressorStats), hipHostMallocDefault));
+    comp_host_n = n_utt;
+  }
+}
+
+void xdtts_griffinlim::compress_one(const float *x, float *out, size_t n, const CompPlan &plan) {
+  const CompUtt one{0, 0, (int)n, 0};
+  launch_compress(x, out, nullptr, 1, 0, (int)compressor_tiles(n), one, plan, comp_agg.p, comp_stats.p, stream);
+}
+
+void xdtts_griffinlim::compress_rows(const float *x, float *out, int r0, int count, const CompPlan &plan) {
+  if (count <= 0) return;
+  const CompUtt &first = comp_tab_host[(size_t)r0], &last = comp_tab_host[(size_t)(r0 + count - 1)];
+  const int tiles = last.tile0 + (int)compressor_tiles((size_t)last.n) - first.tile0;
+  launch_compress(x, out, comp_tab.p + r0, count, first.tile0, tiles, CompUtt{}, plan, comp_agg.p, comp_stats.p + r0, stream);
+}
+
+void xdtts_griffinlim::compressor_fetch(int r0, int count, hipStream_t s) {
+  HIP_CHECK(hipMemcpyAsync(comp_host + r0, comp_stats.p + r0, (size_t)count * sizeof(CompressorStats), hipMemcpyDeviceToHost, s));
+}
+
+void xdtts_griffinlim::push_last_comp(size_t r) {
+  xdtts_compressor_stats st;
+  static_assert(sizeof st == sizeof(CompressorStats), "CompressorStats is xdtts_compressor_stats");
+  std::memcpy(&st, comp_host + r, sizeof st);
+  last_comp.push_back(st);
+}
+
 // The stream stage (stream.hip).
 void xdtts_griffinlim::stream_reserve(size_t floats) {
   if (floats <= st_src.n) return;
@@ -768,6 +808,13 @@ static void enqueue_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
     N = g->resample_one(g->audio.p, N, g->audio_rs.p, g->out_rate);
     out = g->audio_rs.p;
   }
+  // the compressor: on what is delivered, in place, in front of whichever level stage follows (a document's piece included)
+  const bool comp = deliver && g->compressor_on() && N > 0;
+  g->comp_ran = comp;
+  if (comp) {
+    g->compressor_bufs(compressor_tiles(N), 1);
+    g->compress_one(out, out, N, compressor_plan(g->comp, g->out_rate));
+  }
   const bool level = deliver && !(g->sink.dst && g->sink.unlevelled);  // (a document at programme level takes the utterance unlevelled)
   const bool loud = level && g->loudness_on() && N > 0;  // the loudness rule takes the output normalisation's place
   if (loud) out = g->loudness_one(out, N, g->out_rate, true);  // (the limiter works out of place)
@@ -780,6 +827,7 @@ static void enqueue_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
     HIP_CHECK(hipMemcpyAsync(host.p, out, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
   }
   if (loud) g->loudness_fetch(0, 1, g->stream);  // the measurement and the gain travel back behind the audio
+  if (comp) g->compressor_fetch(0, 1, g->stream);
   g->fetch_error_word();
 }
 // ... and its counterpart: the wait and the engine's error word.  The persistent engine needs its grid co-resident (the
@@ -796,6 +844,7 @@ static void collect_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
   }
   const size_t N = (size_t)g->hop * (size_t)(b.F - 1);
   if (deliver && g->loudness_on() && N > 0 && !(g->sink.dst && g->sink.unlevelled)) g->push_last(0);
+  if (deliver && g->comp_ran) g->push_last_comp(0);
   *audio = host.release();
   *n_samples = deliver ? g->delivered(N) : N;
 }
@@ -1075,6 +1124,16 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
       g->limiter_bufs(dtot, (size_t)n_utt);
     }
   }
+  // The handle's compressor: one setting for every utterance, the ragged stage in place on the delivered rows, in front of the
+  // level stage.
+  const bool comp = g->compressor_on();
+  g->comp_ran = comp;
+  const CompPlan comp_plan = compressor_plan(g->comp, g->out_rate);
+  if (comp) {
+    size_t tiles = 0;
+    for (int u = 0; u < n_utt; ++u) tiles += compressor_tiles((size_t)dn[(size_t)u]);
+    g->compressor_bufs(tiles, (size_t)n_utt);
+  }
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
   g->probe_tick();
   for (int attempt = 0;; ++attempt) {
@@ -1101,16 +1160,21 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     // preceded by ONE resample launch (at a rate other than 22050) and ONE two-launch output normalisation (G6) of exactly
     // its utterances, in that order: the level rules hold for the signal the caller receives.
     std::vector<int> tab_pos((size_t)n_utt, 0);
-    if (norm_mode || resampled || loud) {
+    if (norm_mode || resampled || loud || comp) {
       std::vector<int2> tab;
       tab.reserve((size_t)n_utt);
       g->rs_tab_host.clear();
       g->loud_tab_host.clear();
       g->lim_tab_host.clear();
-      int blk = 0, grp = 0, seg = 0, sb = 0, tile = 0;
+      g->comp_tab_host.clear();
+      int blk = 0, grp = 0, seg = 0, sb = 0, tile = 0, ctile = 0;
       for (int u : plan.order) {
         tab_pos[(size_t)u] = (int)tab.size();
         tab.push_back(make_int2(dbase[(size_t)u], dn[(size_t)u]));
+        if (comp) {
+          g->comp_tab_host.push_back({(long long)dbase[(size_t)u], (long long)dbase[(size_t)u], dn[(size_t)u], ctile});
+          ctile += (int)compressor_tiles((size_t)dn[(size_t)u]);
+        }
         if (loud) {
           const size_t n = (size_t)dn[(size_t)u];
           g->loud_tab_host.push_back({(long long)dbase[(size_t)u], dn[(size_t)u], grp, seg, sb});
@@ -1134,11 +1198,13 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
       if (resampled) g->rs_tab.upload(g->rs_tab_host.data(), g->rs_tab_host.size(), st);
       if (loud) g->loud_tab.upload(g->loud_tab_host.data(), g->loud_tab_host.size(), st);
       if (limited) g->lim_tab.upload(g->lim_tab_host.data(), g->lim_tab_host.size(), st);
+      if (comp) g->comp_tab.upload(g->comp_tab_host.data(), g->comp_tab_host.size(), st);
       HIP_CHECK(hipStreamSynchronize(st));
     }
     size_t n_ev = 0;
     auto fetch_audio = [&](const std::vector<int> &utts) {  // after the work just enqueued on `st`
       if (resampled && !utts.empty()) g->resample_rows(g->audio.p, g->audio_rs.p, tab_pos[(size_t)utts[0]], (int)utts.size());
+      if (comp && !utts.empty()) g->compress_rows(dbuf, dbuf, tab_pos[(size_t)utts[0]], (int)utts.size(), comp_plan);
       if (norm_mode && !utts.empty()) {
         int n_max = 0;
         for (int u : utts) n_max = std::max(n_max, dn[(size_t)u]);
@@ -1155,6 +1221,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
         HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, src + dbase[(size_t)u], sizeof(float) * (size_t)dn[(size_t)u], hipMemcpyDeviceToHost,
                                  g->copy_stream));
       if (loud && !utts.empty()) g->loudness_fetch(tab_pos[(size_t)utts[0]], (int)utts.size(), g->copy_stream);
+      if (comp && !utts.empty()) g->compressor_fetch(tab_pos[(size_t)utts[0]], (int)utts.size(), g->copy_stream);
     };
     // the persistent launches, each followed by the fetch of its utterances
     bool used_persistent = false;
@@ -1202,6 +1269,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
       audios[u] = out[(size_t)u].release();
       n_samples[u] = (size_t)dn[(size_t)u];
       if (loud) g->push_last((size_t)tab_pos[(size_t)u]);
+      if (comp) g->push_last_comp((size_t)tab_pos[(size_t)u]);
     }
     return;
   }

@@ -280,10 +280,35 @@ struct xdtts_griffinlim {
   void limit_one(const float *x, size_t n, const xdtts::LimJob &job);
   // Ragged: records lim_tab_host[r0 .. r0 + count) (uploaded by the caller as lim_tab), stats into lim_stats[r0 ..].
   void limit_rows(const float *x, int r0, int count, const xdtts::LimJob &job);
+  // compressor (compressor.hip): with a setting other than the identity, the stage between the resampler and the level stage,
+  // in place on the delivered signal.  Off (the default) and the identity launch and allocate nothing.
+  xdtts::Compressor comp = xdtts::compressor_default();
+  bool comp_set = false;
+  bool compressor_on() const { return comp_set && !xdtts::compressor_is_identity(comp); }
+  bool comp_ran = false;                        // the last delivering run launched the stage: stats travel back
+  DevBuf<xdtts::CompAgg> comp_agg;              // one per tile of a request
+  DevBuf<xdtts::CompressorStats> comp_stats;    // one per utterance of a request
+  DevBuf<xdtts::CompUtt> comp_tab;
+  std::vector<xdtts::CompUtt> comp_tab_host;    // the upload's source: stays until the next request of this handle
+  xdtts::CompressorStats *comp_host = nullptr;  // pinned: the stats travel back behind the audio
+  size_t comp_host_n = 0;
+  std::vector<xdtts_compressor_stats> last_comp;  // xdtts_griffinlim_last_compressor: of the last delivering call, in the caller's order
+  // Aggregates for `tiles` tiles in all and stats for n_utt utterances, device and pinned host.
+  void compressor_bufs(size_t tiles, size_t n_utt);
+  // One utterance x[0 .. n) -> out[0 .. n) (out == x: in place), stats into comp_stats[0]; nothing is uploaded.
+  void compress_one(const float *x, float *out, size_t n, const xdtts::CompPlan &plan);
+  // Ragged: records comp_tab_host[r0 .. r0 + count) (uploaded by the caller as comp_tab, behind compressor_bufs()), stats into
+  // comp_stats[r0 ..].
+  void compress_rows(const float *x, float *out, int r0, int count, const xdtts::CompPlan &plan);
+  // comp_stats[r0 .. r0 + count) -> comp_host, on `s`
+  void compressor_fetch(int r0, int count, hipStream_t s);
+  // the stats of record r of the last fetch -> last_comp
+  void push_last_comp(size_t r);
   void clear_last() {
     last_loud.clear();
     last_lim.clear();
     last_f0.clear();
+    last_comp.clear();
   }
   // the structs of record r of the last fetch -> last_loud (and last_lim where the limiter ran)
   void push_last(size_t r);

@@ -1,6 +1,7 @@
 // kernels.h -- host-side launch interface of the HIP kernels (gfx950).
 #pragma once
 #include "common.h"
+#include "compressor_plan.h"
 #include "f0_plan.h"
 #include "gl_plan.h"
 #include "limiter_plan.h"
@@ -464,6 +465,20 @@ struct LimJob {
 // record u.  Integer and float-bits atomics on the stats only: out and stats are functions of (the utterance, job) alone.
 void launch_limit(const float *x, float *out, const LimUtt *tab_dev, int count, int tile_base, int n_tiles, const LimUtt &one,
                   const LimJob &job, LimiterStats *stats, hipStream_t s);
+
+// ---- compressor (compressor.hip): tent-envelope dynamic range compressor in front of the level stage (include/xdtts.h, compressor_plan.h) ----
+// One utterance of a launch: n samples at x + src0 -> n samples at out + dst0 (in place where they are the same place).  Its
+// workgroups (COMP_TILE samples each) are tile0 .. of the table's numbering, ascending, the utterances back to back.
+struct CompUtt {
+  long long src0, dst0;
+  int n, tile0;
+};
+// Three launches: the stats' initial values, the tiles' aggregates and the peak, then the samples -- n_tiles workgroups each,
+// the first being tile tile_base of the table's numbering (tab_dev == nullptr: the one utterance `one`).  agg holds one
+// record per tile of the WHOLE table (index = the table's tile number); stats[u] belongs to record u.  Integer atomics on the
+// stats only: out and stats are functions of (the utterance, plan) alone.
+void launch_compress(const float *x, float *out, const CompUtt *tab_dev, int count, int tile_base, int n_tiles, const CompUtt &one,
+                     const CompPlan &plan, CompAgg *agg, CompressorStats *stats, hipStream_t s);
 
 // ---- stream (stream.hip): utterances joined with their gaps into one stream, faded, levelled, encoded (include/xdtts.h) -------
 // ONE launch of k_stream_join: job.tab[0 .. n_utt) on the device, ascending off (stream_plan.h: StreamUtt), the utterances'
