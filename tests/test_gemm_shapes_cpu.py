@@ -47,7 +47,9 @@ def test_the_restated_rules_use_the_constants_of_the_sources():
     assert _const(common, "T_MAX") == gs.T_MAX == 512 and _const(kernels, "GEMM_RAGGED_MAX") == gs.GEMM_RAGGED_MAX == 64
     # only the Tacotron2 handle splits K: every GEMM of its handle file goes through run_gemm, the vocoder's never plan
     voc = _src("griffinlim_handle.cpp")
-    assert "gemm_splitk_plan" not in voc and "gemm_splitk_plan" not in _src("api_griffinlim.cpp")
+    assert "gemm_splitk_plan" not in voc
+    for name in ("api_griffinlim.cpp", "api_gl_magnitude.cpp", "api_gl_delivery.cpp", "delivery.cpp"):
+        assert "gemm_splitk_plan" not in _src(name), name
     assert voc.count("launch_gemm_nt(") == 5 and voc.count("a.tile = 32;") == 1 and voc.count(".tile = ") == 1
     taco = _src("tacotron2_handle.cpp")
     assert taco.count("gemm_splitk_plan(") == 1 and taco.count("launch_gemm_nt(") == 1 and taco.count("run_gemm(g);") == 4

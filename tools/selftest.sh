@@ -16,6 +16,7 @@ run limiter_check.py          python tools/limiter_check.py
 run compressor_check.py       python tools/compressor_check.py
 run timbre_check.py           python tools/timbre_check.py
 run document_check.py         python tools/document_check.py 2
+run delivery_hash.py          python tools/delivery_hash.py
 run gl_hash.py                python tools/gl_hash.py
 run gl_tf_sweep.py            python tools/gl_tf_sweep.py
 run headline_call.py          python tools/headline_call.py 3

@@ -113,11 +113,11 @@ struct DocRun {
     total = at;
     if (total == 0) fail(XDTTS_ERR_BAD_ARG, "stream: total is 0 samples");
     const size_t bytes = total * (size_t)stream_sample_bytes(o.format);
-    g->stream_join(total, o, g->out_rate);
+    g->stream_join(total, o, g->dl.out_rate);
     out = PinnedGuard((bytes + 3) / 4);
     HIP_CHECK(hipMemcpyAsync(out.p, g->st_out.p, bytes, hipMemcpyDeviceToHost, g->stream));
     HIP_CHECK(hipStreamSynchronize(g->stream));
-    if (o.level == 1) g->push_last(0);
+    if (o.level == 1) g->dl.push_last(0);
   }
 };
 static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
@@ -147,7 +147,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
         g->sink = xdtts_griffinlim::StreamSink();
       }
     } unhook{h, g};
-    if (doc && doc->o.level == 1 && !g->loudness_on())
+    if (doc && doc->o.level == 1 && !g->dl.loudness_on())
       fail(XDTTS_ERR_BAD_ARG, "stream: level 1 (programme) needs a loudness target on the handle");
     std::vector<PinnedGuard> mel_host(n_utt), audio_host(n_utt);
     std::vector<int> total(n_utt, 0);
@@ -191,7 +191,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
           h->while_decoding = [&, u, predicted] {
             if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * predicted);
             const size_t Fp = pros ? prosody_frames((size_t)predicted, pros[u].rate) : (size_t)predicted;  // the vocoder's frames, not the mel's
-            if (!doc && !audio_host[u].p) audio_host[u] = PinnedGuard(g->delivered((size_t)g->hop * (Fp - 1)));  // (at the handle's output rate)
+            if (!doc && !audio_host[u].p) audio_host[u] = PinnedGuard(g->dl.delivered((size_t)g->hop * (Fp - 1)));  // (at the handle's output rate)
           };
         for (int i = 0; i < 4; ++i) std::swap(h->ev.e[i], per[u].e[i]);  // (per[u] now holds what the handle had: utterance u - 1's set, or its own)
         h->infer_batch_device(padded.data(), lens.data(), (int)lens.size(), o.max_chunk, o, nullptr, &total[u]);
@@ -209,7 +209,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
         if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * total[u]);
         HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));  // the vocoder reads the mel behind the post-net
         HIP_CHECK(hipMemcpyAsync(mel_host[u].p, h->mel_dev.p, (size_t)N_MEL * total[u] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        if (doc) doc->place(u, g->delivered((size_t)g->hop * ((pros ? prosody_frames((size_t)total[u], pros[u].rate) : (size_t)total[u]) - 1)));
+        if (doc) doc->place(u, g->dl.delivered((size_t)g->hop * ((pros ? prosody_frames((size_t)total[u], pros[u].rate) : (size_t)total[u]) - 1)));
         gl_enqueue_from_device_mel(g, h->mel_dev.p, total[u], audio_host[u], pros ? &pros[u] : nullptr);
       }
       gl_collect(g, total[n_utt - 1], audio_host[n_utt - 1], &audio_out[n_utt - 1], &n_samples[n_utt - 1], pros ? &pros[n_utt - 1] : nullptr);

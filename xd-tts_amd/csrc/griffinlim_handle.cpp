@@ -1,5 +1,5 @@
 // griffinlim_handle.cpp -- the vocoder handle (GriffinLim::infer, mod.rs:441-520): mel -> linear, the iteration engines and
-// their fallback, the single-utterance and the batch request paths.
+// their fallback, the magnitude stages, the stream stage, the request paths.  The delivery chain behind the loop: delivery.cpp.
 #include "griffinlim_handle.h"
 
 #include <algorithm>
@@ -13,10 +13,6 @@ xdtts_griffinlim::~xdtts_griffinlim() {
   for (hipEvent_t e : copy_ev) (void)hipEventDestroy(e);
   if (copy_stream) (void)hipStreamDestroy(copy_stream);
   if (host_err) (void)hipHostFree(host_err);
-  if (loud_host) (void)hipHostFree(loud_host);
-  if (lim_host) (void)hipHostFree(lim_host);
-  if (comp_host) (void)hipHostFree(comp_host);
-  if (f0_host) (void)hipHostFree(f0_host);
   if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -182,13 +178,7 @@ void xdtts_griffinlim::f0_prepare(const std::vector<F0Utt> &utts) {
   f0_val.alloc(n);
   f0_ratio.alloc(n);
   f0_stats.alloc(n_utt);
-  if (n_utt > f0_host_n) {
-    if (f0_host) HIP_CHECK(hipHostFree(f0_host));
-    f0_host = nullptr;
-    f0_host_n = 0;
-    HIP_CHECK(hipHostMalloc((void **)&f0_host, n_utt * sizeof(F0Stats), hipHostMallocDefault));
-    f0_host_n = n_utt;
-  }
+  f0_host.reserve(n_utt);
   f0_utts.upload(f0_utts_host.data(), f0_utts_host.size(), stream);
 }
 
@@ -207,13 +197,13 @@ void xdtts_griffinlim::f0_launch(const float *S_dev, const F0Job &job, unsigned 
   launch_f0_frames(S_dev, f0_rows, job.opts, job.q_lo, job.q_hi, tw.p, f0_raw.p, f0_strength.p, stream);
   if (between) HIP_CHECK(hipEventRecord(between, stream));
   launch_f0_track(f0_raw.p, f0_strength.p, f0_utts.p, n_utt, job.opts.threshold, f0_val.p, f0_ratio.p, f0_stats.p, ftab, n_tab, stream);
-  HIP_CHECK(hipMemcpyAsync(f0_host, f0_stats.p, (size_t)n_utt * sizeof(F0Stats), hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(f0_host.p, f0_stats.p, (size_t)n_utt * sizeof(F0Stats), hipMemcpyDeviceToHost, stream));
 }
 
 void xdtts_griffinlim::f0_collect() {
   static_assert(sizeof(xdtts_f0_stats) == sizeof(F0Stats), "F0Stats is xdtts_f0_stats");
   last_f0.resize(f0_utts_host.size());
-  if (!last_f0.empty()) std::memcpy(last_f0.data(), f0_host, last_f0.size() * sizeof(F0Stats));
+  if (!last_f0.empty()) std::memcpy(last_f0.data(), f0_host.p, last_f0.size() * sizeof(F0Stats));
 }
 
 // The initial phase by SPSI (phase_spsi.hip) on a magnitude in place.  Scratch grows with the request and stays.
@@ -246,226 +236,6 @@ void xdtts_griffinlim::spsi_batch(const float *S_dev, const SpsiTables &t, float
               SpsiBufs{spsi_map.p, spsi_comp.p, spsi_entry.p}, ang_out, tprev_out, turns, stream);
 }
 
-// The output-rate stage (resample.hip).  The table is a function of the rate alone: built on the host once per (handle, rate)
-// and kept on the device; the host copy is the upload's source and lives as long as the handle.
-void xdtts_griffinlim::resample_prepare(int rate) {
-  if (rs_table.rate == rate && rs_rows.p) return;
-  HIP_CHECK(hipStreamSynchronize(stream));  // (a launch that reads the table of another rate may be in flight)
-  const std::string msg = resample_check(rate, &rs_plan);
-  if (!msg.empty() || rs_plan.identity) fail(XDTTS_ERR_BAD_ARG, "resample: no table for rate %d", rate);
-  std::vector<float> h;
-  resample_taps(rs_plan, h);
-  rs_table.rate = 0;
-  resample_table(rs_plan, h, rs_table);
-  if (resample_window(rs_table) > RESAMPLE_WINDOW) {  // (never: the rate rule bounds M / L and the entries per phase)
-    rs_table.rate = 0;
-    fail(XDTTS_ERR_BAD_ARG, "resample: rate %d needs a window of %d samples", rate, resample_window(rs_table));
-  }
-  rs_rows.upload(rs_table.rows.data(), rs_table.rows.size(), stream);
-}
-
-size_t xdtts_griffinlim::resample_one(const float *src, size_t n, float *dst, int rate) {
-  resample_prepare(rate);
-  const size_t n_out = resample_n_out(rs_plan, n);
-  if (n_out > (size_t)0x7fffffff) fail(XDTTS_ERR_BAD_ARG, "resample: %zu output samples are more than 2^31 - 1", n_out);
-  const ResampleUtt one{0, 0, (int)n, (int)n_out, 0, 0};
-  launch_resample(src, dst, nullptr, 1, 0, (int)((n_out + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK), one, rs_rows.p, rs_table.L, rs_table.M,
-                  rs_table.Jn, rs_table.T4, stream);
-  return n_out;
-}
-
-void xdtts_griffinlim::resample_rows(const float *src, float *dst, int r0, int count) {
-  if (count <= 0) return;
-  const ResampleUtt &first = rs_tab_host[(size_t)r0], &last = rs_tab_host[(size_t)(r0 + count - 1)];
-  const int nblk = last.blk0 + (last.n_out + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK - first.blk0;
-  launch_resample(src, dst, rs_tab.p + r0, count, first.blk0, nblk, ResampleUtt{}, rs_rows.p, rs_table.L, rs_table.M, rs_table.Jn,
-                  rs_table.T4, stream);
-}
-
-// The loudness stage (loudness.hip).  The table is a function of the rate alone: built on the host once per (handle, rate) and
-// kept on the device; the host copy is the upload's source and lives as long as the handle.
-void xdtts_griffinlim::loudness_prepare(int rate) {
-  if (loud_table_host.rate == rate && loud_table.p) return;
-  HIP_CHECK(hipStreamSynchronize(stream));  // (a launch that reads the table of another rate may be in flight)
-  const std::string msg = loudness_check(rate);
-  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
-  loud_table_host.rate = 0;
-  loudness_table(rate, loud_table_host);
-  loud_table.upload(&loud_table_host, 1, stream);
-}
-
-LoudBufs xdtts_griffinlim::loudness_bufs(size_t groups, size_t n_utt) {
-  groups = std::max<size_t>(groups, 1);
-  n_utt = std::max<size_t>(n_utt, 1);
-  const size_t segs = groups * LOUD_LANES;
-  if (segs > loud_excl.n / 4 || n_utt > loud_res.n) HIP_CHECK(hipStreamSynchronize(stream));  // (growing frees what a launch may read)
-  loud_excl.alloc(segs * 4);
-  loud_agg.alloc(groups * 4);
-  loud_gin.alloc(groups * 4);
-  loud_part.alloc(segs * 2);
-  loud_sub.alloc(groups * 3 + n_utt);  // (h >= 800: at most three sub-blocks begin inside a group of 2048, one more per utterance)
-  loud_peaks.alloc(groups);
-  loud_res.alloc(n_utt);
-  if (n_utt > loud_host_n) {
-    if (loud_host) HIP_CHECK(hipHostFree(loud_host));
-    loud_host = nullptr;
-    loud_host_n = 0;
-    HIP_CHECK(hipHostMalloc((void **)&loud_host, n_utt * sizeof(LoudResult), hipHostMallocDefault));
-    loud_host_n = n_utt;
-  }
-  return LoudBufs{loud_excl.p, loud_agg.p, loud_gin.p, loud_part.p, loud_sub.p, loud_peaks.p};
-}
-
-float *xdtts_griffinlim::loudness_one(float *x, size_t n, int rate, bool scale) {
-  if (n == 0 || n >= ((size_t)1 << 28)) fail(XDTTS_ERR_BAD_ARG, "loudness: need 1 .. 2^28 - 1 samples, got %zu", n);
-  loudness_prepare(rate);
-  const int groups = (int)loudness_groups(n);
-  const LoudBufs b = loudness_bufs((size_t)groups, 1);
-  const LoudUtt one{0, (int)n, 0, 0, 0};
-  const bool on = scale && loudness_on(), lim = on && limiter_on();
-  lim_ran = lim;
-  if (lim) {  // (in front of the launches: growing a buffer drains the stream)
-    limiter_prepare(rate, lim_us);
-    limiter_bufs(n, 1);
-  }
-  launch_loudness_measure(x, nullptr, 1, 0, groups, one, loud_table.p, b, loud_res.p, rate, on ? loudness_target_lin(loud_target) : 0.0,
-                          on && !lim ? loudness_ceiling_lin(loud_ceiling) : 0.0, stream);
-  if (lim) {
-    limit_one(x, n, limiter_job(true, 0, 0.0, loudness_ceiling_lin(loud_ceiling)));
-    return lim_out.p;
-  }
-  if (on) launch_loudness_scale(x, nullptr, 1, 0, groups, one, loud_res.p, stream);
-  return x;
-}
-
-float *xdtts_griffinlim::loudness_rows(float *x, int r0, int count, int rate, bool scale) {
-  if (count <= 0) return x;
-  const LoudUtt &first = loud_tab_host[(size_t)r0], &last = loud_tab_host[(size_t)(r0 + count - 1)];
-  const int groups = last.grp0 + (int)loudness_groups((size_t)last.n) - first.grp0;
-  const LoudBufs b{loud_excl.p, loud_agg.p, loud_gin.p, loud_part.p, loud_sub.p, loud_peaks.p};
-  const bool on = scale && loudness_on(), lim = on && limiter_on();
-  lim_ran = lim;
-  launch_loudness_measure(x, loud_tab.p + r0, count, first.grp0, groups, LoudUtt{}, loud_table.p, b, loud_res.p + r0, rate,
-                          on ? loudness_target_lin(loud_target) : 0.0, on && !lim ? loudness_ceiling_lin(loud_ceiling) : 0.0, stream);
-  if (lim) {
-    limit_rows(x, r0, count, limiter_job(true, r0, 0.0, loudness_ceiling_lin(loud_ceiling)));
-    return lim_out.p;
-  }
-  if (on) launch_loudness_scale(x, loud_tab.p + r0, count, first.grp0, groups, LoudUtt{}, loud_res.p + r0, stream);
-  return x;
-}
-
-void xdtts_griffinlim::loudness_fetch(int r0, int count, hipStream_t s) {
-  HIP_CHECK(hipMemcpyAsync(loud_host + r0, loud_res.p + r0, (size_t)count * sizeof(LoudResult), hipMemcpyDeviceToHost, s));
-  if (lim_ran)
-    HIP_CHECK(hipMemcpyAsync(lim_host + r0, lim_stats.p + r0, (size_t)count * sizeof(LimiterStats), hipMemcpyDeviceToHost, s));
-}
-
-void xdtts_griffinlim::push_last(size_t r) {
-  xdtts_loudness l;
-  static_assert(sizeof l == sizeof(LoudResult), "LoudResult is xdtts_loudness");
-  std::memcpy(&l, loud_host + r, sizeof l);
-  last_loud.push_back(l);
-  if (lim_ran) {
-    xdtts_limiter_stats st;
-    static_assert(sizeof st == sizeof(LimiterStats), "LimiterStats is xdtts_limiter_stats");
-    std::memcpy(&st, lim_host + r, sizeof st);
-    last_lim.push_back(st);
-  }
-}
-
-// The limiter (limiter.hip).  The window is a function of H alone: built on the host when H changes and kept on the device.
-void xdtts_griffinlim::limiter_prepare(int rate, int lookahead_us) {
-  const std::string msg = limiter_check(rate, lookahead_us);
-  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
-  loudness_prepare(rate);  // (the taps)
-  const int H = limiter_half_width(rate, lookahead_us);
-  if (H == lim_H && lim_win.p) return;
-  HIP_CHECK(hipStreamSynchronize(stream));  // (a launch that reads another window may be in flight)
-  lim_H = 0;
-  lim_win_host.resize((size_t)(2 * H + 1));
-  limiter_window(H, lim_win_host.data());
-  lim_win.upload(lim_win_host.data(), lim_win_host.size(), stream);
-  lim_H = H;
-}
-
-void xdtts_griffinlim::limiter_bufs(size_t floats, size_t n_utt) {
-  floats = std::max<size_t>(floats, 1);
-  n_utt = std::max<size_t>(n_utt, 1);
-  if (floats > lim_out.n || n_utt > lim_stats.n) HIP_CHECK(hipStreamSynchronize(stream));  // (growing frees what a launch may touch)
-  lim_out.alloc(floats);
-  lim_stats.alloc(n_utt);
-  if (n_utt > lim_host_n) {
-    if (lim_host) HIP_CHECK(hipHostFree(lim_host));
-    lim_host = nullptr;
-    lim_host_n = 0;
-    HIP_CHECK(hipHostMalloc((void **)&lim_host, n_utt * sizeof(LimiterStats), hipHostMallocDefault));
-    lim_host_n = n_utt;
-  }
-}
-
-LimJob xdtts_griffinlim::limiter_job(bool res_from_loudness, int r0, double gain0, double ceil) const {
-  LimJob j{};
-  j.taps = &loud_table.p->taps[0][0];
-  j.win = lim_win.p;
-  j.res = res_from_loudness ? loud_res.p + r0 : nullptr;
-  j.gain0 = gain0;
-  j.ceil = ceil;
-  j.H = lim_H;
-  return j;
-}
-
-void xdtts_griffinlim::limit_one(const float *x, size_t n, const LimJob &job) {
-  const LimUtt one{0, 0, (int)n, 0};
-  launch_limit(x, lim_out.p, nullptr, 1, 0, (int)limiter_tiles(n), one, job, lim_stats.p, stream);
-}
-
-void xdtts_griffinlim::limit_rows(const float *x, int r0, int count, const LimJob &job) {
-  if (count <= 0) return;
-  const LimUtt &first = lim_tab_host[(size_t)r0], &last = lim_tab_host[(size_t)(r0 + count - 1)];
-  const int tiles = last.tile0 + (int)limiter_tiles((size_t)last.n) - first.tile0;
-  launch_limit(x, lim_out.p, lim_tab.p + r0, count, first.tile0, tiles, LimUtt{}, job, lim_stats.p + r0, stream);
-}
-
-// The compressor (compressor.hip).
-void xdtts_griffinlim::compressor_bufs(size_t tiles, size_t n_utt) {
-  tiles = std::max<size_t>(tiles, 1);
-  n_utt = std::max<size_t>(n_utt, 1);
-  if (tiles > comp_agg.n || n_utt > comp_stats.n) HIP_CHECK(hipStreamSynchronize(stream));  // (growing frees what a launch may touch)
-  comp_agg.alloc(tiles);
-  comp_stats.alloc(n_utt);
-  if (n_utt > comp_host_n) {
-    if (comp_host) HIP_CHECK(hipHostFree(comp_host));
-    comp_host = nullptr;
-    comp_host_n = 0;
-    HIP_CHECK(hipHostMalloc((void **)&comp_host, n_utt * sizeof(CompressorStats), hipHostMallocDefault));
-    comp_host_n = n_utt;
-  }
-}
-
-void xdtts_griffinlim::compress_one(const float *x, float *out, size_t n, const CompPlan &plan) {
-  const CompUtt one{0, 0, (int)n, 0};
-  launch_compress(x, out, nullptr, 1, 0, (int)compressor_tiles(n), one, plan, comp_agg.p, comp_stats.p, stream);
-}
-
-void xdtts_griffinlim::compress_rows(const float *x, float *out, int r0, int count, const CompPlan &plan) {
-  if (count <= 0) return;
-  const CompUtt &first = comp_tab_host[(size_t)r0], &last = comp_tab_host[(size_t)(r0 + count - 1)];
-  const int tiles = last.tile0 + (int)compressor_tiles((size_t)last.n) - first.tile0;
-  launch_compress(x, out, comp_tab.p + r0, count, first.tile0, tiles, CompUtt{}, plan, comp_agg.p, comp_stats.p + r0, stream);
-}
-
-void xdtts_griffinlim::compressor_fetch(int r0, int count, hipStream_t s) {
-  HIP_CHECK(hipMemcpyAsync(comp_host + r0, comp_stats.p + r0, (size_t)count * sizeof(CompressorStats), hipMemcpyDeviceToHost, s));
-}
-
-void xdtts_griffinlim::push_last_comp(size_t r) {
-  xdtts_compressor_stats st;
-  static_assert(sizeof st == sizeof(CompressorStats), "CompressorStats is xdtts_compressor_stats");
-  std::memcpy(&st, comp_host + r, sizeof st);
-  last_comp.push_back(st);
-}
-
 // The stream stage (stream.hip).
 void xdtts_griffinlim::stream_reserve(size_t floats) {
   if (floats <= st_src.n) return;
@@ -486,16 +256,16 @@ void xdtts_griffinlim::stream_join(size_t total, const StreamOpts &o, int rate, 
     st_fade.upload(st_fade_host.data(), st_fade_host.size(), stream);
   }
   st_out.alloc(total * (size_t)stream_sample_bytes(o.format));
-  const bool lim = o.level == 1 && limiter_on();
-  lim_ran = lim;
-  if (o.level == 1) {
-    loudness_prepare(rate);
-    loudness_bufs(loudness_groups(total), 1);
+  const bool lim = o.level == 1 && dl.limiter_on();
+  if (o.level == 1) {  // the programme: ONE row of the delivery chain's level stage, the stream itself
+    DeliveryStages s;
+    s.rate = rate;
+    s.loud = true;
+    s.lim_us = lim ? dl.lim_us : 0;
+    dl.prepare(delivery_plan(s, {total}, {0}, {0}), false);
     st_f32.alloc(total);
   }
   if (lim) {  // the encode then reads the limited stream: the same offsets, the utterances where they lie in it
-    limiter_prepare(rate, lim_us);
-    limiter_bufs(total, 1);
     st_lim_tab_host = st_tab_host;
     for (StreamUtt &r : st_lim_tab_host) r.src0 = (long long)r.off;
     st_lim_tab.upload(st_lim_tab_host.data(), st_lim_tab_host.size(), stream);
@@ -512,19 +282,15 @@ void xdtts_griffinlim::stream_join(size_t total, const StreamOpts &o, int rate, 
   job.seed = o.dither_seed;
   job.fade = o.fade;
   if (o.level == 1) {
-    const int groups = (int)loudness_groups(total);
-    const LoudBufs b = loudness_bufs((size_t)groups, 1);  // (sized above: nothing grows here)
     StreamJob form = job;  // the stream as level 0 / format 0 delivers it: what the programme measurement is defined on
     form.format = STREAM_F32;
     form.dither = 0;
     launch_stream_join(form, st_f32.p, stream);
-    const LoudUtt one{0, (int)total, 0, 0, 0};
-    launch_loudness_measure(st_f32.p, nullptr, 1, 0, groups, one, loud_table.p, b, loud_res.p, rate, loudness_target_lin(loud_target),
-                            lim ? 0.0 : loudness_ceiling_lin(loud_ceiling), stream);
-    job.gain = &loud_res.p->gain;
+    dl.measure(st_f32.p, 0, 1, true);
+    job.gain = &dl.loud_res.p->gain;
     if (lim) {  // fade and gain are in the limited stream already; gaps stay the encoder's constants
-      limit_one(st_f32.p, total, limiter_job(true, 0, 0.0, loudness_ceiling_lin(loud_ceiling)));
-      job.src = lim_out.p;
+      dl.limit(st_f32.p, 0, 1, dl.limiter_job(true, 0, 0.0, loudness_ceiling_lin(dl.loud_ceiling)));
+      job.src = dl.lim_out.p;
       job.tab = st_lim_tab.p;
       job.fade_tab = nullptr;
       job.fade = 0;
@@ -532,7 +298,7 @@ void xdtts_griffinlim::stream_join(size_t total, const StreamOpts &o, int rate, 
     }
   }
   launch_stream_join(job, st_out.p, stream);
-  if (o.level == 1) loudness_fetch(0, 1, stream);
+  if (o.level == 1) dl.fetch_stats(0, 1, stream);
 }
 
 void xdtts_griffinlim::upload_rows(const float *const *S_host, const Rows &rows) {
@@ -796,29 +562,17 @@ void mel_filter_bank(double sr, int n_fft, int n_mels, double fmin, double fmax,
 }
 
 // "Iterations enqueued" -> "audio on its way to a pinned buffer": phase init + iterations + final ISTFT on the S in place
-// (iterate()), the delivery stages if wanted -- the output rate (resample.hip; nothing at 22050) and then the output
-// normalisation, on the signal the caller receives -- ev.e[2], the copy into `host` (taken from the pool here unless the caller
-// brought one, sized for what is delivered) and the engine's error word behind it.  Nothing is waited for.
+// (iterate()), the delivery chain if wanted (delivery.h: one row, its records by value), ev.e[2], the copy into `host` (taken from
+// the pool here unless the caller brought one, sized for what is delivered) and the engine's error word.  Nothing is waited for.
 static void enqueue_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, bool deliver, PinnedGuard &host) {
   size_t N = (size_t)g->hop * (size_t)(b.F - 1);
   g->iterate(b, phase0_dev, iters);
   float *out = g->audio.p;
-  if (deliver && g->out_rate != XDTTS_SAMPLE_RATE && N > 0) {
-    g->audio_rs.alloc(g->delivered(N));
-    N = g->resample_one(g->audio.p, N, g->audio_rs.p, g->out_rate);
-    out = g->audio_rs.p;
+  if (deliver) {  // (a document at programme level takes the utterance unlevelled; sizing behind the loop's launches: growing drains the stream)
+    g->dl.prepare_one(g->dl.stages(g->gopts.output_normalise, g->sink.dst && g->sink.unlevelled), N);
+    out = g->dl.run(g->audio.p, 0, 1, g->gopts.rms_target);
+    N = (size_t)g->dl.plan.dn[0];
   }
-  // the compressor: on what is delivered, in place, in front of whichever level stage follows (a document's piece included)
-  const bool comp = deliver && g->compressor_on() && N > 0;
-  g->comp_ran = comp;
-  if (comp) {
-    g->compressor_bufs(compressor_tiles(N), 1);
-    g->compress_one(out, out, N, compressor_plan(g->comp, g->out_rate));
-  }
-  const bool level = deliver && !(g->sink.dst && g->sink.unlevelled);  // (a document at programme level takes the utterance unlevelled)
-  const bool loud = level && g->loudness_on() && N > 0;  // the loudness rule takes the output normalisation's place
-  if (loud) out = g->loudness_one(out, N, g->out_rate, true);  // (the limiter works out of place)
-  else if (level) launch_gl_output_normalise(out, nullptr, 1, 0, (int)N, g->gopts.output_normalise, g->gopts.rms_target, g->norm_parts.p, g->stream);
   HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
   if (deliver && g->sink.dst) {  // a document run: the utterance stays in HBM, at its place in the staging buffer
     HIP_CHECK(hipMemcpyAsync(g->sink.dst, out, N * sizeof(float), hipMemcpyDeviceToDevice, g->stream));
@@ -826,8 +580,7 @@ static void enqueue_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
     if (!host.p) host = PinnedGuard(N);
     HIP_CHECK(hipMemcpyAsync(host.p, out, N * sizeof(float), hipMemcpyDeviceToHost, g->stream));
   }
-  if (loud) g->loudness_fetch(0, 1, g->stream);  // the measurement and the gain travel back behind the audio
-  if (comp) g->compressor_fetch(0, 1, g->stream);
+  if (deliver) g->dl.fetch_stats(0, 1, g->stream);  // the measurement, the gain and the stats travel back behind the audio
   g->fetch_error_word();
 }
 // ... and its counterpart: the wait and the engine's error word.  The persistent engine needs its grid co-resident (the
@@ -843,10 +596,9 @@ static void collect_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
     if (g->persistent_failed()) fail(XDTTS_ERR_HIP, "Griffin-Lim: the fallback engine reported an exchange failure");
   }
   const size_t N = (size_t)g->hop * (size_t)(b.F - 1);
-  if (deliver && g->loudness_on() && N > 0 && !(g->sink.dst && g->sink.unlevelled)) g->push_last(0);
-  if (deliver && g->comp_ran) g->push_last_comp(0);
+  if (deliver) g->dl.push_last(0);
   *audio = host.release();
-  *n_samples = deliver ? g->delivered(N) : N;
+  *n_samples = deliver ? g->dl.delivered(N) : N;
 }
 
 // The loop alone on a state the caller has put in place (xdtts_griffinlim_infer_linear), then the audio in a pinned host buffer.
@@ -932,8 +684,7 @@ F0Job f0_job_checked(const xdtts_f0_opts *o) {
   F0Job j;
   j.opts = f0_opts_default();
   if (o) std::memcpy(&j.opts, o, sizeof j.opts);
-  const std::string msg = f0_opts_check(j.opts);
-  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  bad_arg_if(f0_opts_check(j.opts));
   f0_quefrency(j.opts, &j.q_lo, &j.q_hi);
   return j;
 }
@@ -987,8 +738,7 @@ static const ContourPoint *contour_points(const xdtts_prosody_contour &c) { retu
 
 void contour_check(const xdtts_prosody_contour *c, size_t n_frames) {
   if (!c) fail(XDTTS_ERR_BAD_ARG, "null contour");
-  const std::string msg = xdtts::contour_check(contour_points(*c), c->n_points, c->lifter, c->log_floor, n_frames);
-  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  bad_arg_if(xdtts::contour_check(contour_points(*c), c->n_points, c->lifter, c->log_floor, n_frames));
 }
 
 void contour_check_at(const xdtts_prosody_contour *c, int u, size_t n_frames) {
@@ -1040,7 +790,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
   const bool contour = staged && pros.contour;
   Rows in, rows;  // the mel's frames F_u, and the frames behind the stage: F'_u
   std::vector<ProsodyUtt> ptab;
-  std::vector<int> abase(n_utt);
+  std::vector<size_t> loop_n((size_t)n_utt);  // the loop's samples per utterance, back to back in its audio
   size_t Ntot = 0;
   for (int u = 0; u < n_utt; ++u) {
     const int Fp = staged ? pros.frames(u, Fin[u]) : Fin[u];
@@ -1050,9 +800,10 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     }
     rows_add(in, (size_t)Fin[u], (size_t)1 << 24, "batch too large");
     rows_add(rows, (size_t)Fp, (size_t)1 << 24, "batch too large");
-    abase[u] = (int)Ntot;
-    Ntot += (size_t)g->hop * (size_t)(Fp - 1);
+    loop_n[(size_t)u] = (size_t)g->hop * (size_t)(Fp - 1);
+    Ntot += loop_n[(size_t)u];
   }
+  const std::vector<long long> abase = delivery_bases(loop_n);
   const std::vector<int> &Fu = rows.F, &fbase = rows.row0;
   HIP_CHECK(hipSetDevice(g->device));
   hipStream_t st = g->stream;
@@ -1085,55 +836,16 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     all.S = g->S_timbre.p;
   }
   g->audio.alloc(std::max<size_t>(Ntot, 1));
-  // What is delivered: at 22050 the loop's audio where it lies; at another rate the resampled utterances back to back in
-  // audio_rs, and everything behind the loop -- the normaliser's table, the fetch copies, the counts -- works from those.
-  const bool resampled = g->out_rate != XDTTS_SAMPLE_RATE;
-  std::vector<int> rbase, dn((size_t)n_utt);
-  for (int u = 0; u < n_utt; ++u) dn[(size_t)u] = g->hop * (Fu[u] - 1);
-  if (resampled) {
-    size_t Rtot = 0;
-    rbase.resize((size_t)n_utt);
-    for (int u = 0; u < n_utt; ++u) {
-      rbase[(size_t)u] = (int)Rtot;
-      Rtot += g->delivered((size_t)dn[(size_t)u]);
-      if (Rtot > (size_t)0x7fffffff) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^31 - 1 samples at rate %d", g->out_rate);
-      dn[(size_t)u] = (int)(Rtot - (size_t)rbase[(size_t)u]);
-    }
-    g->audio_rs.alloc(std::max<size_t>(Rtot, 1));
-    g->resample_prepare(g->out_rate);
-  }
-  const std::vector<int> &dbase = resampled ? rbase : abase;
-  float *const dbuf = resampled ? g->audio_rs.p : g->audio.p;
+  // What is delivered (delivery_plan.h): at 22050 the loop's audio where it lies; at another rate the resampled utterances back
+  // to back, and everything behind the loop works from those.  Counts, places and buffer sizes do not depend on the order of the
+  // rows, which is known only with the launches: here the failure and every growth, in front of the launches.
+  const DeliveryStages stages = g->dl.stages(g->gopts.output_normalise, false);
+  const DeliveryPlan sized = delivery_plan_checked(stages, loop_n, abase, delivery_identity((size_t)n_utt));
+  const std::vector<int> &dn = sized.dn;
+  g->dl.size(sized);
   HIP_CHECK(hipStreamSynchronize(st));  // the host vector above
   const float alpha = g->momentum / (1.0f + g->momentum);
-  // With a loudness target the loudness stage (loudness.hip) takes the output normalisation's place, on the same rows.
-  const bool loud = g->loudness_on();
-  const int norm_mode = loud ? 0 : g->gopts.output_normalise;
   g->clear_last();
-  const bool limited = loud && g->limiter_on();  // k_limit where k_loud_scale ran: out of place, the rows at the same offsets
-  if (loud) {
-    size_t groups = 0, dtot = 0;
-    for (int u = 0; u < n_utt; ++u) {
-      groups += loudness_groups((size_t)dn[(size_t)u]);
-      dtot = std::max(dtot, (size_t)dbase[(size_t)u] + (size_t)dn[(size_t)u]);
-    }
-    g->loudness_prepare(g->out_rate);
-    g->loudness_bufs(groups, (size_t)n_utt);
-    if (limited) {
-      g->limiter_prepare(g->out_rate, g->lim_us);
-      g->limiter_bufs(dtot, (size_t)n_utt);
-    }
-  }
-  // The handle's compressor: one setting for every utterance, the ragged stage in place on the delivered rows, in front of the
-  // level stage.
-  const bool comp = g->compressor_on();
-  g->comp_ran = comp;
-  const CompPlan comp_plan = compressor_plan(g->comp, g->out_rate);
-  if (comp) {
-    size_t tiles = 0;
-    for (int u = 0; u < n_utt; ++u) tiles += compressor_tiles((size_t)dn[(size_t)u]);
-    g->compressor_bufs(tiles, (size_t)n_utt);
-  }
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
   g->probe_tick();
   for (int attempt = 0;; ++attempt) {
@@ -1157,71 +869,21 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     for (int u = 0; u < n_utt; ++u) out.emplace_back((size_t)dn[(size_t)u]);
     Drain drain(g->copy_stream);  // no buffer of `out` goes back to the pool while a copy into it may be in flight
     // The delivery stages.  The utterances of one fetch are consecutive rows of the tables (plan.order), so each fetch is
-    // preceded by ONE resample launch (at a rate other than 22050) and ONE two-launch output normalisation (G6) of exactly
-    // its utterances, in that order: the level rules hold for the signal the caller receives.
-    std::vector<int> tab_pos((size_t)n_utt, 0);
-    if (norm_mode || resampled || loud || comp) {
-      std::vector<int2> tab;
-      tab.reserve((size_t)n_utt);
-      g->rs_tab_host.clear();
-      g->loud_tab_host.clear();
-      g->lim_tab_host.clear();
-      g->comp_tab_host.clear();
-      int blk = 0, grp = 0, seg = 0, sb = 0, tile = 0, ctile = 0;
-      for (int u : plan.order) {
-        tab_pos[(size_t)u] = (int)tab.size();
-        tab.push_back(make_int2(dbase[(size_t)u], dn[(size_t)u]));
-        if (comp) {
-          g->comp_tab_host.push_back({(long long)dbase[(size_t)u], (long long)dbase[(size_t)u], dn[(size_t)u], ctile});
-          ctile += (int)compressor_tiles((size_t)dn[(size_t)u]);
-        }
-        if (loud) {
-          const size_t n = (size_t)dn[(size_t)u];
-          g->loud_tab_host.push_back({(long long)dbase[(size_t)u], dn[(size_t)u], grp, seg, sb});
-          grp += (int)loudness_groups(n);
-          seg += (int)loudness_segments(n);
-          sb += (int)loudness_sub_blocks(g->out_rate, n);
-          if (limited) {
-            g->lim_tab_host.push_back({(long long)dbase[(size_t)u], (long long)dbase[(size_t)u], dn[(size_t)u], tile});
-            tile += (int)limiter_tiles(n);
-          }
-        }
-        if (resampled) {
-          g->rs_tab_host.push_back({(long long)abase[u], (long long)rbase[(size_t)u], g->hop * (Fu[u] - 1), dn[(size_t)u], blk, 0});
-          blk += (dn[(size_t)u] + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK;
-        }
-      }
-      if (norm_mode) {
-        g->norm_tab.upload(tab.data(), tab.size(), st);
-        g->norm_parts.alloc((size_t)GLN_SCRATCH * (size_t)n_utt);
-      }
-      if (resampled) g->rs_tab.upload(g->rs_tab_host.data(), g->rs_tab_host.size(), st);
-      if (loud) g->loud_tab.upload(g->loud_tab_host.data(), g->loud_tab_host.size(), st);
-      if (limited) g->lim_tab.upload(g->lim_tab_host.data(), g->lim_tab_host.size(), st);
-      if (comp) g->comp_tab.upload(g->comp_tab_host.data(), g->comp_tab_host.size(), st);
-      HIP_CHECK(hipStreamSynchronize(st));
-    }
+    // preceded by ONE launch per stage over exactly its utterances, in the chain's order: the level rules hold for the signal
+    // the caller receives.
+    g->dl.prepare(delivery_plan(stages, loop_n, abase, plan.order), true);  // (sized and checked above: nothing grows or throws; drains st)
+    const DeliveryPlan &dp = g->dl.plan;
     size_t n_ev = 0;
     auto fetch_audio = [&](const std::vector<int> &utts) {  // after the work just enqueued on `st`
-      if (resampled && !utts.empty()) g->resample_rows(g->audio.p, g->audio_rs.p, tab_pos[(size_t)utts[0]], (int)utts.size());
-      if (comp && !utts.empty()) g->compress_rows(dbuf, dbuf, tab_pos[(size_t)utts[0]], (int)utts.size(), comp_plan);
-      if (norm_mode && !utts.empty()) {
-        int n_max = 0;
-        for (int u : utts) n_max = std::max(n_max, dn[(size_t)u]);
-        const int r0 = tab_pos[(size_t)utts[0]];
-        launch_gl_output_normalise(dbuf, g->norm_tab.p + r0, (int)utts.size(), 0, n_max, norm_mode, g->gopts.rms_target,
-                                   g->norm_parts.p + (size_t)r0 * GLN_SCRATCH, st);
-      }
-      const float *src = dbuf;  // where the delivered rows lie
-      if (loud && !utts.empty()) src = g->loudness_rows(dbuf, tab_pos[(size_t)utts[0]], (int)utts.size(), g->out_rate, true);
+      const int r0 = utts.empty() ? 0 : dp.tab_pos[(size_t)utts[0]];
+      const float *src = g->dl.run(g->audio.p, r0, (int)utts.size(), g->gopts.rms_target);  // where the delivered rows lie
       hipEvent_t e = g->launch_done(n_ev++);
       HIP_CHECK(hipEventRecord(e, st));
       HIP_CHECK(hipStreamWaitEvent(g->copy_stream, e, 0));
       for (int u : utts)
-        HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, src + dbase[(size_t)u], sizeof(float) * (size_t)dn[(size_t)u], hipMemcpyDeviceToHost,
+        HIP_CHECK(hipMemcpyAsync(out[(size_t)u].p, src + dp.dbase[(size_t)u], sizeof(float) * (size_t)dn[(size_t)u], hipMemcpyDeviceToHost,
                                  g->copy_stream));
-      if (loud && !utts.empty()) g->loudness_fetch(tab_pos[(size_t)utts[0]], (int)utts.size(), g->copy_stream);
-      if (comp && !utts.empty()) g->compressor_fetch(tab_pos[(size_t)utts[0]], (int)utts.size(), g->copy_stream);
+      g->dl.fetch_stats(r0, (int)utts.size(), g->copy_stream);
     };
     // the persistent launches, each followed by the fetch of its utterances
     bool used_persistent = false;
@@ -1251,9 +913,9 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
       v.ang2 = all.ang2 + (size_t)fbase[u] * g->nb;
       v.tprev = all.tprev + (size_t)fbase[u] * g->nb;
       v.frames = all.frames + (size_t)fbase[u] * g->n_fft;
-      v.wss_inv = all.wss_inv + abase[u];
+      v.wss_inv = all.wss_inv + abase[(size_t)u];
       launch_gl_prepare(v, st);
-      g->run_iterations(v, g->iters, alpha, g->audio.p + abase[u]);  // the engine the single-utterance call uses
+      g->run_iterations(v, g->iters, alpha, g->audio.p + abase[(size_t)u]);  // the engine the single-utterance call uses
       used_persistent = used_persistent || g->last_persistent;
       fetch_audio(std::vector<int>(1, u));
     }
@@ -1268,8 +930,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     for (int u = 0; u < n_utt; ++u) {
       audios[u] = out[(size_t)u].release();
       n_samples[u] = (size_t)dn[(size_t)u];
-      if (loud) g->push_last((size_t)tab_pos[(size_t)u]);
-      if (comp) g->push_last_comp((size_t)tab_pos[(size_t)u]);
+      g->dl.push_last((size_t)dp.tab_pos[(size_t)u]);
     }
     return;
   }

@@ -1,6 +1,7 @@
 // griffinlim_handle.h -- the vocoder handle, the host-side mel-bank algebra, and the gl_* request paths the extern "C"
-// functions of api_griffinlim.cpp and api_synthesize.cpp share.
+// functions of api_griffinlim.cpp, api_gl_magnitude.cpp, api_gl_delivery.cpp and api_synthesize.cpp share.
 #pragma once
+#include "delivery.h"
 #include "engine_gate.h"
 #include "kernels.h"
 #include "prosody_contour.h"
@@ -60,8 +61,7 @@ void target_plan(const F0Job &job, const xdtts_pitch_target *t, const xdtts_pros
 inline StreamOpts stream_opts_checked(const xdtts_stream_opts *o) {
   StreamOpts s = stream_opts_default();
   if (o) std::memcpy(&s, o, sizeof s);
-  const std::string msg = stream_opts_check(s);
-  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  bad_arg_if(stream_opts_check(s));
   return s;
 }
 // xdtts_timbre (include/xdtts.h) on top of timbre_plan.h, which knows no status codes: the checked setting (null = the default,
@@ -70,8 +70,7 @@ inline Timbre timbre_checked(const xdtts_timbre *t) {
   static_assert(sizeof(xdtts_timbre) == sizeof(Timbre) && sizeof(Timbre) == 20, "Timbre is xdtts_timbre");
   Timbre s = timbre_default();
   if (t) std::memcpy(&s, t, sizeof s);
-  const std::string msg = timbre_check(s);
-  if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", msg.c_str());
+  bad_arg_if(timbre_check(s));
   return s;
 }
 inline TimbreUtt timbre_utt(int src0, int dst0, int F, const Timbre &t) {
@@ -81,6 +80,15 @@ inline TimbreUtt timbre_utt(int src0, int dst0, int F, const Timbre &t) {
 inline void rows_add(Rows &r, size_t rows, size_t cap, const char *too_large) {
   try {
     r.add(rows, cap, too_large);
+  } catch (const std::length_error &e) {
+    fail(XDTTS_ERR_BAD_ARG, "%s", e.what());
+  }
+}
+// ... and delivery_plan (delivery_plan.h) likewise: more than 2^31 - 1 delivered samples fail with XDTTS_ERR_BAD_ARG and the text
+inline DeliveryPlan delivery_plan_checked(const DeliveryStages &s, const std::vector<size_t> &n, const std::vector<long long> &base,
+                                          const std::vector<int> &order) {
+  try {
+    return delivery_plan(s, n, base, order);
   } catch (const std::length_error &e) {
     fail(XDTTS_ERR_BAD_ARG, "%s", e.what());
   }
@@ -104,8 +112,7 @@ struct xdtts_griffinlim {
   // mel->linear options (xdtts_griffinlim_opts) and the NNLS refinement's operands
   xdtts_griffinlim_opts gopts = [] { xdtts_griffinlim_opts o; xdtts_griffinlim_opts_default(&o); return o; }();  // one source for the defaults
   static constexpr int NBP = 528;  // bins padded to the GEMM's K granule
-  DevBuf<float> basis_p, basisT_p, nnls_x, nnls_r, norm_parts;  // norm_parts: GLN_SCRATCH per utterance
-  DevBuf<int2> norm_tab;  // (first sample, samples) per utterance of a vocoder batch
+  DevBuf<float> basis_p, basisT_p, nnls_x, nnls_r;
   float nnls_step = 0.f;   // 1 / lambda_max(A A^T)
   xdtts::GraphCache graph;  // n_iter x (istft, stft) + final ISTFT for the cached (buffers, F, iterations, momentum, output)
   DevBuf<float2> tw, ang, ang2, tprev, tprev2;  // tprev2: final rebuilt spectrum of the parity hook
@@ -165,8 +172,7 @@ struct xdtts_griffinlim {
   DevBuf<xdtts::F0Stats> f0_stats;
   DevBuf<xdtts::F0Utt> f0_utts;
   std::vector<xdtts::F0Utt> f0_utts_host;
-  xdtts::F0Stats *f0_host = nullptr;  // pinned
-  size_t f0_host_n = 0;
+  xdtts::PinnedArray<xdtts::F0Stats> f0_host;
   int f0_rows = 0;
   std::vector<xdtts_f0_stats> last_f0;  // xdtts_griffinlim_last_f0
   void f0_prepare(const std::vector<xdtts::F0Utt> &utts);
@@ -208,110 +214,10 @@ struct xdtts_griffinlim {
   void spsi_tables(const std::vector<int> &Fu, SpsiTables &t);
   void spsi_batch(const float *S_dev, const SpsiTables &t, float2 *ang_out, float2 *tprev_out, unsigned *turns = nullptr);
 
-  // output rate (resample.hip): the stage between the final ISTFT and the output normalisation.  out_rate 22050 = none.
-  int out_rate = XDTTS_SAMPLE_RATE;
-  xdtts::ResamplePlan out_plan;     // of out_rate (the identity by default): set with it
-  xdtts::ResamplePlan rs_plan;      // of the table below (the parity hooks bring their own rate)
-  xdtts::ResampleTable rs_table;    // host copy: the upload's source, kept with the handle
-  DevBuf<float> rs_rows, rs_in, audio_rs;  // the table; the parity hooks' input; the resampled audio (single call and batch)
-  DevBuf<xdtts::ResampleUtt> rs_tab;
-  std::vector<xdtts::ResampleUtt> rs_tab_host;  // the upload's source: stays until the next request of this handle
-  // The table of `rate` (checked by the caller, not the identity) on the device: built and uploaded once per (handle, rate).
-  void resample_prepare(int rate);
-  // One utterance: src[0 .. n) -> dst[0 .. resample_n_out(n)) on the stream; with the table in place nothing but the launch
-  // (the record travels as a kernel argument).  Returns N'.
-  size_t resample_one(const float *src, size_t n, float *dst, int rate);
-  // Ragged: the records of rs_tab_host (uploaded by the caller as rs_tab, behind resample_prepare()) from row r0, `count` of
-  // them, in one launch.
-  void resample_rows(const float *src, float *dst, int r0, int count);
-  // What a request path delivers for n samples of the loop: N' at the handle's rate, n at 22050.
-  size_t delivered(size_t n) const { return xdtts::resample_n_out(out_plan, n); }
-
-  // loudness (loudness.hip): with a target set, the stage that takes the output normalisation's place behind the resampler --
-  // BS.1770 integrated loudness and true peak of the delivered signal, then one linear gain.  NaN target = off (the default).
-  float loud_target = NAN, loud_ceiling = NAN;
-  bool loudness_on() const { return !std::isnan(loud_target); }
-  xdtts::LoudnessTable loud_table_host{};   // the upload's source, kept with the handle; rate 0 = none yet
-  DevBuf<xdtts::LoudnessTable> loud_table;
-  DevBuf<double> loud_excl, loud_agg, loud_gin, loud_part, loud_sub;  // the scan's scratch (kernels.h: LoudBufs)
-  DevBuf<float2> loud_peaks;
-  DevBuf<xdtts::LoudResult> loud_res;       // one per utterance of a request
-  DevBuf<xdtts::LoudUtt> loud_tab;
-  std::vector<xdtts::LoudUtt> loud_tab_host;  // the upload's source: stays until the next request of this handle
-  xdtts::LoudResult *loud_host = nullptr;   // pinned: the structs travel back behind the audio
-  size_t loud_host_n = 0;
-  std::vector<xdtts_loudness> last_loud;    // xdtts_griffinlim_last_loudness: of the last delivering call, in the caller's order
-  // The coefficients, matrix powers and taps of `rate` on the device: built and uploaded once per (handle, rate).
-  void loudness_prepare(int rate);
-  // Scratch for `groups` workgroups in all (every array is sized from it) and `n_utt` results, device and pinned host.
-  xdtts::LoudBufs loudness_bufs(size_t groups, size_t n_utt);
-  // One utterance, x[0 .. n) at `rate`, on the stream: the measurement into loud_res[0] and, with scale, the gain of the
-  // handle's target applied in place.  Nothing is uploaded (the record travels as a kernel argument).
-  // Returns where the delivered signal lies: x, or -- where the limiter ran -- lim_out.p (out of place, the same offsets).
-  float *loudness_one(float *x, size_t n, int rate, bool scale);
-  // Ragged: records loud_tab_host[r0 .. r0 + count) (uploaded by the caller as loud_tab, behind loudness_prepare() and
-  // loudness_bufs()), results into loud_res[r0 ..].  With the limiter: lim_tab_host / lim_tab likewise, behind limiter_prepare()
-  // and limiter_bufs(); returns as loudness_one (src0 = dst0 in the records).
-  float *loudness_rows(float *x, int r0, int count, int rate, bool scale);
-  // loud_res[r0 .. r0 + count) -> loud_host (and, with the limiter, lim_stats -> lim_host), on `s`
-  void loudness_fetch(int r0, int count, hipStream_t s);
-
-  // limiter (limiter.hip): with a look-ahead set beside a target AND a ceiling, the measurement forms the gain without the
-  // ceiling and k_limit takes k_loud_scale's place, out of place into lim_out.  0 = off (the default).
-  int lim_us = 0;
-  bool limiter_on() const { return lim_us != 0 && loudness_on() && !std::isnan(loud_ceiling); }
-  bool lim_ran = false;                       // the last loudness_one / _rows / stream_join launched k_limit: stats travel back
-  int lim_H = 0;                              // the half width whose window is on the device; 0 = none yet
-  std::vector<float> lim_win_host;            // the upload's source, kept with the handle
-  DevBuf<float> lim_win, lim_out;
-  DevBuf<xdtts::LimiterStats> lim_stats;      // one per utterance of a request
-  DevBuf<xdtts::LimUtt> lim_tab;
-  std::vector<xdtts::LimUtt> lim_tab_host;    // the upload's source: stays until the next request of this handle
-  xdtts::LimiterStats *lim_host = nullptr;    // pinned: the stats travel back behind the loudness structs
-  size_t lim_host_n = 0;
-  std::vector<xdtts_limiter_stats> last_lim;  // xdtts_griffinlim_last_limiter: of the last delivering call, in the caller's order
-  // The window of H(rate, lookahead_us) on the device (built and uploaded when H changes) and the loudness table's taps.
-  void limiter_prepare(int rate, int lookahead_us);
-  // lim_out with room for `floats`, stats for n_utt utterances, device and pinned host.
-  void limiter_bufs(size_t floats, size_t n_utt);
-  // the job of the handle's settings reading loud_res + r0 (res_from_loudness), or of the stage alone with (gain0, ceil)
-  xdtts::LimJob limiter_job(bool res_from_loudness, int r0, double gain0, double ceil) const;
-  // One utterance x[0 .. n) -> lim_out[0 .. n), stats into lim_stats[0]; nothing is uploaded.
-  void limit_one(const float *x, size_t n, const xdtts::LimJob &job);
-  // Ragged: records lim_tab_host[r0 .. r0 + count) (uploaded by the caller as lim_tab), stats into lim_stats[r0 ..].
-  void limit_rows(const float *x, int r0, int count, const xdtts::LimJob &job);
-  // compressor (compressor.hip): with a setting other than the identity, the stage between the resampler and the level stage,
-  // in place on the delivered signal.  Off (the default) and the identity launch and allocate nothing.
-  xdtts::Compressor comp = xdtts::compressor_default();
-  bool comp_set = false;
-  bool compressor_on() const { return comp_set && !xdtts::compressor_is_identity(comp); }
-  bool comp_ran = false;                        // the last delivering run launched the stage: stats travel back
-  DevBuf<xdtts::CompAgg> comp_agg;              // one per tile of a request
-  DevBuf<xdtts::CompressorStats> comp_stats;    // one per utterance of a request
-  DevBuf<xdtts::CompUtt> comp_tab;
-  std::vector<xdtts::CompUtt> comp_tab_host;    // the upload's source: stays until the next request of this handle
-  xdtts::CompressorStats *comp_host = nullptr;  // pinned: the stats travel back behind the audio
-  size_t comp_host_n = 0;
-  std::vector<xdtts_compressor_stats> last_comp;  // xdtts_griffinlim_last_compressor: of the last delivering call, in the caller's order
-  // Aggregates for `tiles` tiles in all and stats for n_utt utterances, device and pinned host.
-  void compressor_bufs(size_t tiles, size_t n_utt);
-  // One utterance x[0 .. n) -> out[0 .. n) (out == x: in place), stats into comp_stats[0]; nothing is uploaded.
-  void compress_one(const float *x, float *out, size_t n, const xdtts::CompPlan &plan);
-  // Ragged: records comp_tab_host[r0 .. r0 + count) (uploaded by the caller as comp_tab, behind compressor_bufs()), stats into
-  // comp_stats[r0 ..].
-  void compress_rows(const float *x, float *out, int r0, int count, const xdtts::CompPlan &plan);
-  // comp_stats[r0 .. r0 + count) -> comp_host, on `s`
-  void compressor_fetch(int r0, int count, hipStream_t s);
-  // the stats of record r of the last fetch -> last_comp
-  void push_last_comp(size_t r);
-  void clear_last() {
-    last_loud.clear();
-    last_lim.clear();
-    last_f0.clear();
-    last_comp.clear();
-  }
-  // the structs of record r of the last fetch -> last_loud (and last_lim where the limiter ran)
-  void push_last(size_t r);
+  // The delivery chain behind the loop (delivery.h): output rate, compressor, output normalisation or loudness with or without
+  // the limiter -- settings, tables, buffers, the stats of the last call, and the one runner of every request path.
+  xdtts::Delivery dl;
+  void clear_last() { dl.clear_last(), last_f0.clear(); }
 
   // stream (stream.hip): the utterances of a sequence joined with their gaps, faded, levelled and encoded -- the stage behind
   // everything above (xdtts_griffinlim_join, xdtts_synthesize_document).
@@ -333,8 +239,8 @@ struct xdtts_griffinlim {
   void stream_reserve(size_t floats);
   // The stage on the stream, from st_tab_host (src0 into st_src) -> st_out (total * sample_bytes bytes): the table and the fade
   // table go up, then at level 0 ONE k_stream_join launch; at level 1 the fp32 stream is formed first (format 0, no gain),
-  // measured once by the loudness kernels at `rate`, and the encode launch reads the gain from loud_res[0] on the device --
-  // the struct travels back behind it (loud_host[0]).  Checked arguments.
+  // measured once by the delivery chain's loudness stage at `rate` (with the limiter where it is on), and the encode launch reads
+  // the gain from dl.loud_res[0] on the device -- the structs travel back behind it.  Checked arguments.
   // (begin: recorded behind the uploads, in front of the first launch)
   void stream_join(size_t total, const xdtts::StreamOpts &o, int rate, hipEvent_t begin = nullptr);
 

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "compressor_plan.h"
+#include "delivery_plan.h"
 #include "f0_plan.h"
 #include "gl_plan.h"
 #include "limiter_plan.h"
@@ -402,10 +403,7 @@ void launch_spsi_export(const unsigned *turns, const float2 *ang, int F, int nb,
 // ---- output rate (resample.hip): 22 050 Hz audio -> rate Q behind the loop, polyphase windowed sinc (include/xdtts.h) ---------
 // One utterance of a launch: n samples at x + src0 -> n_out = resample_n_out(n) samples at y + dst0; its workgroups are blk0 ..
 // blk0 + ceil(n_out / RESAMPLE_BLOCK) of the table's numbering (ascending, the utterances back to back).
-struct ResampleUtt {
-  long long src0, dst0;
-  int n, n_out, blk0, pad;
-};
+// (struct ResampleUtt: delivery_plan.h)
 // nblk workgroups, the first being number blk_base of the table's numbering (a launch may cover a run of consecutive utterances:
 // tab_dev points at the first of them, n_utt counts them).  tab_dev == nullptr: the one utterance `one` (blk0 = 0), nothing
 // is read but the arguments.  rows_dev = ResampleTable::rows on the device.  An output's bits do not depend on what else the
@@ -417,10 +415,7 @@ void launch_resample(const float *x, float *y, const ResampleUtt *tab_dev, int n
 // One utterance of a launch: n samples at x + src0.  Its workgroups (LOUD_GROUP samples each) are grp0 .. of the table's
 // numbering, its segments (LOUD_SEG samples) seg0 .., its 100 ms sub-blocks sb0 .. -- ascending, the utterances back to back;
 // those three also index the scratch arrays below.
-struct LoudUtt {
-  long long src0;
-  int n, grp0, seg0, sb0;
-};
+// (struct LoudUtt: delivery_plan.h)
 struct LoudResult {  // == xdtts_loudness (include/xdtts.h)
   double mean_square, true_peak, sample_peak, gain;
   int blocks, gated;
@@ -448,10 +443,7 @@ void launch_loudness_scale(float *x, const LoudUtt *tab_dev, int count, int grp_
 // ---- limiter (limiter.hip): look-ahead true-peak limiter where the loudness stage scaled (include/xdtts.h, limiter_plan.h) ------
 // One utterance of a launch: n samples at x + src0 -> n samples at out + dst0 (out of place).  Its workgroups (LIM_TILE outputs
 // each) are tile0 .. of the table's numbering, ascending, the utterances back to back.
-struct LimUtt {
-  long long src0, dst0;
-  int n, tile0;
-};
+// (LimUtt = TileUtt: delivery_plan.h)
 struct LimJob {
   const float *taps;       // LoudnessTable::taps on the device
   const float *win;        // the 2 H + 1 weights of limiter_window on the device
@@ -469,10 +461,7 @@ void launch_limit(const float *x, float *out, const LimUtt *tab_dev, int count, 
 // ---- compressor (compressor.hip): tent-envelope dynamic range compressor in front of the level stage (include/xdtts.h, compressor_plan.h) ----
 // One utterance of a launch: n samples at x + src0 -> n samples at out + dst0 (in place where they are the same place).  Its
 // workgroups (COMP_TILE samples each) are tile0 .. of the table's numbering, ascending, the utterances back to back.
-struct CompUtt {
-  long long src0, dst0;
-  int n, tile0;
-};
+// (CompUtt = TileUtt: delivery_plan.h)
 // Three launches: the stats' initial values, the tiles' aggregates and the peak, then the samples -- n_tiles workgroups each,
 // the first being tile tile_base of the table's numbering (tab_dev == nullptr: the one utterance `one`).  agg holds one
 // record per tile of the WHOLE table (index = the table's tile number); stats[u] belongs to record u.  Integer atomics on the
