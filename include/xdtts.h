@@ -908,6 +908,81 @@ xdtts_status xdtts_compressor_envelope(const float *audio, size_t n, int32_t rat
 xdtts_status xdtts_compressor_reference(const float *audio, size_t n, int32_t rate, const xdtts_compressor *c, float *out,
                                         xdtts_compressor_stats *stats);
 
+/* Pause control: the silence stage, the LAST stage of the delivery chain -- behind the level stage, at the delivered rate, out
+ * of place.  It trims the near-silence a Tacotron2 utterance starts and ends with down to lead_ms / trail_ms, and caps the
+ * pauses inside it at max_pause_ms, so that the gap a listener hears between two pieces of xdtts_synthesize_document is
+ * trail + break + lead wherever both pieces have sound and at least that much silence of their own.  The output's length is
+ * decided on the device; nothing between the loop and the copy to the host waits for it.  All decisions are integers and
+ * comparisons.  The definition, exactly -- x the n fp32 samples at rate Q, s the settings:
+ *   plan    in double on the host: W = Q / 200 (integer division: a 5 ms window, 40 .. 480 samples); win(ms) =
+ *           (int) floor(ms / 5.0 + 0.5); min_w, lead_w, trail_w, pause_w = win of their fields; fade = min(W / 2,
+ *           (int) floor(fade_ms Q / 1000.0 + 0.5)); tfac = (float) pow(10.0, threshold_db / 20.0); the fade gains T[k], k < fade,
+ *           are the rising half of the stream stage's table: T[k] = (float)(0.5 - 0.5 cos(pi (k + 0.5) / fade)).
+ *   1 peaks   nw = ceil(n / W) windows; window w covers len_w samples from w W (W, but for the last one).  p_w = max |x_i| over
+ *             the window, P = max_w p_w: maxima, exact whatever the order.
+ *   2 candidates  a0_w = p_w > fl(P tfac): one fp32 product, a strict comparison (P == 0: none).
+ *   3 sound   a_w = a0_w and the maximal run of consecutive candidates that contains w has at least max(min_w, 1) windows.
+ *   4 no sound anywhere: any_sound = 0, the first min(nw, max(1, lead_w + trail_w)) windows are kept.
+ *   5 else, with A the first and Z the last sound window, w is kept when a_w, or w < A and A - w <= lead_w, or w > Z and
+ *             w - Z <= trail_w, or -- between its nearest sound windows l < w < r -- pause_w == 0 or w - l <= pause_w -
+ *             pause_w / 2 or r - w <= pause_w / 2: a pause of more than pause_w windows shrinks to exactly pause_w.
+ *   6 output  the kept windows in order; n_out = the sum of their len_w; lead_cut, trail_cut, pause_cut = the samples dropped in
+ *             front of A, behind Z (without sound: all of them) and between; n_cuts = the places where a kept window has a
+ *             dropped neighbour.
+ *   7 fades   a kept window w > 0 whose window w - 1 is dropped: sample k < fade becomes fl(x T[k]); a kept window w < nw - 1
+ *             whose window w + 1 is dropped: sample len_w - 1 - k becomes fl(x T[k]), k < fade.  fade <= W / 2: they never meet.
+ *             Every other sample is copied.
+ * Settings: threshold_db in [-96, -6] (dB under the utterance's own sample peak), min_sound_ms in [0, 500], lead_ms and trail_ms
+ * in [0, 10000], max_pause_ms 0 (pauses untouched) or in [20, 60000], fade_ms in [0, 2.5], all finite; the rate is what
+ * xdtts_griffinlim_set_output_rate accepts; 1 <= n < 2^28.  Anything else is XDTTS_ERR_BAD_ARG before a device is touched, the
+ * message names the field.  The stage sees what the level stage delivered, and the level stage the untrimmed utterance (the
+ * gates of BS.1770 make a loudness target insensitive to the difference).  Honoured by every entry that delivers an utterance:
+ * the single calls, both halves of a sequence, the batch, a demoted engine's retry, and the pieces of
+ * xdtts_synthesize_document, whose records take n_out (its own edge fade is independent of the stage's fades).  Buffers handed
+ * out are sized for the untrimmed utterance; n_samples = n_out.  Off (the default): nothing new is launched or allocated, and
+ * every result keeps its bits.
+ * Out of scope: trimming in the frame domain in front of the loop, absolute dBFS thresholds, crossfades across a cut; the
+ * result for non-finite samples is not specified. */
+typedef struct {
+  float threshold_db;   /* [-96, -6]   dB under the utterance's own sample peak; default -40 */
+  float min_sound_ms;   /* [0, 500]    sound shorter than this counts as silence (clicks); default 20 */
+  float lead_ms;        /* [0, 10000]  silence kept in front of the first sound; default 50 */
+  float trail_ms;       /* [0, 10000]  silence kept behind the last sound; default 100 */
+  float max_pause_ms;   /* 0 = pauses inside the utterance untouched (default), else [20, 60000] */
+  float fade_ms;        /* [0, 2.5]    raised-cosine fade either side of every cut; default 2 */
+} xdtts_silence;
+typedef struct {
+  uint32_t n_in, n_out;                     /* samples in front of and behind the stage */
+  uint32_t lead_cut, trail_cut, pause_cut;  /* samples dropped: n_out + lead_cut + trail_cut + pause_cut == n_in */
+  uint32_t n_cuts;                          /* places where a kept window has a dropped neighbour */
+  float    peak;                            /* P */
+  uint32_t any_sound;                       /* 0 where no window is sound */
+} xdtts_silence_stats;
+void xdtts_silence_default(xdtts_silence *s);   /* {-40, 20, 50, 100, 0, 2} */
+/* s == NULL switches the stage off (the default).  The fields are looked at before the handle. */
+xdtts_status xdtts_griffinlim_set_silence(xdtts_griffinlim *g, const xdtts_silence *s);
+/* *on = 1 and *s = the setting, or *on = 0 and *s = the default; either pointer may be NULL */
+xdtts_status xdtts_griffinlim_get_silence(const xdtts_griffinlim *g, xdtts_silence *s, int32_t *on);
+/* The stats of each utterance of the last delivering call, shaped like xdtts_griffinlim_last_compressor; *n = 0 unless the
+ * stage is set. */
+xdtts_status xdtts_griffinlim_last_silence(const xdtts_griffinlim *g, xdtts_silence_stats *out, size_t cap, size_t *n);
+/* The stage alone on the caller's audio at a given rate, whatever the handle's settings.  The parity hook: out / outs[u] hold n
+ * floats, of which the first stats.n_out are written -- they and the stats equal xdtts_silence_reference bit for bit, and every
+ * row of the ragged form equals the single call's.  Argument errors come back before a device is touched.  Afterwards
+ * xdtts_griffinlim_last_timings ms[0] is the stage alone. */
+xdtts_status xdtts_griffinlim_trim(xdtts_griffinlim *g, const float *audio, size_t n, int32_t rate, const xdtts_silence *s, float *out,
+                                   xdtts_silence_stats *stats);
+xdtts_status xdtts_griffinlim_trim_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt, int32_t rate,
+                                         const xdtts_silence *s, float *const *outs, xdtts_silence_stats *stats);
+/* Host arithmetic, no handle, no device.  _plan: the host integers and the threshold's factor; any pointer may be NULL.
+ * _keep: keep[0 .. ceil(n / W)) = 1 where the window is kept.  _reference: the definition as serial plain C++; out holds n
+ * floats (not the input's), of which n_out are written; stats may be NULL. */
+xdtts_status xdtts_silence_plan(int32_t rate, const xdtts_silence *s, int32_t *W, int32_t *min_w, int32_t *lead_w, int32_t *trail_w,
+                                int32_t *pause_w, int32_t *fade, float *tfac);
+xdtts_status xdtts_silence_keep(const float *audio, size_t n, int32_t rate, const xdtts_silence *s, uint8_t *keep);
+xdtts_status xdtts_silence_reference(const float *audio, size_t n, int32_t rate, const xdtts_silence *s, float *out,
+                                     xdtts_silence_stats *stats);
+
 /* Document output: the utterances of a sequence joined with their <break> silences into ONE stream, faded at their edges,
  * levelled by one programme gain and encoded, on the device -- the output stage of XdTts::generate_audio (src/lib.rs:60-108:
  * every piece written as i16, the silences between them, one PCM stream).  The last stage of the delivery chain: rate ->

@@ -469,6 +469,37 @@ class GriffinLim {
     if (stats) *stats = st;
     return out;
   }
+  // Pause control (xdtts_griffinlim_set_silence): nullptr = off, the default.  The last stage of the delivery chain: edge silence
+  // trimmed to lead_ms / trail_ms, pauses capped at max_pause_ms; every delivering entry then returns n_out samples.
+  static xdtts_silence default_silence() {
+    xdtts_silence s{};
+    xdtts_silence_default(&s);
+    return s;
+  }
+  void set_silence(const xdtts_silence *s) { check(xdtts_griffinlim_set_silence(g_, s)); }
+  // ... the setting, and whether the stage is on
+  bool silence_setting(xdtts_silence *s) const {
+    int32_t on = 0;
+    check(xdtts_griffinlim_get_silence(g_, s, &on));
+    return on != 0;
+  }
+  // ... the stats of each utterance of the last delivering call (empty unless the stage is set)
+  std::vector<xdtts_silence_stats> last_silence() const {
+    size_t n = 0;
+    check(xdtts_griffinlim_last_silence(g_, nullptr, 0, &n));
+    std::vector<xdtts_silence_stats> out(n);
+    if (n) check(xdtts_griffinlim_last_silence(g_, out.data(), out.size(), &n));
+    return out;
+  }
+  // ... and the stage alone on the caller's audio (xdtts_griffinlim_trim): the n_out samples, the bits of xdtts_silence_reference
+  std::vector<float> trim(const std::vector<float> &audio, int32_t rate, const xdtts_silence &s, xdtts_silence_stats *stats = nullptr) const {
+    std::vector<float> out(audio.size());
+    xdtts_silence_stats st{};
+    check(xdtts_griffinlim_trim(g_, audio.data(), audio.size(), rate, &s, out.data(), &st));
+    out.resize(st.n_out);
+    if (stats) *stats = st;
+    return out;
+  }
   // The voice of this handle (xdtts_griffinlim_set_timbre): vocal-tract length and breathiness on the magnitude behind the prosody
   // stage.  The default is the identity, which launches nothing; every entry that runs mel -> linear itself honours the setting.
   static xdtts_timbre default_timbre() {

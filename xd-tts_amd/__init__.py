@@ -211,6 +211,34 @@ class CompressorStats(C.Structure):
         return (self.peak, self.max_over, self.engaged, self.compressed)
 
 
+class Silence(C.Structure):
+    """xdtts_silence: the silence stage, the last of the delivery chain.  threshold_db in [-96, -6] (dB under the utterance's own
+    sample peak), min_sound_ms in [0, 500], lead_ms and trail_ms in [0, 10000], max_pause_ms 0 (pauses untouched) or in
+    [20, 60000], fade_ms in [0, 2.5].  Silence() holds the library's defaults (-40, 20, 50, 100, 0, 2); keywords override fields."""
+
+    _fields_ = [("threshold_db", C.c_float), ("min_sound_ms", C.c_float), ("lead_ms", C.c_float), ("trail_ms", C.c_float),
+                ("max_pause_ms", C.c_float), ("fade_ms", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib.xdtts_silence_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def astuple(self):
+        return (self.threshold_db, self.min_sound_ms, self.lead_ms, self.trail_ms, self.max_pause_ms, self.fade_ms)
+
+
+class SilenceStats(C.Structure):
+    """xdtts_silence_stats: what the silence stage did to one utterance."""
+
+    _fields_ = [("n_in", C.c_uint32), ("n_out", C.c_uint32), ("lead_cut", C.c_uint32), ("trail_cut", C.c_uint32), ("pause_cut", C.c_uint32),
+                ("n_cuts", C.c_uint32), ("peak", C.c_float), ("any_sound", C.c_uint32)]
+
+    def astuple(self):
+        return (self.n_in, self.n_out, self.lead_cut, self.trail_cut, self.pause_cut, self.n_cuts, self.peak, self.any_sound)
+
+
 STREAM_F32, STREAM_PCM16, STREAM_ULAW, STREAM_ALAW = 0, 1, 2, 3
 _STREAM_DTYPE = {STREAM_F32: np.float32, STREAM_PCM16: np.dtype("<i2"), STREAM_ULAW: np.uint8, STREAM_ALAW: np.uint8}
 
@@ -374,6 +402,15 @@ SYMBOLS = {
     "xdtts_compressor_level": (_I32, [_VP, _SZ, _VP]),
     "xdtts_compressor_envelope": (_I32, [_VP, _SZ, _I32, _VP, _VP]),
     "xdtts_compressor_reference": (_I32, [_VP, _SZ, _I32, _VP, _VP, _VP]),
+    "xdtts_silence_default": (None, [_VP]),
+    "xdtts_griffinlim_set_silence": (_I32, [_VP, _VP]),
+    "xdtts_griffinlim_get_silence": (_I32, [_VP, _VP, C.POINTER(_I32)]),
+    "xdtts_griffinlim_last_silence": (_I32, [_VP, _VP, _SZ, C.POINTER(_SZ)]),
+    "xdtts_griffinlim_trim": (_I32, [_VP, _VP, _SZ, _I32, _VP, _VP, _VP]),
+    "xdtts_griffinlim_trim_batch": (_I32, [_VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
+    "xdtts_silence_plan": (_I32, [_I32, _VP] + [C.POINTER(_I32)] * 6 + [C.POINTER(C.c_float)]),
+    "xdtts_silence_keep": (_I32, [_VP, _SZ, _I32, _VP, _VP]),
+    "xdtts_silence_reference": (_I32, [_VP, _SZ, _I32, _VP, _VP, _VP]),
     "xdtts_griffinlim_free": (None, [_VP]),
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
@@ -1373,6 +1410,46 @@ class GriffinLim:
             _check(lib.xdtts_griffinlim_compress_batch(self._h, ip, ns, n, int(rate), C.byref(compressor), op, stats))
         return outs, [stats[i] for i in range(n)]
 
+    # -- silence: edge silence trimmed, pauses capped; the last stage of the delivery chain ----
+    def set_silence(self, silence=None):
+        """The handle's silence stage from now on: a Silence, or None for off (the default).  It runs behind the level stage on
+        every entry that delivers an utterance, which then returns n_out samples; last_silence() has the stats of each."""
+        _check(lib.xdtts_griffinlim_set_silence(self._h, _opt_ref(silence)))
+
+    def get_silence(self):
+        """The Silence that is set, or None where the stage is off."""
+        s, on = Silence(), C.c_int32()
+        _check(lib.xdtts_griffinlim_get_silence(self._h, C.byref(s), C.byref(on)))
+        return s if on.value else None
+
+    def last_silence(self):
+        """[SilenceStats] of the last delivering call, in the caller's order; [] unless the stage is set."""
+        n = C.c_size_t()
+        _check(lib.xdtts_griffinlim_last_silence(self._h, None, 0, C.byref(n)))
+        out = (SilenceStats * max(n.value, 1))()
+        _check(lib.xdtts_griffinlim_last_silence(self._h, out, n.value, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
+    def trim(self, audio, rate, silence):
+        """The stage alone on `audio`, whatever the handle's settings: (out[:n_out], SilenceStats), the bits of silence_reference()."""
+        outs, stats = self.trim_batch([audio], rate, silence)
+        return outs[0], stats[0]
+
+    def trim_batch(self, audios, rate, silence):
+        """The ragged stage: one set of launches for all audios, every output and struct the single call's bit for bit."""
+        xs = [np.ascontiguousarray(a, dtype=np.float32).ravel() for a in audios]
+        n = len(xs)
+        outs = [np.empty(x.size, dtype=np.float32) for x in xs]
+        stats = (SilenceStats * max(n, 1))()
+        ip = (C.c_void_p * max(n, 1))(*[x.ctypes.data for x in xs])
+        op = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        ns = (C.c_size_t * max(n, 1))(*[x.size for x in xs])
+        if n == 1:
+            _check(lib.xdtts_griffinlim_trim(self._h, ip[0], ns[0], int(rate), C.byref(silence), op[0], stats))
+        else:
+            _check(lib.xdtts_griffinlim_trim_batch(self._h, ip, ns, n, int(rate), C.byref(silence), op, stats))
+        return [o[:stats[i].n_out] for i, o in enumerate(outs)], [stats[i] for i in range(n)]
+
     # -- stream: a sequence joined with its gaps, faded, levelled and encoded on the device ----
     def join(self, audios, gaps=None, rate=SAMPLE_RATE, opts=None, guard=0):
         """xdtts_griffinlim_join: the stage alone on the caller's audios (fp32, each read where it lies: a view's address decides
@@ -1581,6 +1658,35 @@ def compressor_reference(audio, rate, compressor):
     _check(lib.xdtts_compressor_reference(_ptr(x) if x.size else None, x.size, int(rate), C.byref(compressor), _ptr(out) if x.size else None,
                                           C.byref(st)))
     return out, st
+
+
+def silence_plan(rate, silence):
+    """xdtts_silence_plan (host arithmetic): {"W", "min_w", "lead_w", "trail_w", "pause_w", "fade", "tfac"} -- the window in
+    samples, the settings in windows, the fade in samples, and the threshold's factor (a float32)."""
+    v = [C.c_int32() for _ in range(6)]
+    t = C.c_float()
+    _check(lib.xdtts_silence_plan(int(rate), C.byref(silence), *[C.byref(x) for x in v], C.byref(t)))
+    d = dict(zip(("W", "min_w", "lead_w", "trail_w", "pause_w", "fade"), (x.value for x in v)))
+    d["tfac"] = np.float32(t.value)
+    return d
+
+
+def silence_keep(audio, rate, silence):
+    """xdtts_silence_keep: the per-window decisions, uint8 [ceil(n / W)] (host arithmetic)."""
+    x = np.ascontiguousarray(audio, dtype=np.float32).ravel()
+    W = int(rate) // 200
+    keep = np.zeros(max((x.size + W - 1) // max(W, 1), 1), dtype=np.uint8)
+    _check(lib.xdtts_silence_keep(_ptr(x) if x.size else None, x.size, int(rate), C.byref(silence), _ptr(keep)))
+    return keep
+
+
+def silence_reference(audio, rate, silence):
+    """xdtts_silence_reference: the definition as serial plain C++ on the host: (out[:n_out], SilenceStats)."""
+    x = np.ascontiguousarray(audio, dtype=np.float32).ravel()
+    out = np.empty(max(x.size, 1), dtype=np.float32)
+    st = SilenceStats()
+    _check(lib.xdtts_silence_reference(_ptr(x) if x.size else None, x.size, int(rate), C.byref(silence), _ptr(out), C.byref(st)))
+    return out[:st.n_out].copy(), st
 
 
 def timbre_noise_bits(seed, frame, bin):

@@ -451,6 +451,124 @@ xdtts_status xdtts_griffinlim_compress(xdtts_griffinlim *g, const float *audio, 
   return xdtts_griffinlim_compress_batch(g, &audio, &n, 1, rate, c, &out, stats);
 }
 
+// ---- silence: edge silence trimmed, pauses capped, behind the level stage (silence_plan.h, silence.hip) -------------------------
+
+static_assert(sizeof(xdtts_silence) == sizeof(Silence) && offsetof(xdtts_silence, fade_ms) == offsetof(Silence, fade_ms),
+              "xdtts_silence and Silence share one layout");
+static_assert(sizeof(xdtts_silence_stats) == sizeof(SilenceStats) && offsetof(xdtts_silence_stats, any_sound) == offsetof(SilenceStats, any_sound),
+              "xdtts_silence_stats and SilenceStats share one layout");
+
+// the checked setting (null is an error here: the entry that takes "off" looks at the pointer first)
+static Silence silence_checked(const xdtts_silence *s) {
+  if (!s) fail(XDTTS_ERR_BAD_ARG, "silence: null settings");
+  Silence v;
+  std::memcpy(&v, s, sizeof v);
+  bad_arg_if(silence_check(v));
+  return v;
+}
+
+void xdtts_silence_default(xdtts_silence *s) {
+  if (!s) return;
+  const Silence d = silence_default();
+  std::memcpy(s, &d, sizeof d);
+}
+
+xdtts_status xdtts_silence_plan(int32_t rate, const xdtts_silence *s, int32_t *W, int32_t *min_w, int32_t *lead_w, int32_t *trail_w,
+                                int32_t *pause_w, int32_t *fade, float *tfac) {
+  return guard([&] {
+    const Silence v = silence_checked(s);
+    bad_arg_if(silence_rate_check(rate));
+    const SilPlan p = silence_plan(v, rate);
+    if (W) *W = p.W;
+    if (min_w) *min_w = p.min_w;
+    if (lead_w) *lead_w = p.lead_w;
+    if (trail_w) *trail_w = p.trail_w;
+    if (pause_w) *pause_w = p.pause_w;
+    if (fade) *fade = p.fade;
+    if (tfac) *tfac = p.tfac;
+  });
+}
+
+xdtts_status xdtts_silence_keep(const float *audio, size_t n, int32_t rate, const xdtts_silence *s, uint8_t *keep) {
+  return guard([&] {
+    const Silence v = silence_checked(s);
+    bad_arg_if(silence_args_check(v, rate, n));
+    if (!audio || !keep) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    silence_keep(audio, n, silence_plan(v, rate), keep);
+  });
+}
+
+xdtts_status xdtts_silence_reference(const float *audio, size_t n, int32_t rate, const xdtts_silence *s, float *out, xdtts_silence_stats *stats) {
+  return guard([&] {
+    const Silence v = silence_checked(s);
+    bad_arg_if(silence_args_check(v, rate, n));
+    if (!audio || !out || audio == out) fail(XDTTS_ERR_BAD_ARG, "null argument (or out == audio: the stage works out of place)");
+    const SilenceStats st = silence_reference(audio, n, rate, v, out);
+    if (stats) std::memcpy(stats, &st, sizeof st);
+  });
+}
+
+xdtts_status xdtts_griffinlim_set_silence(xdtts_griffinlim *g, const xdtts_silence *s) {
+  return guard([&] {
+    Silence v = silence_default();
+    if (s) v = silence_checked(s);  // the fields first: reported without a handle
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->dl.sil = v;
+    g->dl.sil_set = s != nullptr;
+  });
+}
+
+xdtts_status xdtts_griffinlim_get_silence(const xdtts_griffinlim *g, xdtts_silence *s, int32_t *on) {
+  return guard([&] {
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (s) std::memcpy(s, &g->dl.sil, sizeof g->dl.sil);
+    if (on) *on = g->dl.sil_set ? 1 : 0;
+  });
+}
+
+xdtts_status xdtts_griffinlim_last_silence(const xdtts_griffinlim *g, xdtts_silence_stats *out, size_t cap, size_t *n) {
+  return last_stats_out(g, g ? &g->dl.last_sil : nullptr, false, out, cap, n);
+}
+
+// The stage alone, single call and ragged batch: the audios one behind the other on the device, the three launches of
+// launch_silence out of place (the single call passes its record by value, the batch uploads the table), the full-length rows
+// and the stats back: outs[u] holds n[u] floats, of which stats[u].n_out are the output.  last_timings: ms[0] = the stage alone.
+xdtts_status xdtts_griffinlim_trim_batch(xdtts_griffinlim *g, const float *const *audios, const size_t *n, int32_t n_utt, int32_t rate,
+                                         const xdtts_silence *s, float *const *outs, xdtts_silence_stats *stats) {
+  return guard([&] {
+    const Silence v = silence_checked(s);
+    if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    if (!n) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    size_t tot = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      const std::string msg = silence_args_check(v, rate, n[u]);
+      if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "utterance %d: %s", u, msg.c_str());
+      tot += n[u];
+      if (tot > (size_t)0x7fffffff) fail(XDTTS_ERR_BAD_ARG, "batch too large: more than 2^31 - 1 samples");
+    }
+    if (!g || !audios || !outs || !stats) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    for (int u = 0; u < n_utt; ++u)
+      if (!audios[u] || !outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null audio / out", u);
+    DeliveryStages ds;
+    ds.rate = rate;
+    ds.sil = true;
+    ds.sil_plan = silence_plan(v, rate);
+    std::lock_guard<std::mutex> lk(g->mu);
+    stage_hook(g, ds, audios, n, n_utt, outs, [&](Delivery &dl) {
+      dl.trim(dl.rs_in.p, 0, n_utt);
+      return dl.sil_out.p;
+    });
+    std::memcpy(stats, g->dl.sil_host.p, (size_t)n_utt * sizeof(xdtts_silence_stats));
+  });
+}
+
+xdtts_status xdtts_griffinlim_trim(xdtts_griffinlim *g, const float *audio, size_t n, int32_t rate, const xdtts_silence *s, float *out,
+                                   xdtts_silence_stats *stats) {
+  return xdtts_griffinlim_trim_batch(g, &audio, &n, 1, rate, s, &out, stats);
+}
+
 // ---- stream: the sequence joined with its gaps, faded, levelled, encoded (stream_plan.h, stream.hip) ----------------------------
 
 static_assert(sizeof(xdtts_stream_opts) == sizeof(StreamOpts) && offsetof(xdtts_stream_opts, fade) == offsetof(StreamOpts, fade),

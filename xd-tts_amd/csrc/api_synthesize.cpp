@@ -107,6 +107,14 @@ struct DocRun {
     g->sink.dst = g->st_src.p + src0;
     g->sink.unlevelled = o.level == 1;
   }
+  // behind utterance u's collect, in front of the next place(): the silence stage decided on the device that u delivers
+  // n_out <= N samples -- its record takes n_out, and the stream goes on behind them (the staging buffer keeps room for N)
+  void trimmed(int u, size_t n_out) {
+    if (n_out >= n[(size_t)u]) return;
+    g->st_tab_host[(size_t)u].n = (int32_t)n_out;
+    n[(size_t)u] = n_out;
+    at = off[(size_t)u] + n_out + gap(u + 1);
+  }
   // behind the last collect: the level-1 measurement if asked for, ONE k_stream_join launch, ONE copy to the host
   void finish() {
     g->sink = xdtts_griffinlim::StreamSink();
@@ -204,6 +212,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
         // the frame loop of u has drained, and it waited for the vocoder of u - 1: collect that audio now
         if (u > 0) {
           gl_collect(g, total[u - 1], audio_host[u - 1], &audio_out[u - 1], &n_samples[u - 1], pros ? &pros[u - 1] : nullptr);
+          if (doc) doc->trimmed(u - 1, n_samples[u - 1]);
           add_gl();
         }
         if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * total[u]);
@@ -213,6 +222,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
         gl_enqueue_from_device_mel(g, h->mel_dev.p, total[u], audio_host[u], pros ? &pros[u] : nullptr);
       }
       gl_collect(g, total[n_utt - 1], audio_host[n_utt - 1], &audio_out[n_utt - 1], &n_samples[n_utt - 1], pros ? &pros[n_utt - 1] : nullptr);
+      if (doc) doc->trimmed(n_utt - 1, n_samples[n_utt - 1]);
       add_gl();
       if (doc) doc->finish();
       h->finish_timings();  // (stream sync: every mel has landed; last_ms = the last utterance's phases)

@@ -1,11 +1,12 @@
 // delivery.cpp -- the delivery chain's state and its one runner (delivery.h): per-rate tables, buffers, the record tables' uploads
-// and the launches of resample -> compressor -> output normalisation | loudness (-> limiter), for a single request and a batch.
+// and the launches of resample -> compressor -> output normalisation | loudness (-> limiter) -> silence, for a single request and
+// a batch.
 #include "delivery.h"
 
 namespace xdtts {
 
 static_assert(sizeof(NormUtt) == sizeof(int2) && sizeof(xdtts_loudness) == sizeof(LoudResult) && sizeof(xdtts_limiter_stats) == sizeof(LimiterStats) &&
-                  sizeof(xdtts_compressor_stats) == sizeof(CompressorStats), "the records and stats of the kernels are the boundary's, byte for byte");
+                  sizeof(xdtts_compressor_stats) == sizeof(CompressorStats) && sizeof(xdtts_silence_stats) == sizeof(SilenceStats), "the records and stats of the kernels are the boundary's, byte for byte");
 
 void Delivery::resample_prepare(int rate) {
   if (rs_table.rate == rate && rs_rows.p) return;
@@ -45,6 +46,16 @@ void Delivery::limiter_prepare(int rate, int lookahead_us) {
   lim_H = H;
 }
 
+void Delivery::silence_prepare(const SilPlan &p) {
+  if (p.fade == 0 || (p.fade == sil_fade && sil_fade_tab.p)) return;
+  HIP_CHECK(hipStreamSynchronize(stream));  // (a launch that reads the gains of another fade may be in flight)
+  sil_fade = 0;
+  sil_fade_host.resize((size_t)p.fade);
+  silence_fade_table(p, sil_fade_host.data());
+  sil_fade_tab.upload(sil_fade_host.data(), sil_fade_host.size(), stream);
+  sil_fade = p.fade;
+}
+
 void Delivery::size(const DeliveryPlan &p) {
   const DeliveryStages &s = p.stages;
   const size_t n_utt = std::max<size_t>(p.dn.size(), 1);
@@ -81,6 +92,20 @@ void Delivery::size(const DeliveryPlan &p) {
     comp_host.reserve(n_utt);
   }
   if (s.norm_mode) norm_parts.alloc((size_t)GLN_SCRATCH * n_utt);
+  if (s.sil) {
+    silence_prepare(s.sil_plan);
+    const size_t floats = std::max<size_t>(p.lim_extent, 1), wins = std::max<size_t>(p.sil_wins, 1), tiles = std::max<size_t>(p.sil_tiles, 1);
+    if (floats > sil_out.n || wins > sil_pw.n || tiles > sil_tpk.n || n_utt > sil_stats.n)
+      HIP_CHECK(hipStreamSynchronize(stream));  // (growing frees what a launch may touch)
+    sil_out.alloc(floats);
+    sil_pw.alloc(wins);
+    sil_wl.alloc(wins);
+    sil_wr.alloc(wins);
+    sil_woff.alloc(wins);
+    sil_tpk.alloc(tiles);
+    sil_stats.alloc(n_utt);
+    sil_host.reserve(n_utt);
+  }
 }
 
 void Delivery::prepare_one(const DeliveryStages &s, size_t n) {
@@ -101,6 +126,7 @@ void Delivery::prepare(DeliveryPlan p, bool with_tables) {
   if (t.loud) loud_tab.upload(plan.loud.data(), plan.loud.size(), stream);
   if (t.lim_us) lim_tab.upload(plan.lim.data(), plan.lim.size(), stream);
   if (t.comp) comp_tab.upload(plan.comp.data(), plan.comp.size(), stream);
+  if (t.sil) sil_tab.upload(plan.sil.data(), plan.sil.size(), stream);
   if (t.any()) HIP_CHECK(hipStreamSynchronize(stream));  // the tables are up: the plan's vectors are no upload's source any more
 }
 
@@ -135,9 +161,24 @@ void Delivery::limit(const float *x, int r0, int count, const LimJob &job) {
                lim_stats.p + r0, stream);
 }
 
+void Delivery::trim(const float *x, int r0, int count) {
+  const DeliveryExtents e = delivery_extents(plan, r0, count);
+  const SilPlan &sp = plan.stages.sil_plan;
+  launch_silence(x, sil_out.p, tables ? sil_tab.p + r0 : nullptr, count, e.stile0, e.stiles, tables ? SilUtt{} : plan.sil[(size_t)r0], sp,
+                 sp.fade > 0 ? sil_fade_tab.p : nullptr, SilBufs{sil_pw.p, sil_tpk.p, sil_wl.p, sil_wr.p, sil_woff.p}, sil_stats.p + r0, stream);
+}
+
 // THE delivery order: the output rate, then the compressor in place on what is delivered, then the level stage -- the output
-// normalisation, or with a target the loudness rule in its place, whose gain the limiter applies out of place where it is on.
+// normalisation, or with a target the loudness rule in its place, whose gain the limiter applies out of place where it is on --
+// and behind them all the silence stage, out of place, on what the level stage delivered.
 float *Delivery::run(float *loop_audio, int r0, int count, float rms_target) {
+  float *x = level(loop_audio, r0, count, rms_target);
+  if (count <= 0 || !plan.stages.sil) return x;
+  trim(x, r0, count);
+  return sil_out.p;
+}
+
+float *Delivery::level(float *loop_audio, int r0, int count, float rms_target) {
   const DeliveryStages &s = plan.stages;
   float *x = s.resampled ? audio_rs.p : loop_audio;
   if (count <= 0) return x;
@@ -163,6 +204,7 @@ void Delivery::fetch_stats(int r0, int count, hipStream_t s) {
   if (st.loud) HIP_CHECK(hipMemcpyAsync(loud_host.p + r0, loud_res.p + r0, (size_t)count * sizeof(LoudResult), hipMemcpyDeviceToHost, s));
   if (st.lim_us) HIP_CHECK(hipMemcpyAsync(lim_host.p + r0, lim_stats.p + r0, (size_t)count * sizeof(LimiterStats), hipMemcpyDeviceToHost, s));
   if (st.comp) HIP_CHECK(hipMemcpyAsync(comp_host.p + r0, comp_stats.p + r0, (size_t)count * sizeof(CompressorStats), hipMemcpyDeviceToHost, s));
+  if (st.sil) HIP_CHECK(hipMemcpyAsync(sil_host.p + r0, sil_stats.p + r0, (size_t)count * sizeof(SilenceStats), hipMemcpyDeviceToHost, s));
 }
 
 void Delivery::push_last(size_t r) {
@@ -174,6 +216,7 @@ void Delivery::push_last(size_t r) {
   if (st.loud) push(last_loud, loud_host.p + r);
   if (st.lim_us) push(last_lim, lim_host.p + r);
   if (st.comp) push(last_comp, comp_host.p + r);
+  if (st.sil) push(last_sil, sil_host.p + r);
 }
 
 }  // namespace xdtts

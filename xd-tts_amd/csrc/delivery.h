@@ -1,6 +1,6 @@
 // delivery.h -- the delivery chain behind the Griffin-Lim loop as one member of the vocoder handle: its settings, the per-rate
 // tables, scratch, record tables and pinned stats of the stages (resample.hip, compressor.hip, loudness.hip, limiter.hip, the
-// output normalisation of griffinlim.hip), and the ONE runner every request path goes through.  The arithmetic is delivery_plan.h's.
+// output normalisation of griffinlim.hip, silence.hip), and the ONE runner every request path goes through.  The arithmetic is delivery_plan.h's.
 #pragma once
 #include "kernels.h"
 #include "runtime.h"
@@ -49,6 +49,9 @@ struct Delivery {
   // k_loud_scale's place, out of place into lim_out
   bool limiter_on() const { return lim_us != 0 && loudness_on() && !std::isnan(loud_ceiling); }
   bool compressor_on() const { return comp_set && !compressor_is_identity(comp); }
+  Silence sil = silence_default();   // the silence stage: the last one, out of place into sil_out
+  bool sil_set = false;
+  bool silence_on() const { return sil_set; }
   // What a request path delivers for n samples of the loop: N' at the handle's rate, n at 22050.
   size_t delivered(size_t n) const { return resample_n_out(out_plan, n); }
   // The stages of a request path under these settings; norm_mode: xdtts_griffinlim_opts.output_normalise; unlevelled: a document
@@ -56,7 +59,7 @@ struct Delivery {
   DeliveryStages stages(int norm_mode, bool unlevelled) const {
     const bool c = compressor_on();
     return delivery_stages(out_rate, out_plan, c, c ? compressor_plan(comp, out_rate) : CompPlan{}, loudness_on(), limiter_on() ? lim_us : 0,
-                           norm_mode, unlevelled);
+                           norm_mode, unlevelled, silence_on(), silence_on() ? silence_plan(sil, out_rate) : SilPlan{});
   }
 
   // ---- per-rate tables: functions of the rate (the limiter's: of H) alone, built on the host once per (handle, rate) and kept on
@@ -72,6 +75,10 @@ struct Delivery {
   void resample_prepare(int rate);  // (checked by the caller, not the identity)
   void loudness_prepare(int rate);
   void limiter_prepare(int rate, int lookahead_us);  // ... and the loudness table's taps
+  int sil_fade = 0;                 // the fade whose gains are on the device; 0 = none yet
+  std::vector<float> sil_fade_host;
+  DevBuf<float> sil_fade_tab;
+  void silence_prepare(const SilPlan &p);  // (the gains are a function of plan.fade alone)
 
   // ---- scratch: grows with the request and stays; growing drains the stream first ----
   DevBuf<float> rs_in, audio_rs;  // the stage hooks' input; the resampled audio
@@ -83,9 +90,13 @@ struct Delivery {
   DevBuf<CompAgg> comp_agg;          // one per tile
   DevBuf<CompressorStats> comp_stats;  // one per utterance
   DevBuf<float> norm_parts;          // GLN_SCRATCH per utterance
+  DevBuf<float> sil_out, sil_pw, sil_tpk;  // the stage's output rows; one peak per window, one per tile
+  DevBuf<int> sil_wl, sil_wr, sil_woff;    // per window: the scans' scratch, the output offset
+  DevBuf<SilenceStats> sil_stats;    // one per utterance
   PinnedArray<LoudResult> loud_host;  // the structs travel back behind the audio
   PinnedArray<LimiterStats> lim_host;
   PinnedArray<CompressorStats> comp_host;
+  PinnedArray<SilenceStats> sil_host;
 
   // ---- the request in flight: its plan (whose vectors are the sources of the record tables' uploads; prepare() returns behind
   // them, so the next prepare() may replace the plan at any time) and the tables on the device ----
@@ -96,6 +107,7 @@ struct Delivery {
   DevBuf<LoudUtt> loud_tab;
   DevBuf<LimUtt> lim_tab;
   DevBuf<NormUtt> norm_tab;
+  DevBuf<SilUtt> sil_tab;
   // Buffers and per-rate tables for p's stages, in front of the launches.
   void size(const DeliveryPlan &p);
   // size(p), p becomes the plan in place and -- with_tables -- its records go up on the stream, which is drained behind them.
@@ -105,24 +117,32 @@ struct Delivery {
   // 2^31 - 1 resampled samples, 2^28 or more into the loudness stage)
   void prepare_one(const DeliveryStages &s, size_t n);
   // The stages of rows r0 .. r0 + count of the plan in place, in the fixed order, on the stream: loop_audio (the loop's, where the
-  // plan's bases point) -> the delivered rows, which lie at dbase of the returned buffer (loop_audio, audio_rs or lim_out).
+  // plan's bases point) -> the delivered rows, which lie at dbase of the returned buffer (loop_audio, audio_rs, lim_out or
+  // sil_out).  Behind the silence stage a row holds out_samples() samples, known once its stats have travelled back.
   float *run(float *loop_audio, int r0, int count, float rms_target);
+  float *level(float *loop_audio, int r0, int count, float rms_target);  // ... everything in front of the silence stage
   // ... the stages one by one, for run(), the level-1 stream and the hooks of a stage alone
   void resample(const float *src, float *dst, int r0, int count);
   void compress(const float *x, float *out, int r0, int count);
   void measure(const float *x, int r0, int count, bool to_target);  // -> loud_res[r0 ..]; to_target: the gain of the settings, else 1
   void limit(const float *x, int r0, int count, const LimJob &job);  // -> lim_out, lim_stats[r0 ..]
+  void trim(const float *x, int r0, int count);                      // -> sil_out, sil_stats[r0 ..]
   // the job of the settings reading loud_res + r0 (res_from_loudness), or of the stage alone with (gain0, ceil)
   LimJob limiter_job(bool res_from_loudness, int r0, double gain0, double ceil) const;
   // the stats of rows r0 .. r0 + count of the stages that ran -> the pinned arrays, on s
   void fetch_stats(int r0, int count, hipStream_t s);
+  // What utterance u (the caller's order) of the plan in place delivers: n_out of the silence stage where it ran -- behind a
+  // drained fetch_stats -- else dn.
+  size_t out_samples(size_t u) const { return plan.stages.sil ? (size_t)sil_host.p[plan.tab_pos[u]].n_out : (size_t)plan.dn[u]; }
 
-  // ---- what the last delivering call measured, in the caller's order (xdtts_griffinlim_last_loudness / _limiter / _compressor) ----
+  // ---- what the last delivering call measured, in the caller's order (xdtts_griffinlim_last_loudness / _limiter / _compressor /
+  // _silence) ----
   std::vector<xdtts_loudness> last_loud;
   std::vector<xdtts_limiter_stats> last_lim;
   std::vector<xdtts_compressor_stats> last_comp;
+  std::vector<xdtts_silence_stats> last_sil;
   void push_last(size_t r);  // row r of the last fetch_stats
-  void clear_last() { last_loud.clear(), last_lim.clear(), last_comp.clear(); }
+  void clear_last() { last_loud.clear(), last_lim.clear(), last_comp.clear(), last_sil.clear(); }
 };
 
 }  // namespace xdtts

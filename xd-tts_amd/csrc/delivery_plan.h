@@ -1,5 +1,5 @@
 // delivery_plan.h -- the host arithmetic of the delivery chain behind the Griffin-Lim loop: which stages run (resample, then
-// compressor, then output normalisation or loudness with or without the limiter), where every utterance's delivered samples
+// compressor, then output normalisation or loudness with or without the limiter, then the silence stage), where every utterance's delivered samples
 // lie, the per-utterance records of the stages' launches with their running workgroup numbers, the totals every buffer is
 // sized from, and the launch extents of a run of consecutive rows.  Plain host C++, no HIP: tests/delivery_plan_test.cpp drives
 // it on a machine without a GPU.
@@ -15,6 +15,7 @@
 #include "limiter_plan.h"
 #include "loudness_plan.h"
 #include "resample_plan.h"
+#include "silence_plan.h"
 
 namespace xdtts {
 
@@ -40,6 +41,12 @@ struct TileUtt {
 };
 using LimUtt = TileUtt;
 using CompUtt = TileUtt;
+// the silence stage's: n samples at x + src0 -> at most n samples at out + dst0; workgroups (SIL_TILE samples) tile0 .. index the
+// tile peaks, windows win0 .. the per-window scratch
+struct SilUtt {
+  long long src0, dst0;
+  int n, tile0, win0, pad;
+};
 // the output normaliser's: n samples from `first` (an int2 on the device)
 struct NormUtt {
   int first, n;
@@ -53,12 +60,15 @@ struct DeliveryStages {
   int lim_us = 0;     // the limiter's look-ahead, 0 = off
   int norm_mode = 0;  // the output normalisation's mode, 0 = off
   CompPlan comp_plan{};
-  bool any() const { return resampled || comp || loud || lim_us || norm_mode; }
+  bool sil = false;   // the silence stage, behind everything else
+  SilPlan sil_plan{};
+  bool any() const { return resampled || comp || loud || lim_us || norm_mode || sil; }
 };
 // lim_on needs loud_on (the limiter takes the place of the loudness stage's gain); the loudness rule takes the output
 // normalisation's place; unlevelled (a document at programme level takes its utterances so) switches both level stages off.
+// The silence stage depends on none of them.
 inline DeliveryStages delivery_stages(int rate, const ResamplePlan &rs, bool comp_on, const CompPlan &comp_plan, bool loud_on, int lim_us,
-                                      int norm_mode, bool unlevelled) {
+                                      int norm_mode, bool unlevelled, bool sil_on = false, const SilPlan &sil_plan = SilPlan{}) {
   DeliveryStages s;
   s.rate = rate;
   s.rs = rs;
@@ -68,6 +78,8 @@ inline DeliveryStages delivery_stages(int rate, const ResamplePlan &rs, bool com
   s.loud = loud_on && !unlevelled;
   s.lim_us = s.loud ? lim_us : 0;
   s.norm_mode = s.loud || unlevelled ? 0 : norm_mode;
+  s.sil = sil_on;
+  s.sil_plan = sil_plan;
   return s;
 }
 
@@ -83,9 +95,10 @@ struct DeliveryPlan {
   std::vector<LoudUtt> loud;
   std::vector<LimUtt> lim;
   std::vector<NormUtt> norm;
+  std::vector<SilUtt> sil;
   // what the buffers are sized from: resampled samples, loudness groups, limiter tiles, compressor tiles, the floats the limiter's
-  // output spans (its rows lie where the delivered ones do)
-  size_t rs_total = 0, groups = 0, lim_tiles = 0, comp_tiles = 0, lim_extent = 0;
+  // output spans (its rows lie where the delivered ones do, and so do the silence stage's), the silence stage's tiles and windows
+  size_t rs_total = 0, groups = 0, lim_tiles = 0, comp_tiles = 0, lim_extent = 0, sil_tiles = 0, sil_wins = 0;
 };
 
 // base[u] for utterances back to back
@@ -121,7 +134,7 @@ inline DeliveryPlan delivery_plan(const DeliveryStages &s, const std::vector<siz
     p.lim_extent = std::max(p.lim_extent, (size_t)p.dbase[u] + (size_t)p.dn[u]);
   }
   p.rs_total = rtot;
-  int blk = 0, grp = 0, seg = 0, sb = 0, tile = 0, ctile = 0;
+  int blk = 0, grp = 0, seg = 0, sb = 0, tile = 0, ctile = 0, stile = 0, swin = 0;
   for (int u : order) {
     const long long d0 = p.dbase[(size_t)u];
     const int dn = p.dn[(size_t)u];
@@ -141,12 +154,17 @@ inline DeliveryPlan delivery_plan(const DeliveryStages &s, const std::vector<siz
       p.lim.push_back({d0, d0, dn, tile});
       tile += (int)limiter_tiles((size_t)dn);
     }
+    if (s.sil) {
+      p.sil.push_back({d0, d0, dn, stile, swin, 0});
+      stile += (int)silence_tiles((size_t)dn);
+      swin += (int)silence_windows((size_t)dn, s.sil_plan.W);
+    }
     if (s.resampled) {
       p.rs.push_back({base[(size_t)u], d0, (int)n[(size_t)u], dn, blk, 0});
       blk += (dn + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK;
     }
   }
-  p.groups = (size_t)grp, p.lim_tiles = (size_t)tile, p.comp_tiles = (size_t)ctile;
+  p.groups = (size_t)grp, p.lim_tiles = (size_t)tile, p.comp_tiles = (size_t)ctile, p.sil_tiles = (size_t)stile, p.sil_wins = (size_t)swin;
   return p;
 }
 inline std::vector<int> delivery_identity(size_t n) {
@@ -157,7 +175,7 @@ inline std::vector<int> delivery_identity(size_t n) {
 
 // One launch per stage over rows r0 .. r0 + count: each stage's first workgroup and its workgroups in all, and the longest row
 struct DeliveryExtents {
-  int blk0 = 0, blocks = 0, grp0 = 0, groups = 0, tile0 = 0, tiles = 0, ctile0 = 0, ctiles = 0, n_max = 0;
+  int blk0 = 0, blocks = 0, grp0 = 0, groups = 0, tile0 = 0, tiles = 0, ctile0 = 0, ctiles = 0, n_max = 0, stile0 = 0, stiles = 0;
 };
 inline DeliveryExtents delivery_extents(const DeliveryPlan &p, int r0, int count) {
   DeliveryExtents e;
@@ -167,6 +185,7 @@ inline DeliveryExtents delivery_extents(const DeliveryPlan &p, int r0, int count
   if (!p.loud.empty()) e.grp0 = p.loud[a].grp0, e.groups = p.loud[b].grp0 + (int)loudness_groups((size_t)p.loud[b].n) - e.grp0;
   if (!p.lim.empty()) e.tile0 = p.lim[a].tile0, e.tiles = p.lim[b].tile0 + (int)limiter_tiles((size_t)p.lim[b].n) - e.tile0;
   if (!p.comp.empty()) e.ctile0 = p.comp[a].tile0, e.ctiles = p.comp[b].tile0 + (int)compressor_tiles((size_t)p.comp[b].n) - e.ctile0;
+  if (!p.sil.empty()) e.stile0 = p.sil[a].tile0, e.stiles = p.sil[b].tile0 + (int)silence_tiles((size_t)p.sil[b].n) - e.stile0;
   for (size_t r = a; r <= b; ++r) e.n_max = std::max(e.n_max, p.norm[r].n);
   return e;
 }

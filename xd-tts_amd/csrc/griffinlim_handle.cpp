@@ -598,7 +598,7 @@ static void collect_run(xdtts_griffinlim *g, const GlBufs &b, const float *phase
   const size_t N = (size_t)g->hop * (size_t)(b.F - 1);
   if (deliver) g->dl.push_last(0);
   *audio = host.release();
-  *n_samples = deliver ? g->dl.delivered(N) : N;
+  *n_samples = deliver ? g->dl.out_samples(0) : N;  // (dn, or what the silence stage decided on the device: its stats have landed)
 }
 
 // The loop alone on a state the caller has put in place (xdtts_griffinlim_infer_linear), then the audio in a pinned host buffer.
@@ -929,7 +929,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     }
     for (int u = 0; u < n_utt; ++u) {
       audios[u] = out[(size_t)u].release();
-      n_samples[u] = (size_t)dn[(size_t)u];
+      n_samples[u] = g->dl.out_samples((size_t)u);  // (dn[u], or n_out of the silence stage: the buffer holds dn[u] floats)
       g->dl.push_last((size_t)dp.tab_pos[(size_t)u]);
     }
     return;

@@ -469,6 +469,20 @@ void launch_limit(const float *x, float *out, const LimUtt *tab_dev, int count, 
 void launch_compress(const float *x, float *out, const CompUtt *tab_dev, int count, int tile_base, int n_tiles, const CompUtt &one,
                      const CompPlan &plan, CompAgg *agg, CompressorStats *stats, hipStream_t s);
 
+// ---- silence (silence.hip): edge silence trimmed and pauses capped, the last stage of the delivery chain (include/xdtts.h, silence_plan.h) ----
+// One utterance of a launch: n samples at x + src0 -> n_out <= n samples at out + dst0, out of place (SilUtt: delivery_plan.h).
+// Its workgroups (SIL_TILE samples each) are tile0 .. of the table's numbering and its windows win0 .., ascending, the utterances
+// back to back.  Three launches: the windows' peaks (n_tiles workgroups, the first being tile tile_base; tab_dev == nullptr: the
+// one utterance `one`), the plan (one workgroup per utterance), the gather (n_tiles workgroups).  The scratch holds one entry
+// per window (pw, wl, wr, woff) and per tile (tpk) of the WHOLE table; stats[u] belongs to record u.  fade_tab: plan.fade gains
+// on the device (null where fade is 0).  n_out is decided on the device: nothing waits for the host.
+struct SilBufs {
+  float *pw, *tpk;
+  int *wl, *wr, *woff;
+};
+void launch_silence(const float *x, float *out, const SilUtt *tab_dev, int count, int tile_base, int n_tiles, const SilUtt &one,
+                    const SilPlan &plan, const float *fade_tab, const SilBufs &b, SilenceStats *stats, hipStream_t s);
+
 // ---- stream (stream.hip): utterances joined with their gaps into one stream, faded, levelled, encoded (include/xdtts.h) -------
 // ONE launch of k_stream_join: job.tab[0 .. n_utt) on the device, ascending off (stream_plan.h: StreamUtt), the utterances'
 // samples at job.src + src0; out = total * sample_bytes bytes, 16-byte aligned -- nothing at or behind that is written.
