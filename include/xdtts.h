@@ -248,7 +248,14 @@ xdtts_status xdtts_mel_filter_bank(float sample_rate, size_t n_fft, size_t n_mel
                                    float fmax_or_nan, float *out);
 
 /* GriffinLim::new(mel_basis, noverlap, power, iter, momentum) -- src/tacotron2/mod.rs:456.
- * n_fft = 2*(n_bins-1); hop = n_fft - noverlap. */
+ * n_fft = 2*(n_bins-1); hop = n_fft - noverlap.
+ * Accepted, anything else is XDTTS_ERR_BAD_ARG and *out stays null:
+ *   n_bins 513 and noverlap 768 (n_fft 1024, hop 256: what the framed-FFT kernels are built for)
+ *   mel_basis  n_mels x n_bins of full row rank, n_mels a positive multiple of 16 (a rank-deficient basis is refused by name)
+ *   power      finite and > 0          momentum   finite and >= 0 (0: plain Griffin-Lim)
+ *   iters      any count, 0 included (0: the inverse STFT of the magnitude under the initial phase)
+ * The entries that take a mel (n_mels x F) refuse one whose row count is not the basis's.  Every xdtts_synthesize* entry
+ * hands the vocoder the model's 80-row mel where it lies on the device, and so refuses a handle whose n_mels is not 80. */
 xdtts_status xdtts_griffinlim_new(const float *mel_basis, size_t n_mels, size_t n_bins,
                                   size_t noverlap, float power, size_t iters, float momentum,
                                   int32_t device_id, xdtts_griffinlim **out);

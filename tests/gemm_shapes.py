@@ -71,7 +71,12 @@ def plan(site, M, batch=1, force_tile=0, force_nosplit=False):
     """What launch_gemm_nt / gemm_splitk_plan choose for `batch` items of M rows at a call site, or, with M a sequence of
     per-item row counts, for that ragged batch (the post-net's: g.M = the longest item, Mz the items).
     force_tile / force_nosplit: XDTTS_GEMM_TILE / XDTTS_GEMM_SPLITK=1 of the forced-tile child process."""
-    s = SITES[site]
+    return plan_of(SITES[site], M, batch, force_tile, force_nosplit)
+
+
+def plan_of(s, M, batch=1, force_tile=0, force_nosplit=False):
+    """plan() for a site given by its dict (N, K, lda, split, tile) -- vocoder_params.py hands in the vocoder's sites at another
+    band count than 80."""
     N, K, lda = s["N"], s["K"], s["lda"]
     Mz = [M] * batch if isinstance(M, (int, np.integer)) else [int(m) for m in M]
     M, batch = max(Mz), len(Mz)
@@ -282,9 +287,9 @@ def chirps(n):
     return (y + 0.01 * rng.standard_normal(n)).astype(np.float32)
 
 
-def log_mel_chain(B, m, dtype, floor=1e-5):
-    """ln(max(B @ m^1.7, floor)) in `dtype`: the analysis chain behind the magnitude under the default conventions."""
-    mel = B.astype(dtype) @ (m.astype(dtype) ** dtype(1.7))
+def log_mel_chain(B, m, dtype, floor=1e-5, power=1.7):
+    """ln(max(B @ m^power, floor)) in `dtype`: the analysis chain behind the magnitude under the default conventions."""
+    mel = B.astype(dtype) @ (m.astype(dtype) ** dtype(power))
     assert mel.dtype == dtype
     return np.log(np.maximum(mel, dtype(floor)))
 

@@ -73,7 +73,9 @@ xdtts_status xdtts_griffinlim_new(const float *mel_basis, size_t n_mels, size_t 
     if (n_fft - noverlap != n_fft / 4)
       fail(XDTTS_ERR_BAD_ARG, "hop %zu unsupported: the framed-FFT kernels are built for hop = n_fft/4 = 256 (mod.rs:456)", n_fft - noverlap);
     if (n_mels % 16 != 0) fail(XDTTS_ERR_BAD_ARG, "n_mels %zu must be a multiple of 16", n_mels);
-    if (!(power > 0) || momentum < 0) fail(XDTTS_ERR_BAD_ARG, "bad power/momentum");
+    // (written so that a NaN fails each test: `momentum < 0` alone is false for it)
+    if (!(power > 0) || !std::isfinite(power)) fail(XDTTS_ERR_BAD_ARG, "power %g must be finite and > 0", (double)power);
+    if (!(momentum >= 0) || !std::isfinite(momentum)) fail(XDTTS_ERR_BAD_ARG, "momentum %g must be finite and >= 0", (double)momentum);
     device_id = select_device(device_id);
     auto g = std::make_unique<xdtts_griffinlim>();
     g->device = device_id;

@@ -9,6 +9,14 @@ using namespace xdtts;
 
 // ---- XdTts::infer (src/lib.rs:110-159) --------------------------------------------------------------
 
+// The two handles of every xdtts_synthesize* entry, before a lock is taken or anything is enqueued: one device, and a vocoder
+// whose basis has the model's N_MEL rows -- it reads the model's [N_MEL][F] mel where it lies in HBM as [n_mels][F] (fewer rows:
+// wrong audio; more: a read past the buffer).
+static void pair_check(const xdtts_tacotron2 *h, const xdtts_griffinlim *g) {
+  if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
+  if (g->n_mels != N_MEL) fail(XDTTS_ERR_BAD_ARG, "the vocoder's basis has %d mel bands, the model's mel has %d", g->n_mels, N_MEL);
+}
+
 // (pros == cont == null: xdtts_synthesize_ids; else the prosody stage between mel -> linear and the loop, fields checked by the caller)
 static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n, const size_t *splits,
                                    size_t n_splits, const xdtts_infer_opts *opts, const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **mel,
@@ -16,7 +24,7 @@ static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, cons
                                    const xdtts_pitch_target *tg = nullptr, const xdtts_prosody_contour *const *tc = nullptr) {
   return guard([&] {
     if (!h || !g || !mel || !n_frames || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
-    if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
+    pair_check(h, g);
     *mel = nullptr;
     *audio = nullptr;
     *n_frames = *n_samples = 0;
@@ -134,7 +142,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
                                         DocRun *doc = nullptr) {
   return guard([&] {
     if (!h || !g || !ids || !n_ids || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "null argument / no utterance");
-    if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
+    pair_check(h, g);
     for (int u = 0; u < n_utt; ++u) {
       audios[u] = nullptr;
       n_frames[u] = n_samples[u] = 0;
@@ -266,7 +274,7 @@ static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, co
                                      const xdtts_prosody_contour *const *tc = nullptr) {
   return guard([&] {
     if (!h || !g || !ids || !lens || !utt_chunks || !n_frames || !audios || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
-    if (h->device != g->device) fail(XDTTS_ERR_BAD_ARG, "tacotron2 and griffin-lim handles live on different devices");
+    pair_check(h, g);
     if (B <= 0 || n_utt <= 0 || t_stride <= 0) fail(XDTTS_ERR_BAD_ARG, "batch %d / utterances %d / stride %d out of range", B, n_utt, t_stride);
     long nchunks = 0;
     for (int u = 0; u < n_utt; ++u) {

@@ -89,26 +89,26 @@ __global__ __launch_bounds__(256) void k_gemm_nt(GemmArgs g) {
   float *C = g.C + (size_t)z * g.strideC + (g.ragged ? g.Cz[z] : 0);
   const float *R = g.R ? g.R + (size_t)z * g.strideR : nullptr;
 
-  // global -> LDS assignment: thread loads MT float4 of A and NT of W per slab (rows lr + 32 r)
-  const int lr = tid >> 3, lc = (tid & 7) * 4;
+  // this block's K range [kbeg, kbeg + KL): whole slabs per slice
+  const int kper = ((g.K + BK - 1) / BK + nks - 1) / nks * BK, kbeg = ks * kper, KL = min(g.K - kbeg, kper);
+  // global -> LDS assignment: thread loads MT float4 of A and NT of W per slab (rows lr + 32 r), columns lc .. lc + 3 of the slab.
+  // GEMM_FETCH loads in every slot of the pipeline and GEMM_STAGE masks: a lane whose columns lie outside the slice (the upper half
+  // of a 16-column last slab, a slab past the last) loads its columns of slab 0 instead.  Those exist when lc < KL; with KL = 16
+  // (a 16-band mel basis: K = 16) the lanes with lc >= 16 have no column in any slab, are masked throughout, and load from column
+  // 0 of the slice -- lcs, not lc, goes into the address, so that no lane forms one at or beyond column K of its row.
+  const int lr = tid >> 3, lc = (tid & 7) * 4, lcs = lc < KL ? lc : 0;
   bool a_ok[MT], b_ok[NT];
   const float *a_src[MT], *b_src[NT];
 #pragma unroll
   for (int r = 0; r < MT; ++r) {
     a_ok[r] = m0 + lr + 32 * r < M;
-    a_src[r] = A + (size_t)(a_ok[r] ? m0 + lr + 32 * r : M - 1) * g.lda + lc;
+    a_src[r] = A + (size_t)(a_ok[r] ? m0 + lr + 32 * r : M - 1) * g.lda + kbeg + lcs;
   }
 #pragma unroll
   for (int r = 0; r < NT; ++r) {
     b_ok[r] = n0 + lr + 32 * r < g.N;
-    b_src[r] = g.W + (size_t)(b_ok[r] ? n0 + lr + 32 * r : g.N - 1) * g.K + lc;
+    b_src[r] = g.W + (size_t)(b_ok[r] ? n0 + lr + 32 * r : g.N - 1) * g.K + kbeg + lcs;
   }
-  // this block's K range [kbeg, kbeg + KL): whole slabs per slice
-  const int kper = ((g.K + BK - 1) / BK + nks - 1) / nks * BK, kbeg = ks * kper, KL = min(g.K - kbeg, kper);
-#pragma unroll
-  for (int r = 0; r < MT; ++r) a_src[r] += kbeg;
-#pragma unroll
-  for (int r = 0; r < NT; ++r) b_src[r] += kbeg;
   const int nslab = (KL + BK - 1) / BK;
   const int fi = lane & 15, fg = lane >> 4;
   f32x4 acc[MT][NT];
