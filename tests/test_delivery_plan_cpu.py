@@ -51,7 +51,7 @@ def test_the_delivery_arithmetic_lives_in_the_header_alone():
         if name != "delivery_plan.h":
             assert not re.search(r"\bstruct (ResampleUtt|LoudUtt|TileUtt|LimUtt|CompUtt) \{", _read(os.path.join(CSRC, name))), name
     # the request paths and the boundary launch no delivery stage themselves: they go through Delivery
-    for name in ("griffinlim_handle.cpp", "api_griffinlim.cpp", "api_gl_magnitude.cpp", "api_gl_delivery.cpp", "api_synthesize.cpp"):
+    for name in ("griffinlim_handle.cpp", "magnitude.cpp", "api_griffinlim.cpp", "api_gl_magnitude.cpp", "api_gl_delivery.cpp", "api_synthesize.cpp"):
         src = _read(os.path.join(CSRC, name))
         for launch in ("launch_gl_output_normalise(", "launch_loudness_scale(", "launch_resample(", "launch_compress(", "launch_limit("):
             assert launch not in src, (name, launch)

@@ -2,7 +2,7 @@
 ragged form against the single one, the mode's plumbing, its composition with the loop on both engines, the property the
 stage exists for measured on the device, and the batch / sequence contracts in mode 1.
 
-SPSI_L restates the segment length of the scan (kernels.h): the frame counts below are one segment, a partial last segment,
+SPSI_L restates the segment length of the scan (magnitude_plan.h): the frame counts below are one segment, a partial last segment,
 several segments, and more segments than one carry step."""
 import os
 import subprocess
@@ -24,7 +24,7 @@ RAGGED_FRAMES = (1, 2 * SPSI_L + 1, 3, SPSI_L, 40)
 
 
 def test_the_segment_length_is_the_librarys():
-    with open(os.path.join(ROOT, "xd-tts_amd", "csrc", "kernels.h")) as f:
+    with open(os.path.join(ROOT, "xd-tts_amd", "csrc", "magnitude_plan.h")) as f:
         assert "constexpr int SPSI_L = %d;" % SPSI_L in f.read()
 
 

@@ -40,12 +40,12 @@ xdtts_status last_stats_out(const xdtts_griffinlim *g, const std::vector<T> *las
 }
 
 // A single mel request from the host: the handle's lock, the mel up, the one single-utterance request path
-inline void infer_host_mel(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames, const ProsodyArg &p, float **audio, size_t *n_samples) {
+inline void infer_host_mel(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames, const MagnitudeRequest &req, float **audio, size_t *n_samples) {
   std::lock_guard<std::mutex> lk(g->mu);
   HIP_CHECK(hipSetDevice(g->device));
   g->mel_in.upload(mel, n_mels * n_frames, g->stream);
   HIP_CHECK(hipStreamSynchronize(g->stream));
-  gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, p, audio, n_samples);
+  gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, req, audio, n_samples);
 }
 
 // A magnitude hook's result out: utterance u's rows of src [rows.total][nb] transposed into `frames` (the boundary layout,
@@ -65,11 +65,9 @@ inline void rows_to_host(xdtts_griffinlim *g, const float *src, const Rows &rows
   }
 }
 
-// GriffinLim::infer for several utterances at once (api_griffinlim.cpp).  pros == cont == null: xdtts_griffinlim_infer_batch; else
-// one checked prosody or contour per utterance; job: a pitch-target request (checked options and targets, contours that may be null).
+// GriffinLim::infer for several utterances at once (api_griffinlim.cpp).  ask: what the entry puts between mel -> linear and the
+// loop, fields checked; each utterance is checked against its frame count here.
 xdtts_status gl_infer_batch(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames, int32_t n_utt,
-                            const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **audios, size_t *n_samples,
-                            const F0Job *job = nullptr, const xdtts_pitch_target *tg = nullptr,
-                            const xdtts_prosody_contour *const *tc = nullptr);
+                            const MagnitudeAsk &ask, float **audios, size_t *n_samples);
 
 }  // namespace xdtts

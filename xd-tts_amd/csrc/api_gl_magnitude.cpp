@@ -7,6 +7,28 @@
 
 using namespace xdtts;
 
+// The parity hook of a magnitude stage alone: the utterances' magnitudes one behind the other on the device (rows plan.in of S),
+// ev.e[3], the plan in place (with_tables: the form a batch runs -- the tables go up and the stream is drained; else the single
+// request's), ev.e[0], the stage, ev.e[1], the rows plan.rows of the buffer it returns back in the boundary layout (ev.e[2]
+// behind the layout change), the wait.
+template <class Stage>
+static void stage_hook(xdtts_griffinlim *g, const float *const *S, MagnitudePlan plan, bool with_tables, float *const *S_outs, Stage stage) {  // (the caller holds g->mu)
+  HIP_CHECK(hipSetDevice(g->device));
+  g->bufs((int)plan.loop_rows);  // (frames: the boundary-layout staging of both directions)
+  g->upload_rows(S, plan.in);
+  HIP_CHECK(hipEventRecord(g->ev.e[3], g->stream));
+  g->mg.prepare(std::move(plan), with_tables);
+  HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+  const float *out = stage(g->mg);
+  HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));  // last_timings: ms[0] = the stage alone, ms[1] = the layout change behind it
+  rows_to_host(g, out, g->mg.plan.rows, S_outs);
+  g->finish_timings();  // (drains the stream: the tables and the outputs)
+}
+static void frames_out(const xdtts_griffinlim *g, size_t *n_frames_out) {
+  for (int u = 0; n_frames_out && u < g->mg.plan.rows.n(); ++u) n_frames_out[u] = (size_t)g->mg.plan.rows.F[(size_t)u];
+}
+static const std::vector<Timbre> NO_TIMBRE;
+
 extern "C" {
 
 // ---- prosody: rate and pitch on the magnitude between mel -> linear and the loop (prosody.hip) --------------------------------
@@ -27,22 +49,10 @@ xdtts_status xdtts_griffinlim_prosody_linear(xdtts_griffinlim *g, const float *S
     if (n_frames_out) *n_frames_out = 0;
     if (!g || !S || !p || !S_out) fail(XDTTS_ERR_BAD_ARG, "null argument");
     if (n_frames == 0) fail(XDTTS_ERR_BAD_ARG, "need at least 1 frame");
-    prosody_check(p, n_frames);
+    MagnitudePlan plan = magnitude_plan_checked(magnitude_request(MagnitudeAsk::prosody(p), 1, &n_frames), &n_frames, NO_TIMBRE, 0);
     std::lock_guard<std::mutex> lk(g->mu);
-    HIP_CHECK(hipSetDevice(g->device));
-    const int F = (int)n_frames, Fmax = std::max(F, (int)prosody_frames(n_frames, p->rate));
-    g->bufs(Fmax);
-    // boundary layout (nb x F) -> device layout [F][nb], the stage, and back: (nb x F')
-    g->frames.upload(S, (size_t)F * g->nb, g->stream);
-    launch_transpose(g->frames.p, g->S.p, g->nb, F, g->stream);
-    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
-    const int Fp = g->prosody(ProsodyArg(p), F);
-    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));  // last_timings: ms[0] = the stage alone, ms[1] = the layout change behind it
-    launch_transpose(g->prosody_S(ProsodyArg(p)), g->frames.p, Fp, g->nb, g->stream);
-    HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
-    HIP_CHECK(hipMemcpyAsync(S_out, g->frames.p, (size_t)Fp * g->nb * sizeof(float), hipMemcpyDeviceToHost, g->stream));
-    g->finish_timings();  // (drains the stream)
-    if (n_frames_out) *n_frames_out = (size_t)Fp;
+    stage_hook(g, &S, std::move(plan), false, &S_out, [&](Magnitude &m) { return m.run(g->S.p); });  // (the identity launches nothing: S's bits)
+    frames_out(g, n_frames_out);
   });
 }
 
@@ -53,8 +63,7 @@ xdtts_status xdtts_griffinlim_infer_prosody(xdtts_griffinlim *g, const float *me
     if (n_samples) *n_samples = 0;
     if (!g || !mel || !p || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     mel_check(g, n_mels, n_frames);
-    prosody_check(p, n_frames);
-    infer_host_mel(g, mel, n_mels, n_frames, ProsodyArg(p), audio, n_samples);
+    infer_host_mel(g, mel, n_mels, n_frames, magnitude_request(MagnitudeAsk::prosody(p), 1, &n_frames), audio, n_samples);
   });
 }
 
@@ -67,7 +76,7 @@ xdtts_status xdtts_griffinlim_infer_batch_prosody(xdtts_griffinlim *g, const flo
     prosody_check_array(p, n_utt);
   });
   if (st != XDTTS_OK) return st;
-  return gl_infer_batch(g, mels, n_mels, n_frames, n_utt, p, nullptr, audios, n_samples);
+  return gl_infer_batch(g, mels, n_mels, n_frames, n_utt, MagnitudeAsk::prosody(p), audios, n_samples);
 }
 
 // Parity hook of the ragged stage alone: the utterances' magnitudes one behind the other on the device, one k_prosody_batch
@@ -78,36 +87,15 @@ xdtts_status xdtts_griffinlim_prosody_linear_batch(xdtts_griffinlim *g, const fl
     for (int u = 0; n_frames_out && u < n_utt; ++u) n_frames_out[u] = 0;
     prosody_check_array(p, n_utt);
     if (!g || !S || !n_frames || !S_outs) fail(XDTTS_ERR_BAD_ARG, "null argument");
-    std::vector<ProsodyUtt> tab((size_t)n_utt);
-    Rows in, out;
     for (int u = 0; u < n_utt; ++u) {
       if (!S[u] || !S_outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
       if (n_frames[u] == 0) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 1 frame", u);
       prosody_check_at(&p[u], u, n_frames[u]);
-      const size_t Fp = prosody_frames(n_frames[u], p[u].rate);
-      tab[(size_t)u] = {(int)in.total, (int)n_frames[u], (int)out.total, (int)Fp, p[u].rate, p[u].pitch, p[u].lifter, p[u].log_floor};
-      rows_add(in, n_frames[u], (size_t)1 << 24, "batch too large");
-      rows_add(out, Fp, (size_t)1 << 24, "batch too large");
     }
-    const size_t Fout = out.total;
+    MagnitudePlan plan = magnitude_plan_checked(magnitude_request(MagnitudeAsk::prosody(p), n_utt, nullptr), n_frames, NO_TIMBRE, 0, true);
     std::lock_guard<std::mutex> lk(g->mu);
-    HIP_CHECK(hipSetDevice(g->device));
-    const size_t nb = (size_t)g->nb;
-    g->bufs((int)std::max(in.total, Fout));  // (frames: the boundary-layout staging of both directions)
-    g->S_pros.alloc(Fout * nb);
-    g->pros_tab.upload(tab.data(), tab.size(), g->stream);
-    g->upload_rows(S, in);
-    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
-    if (env::equals(env::PROSODY_BATCH, "loop")) {  // developer comparison aid (tools/prosody_check.py): one k_prosody launch per utterance
-      for (const ProsodyUtt &t : tab)
-        launch_prosody(g->S.p + (size_t)t.src0 * nb, g->S_pros.p + (size_t)t.dst0 * nb, t.F, t.Fout, t.rate, t.pitch, t.lifter, t.log_floor, g->tw.p, g->stream);
-    } else {
-      launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)Fout, g->tw.p, g->stream);
-    }
-    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
-    rows_to_host(g, g->S_pros.p, out, S_outs);
-    g->finish_timings();  // (drains the stream: the table and the outputs)
-    for (int u = 0; n_frames_out && u < n_utt; ++u) n_frames_out[u] = (size_t)tab[(size_t)u].Fout;
+    stage_hook(g, S, std::move(plan), true, S_outs, [&](Magnitude &m) { return m.prosody(g->S.p), m.S_pros.p; });
+    frames_out(g, n_frames_out);
   });
 }
 
@@ -144,29 +132,18 @@ xdtts_status xdtts_griffinlim_contour_linear_batch(xdtts_griffinlim *g, const fl
     contour_check_array(c, n_utt);
     if (!S || !n_frames || !S_outs) fail(XDTTS_ERR_BAD_ARG, "null argument");
     std::vector<ContourTable> tabs((size_t)n_utt);
-    Rows in, out;
     for (int u = 0; u < n_utt; ++u) {
       if (!S[u] || !S_outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
       if (n_frames[u] == 0) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 1 frame", u);
       contour_check_at(&c[u], u, n_frames[u]);
       contour_table(c[u], n_frames[u], tabs[(size_t)u]);
-      rows_add(in, n_frames[u], (size_t)1 << 24, "batch too large");
-      rows_add(out, (size_t)tabs[(size_t)u].Fout, (size_t)1 << 24, "batch too large");
     }
+    MagnitudePlan plan = magnitude_plan_checked(MagnitudeRequest::contours(std::move(tabs)), n_frames, NO_TIMBRE, 0, true);
     if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");  // (behind the contours and their frame counts: those need no device)
     std::lock_guard<std::mutex> lk(g->mu);
-    HIP_CHECK(hipSetDevice(g->device));
-    g->bufs((int)std::max(in.total, out.total));  // (frames: the boundary-layout staging of both directions)
-    g->upload_rows(S, in);
-    HIP_CHECK(hipEventRecord(g->ev.e[3], g->stream));
-    g->contour_upload(tabs.data(), n_utt);
-    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
-    g->contour_launch();
-    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
-    rows_to_host(g, g->S_pros.p, out, S_outs);
-    g->finish_timings();  // (drains the stream: the tables and the outputs)
+    stage_hook(g, S, std::move(plan), false, S_outs, [&](Magnitude &m) { return m.prosody(g->S.p), m.S_pros.p; });  // (ev.e[0]: behind the table's upload)
     HIP_CHECK(hipEventElapsedTime(&g->last_ms[2], g->ev.e[3], g->ev.e[2]));  // the total takes the table's upload in
-    for (int u = 0; n_frames_out && u < n_utt; ++u) n_frames_out[u] = (size_t)out.F[(size_t)u];
+    frames_out(g, n_frames_out);
   });
 }
 
@@ -187,9 +164,7 @@ xdtts_status xdtts_griffinlim_infer_contour(xdtts_griffinlim *g, const float *me
     contour_check(c, std::max<size_t>(n_frames, 2));  // the fields first: reported without a handle
     if (!g || !mel || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     mel_check(g, n_mels, n_frames);
-    ContourTable tab;
-    contour_table(*c, n_frames, tab);
-    infer_host_mel(g, mel, n_mels, n_frames, ProsodyArg(&tab), audio, n_samples);
+    infer_host_mel(g, mel, n_mels, n_frames, magnitude_request(MagnitudeAsk::contour(c), 1, &n_frames), audio, n_samples);
   });
 }
 
@@ -200,7 +175,7 @@ xdtts_status xdtts_griffinlim_infer_batch_contour(xdtts_griffinlim *g, const flo
     contour_check_array(c, n_utt);
   });
   if (st != XDTTS_OK) return st;
-  return gl_infer_batch(g, mels, n_mels, n_frames, n_utt, nullptr, c, audios, n_samples);
+  return gl_infer_batch(g, mels, n_mels, n_frames, n_utt, MagnitudeAsk::contour(c), audios, n_samples);
 }
 
 // ---- pitch tracker and pitch targets (f0_plan.h, f0.hip: k_f0_frames, k_f0_track) ----------------------------------------------
@@ -245,34 +220,32 @@ xdtts_status xdtts_f0_track_reference(const float *raw, const float *strength, s
 }
 
 xdtts_status xdtts_griffinlim_last_f0(const xdtts_griffinlim *g, xdtts_f0_stats *out, size_t cap, size_t *n) {
-  return last_stats_out(g, g ? &g->last_f0 : nullptr, true, out, cap, n);
+  return last_stats_out(g, g ? &g->mg.last_f0 : nullptr, true, out, cap, n);
 }
 
 // The tracker's results of the rows `rows` to the host (any array, and any element of one, may be null), the wait, the stats.
-// Behind f0_launch() on g->stream; ev.e[0 .. 2] recorded by the caller.
+// Behind Magnitude::track() on g->stream; ev.e[0 .. 2] recorded by the caller.
 static void f0_fetch(xdtts_griffinlim *g, const Rows &rows, float *const *raw_outs, float *const *strength_outs, float *const *f0_outs,
                      float *const *ratio_outs, xdtts_f0_stats *stats) {
   for (int u = 0; u < rows.n(); ++u) {
     const size_t r0 = (size_t)rows.row0[(size_t)u], nbytes = (size_t)rows.F[(size_t)u] * sizeof(float);
-    if (raw_outs && raw_outs[u]) HIP_CHECK(hipMemcpyAsync(raw_outs[u], g->f0_raw.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
-    if (strength_outs && strength_outs[u]) HIP_CHECK(hipMemcpyAsync(strength_outs[u], g->f0_strength.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
-    if (f0_outs && f0_outs[u]) HIP_CHECK(hipMemcpyAsync(f0_outs[u], g->f0_val.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
-    if (ratio_outs && ratio_outs[u]) HIP_CHECK(hipMemcpyAsync(ratio_outs[u], g->f0_ratio.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
+    if (raw_outs && raw_outs[u]) HIP_CHECK(hipMemcpyAsync(raw_outs[u], g->mg.f0_raw.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
+    if (strength_outs && strength_outs[u]) HIP_CHECK(hipMemcpyAsync(strength_outs[u], g->mg.f0_strength.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
+    if (f0_outs && f0_outs[u]) HIP_CHECK(hipMemcpyAsync(f0_outs[u], g->mg.f0_val.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
+    if (ratio_outs && ratio_outs[u]) HIP_CHECK(hipMemcpyAsync(ratio_outs[u], g->mg.f0_ratio.p + r0, nbytes, hipMemcpyDeviceToHost, g->stream));
   }
   g->finish_timings();  // (drains the stream)
   g->clear_last();
-  g->f0_collect();
-  if (stats && !g->last_f0.empty()) std::memcpy(stats, g->last_f0.data(), g->last_f0.size() * sizeof(xdtts_f0_stats));
+  g->mg.collect();
+  if (stats && !g->mg.last_f0.empty()) std::memcpy(stats, g->mg.last_f0.data(), g->mg.last_f0.size() * sizeof(xdtts_f0_stats));
 }
 
 // The tracker alone on S_dev [rows.total][nb]: no target, no table.  ms[0] = k_f0_frames, ms[1] = k_f0_track.
 static void f0_run(xdtts_griffinlim *g, const float *S_dev, const Rows &rows, const F0Job &job, float *const *raw_outs,
                    float *const *strength_outs, float *const *f0_outs, xdtts_f0_stats *stats) {
-  std::vector<F0Utt> utts;
-  for (int u = 0; u < rows.n(); ++u) utts.push_back({rows.row0[(size_t)u], rows.F[(size_t)u], -1, 0, 1.0f, 1.0f});
-  g->f0_prepare(utts);
+  g->mg.prepare(magnitude_plan_tracker(rows, job), false);
   HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
-  g->f0_launch(S_dev, job, nullptr, 0, g->ev.e[1]);
+  g->mg.track(S_dev, g->ev.e[1]);
   HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
   f0_fetch(g, rows, raw_outs, strength_outs, f0_outs, nullptr, stats);
 }
@@ -358,22 +331,19 @@ xdtts_status xdtts_griffinlim_pitch_target_linear_batch(xdtts_griffinlim *g, con
       if (!S[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
       if (c && c[u]) contour_check_at(c[u], u, std::max<size_t>(n_frames[u], 2));  // the fields first
     }
-    Rows in, out;
+    Rows in;
     f0_rows_checked(in, n_frames, n_utt);
-    TargetPlan plan;
-    target_plan(job, t, c, n_utt, n_frames, plan);
-    for (int u = 0; u < n_utt; ++u) rows_add(out, (size_t)plan.tabs[(size_t)u].Fout, (size_t)1 << 24, "batch too large");
+    MagnitudePlan plan = magnitude_plan_checked(magnitude_request(MagnitudeAsk::target(&job, t, c, true), n_utt, n_frames, 0), n_frames, NO_TIMBRE, 0, true);
     if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
     std::lock_guard<std::mutex> lk(g->mu);
     HIP_CHECK(hipSetDevice(g->device));
-    g->bufs((int)std::max(in.total, out.total));
+    g->bufs((int)plan.loop_rows);
     g->upload_rows(S, in);
-    g->contour_upload(plan.tabs.data(), n_utt, true);
-    g->f0_prepare_contour(plan.job);
+    g->mg.prepare(std::move(plan), false);
     HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
-    g->f0_launch(g->S.p, plan.job, g->contour_ftab.p, g->contour_n_tab, g->ev.e[1]);
-    g->contour_launch();
-    rows_to_host(g, g->S_pros.p, out, S_outs);
+    g->mg.track(g->S.p, g->ev.e[1]);
+    g->mg.prosody(g->S.p);
+    rows_to_host(g, g->mg.S_pros.p, g->mg.plan.rows, S_outs);
     f0_fetch(g, in, nullptr, nullptr, nullptr, ratio_outs, stats);
   });
 }
@@ -395,14 +365,7 @@ xdtts_status xdtts_griffinlim_infer_pitch_target(xdtts_griffinlim *g, const floa
     if (c) contour_check(c, std::max<size_t>(n_frames, 2));
     if (!g || !mel || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     mel_check(g, n_mels, n_frames);
-    TargetPlan plan;
-    target_plan(job, t, c ? &c : nullptr, 1, &n_frames, plan);
-    std::lock_guard<std::mutex> lk(g->mu);
-    HIP_CHECK(hipSetDevice(g->device));
-    g->mel_in.upload(mel, n_mels * n_frames, g->stream);
-    HIP_CHECK(hipStreamSynchronize(g->stream));
-    gl_run_from_device_mel(g, g->mel_in.p, (int)n_frames, plan.arg(), audio, n_samples);
-    if (plan.active) g->f0_collect();
+    infer_host_mel(g, mel, n_mels, n_frames, magnitude_request(MagnitudeAsk::target(&job, t, c ? &c : nullptr), 1, &n_frames), audio, n_samples);
   });
 }
 
@@ -419,7 +382,7 @@ xdtts_status xdtts_griffinlim_infer_batch_pitch_target(xdtts_griffinlim *g, cons
       if (c[u]) contour_check_at(c[u], u, 2);
   });
   if (st != XDTTS_OK) return st;
-  return gl_infer_batch(g, mels, n_mels, n_frames, n_utt, nullptr, nullptr, audios, n_samples, &job, t, c);
+  return gl_infer_batch(g, mels, n_mels, n_frames, n_utt, MagnitudeAsk::target(&job, t, c), audios, n_samples);
 }
 
 // ---- initial phase: the seeded random stream (0) or Single Pass Spectrogram Inversion (1; phase_spsi.hip) ---------------------
@@ -429,7 +392,7 @@ xdtts_status xdtts_griffinlim_set_phase_init(xdtts_griffinlim *g, int32_t mode) 
     if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
     if (mode != 0 && mode != 1) fail(XDTTS_ERR_BAD_ARG, "phase_init must be 0 (seeded random) or 1 (SPSI), got %d", mode);
     std::lock_guard<std::mutex> lk(g->mu);
-    g->phase_init = mode;
+    g->mg.phase_init = mode;
   });
 }
 
@@ -437,7 +400,7 @@ xdtts_status xdtts_griffinlim_get_phase_init(const xdtts_griffinlim *g, int32_t 
   return guard([&] {
     if (!g || !mode) fail(XDTTS_ERR_BAD_ARG, "null argument");
     std::lock_guard<std::mutex> lk(g->mu);
-    *mode = g->phase_init;
+    *mode = g->mg.phase_init;
   });
 }
 
@@ -462,20 +425,17 @@ xdtts_status xdtts_griffinlim_spsi_phase_batch(xdtts_griffinlim *g, const float 
     const size_t nb = (size_t)g->nb, ne = Ftot * nb;
     GlBufs b = g->bufs((int)Ftot);
     g->upload_rows(S, rows);
-    xdtts_griffinlim::SpsiTables tab;
-    g->spsi_tables(Fu, tab);
-    g->spsi_turns.alloc(ne);
+    g->mg.prepare(magnitude_plan_checked(MagnitudeRequest::none(n_utt), n_frames, NO_TIMBRE, 1), n_utt > 1);  // (one utterance: the form the single-utterance entries run)
+    g->mg.spsi_turns.alloc(ne);
     g->phase0.alloc(ne * 3);  // staging in the boundary layout: the angles, then the turns
     float2 *ang_out = reinterpret_cast<float2 *>(g->phase0.p);
     unsigned *turns_out = reinterpret_cast<unsigned *>(g->phase0.p + ne * 2);
-    HIP_CHECK(hipStreamSynchronize(g->stream));  // the host tables
     HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
-    if (n_utt == 1) g->spsi(g->S.p, Fu[0], b.ang, b.tprev, g->spsi_turns.p);  // (the form the single-utterance entries run)
-    else g->spsi_batch(g->S.p, tab, b.ang, b.tprev, g->spsi_turns.p);
+    g->mg.spsi(g->S.p, b.ang, b.tprev, g->mg.spsi_turns.p);
     HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
     for (int u = 0; u < n_utt; ++u) {
       const size_t r0 = (size_t)row0[(size_t)u] * nb;
-      launch_spsi_export(g->spsi_turns.p + r0, b.ang + r0, Fu[(size_t)u], g->nb, turns_out + r0, ang_out + r0, g->stream);
+      launch_spsi_export(g->mg.spsi_turns.p + r0, b.ang + r0, Fu[(size_t)u], g->nb, turns_out + r0, ang_out + r0, g->stream);
     }
     HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
     for (int u = 0; u < n_utt; ++u) {
@@ -506,7 +466,7 @@ xdtts_status xdtts_griffinlim_set_timbre(xdtts_griffinlim *g, const xdtts_timbre
     const Timbre s = timbre_checked(t);  // (the fields before the handle; a failure leaves the setting as it was)
     if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
     std::lock_guard<std::mutex> lk(g->mu);
-    g->timbre = s;
+    g->mg.timbre = s;
   });
 }
 
@@ -514,7 +474,7 @@ xdtts_status xdtts_griffinlim_get_timbre(xdtts_griffinlim *g, xdtts_timbre *t) {
   return guard([&] {
     if (!g || !t) fail(XDTTS_ERR_BAD_ARG, "null argument");
     std::lock_guard<std::mutex> lk(g->mu);
-    std::memcpy(t, &g->timbre, sizeof g->timbre);
+    std::memcpy(t, &g->mg.timbre, sizeof g->mg.timbre);
   });
 }
 
@@ -537,31 +497,16 @@ xdtts_status xdtts_griffinlim_timbre_linear_batch(xdtts_griffinlim *g, const flo
       any = any || !timbre_is_identity(ts[(size_t)u]);
     }
     if (!g || !S || !n_frames || !S_outs) fail(XDTTS_ERR_BAD_ARG, "null argument");
-    Rows rows;
-    for (int u = 0; u < n_utt; ++u) {
+    for (int u = 0; u < n_utt; ++u)
       if (!S[u] || !S_outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
-      rows_add(rows, n_frames[u], (size_t)1 << 24, "batch too large");
-    }
+    MagnitudePlan plan = magnitude_plan_checked(MagnitudeRequest::none(n_utt), n_frames, ts, 0);
     std::lock_guard<std::mutex> lk(g->mu);
-    const size_t nb = (size_t)g->nb;
     if (!any) {  // the identity: S's bits, nothing launched, nothing allocated
       for (int u = 0; u < n_utt; ++u)
-        if (S_outs[u] != S[u]) std::memmove(S_outs[u], S[u], n_frames[u] * nb * sizeof(float));
+        if (S_outs[u] != S[u]) std::memmove(S_outs[u], S[u], n_frames[u] * (size_t)g->nb * sizeof(float));
       return;
     }
-    HIP_CHECK(hipSetDevice(g->device));
-    g->bufs((int)rows.total);  // (frames: the boundary-layout staging of both directions)
-    g->S_timbre.alloc(rows.total * nb);
-    g->timbre_tab_host.clear();
-    for (int u = 0; u < n_utt; ++u) g->timbre_tab_host.push_back(timbre_utt(rows.row0[(size_t)u], rows.row0[(size_t)u], rows.F[(size_t)u], ts[(size_t)u]));
-    if (n_utt > 1) g->timbre_tab.upload(g->timbre_tab_host.data(), g->timbre_tab_host.size(), g->stream);
-    g->upload_rows(S, rows);
-    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
-    if (n_utt == 1) g->timbre_one(g->S.p, rows.F[0], ts[0]);
-    else g->timbre_rows(g->S.p, (int)rows.total);
-    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
-    rows_to_host(g, g->S_timbre.p, rows, S_outs);
-    g->finish_timings();  // (drains the stream: the table and the outputs)
+    stage_hook(g, S, std::move(plan), n_utt > 1, S_outs, [&](Magnitude &m) { return m.voice(g->S.p), m.S_timbre.p; });
   });
 }
 

@@ -14,26 +14,18 @@ using namespace xdtts;
 // kernel takes as many utterances per launch as fit one workgroup per CU.  Every utterance's audio is bit-identical to what
 // xdtts_griffinlim_infer returns for it alone.  (the arguments: api_gl.h)
 xdtts_status xdtts::gl_infer_batch(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames, int32_t n_utt,
-                                   const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **audios, size_t *n_samples,
-                                   const F0Job *job, const xdtts_pitch_target *tg, const xdtts_prosody_contour *const *tc) {
+                                   const MagnitudeAsk &ask, float **audios, size_t *n_samples) {
   return guard([&] {
     if (!g || !mels || !n_frames || !audios || !n_samples || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "bad argument");
     mel_check(g, n_mels);
     Rows rows;
-    std::vector<ContourTable> tabs(cont ? (size_t)n_utt : 0);
     for (int u = 0; u < n_utt; ++u) {
       audios[u] = nullptr;
       n_samples[u] = 0;
       if (!mels[u] || n_frames[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 2 frames", u);
-      if (pros) prosody_check_at(&pros[u], u, n_frames[u]);
-      if (cont) {
-        contour_check_at(&cont[u], u, n_frames[u]);
-        contour_table(cont[u], n_frames[u], tabs[(size_t)u]);
-      }
       rows_add(rows, n_frames[u], (size_t)1 << 24, "batch too large");
     }
-    TargetPlan plan;
-    if (job) target_plan(*job, tg, tc, n_utt, n_frames, plan);
+    const MagnitudeRequest req = magnitude_request(ask, n_utt, n_frames, 0);
     const size_t Ftot = rows.total;
     std::lock_guard<std::mutex> lk(g->mu);
     HIP_CHECK(hipSetDevice(g->device));
@@ -44,8 +36,7 @@ xdtts_status xdtts::gl_infer_batch(xdtts_griffinlim *g, const float *const *mels
         std::memcpy(mel_all.p + m * Ftot + rows.row0[u], mels[u] + m * n_frames[u], sizeof(float) * n_frames[u]);
     g->mel_in.upload(mel_all.p, (size_t)n_mels * Ftot, g->stream);
     HIP_CHECK(hipStreamSynchronize(g->stream));  // the staging buffer goes back to the pool
-    gl_batch_from_device(g, g->mel_in.p, rows.F, audios, n_samples, job ? plan.arg() : (cont ? ProsodyArg(tabs.data()) : ProsodyArg(pros)));
-    if (job && plan.active) g->f0_collect();
+    gl_batch_from_device(g, g->mel_in.p, rows.F, audios, n_samples, req);
   });
 }
 
@@ -87,7 +78,8 @@ xdtts_status xdtts_griffinlim_new(const float *mel_basis, size_t n_mels, size_t 
     g->power = power;
     g->momentum = momentum;
     HIP_CHECK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    g->dl.stream = g->stream;
+    g->dl.stream = g->mg.stream = g->stream;
+    g->mg.nb = g->nb;
     g->ev.create();
     g->an_ev.create();
     std::vector<float> pinv;
@@ -112,6 +104,7 @@ xdtts_status xdtts_griffinlim_new(const float *mel_basis, size_t n_mels, size_t 
     }
     g->tw.upload(tw.data(), tw.size(), g->stream);
     g->win.upload(win.data(), win.size(), g->stream);
+    g->mg.tw = g->tw.p;
     HIP_CHECK(hipStreamSynchronize(g->stream));
     *out = g.release();
   });
@@ -161,13 +154,13 @@ xdtts_status xdtts_griffinlim_infer(xdtts_griffinlim *g, const float *mel, size_
     *audio = nullptr;
     *n_samples = 0;
     mel_check(g, n_mels, n_frames);
-    infer_host_mel(g, mel, n_mels, n_frames, nullptr, audio, n_samples);
+    infer_host_mel(g, mel, n_mels, n_frames, MagnitudeRequest::none(1), audio, n_samples);
   });
 }
 
 xdtts_status xdtts_griffinlim_infer_batch(xdtts_griffinlim *g, const float *const *mels, size_t n_mels, const size_t *n_frames,
                                           int32_t n_utt, float **audios, size_t *n_samples) {
-  return gl_infer_batch(g, mels, n_mels, n_frames, n_utt, nullptr, nullptr, audios, n_samples);
+  return gl_infer_batch(g, mels, n_mels, n_frames, n_utt, MagnitudeAsk(), audios, n_samples);
 }
 
 xdtts_status xdtts_griffinlim_mel_to_linear(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,

@@ -17,11 +17,10 @@ static void pair_check(const xdtts_tacotron2 *h, const xdtts_griffinlim *g) {
   if (g->n_mels != N_MEL) fail(XDTTS_ERR_BAD_ARG, "the vocoder's basis has %d mel bands, the model's mel has %d", g->n_mels, N_MEL);
 }
 
-// (pros == cont == null: xdtts_synthesize_ids; else the prosody stage between mel -> linear and the loop, fields checked by the caller)
+// (ask: nothing -- xdtts_synthesize_ids -- or the magnitude chain between mel -> linear and the loop, fields checked by the caller)
 static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n, const size_t *splits,
-                                   size_t n_splits, const xdtts_infer_opts *opts, const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **mel,
-                                   size_t *n_frames, float **audio, size_t *n_samples, const F0Job *job = nullptr,
-                                   const xdtts_pitch_target *tg = nullptr, const xdtts_prosody_contour *const *tc = nullptr) {
+                                   size_t n_splits, const xdtts_infer_opts *opts, const MagnitudeAsk &ask, float **mel, size_t *n_frames,
+                                   float **audio, size_t *n_samples) {
   return guard([&] {
     if (!h || !g || !mel || !n_frames || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     pair_check(h, g);
@@ -43,33 +42,27 @@ static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, cons
     HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));
     HIP_CHECK(hipMemcpyAsync(mel_host.p, h->mel_dev.p, (size_t)N_MEL * total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     Drain drain(h->stream);  // the pinned buffer does not go back to the pool with the copy in flight
-    if (pros) prosody_check(pros, (size_t)total);  // (the frame count is known only now; nothing of the vocoder has been enqueued)
-    ContourTable tab;
-    if (cont) {
-      contour_check(cont, (size_t)total);
-      contour_table(*cont, (size_t)total, tab);
-    }
-    TargetPlan plan;  // (a pitch-target request: checked options and target, a contour that may be null)
-    const size_t total_frames = (size_t)total;
-    if (job) target_plan(*job, tg, tc, 1, &total_frames, plan);
-    gl_run_from_device_mel(g, h->mel_dev.p, total, job ? plan.arg() : (cont ? ProsodyArg(&tab) : ProsodyArg(pros)), audio, n_samples);
-    if (job && plan.active) g->f0_collect();
+    const size_t total_frames = (size_t)total;  // (the frame count is known only now; nothing of the vocoder has been enqueued)
+    gl_run_from_device_mel(g, h->mel_dev.p, total, magnitude_request(ask, 1, &total_frames), audio, n_samples);
     h->finish_timings();  // (stream sync: the mel has landed)
     *mel = mel_host.release();
     *n_frames = (size_t)total;
   });
 }
 
-// The prosody array of the batch and sequence entries, before a handle is looked at; the outputs are cleared first, so that a
-// rejected call returns nothing.
+// The outputs of a batch or sequence entry are cleared before its fields are checked, so that a rejected call returns nothing.
+static void null_outputs(int32_t n_utt, float **mels, size_t *n_frames, float **audios, size_t *n_samples) {
+  for (int u = 0; u < n_utt; ++u) {
+    if (mels) mels[u] = nullptr;
+    if (audios) audios[u] = nullptr;
+    if (n_frames) n_frames[u] = 0;
+    if (n_samples) n_samples[u] = 0;
+  }
+}
+// The prosody array of the batch and sequence entries, before a handle is looked at
 static xdtts_status check_prosody_array(const xdtts_prosody *p, int32_t n_utt, float **mels, size_t *n_frames, float **audios, size_t *n_samples) {
   return guard([&] {
-    for (int u = 0; u < n_utt; ++u) {
-      if (mels) mels[u] = nullptr;
-      if (audios) audios[u] = nullptr;
-      if (n_frames) n_frames[u] = 0;
-      if (n_samples) n_samples[u] = 0;
-    }
+    null_outputs(n_utt, mels, n_frames, audios, n_samples);
     prosody_check_array(p, n_utt);
   });
 }
@@ -153,6 +146,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
     std::lock_guard<std::mutex> lk2(g->mu);
     std::lock_guard<ChipLock> chip(chip_mutex(h->device));  // the whole sequence: co-resident launches of two streams are in flight
     g->clear_last();  // (gl_collect appends utterance by utterance)
+    const MagnitudeAsk ask = pros ? MagnitudeAsk::prosody(pros) : MagnitudeAsk();
     const xdtts_infer_opts o = resolve_opts(opts);
     struct Hook {  // (the hook never outlives this call, whatever throws)
       xdtts_tacotron2 *h;
@@ -206,7 +200,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
         if (predicted >= 2)
           h->while_decoding = [&, u, predicted] {
             if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * predicted);
-            const size_t Fp = pros ? prosody_frames((size_t)predicted, pros[u].rate) : (size_t)predicted;  // the vocoder's frames, not the mel's
+            const size_t Fp = (size_t)magnitude_request(ask.at(u), 1, nullptr).frames(0, (int)predicted);  // the vocoder's frames, not the mel's
             if (!doc && !audio_host[u].p) audio_host[u] = PinnedGuard(g->dl.delivered((size_t)g->hop * (Fp - 1)));  // (at the handle's output rate)
           };
         for (int i = 0; i < 4; ++i) std::swap(h->ev.e[i], per[u].e[i]);  // (per[u] now holds what the handle had: utterance u - 1's set, or its own)
@@ -216,20 +210,21 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
         if (predicted != total[u]) mel_host[u] = PinnedGuard(), audio_host[u] = PinnedGuard();  // (the stop rule decided otherwise: sized below)
         steps_sum += h->last_steps;
         if (total[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: mel has %d frame(s); the vocoder needs at least 2", u, total[u]);
-        if (pros) prosody_check_at(&pros[u], u, (size_t)total[u]);  // (the frame count is known only now)
+        const size_t mel_frames = (size_t)total[u];
+        const MagnitudeRequest req = magnitude_request(ask.at(u), 1, &mel_frames, u);  // (the frame count is known only now)
         // the frame loop of u has drained, and it waited for the vocoder of u - 1: collect that audio now
         if (u > 0) {
-          gl_collect(g, total[u - 1], audio_host[u - 1], &audio_out[u - 1], &n_samples[u - 1], pros ? &pros[u - 1] : nullptr);
+          gl_collect(g, audio_host[u - 1], &audio_out[u - 1], &n_samples[u - 1]);  // (the plan in place is still utterance u - 1's)
           if (doc) doc->trimmed(u - 1, n_samples[u - 1]);
           add_gl();
         }
         if (!mel_host[u].p) mel_host[u] = PinnedGuard((size_t)N_MEL * total[u]);
         HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));  // the vocoder reads the mel behind the post-net
         HIP_CHECK(hipMemcpyAsync(mel_host[u].p, h->mel_dev.p, (size_t)N_MEL * total[u] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        if (doc) doc->place(u, g->dl.delivered((size_t)g->hop * ((pros ? prosody_frames((size_t)total[u], pros[u].rate) : (size_t)total[u]) - 1)));
-        gl_enqueue_from_device_mel(g, h->mel_dev.p, total[u], audio_host[u], pros ? &pros[u] : nullptr);
+        if (doc) doc->place(u, g->dl.delivered((size_t)g->hop * (size_t)(req.frames(0, total[u]) - 1)));
+        gl_enqueue_from_device_mel(g, h->mel_dev.p, total[u], audio_host[u], req);
       }
-      gl_collect(g, total[n_utt - 1], audio_host[n_utt - 1], &audio_out[n_utt - 1], &n_samples[n_utt - 1], pros ? &pros[n_utt - 1] : nullptr);
+      gl_collect(g, audio_host[n_utt - 1], &audio_out[n_utt - 1], &n_samples[n_utt - 1]);
       if (doc) doc->trimmed(n_utt - 1, n_samples[n_utt - 1]);
       add_gl();
       if (doc) doc->finish();
@@ -266,12 +261,11 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
 // src/tacotron2/mod.rs:422-434), the post-net writes every utterance's chunks side by side on the time axis
 // (mod.rs:430), and the vocoder batch reads that mel where it lies in HBM -- no copy to the host and back, no
 // re-staging between the two halves.  The per-utterance mels leave for the host while the vocoder runs.
-// (pros == cont == null: xdtts_synthesize_batch; else one prosody or one contour per utterance, fields checked by the caller)
+// (ask: nothing -- xdtts_synthesize_batch -- or the magnitude chain's request per utterance, fields checked by the caller)
 static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
                                      int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
-                                     const int32_t *fixed_steps_per_item, const xdtts_prosody *pros, const xdtts_prosody_contour *cont, float **mels, size_t *n_frames,
-                                     float **audios, size_t *n_samples, const F0Job *job = nullptr, const xdtts_pitch_target *tg = nullptr,
-                                     const xdtts_prosody_contour *const *tc = nullptr) {
+                                     const int32_t *fixed_steps_per_item, const MagnitudeAsk &ask, float **mels, size_t *n_frames, float **audios,
+                                     size_t *n_samples) {
   return guard([&] {
     if (!h || !g || !ids || !lens || !utt_chunks || !n_frames || !audios || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     pair_check(h, g);
@@ -293,23 +287,14 @@ static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, co
     int total = 0;
     const std::vector<int> F = h->infer_batch_device(padded.data(), lens, B, T, o, fixed_steps_per_item, &total);
     std::vector<int> Fu(n_utt, 0), col0(n_utt, 0);
-    std::vector<ContourTable> tabs(cont ? (size_t)n_utt : 0);
     for (int u = 0, b = 0, off = 0; u < n_utt; ++u) {
       col0[u] = off;
       for (int k = 0; k < utt_chunks[u]; ++k) Fu[u] += F[b++];
       off += Fu[u];
       if (Fu[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d has %d mel frame(s); the vocoder needs at least 2", u, Fu[u]);
-      if (pros) prosody_check_at(&pros[u], u, (size_t)Fu[u]);  // (nothing of the vocoder has been enqueued)
-      if (cont) {
-        contour_check_at(&cont[u], u, (size_t)Fu[u]);
-        contour_table(cont[u], (size_t)Fu[u], tabs[(size_t)u]);
-      }
     }
-    TargetPlan plan;  // (a pitch-target request: checked options and targets, contours that may be null)
-    if (job) {
-      const std::vector<size_t> Fz(Fu.begin(), Fu.end());
-      target_plan(*job, tg, tc, n_utt, Fz.data(), plan);
-    }
+    const std::vector<size_t> Fz(Fu.begin(), Fu.end());
+    const MagnitudeRequest req = magnitude_request(ask, n_utt, Fz.data(), 0);  // (nothing of the vocoder has been enqueued)
     // the vocoder stream reads the mel behind the post-net (event 3 of infer_batch_device); the host copies of the
     // mel follow on the mel-gen stream and overlap the vocoder
     HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));
@@ -323,8 +308,7 @@ static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, co
                                    sizeof(float) * (size_t)Fu[u], N_MEL, hipMemcpyDeviceToHost, h->stream));
       }
     }
-    gl_batch_from_device(g, h->mel_dev.p, Fu, audios, n_samples, job ? plan.arg() : (cont ? ProsodyArg(tabs.data()) : ProsodyArg(pros)));
-    if (job && plan.active) g->f0_collect();
+    gl_batch_from_device(g, h->mel_dev.p, Fu, audios, n_samples, req);
     try {
       h->finish_timings();  // (stream sync: the mel copies have landed)
     } catch (...) {  // the caller gets either every buffer of the call or none
@@ -347,7 +331,7 @@ extern "C" {
 xdtts_status xdtts_synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
                                   const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts, float **mel,
                                   size_t *n_frames, float **audio, size_t *n_samples) {
-  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, nullptr, nullptr, mel, n_frames, audio, n_samples);
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, MagnitudeAsk(), mel, n_frames, audio, n_samples);
 }
 
 // ... with a prosody: the mel returned is Tacotron2's own, the audio has hop * (F' - 1) samples
@@ -360,7 +344,7 @@ xdtts_status xdtts_synthesize_ids_prosody(xdtts_tacotron2 *h, xdtts_griffinlim *
     prosody_check(p, 2);  // the fields, before a device is touched
   });
   if (st != XDTTS_OK) return st;
-  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, p, nullptr, mel, n_frames, audio, n_samples);
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, MagnitudeAsk::prosody(p), mel, n_frames, audio, n_samples);
 }
 
 // ... with a contour (rate, pitch and gain that vary inside the utterance): the audio has hop * (F' - 1) samples, F' from the
@@ -371,7 +355,7 @@ xdtts_status xdtts_synthesize_ids_contour(xdtts_tacotron2 *h, xdtts_griffinlim *
                                           size_t *n_samples) {
   xdtts_status st = guard([&] { contour_check(c, 2); });  // the fields, before a device is touched
   if (st != XDTTS_OK) return st;
-  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, nullptr, c, mel, n_frames, audio, n_samples);
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, MagnitudeAsk::contour(c), mel, n_frames, audio, n_samples);
 }
 
 xdtts_status xdtts_synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
@@ -435,7 +419,7 @@ xdtts_status xdtts_synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, con
                                     int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
                                     const int32_t *fixed_steps_per_item, float **mels, size_t *n_frames, float **audios,
                                     size_t *n_samples) {
-  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, nullptr, nullptr, mels, n_frames, audios, n_samples);
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, MagnitudeAsk(), mels, n_frames, audios, n_samples);
 }
 
 // ... one prosody per utterance: the ragged stage behind the batch's one mel -> linear GEMM
@@ -445,7 +429,7 @@ xdtts_status xdtts_synthesize_batch_prosody(xdtts_tacotron2 *h, xdtts_griffinlim
                                             float **audios, size_t *n_samples) {
   const xdtts_status st = check_prosody_array(p, n_utt, mels, n_frames, audios, n_samples);
   if (st != XDTTS_OK) return st;
-  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, p, nullptr, mels, n_frames, audios, n_samples);
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, MagnitudeAsk::prosody(p), mels, n_frames, audios, n_samples);
 }
 
 // ... one contour per utterance: the ragged contour stage behind the batch's one mel -> linear GEMM
@@ -454,16 +438,11 @@ xdtts_status xdtts_synthesize_batch_contour(xdtts_tacotron2 *h, xdtts_griffinlim
                                             const int32_t *fixed_steps_per_item, const xdtts_prosody_contour *c, float **mels, size_t *n_frames,
                                             float **audios, size_t *n_samples) {
   const xdtts_status st = guard([&] {
-    for (int u = 0; u < n_utt; ++u) {
-      if (mels) mels[u] = nullptr;
-      if (audios) audios[u] = nullptr;
-      if (n_frames) n_frames[u] = 0;
-      if (n_samples) n_samples[u] = 0;
-    }
+    null_outputs(n_utt, mels, n_frames, audios, n_samples);
     contour_check_array(c, n_utt);
   });
   if (st != XDTTS_OK) return st;
-  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, nullptr, c, mels, n_frames, audios, n_samples);
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, MagnitudeAsk::contour(c), mels, n_frames, audios, n_samples);
 }
 
 // ... with a pitch target (xdtts_pitch_target): tracker, target and contour stage behind mel -> linear; the table is built once
@@ -479,7 +458,7 @@ xdtts_status xdtts_synthesize_ids_pitch_target(xdtts_tacotron2 *h, xdtts_griffin
     if (c) contour_check(c, 2);
   });
   if (st != XDTTS_OK) return st;
-  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, nullptr, nullptr, mel, n_frames, audio, n_samples, &job, t, c ? &c : nullptr);
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, MagnitudeAsk::target(&job, t, c ? &c : nullptr), mel, n_frames, audio, n_samples);
 }
 
 // ... one target per utterance, contours that may be null
@@ -490,20 +469,14 @@ xdtts_status xdtts_synthesize_batch_pitch_target(xdtts_tacotron2 *h, xdtts_griff
                                                  size_t *n_samples) {
   F0Job job;
   const xdtts_status st = guard([&] {
-    for (int u = 0; u < n_utt; ++u) {
-      if (mels) mels[u] = nullptr;
-      if (audios) audios[u] = nullptr;
-      if (n_frames) n_frames[u] = 0;
-      if (n_samples) n_samples[u] = 0;
-    }
+    null_outputs(n_utt, mels, n_frames, audios, n_samples);
     job = f0_job_checked(o);
     pitch_target_check_array(t, n_utt);
     for (int u = 0; c && u < n_utt; ++u)
       if (c[u]) contour_check_at(c[u], u, 2);
   });
   if (st != XDTTS_OK) return st;
-  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, nullptr, nullptr, mels, n_frames, audios, n_samples,
-                          &job, t, c);
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, MagnitudeAsk::target(&job, t, c), mels, n_frames, audios, n_samples);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // griffinlim_handle.cpp -- the vocoder handle (GriffinLim::infer, mod.rs:441-520): mel -> linear, the iteration engines and
-// their fallback, the magnitude stages, the stream stage, the request paths.  The delivery chain behind the loop: delivery.cpp.
+// their fallback, the stream stage, the request paths.  The magnitude chain in front of the loop: magnitude.cpp; the delivery
+// chain behind it: delivery.cpp.
 #include "griffinlim_handle.h"
 
 #include <algorithm>
@@ -104,136 +105,6 @@ void xdtts_griffinlim::mel_to_linear(const float *mel_dev_ptr, int F) {
     launch_gemm_nt(u, stream);
   }
   launch_gl_pow_rows(nnls_x.p, NBP, S.p, nb, F, ex, stream);
-}
-
-// The prosody stage (prosody.hip) on the S that mel -> linear (or an upload) left in place: S_pros [F'][nb].
-int xdtts_griffinlim::prosody(const ProsodyArg &arg, int F) {
-  if (arg.identity(0)) return F;
-  if (arg.contour) {
-    const int Fp = contour_upload(arg.contour, 1, arg.f0 != nullptr);
-    if (arg.f0) {  // the tracker and the target write the table's pitches in front of the stage that reads them
-      f0_prepare_contour(*arg.f0);
-      f0_launch(S.p, *arg.f0, contour_ftab.p, contour_n_tab);
-    }
-    contour_launch();
-    return Fp;
-  }
-  const xdtts_prosody &p = *arg.uniform;
-  const int Fp = (int)prosody_frames((size_t)F, p.rate);
-  S_pros.alloc((size_t)Fp * nb);
-  launch_prosody(S.p, S_pros.p, F, Fp, p.rate, p.pitch, p.lifter, p.log_floor, tw.p, stream);
-  return Fp;
-}
-
-int xdtts_griffinlim::contour_upload(const ContourTable *tabs, int n_utt, bool keep_pitch) {
-  contour_utts_host.clear();
-  int src = 0, dst = 0, ntab = 0;
-  for (int u = 0; u < n_utt; ++u) {
-    const ContourTable &t = tabs[u];
-    contour_utts_host.push_back({src, t.F, dst, t.Fout, ntab, t.lifter, t.log_floor, t.identity ? 1 : 0});
-    src += t.F;
-    dst += t.Fout;
-    ntab += (int)t.c.size();
-  }
-  contour_n_tab = ntab;
-  contour_rows = dst;
-  contour_ftab_host.assign((size_t)(keep_pitch ? 4 : 3) * std::max(ntab, 1), 0u);
-  for (int u = 0; u < n_utt; ++u) {
-    const ContourTable &t = tabs[u];
-    const size_t at = (size_t)contour_utts_host[(size_t)u].tab0, n = t.c.size();
-    if (!n) continue;
-    std::memcpy(&contour_ftab_host[at], t.c.data(), n * sizeof(unsigned));
-    std::memcpy(&contour_ftab_host[(size_t)ntab + at], t.pitch.data(), n * sizeof(float));
-    std::memcpy(&contour_ftab_host[(size_t)2 * ntab + at], t.gain.data(), n * sizeof(float));
-    if (keep_pitch) std::memcpy(&contour_ftab_host[(size_t)3 * ntab + at], t.pitch.data(), n * sizeof(float));
-  }
-  contour_utts.upload(contour_utts_host.data(), contour_utts_host.size(), stream);
-  contour_ftab.upload(contour_ftab_host.data(), contour_ftab_host.size(), stream);
-  S_pros.alloc((size_t)std::max(dst, 1) * nb);
-  return dst;
-}
-
-void xdtts_griffinlim::contour_launch() {
-  launch_prosody_contour(S.p, S_pros.p, contour_utts.p, (int)contour_utts_host.size(), contour_ftab.p, contour_n_tab, contour_rows, tw.p, stream);
-}
-
-// The timbre stage (timbre.hip) on a magnitude in place, out of place into S_timbre.
-void xdtts_griffinlim::timbre_one(const float *S_in, int F, const Timbre &t) {
-  launch_timbre(S_in, S_timbre.p, nullptr, 1, timbre_utt(0, 0, F, t), F, tw.p, stream);
-}
-void xdtts_griffinlim::timbre_rows(const float *S_in, int rows_all) {
-  launch_timbre(S_in, S_timbre.p, timbre_tab.p, (int)timbre_tab_host.size(), TimbreUtt{}, rows_all, tw.p, stream);
-}
-
-// The pitch tracker (f0.hip).  Buffers grow with the request and stay; a growth happens behind a drained stream (every request
-// path starts there).
-void xdtts_griffinlim::f0_prepare(const std::vector<F0Utt> &utts) {
-  f0_utts_host = utts;
-  int rows = 0;
-  for (const F0Utt &u : utts) rows = std::max(rows, u.row0 + u.F);
-  f0_rows = rows;
-  const size_t n = (size_t)std::max(rows, 1), n_utt = std::max<size_t>(utts.size(), 1);
-  f0_raw.alloc(n);
-  f0_strength.alloc(n);
-  f0_val.alloc(n);
-  f0_ratio.alloc(n);
-  f0_stats.alloc(n_utt);
-  f0_host.reserve(n_utt);
-  f0_utts.upload(f0_utts_host.data(), f0_utts_host.size(), stream);
-}
-
-void xdtts_griffinlim::f0_prepare_contour(const F0Job &job) {
-  std::vector<F0Utt> utts;
-  for (size_t u = 0; u < contour_utts_host.size(); ++u) {
-    const ContourUtt &c = contour_utts_host[u];
-    const PitchTarget &t = job.targets[u];
-    utts.push_back({c.src0, c.F, c.identity ? -1 : c.tab0, t.mode, t.value, t.range});
-  }
-  f0_prepare(utts);
-}
-
-void xdtts_griffinlim::f0_launch(const float *S_dev, const F0Job &job, unsigned *ftab, int n_tab, hipEvent_t between) {
-  const int n_utt = (int)f0_utts_host.size();
-  launch_f0_frames(S_dev, f0_rows, job.opts, job.q_lo, job.q_hi, tw.p, f0_raw.p, f0_strength.p, stream);
-  if (between) HIP_CHECK(hipEventRecord(between, stream));
-  launch_f0_track(f0_raw.p, f0_strength.p, f0_utts.p, n_utt, job.opts.threshold, f0_val.p, f0_ratio.p, f0_stats.p, ftab, n_tab, stream);
-  HIP_CHECK(hipMemcpyAsync(f0_host.p, f0_stats.p, (size_t)n_utt * sizeof(F0Stats), hipMemcpyDeviceToHost, stream));
-}
-
-void xdtts_griffinlim::f0_collect() {
-  static_assert(sizeof(xdtts_f0_stats) == sizeof(F0Stats), "F0Stats is xdtts_f0_stats");
-  last_f0.resize(f0_utts_host.size());
-  if (!last_f0.empty()) std::memcpy(last_f0.data(), f0_host.p, last_f0.size() * sizeof(F0Stats));
-}
-
-// The initial phase by SPSI (phase_spsi.hip) on a magnitude in place.  Scratch grows with the request and stays.
-void xdtts_griffinlim::spsi(const float *S_dev, int F, float2 *ang_out, float2 *tprev_out, unsigned *turns) {
-  const size_t nseg = spsi_segments(F);
-  spsi_map.alloc((size_t)F * nb);
-  spsi_comp.alloc(nseg * nb);
-  spsi_entry.alloc(nseg * nb);
-  launch_spsi(S_dev, F, nullptr, nullptr, (int)nseg, 1, nseg > 1, SpsiBufs{spsi_map.p, spsi_comp.p, spsi_entry.p}, ang_out, tprev_out, turns, stream);
-}
-
-void xdtts_griffinlim::spsi_tables(const std::vector<int> &Fu, SpsiTables &t) {
-  t = SpsiTables();
-  for (int F : Fu) {
-    const int nseg = (int)spsi_segments(F);
-    t.utts.push_back({(int)t.segs.size(), nseg});
-    for (int k = 0; k < nseg; ++k) t.segs.push_back({t.rows + k * SPSI_L, std::min(SPSI_L, F - k * SPSI_L), k == 0, k + 1 == nseg});
-    t.chained = t.chained || nseg > 1;
-    t.rows += F;
-  }
-  spsi_segs.upload(t.segs.data(), t.segs.size(), stream);
-  spsi_utts.upload(t.utts.data(), t.utts.size(), stream);
-  spsi_map.alloc((size_t)t.rows * nb);
-  spsi_comp.alloc(t.segs.size() * nb);
-  spsi_entry.alloc(t.segs.size() * nb);
-}
-
-void xdtts_griffinlim::spsi_batch(const float *S_dev, const SpsiTables &t, float2 *ang_out, float2 *tprev_out, unsigned *turns) {
-  launch_spsi(S_dev, t.rows, spsi_segs.p, spsi_utts.p, (int)t.segs.size(), (int)t.utts.size(), t.chained,
-              SpsiBufs{spsi_map.p, spsi_comp.p, spsi_entry.p}, ang_out, tprev_out, turns, stream);
 }
 
 // The stream stage (stream.hip).
@@ -419,16 +290,16 @@ bool xdtts_griffinlim::persistent_failed() {
 }
 
 // phase init + iterations + final ISTFT; S already in place.  Result in audio (device).
-// phase_init 1 without a caller's phase0: the SPSI stage on g.S (S, or S' behind a prosody stage) writes the angles and the
-// zero previous spectrum, and the engines then take the route of a caller-supplied phase0.  The stage counts as preparation:
+// phase_init 1 without a caller's phase0: the SPSI stage of the magnitude plan in place on g.S (what its run() returned) writes
+// the angles and the zero previous spectrum, and the engines then take the route of a caller-supplied phase0.  The stage counts as preparation:
 // ev.e[1] moves behind it, so last_ms[0] covers mel -> linear, prosody and the initial phase.  A retry after a demotion
 // comes through here again and recomputes the phase from the intact S.
 void xdtts_griffinlim::iterate(const GlBufs &g, const float *phase0_dev, int n_iter) {
   const float alpha = momentum / (1.0f + momentum);
   int TF = 0, nblk = 0;
-  const bool use_spsi = !phase0_dev && phase_init == 1;
+  const bool use_spsi = !phase0_dev && mg.plan.spsi;
   if (use_spsi) {
-    spsi(g.S, g.F, g.ang, g.tprev);
+    mg.spsi(g.S, g.ang, g.tprev);
     HIP_CHECK(hipEventRecord(ev.e[1], stream));
   }
   if (persistent_usable() && gl_persistent_plan(g.F, n_cu, &TF, &nblk)) {
@@ -607,62 +478,46 @@ void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *pha
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
   g->probe_tick();
   g->clear_last();
+  g->mg.prepare(magnitude_plan_checked(MagnitudeRequest::none(1), &b.F, std::vector<Timbre>(), g->mg.phase_init), false);  // (the initial phase alone)
   PinnedGuard host;
   enqueue_run(g, b, phase0_dev, iters, normalise, host);
   collect_run(g, b, phase0_dev, iters, normalise, host, audio, n_samples);
 }
 
-// The loop's buffers for a mel of F frames and prosody p (or none): F' frames, sized for max(F, F')
-static GlBufs request_bufs(xdtts_griffinlim *g, int F, const ProsodyArg &p) {
-  const int Fp = p.frames(0, F);
-  GlBufs b = g->bufs(std::max(F, Fp));  // (before mel -> linear: growing S would drop its contents; in gl_collect nothing grows)
-  b.F = Fp;
-  if (g->timbre_on()) g->S_timbre.alloc((size_t)Fp * g->nb);  // (the identity allocates nothing)
+// The loop's buffers for the magnitude plan in place: F' frames, sized for max(F, F'), reading what the chain's run() returns
+static GlBufs request_bufs(xdtts_griffinlim *g) {
+  GlBufs b = g->bufs((int)g->mg.plan.loop_rows);  // (sized by the enqueue in front of mel -> linear, where growing S drops no contents: nothing grows here)
+  b.F = (int)g->mg.plan.rows.total;
+  b.S = g->mg.loop_S(g->S.p);
   return b;
 }
 // GriffinLim::infer (G1..G6) from a mel in HBM, in two halves for a caller that overlaps the vocoder with other work
 // (xdtts_synthesize_sequence): everything enqueued on g->stream, nothing waited for; then collect_run.  Caller holds g->mu and the
 // chip lock.
-// (p: nothing, a prosody the caller has checked against F, or the table of a contour built for F -- the stage then sits between
-// mel -> linear and the loop, which runs on S' with F' frames; the identity launches nothing.  gl_collect takes the same F and p.)
-void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const ProsodyArg &p) {
-  GlBufs b = request_bufs(g, F, p);
+// (req: checked against F -- the loop runs on what the magnitude chain returns, with F' frames.  gl_collect works from the plan
+// this leaves in place: S, S' and the timbre's output are intact, a demoted engine's retry runs on them again.)
+void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const MagnitudeRequest &req) {
+  MagnitudePlan plan = magnitude_plan_checked(req, &F, g->mg.timbres(), g->mg.phase_init);
+  g->bufs((int)plan.loop_rows);
   HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+  g->mg.prepare(std::move(plan), false);  // (a contour's table goes up on the stream; nothing is waited for)
   g->mel_to_linear(mel_dev_ptr, F);
-  if (p) {
-    g->prosody(p, F);
-    b.S = g->prosody_S(p);
-  }
-  if (g->timbre_on()) {  // the handle's voice: behind the prosody stage (the tracker saw the unmodified voice), in front of the phase
-    g->timbre_one(b.S, b.F, g->timbre);
-    b.S = g->S_timbre.p;
-  }
+  g->mg.run(g->S.p);
   HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
   g->probe_tick();
-  enqueue_run(g, b, nullptr, g->iters, true, host);  // (the sequence hands in a buffer it took from the pool while the frame loop ran)
+  enqueue_run(g, request_bufs(g), nullptr, g->iters, true, host);  // (the sequence hands in a buffer it took from the pool while the frame loop ran)
 }
-void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const ProsodyArg &p) {
-  GlBufs b = request_bufs(g, F, p);
-  if (p) b.S = g->prosody_S(p);
-  if (g->timbre_on()) b.S = g->S_timbre.p;  // (intact: a demoted engine's retry runs on it again)
-  collect_run(g, b, nullptr, g->iters, true, host, audio, n_samples);
+void gl_collect(xdtts_griffinlim *g, PinnedGuard &host, float **audio, size_t *n_samples) {
+  collect_run(g, request_bufs(g), nullptr, g->iters, true, host, audio, n_samples);
 }
 
-void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const ProsodyArg &p, float **audio, size_t *n_samples) {
+void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const MagnitudeRequest &req, float **audio, size_t *n_samples) {
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
   g->clear_last();
   PinnedGuard host;
-  gl_enqueue_from_device_mel(g, mel_dev_ptr, F, host, p);
-  gl_collect(g, F, host, audio, n_samples, p);
-}
-
-// F' = F at rate 1, else max(floor((F - 1) / rate + 0.5), 1) + 1, in double
-size_t prosody_frames(size_t F, float rate) {
-  if (!std::isfinite(rate) || rate < 0.25f || rate > 4.0f) return 0;
-  if (rate == 1.0f) return F;
-  if (F < 2) return 0;
-  const double n = std::floor((double)(F - 1) / (double)rate + 0.5);
-  return (size_t)std::max(n, 1.0) + 1;
+  gl_enqueue_from_device_mel(g, mel_dev_ptr, F, host, req);
+  gl_collect(g, host, audio, n_samples);
+  g->mg.collect();
 }
 
 // The argument rules of xdtts_prosody for a request of n_frames frames; at most 2^20 frames go in (F' <= 2^22: the frame
@@ -674,7 +529,7 @@ void prosody_check(const xdtts_prosody *p, size_t n_frames) {
   if (p->lifter < 1 || p->lifter > 255) fail(XDTTS_ERR_BAD_ARG, "prosody lifter %d is not in [1, 255]", p->lifter);
   if (!std::isfinite(p->log_floor) || !(p->log_floor > 0.f)) fail(XDTTS_ERR_BAD_ARG, "prosody log_floor %g is not a positive number", (double)p->log_floor);
   if (n_frames > ((size_t)1 << 20)) fail(XDTTS_ERR_BAD_ARG, "prosody takes at most 2^20 frames, got %zu", n_frames);
-  if (!prosody_is_identity(*p) && n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "prosody needs at least 2 frames, got %zu", n_frames);
+  if ((p->rate != 1.0f || p->pitch != 1.0f) && n_frames < 2) fail(XDTTS_ERR_BAD_ARG, "prosody needs at least 2 frames, got %zu", n_frames);
 }
 
 static_assert(sizeof(xdtts_prosody_point) == sizeof(ContourPoint) && offsetof(xdtts_prosody_point, gain) == offsetof(ContourPoint, gain),
@@ -700,38 +555,30 @@ void pitch_target_check_array(const xdtts_pitch_target *t, int n_utt) {
   }
 }
 
-void target_plan(const F0Job &job, const xdtts_pitch_target *t, const xdtts_prosody_contour *const *c, int n_utt, const size_t *n_frames,
-                 TargetPlan &p) {
-  p.job = job;
-  p.targets.resize((size_t)n_utt);
-  p.tabs.assign((size_t)n_utt, ContourTable());
-  p.active = p.any_contour = false;
-  for (int u = 0; u < n_utt; ++u) {
-    std::memcpy(&p.targets[(size_t)u], &t[u], sizeof(PitchTarget));
-    p.active = p.active || !pitch_target_is_identity(p.targets[(size_t)u]);
-    p.any_contour = p.any_contour || (c && c[u]);
+static_assert(sizeof(xdtts_prosody) == sizeof(Prosody) && offsetof(xdtts_prosody, log_floor) == offsetof(Prosody, log_floor) &&
+                  sizeof(xdtts_prosody_contour) == sizeof(Contour) && offsetof(xdtts_prosody_contour, log_floor) == offsetof(Contour, log_floor),
+              "the layouts of magnitude_plan.h");
+MagnitudeRequest magnitude_request(const MagnitudeAsk &a, int n_utt, const size_t *n_frames, int first) {
+  if (a.job) {
+    std::vector<ContourTable> tabs;
+    std::vector<PitchTarget> targets((size_t)n_utt);
+    std::memcpy(targets.data(), a.tg, (size_t)n_utt * sizeof(PitchTarget));
+    bool active = false, any_contour = false;
+    bad_arg_if(target_tables(targets.data(), reinterpret_cast<const Contour *const *>(a.tc), n_utt, n_frames, tabs, &active, &any_contour));
+    if (active || a.tracked) return MagnitudeRequest::targets(std::move(tabs), *a.job, std::move(targets));
+    return any_contour ? MagnitudeRequest::contours(std::move(tabs)) : MagnitudeRequest::none(n_utt);  // (the bits of the contour entry, or of the plain one)
   }
-  for (int u = 0; u < n_utt; ++u) {
-    const size_t F = n_frames[u];
-    ContourTable &tab = p.tabs[(size_t)u];
-    if (c && c[u]) {
-      contour_check_at(c[u], u, F);
-      contour_table(*c[u], F, tab);
-    } else {
-      tab.F = tab.Fout = (int)F;  // (the identity: no table)
+  if (a.cont) {
+    std::vector<ContourTable> tabs((size_t)n_utt);
+    for (int u = 0; u < n_utt; ++u) {
+      first < 0 ? contour_check(&a.cont[u], n_frames[u]) : contour_check_at(&a.cont[u], first + u, n_frames[u]);
+      contour_table(a.cont[u], n_frames[u], tabs[(size_t)u]);
     }
-    if (p.active && (F < 1 || F > F0_MAX_FRAMES)) fail(XDTTS_ERR_BAD_ARG, "utterance %d: the pitch tracker takes 1 .. %zu frames, got %zu", u, F0_MAX_FRAMES, F);
-    if (pitch_target_is_identity(p.targets[(size_t)u])) continue;
-    if (F < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: a pitch target that is not the identity takes 2 .. %zu frames, got %zu", u, F0_MAX_FRAMES, F);
-    if (tab.identity) {  // the rate-1 table: c[m] = 65536 m, pitch 1, gain 1, F' = F
-      tab.identity = false;
-      tab.c.resize(F);
-      for (size_t m = 0; m < F; ++m) tab.c[m] = (uint32_t)(65536u * m);
-      tab.pitch.assign(F, 1.0f);
-      tab.gain.assign(F, 1.0f);
-    }
+    return MagnitudeRequest::contours(std::move(tabs));
   }
-  p.job.targets = p.targets.data();
+  if (!a.pros) return MagnitudeRequest::none(n_utt);
+  for (int u = 0; n_frames && u < n_utt; ++u) first < 0 ? prosody_check(&a.pros[u], n_frames[u]) : prosody_check_at(&a.pros[u], first + u, n_frames[u]);
+  return MagnitudeRequest::uniform(reinterpret_cast<const Prosody *>(a.pros), n_utt);
 }
 
 static const ContourPoint *contour_points(const xdtts_prosody_contour &c) { return reinterpret_cast<const ContourPoint *>(c.points); }
@@ -777,64 +624,27 @@ void prosody_check_array(const xdtts_prosody *p, int n_utt) {
 // fbase[u] .. fbase[u] + Fu[u].  mel -> linear is one GEMM over all frames, and the persistent kernel takes as many
 // utterances per launch as fit one workgroup per CU (gl_plan.h: gl_batch_plan).  Caller holds g->mu.  The reads of the mel
 // are enqueued on g->stream: the caller orders them behind the mel's producer (a stream sync or an event wait on g->stream).
-// pros: nothing, or one prosody per utterance, each checked by the caller against its frame count, or one contour table per
-// utterance, each built for its frame count.  With one that is not the identity the ragged stage (k_prosody_batch, or
-// k_prosody_contour) follows the GEMM: S [sum F_u] -> S_pros [sum F'_u], and everything behind it --
-// the rows of the loop's arrays, the packing into launches, the audio -- works from F'_u and reads S_pros.  Without one,
+// req: what the caller has checked against (or built for) the frame counts.  With an utterance that is not the identity the
+// ragged stages (magnitude.h) follow the GEMM: S [sum F_u] -> S_pros [sum F'_u], and everything behind them -- the rows of the
+// loop's arrays, the packing into launches, the audio -- works from F'_u and reads what the chain returns.  Without one,
 // nothing new is launched.
 void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fin, float **audios, size_t *n_samples,
-                          const ProsodyArg &pros) {
+                          const MagnitudeRequest &req) {
   const int n_utt = (int)Fin.size();
-  bool staged = false;
-  for (int u = 0; pros && u < n_utt; ++u) staged = staged || !pros.identity(u);
-  const bool contour = staged && pros.contour;
-  Rows in, rows;  // the mel's frames F_u, and the frames behind the stage: F'_u
-  std::vector<ProsodyUtt> ptab;
-  std::vector<size_t> loop_n((size_t)n_utt);  // the loop's samples per utterance, back to back in its audio
-  size_t Ntot = 0;
-  for (int u = 0; u < n_utt; ++u) {
-    const int Fp = staged ? pros.frames(u, Fin[u]) : Fin[u];
-    if (staged && !contour) {
-      const xdtts_prosody &p = pros.uniform[u];
-      ptab.push_back({(int)in.total, Fin[u], (int)rows.total, Fp, p.rate, p.pitch, p.lifter, p.log_floor});
-    }
-    rows_add(in, (size_t)Fin[u], (size_t)1 << 24, "batch too large");
-    rows_add(rows, (size_t)Fp, (size_t)1 << 24, "batch too large");
-    loop_n[(size_t)u] = (size_t)g->hop * (size_t)(Fp - 1);
-    Ntot += loop_n[(size_t)u];
-  }
-  const std::vector<long long> abase = delivery_bases(loop_n);
-  const std::vector<int> &Fu = rows.F, &fbase = rows.row0;
+  MagnitudePlan mplan = magnitude_plan_checked(req, Fin.data(), g->mg.timbres(), g->mg.phase_init);
   HIP_CHECK(hipSetDevice(g->device));
   hipStream_t st = g->stream;
-  std::vector<int> fl(rows.total);
-  for (int u = 0; u < n_utt; ++u)
-    for (int f = 0; f < Fu[u]; ++f) fl[(size_t)fbase[u] + f] = f;
-  g->frame_local.upload(fl.data(), fl.size(), st);
-  const bool use_spsi = g->phase_init == 1;
-  xdtts_griffinlim::SpsiTables spsi_tab;
-  if (use_spsi) g->spsi_tables(Fu, spsi_tab);  // (of the frames behind the prosody stage)
-  GlBufs all = g->bufs((int)std::max(in.total, rows.total));
+  GlBufs all = g->bufs((int)mplan.loop_rows);
+  g->mg.prepare(std::move(mplan), true);  // (drains st behind the tables)
+  const Rows &in = g->mg.plan.in, &rows = g->mg.plan.rows;  // the mel's frames F_u, and the frames behind the stages: F'_u
+  const std::vector<int> &Fu = rows.F, &fbase = rows.row0;
   all.F = (int)rows.total;
-  if (staged) {
-    if (contour) {
-      g->contour_upload(pros.contour, n_utt, pros.f0 != nullptr);  // (its rows are `in` and `rows`: the utterances back to back)
-      if (pros.f0) g->f0_prepare_contour(*pros.f0);
-    }
-    else g->pros_tab.upload(ptab.data(), ptab.size(), st);
-    g->S_pros.alloc(rows.total * (size_t)g->nb);
-    all.S = g->S_pros.p;
-  }
-  // The handle's timbre: one setting for every utterance, the ragged stage on the rows behind the prosody stage (src0 = dst0).
-  const bool timbre = g->timbre_on();
-  const float *const S_staged = all.S;  // what the timbre stage reads: S, or S_pros
-  if (timbre) {
-    g->timbre_tab_host.clear();
-    for (int u = 0; u < n_utt; ++u) g->timbre_tab_host.push_back(timbre_utt(fbase[u], fbase[u], Fu[u], g->timbre));
-    g->timbre_tab.upload(g->timbre_tab_host.data(), g->timbre_tab_host.size(), st);
-    g->S_timbre.alloc(rows.total * (size_t)g->nb);
-    all.S = g->S_timbre.p;
-  }
+  all.S = g->mg.loop_S(g->S.p);
+  const bool use_spsi = g->mg.plan.spsi;
+  std::vector<size_t> loop_n((size_t)n_utt);  // the loop's samples per utterance, back to back in its audio
+  size_t Ntot = 0;
+  for (int u = 0; u < n_utt; ++u) Ntot += loop_n[(size_t)u] = (size_t)g->hop * (size_t)(Fu[(size_t)u] - 1);
+  const std::vector<long long> abase = delivery_bases(loop_n);
   g->audio.alloc(std::max<size_t>(Ntot, 1));
   // What is delivered (delivery_plan.h): at 22050 the loop's audio where it lies; at another rate the resampled utterances back
   // to back, and everything behind the loop works from those.  Counts, places and buffer sizes do not depend on the order of the
@@ -843,7 +653,6 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
   const DeliveryPlan sized = delivery_plan_checked(stages, loop_n, abase, delivery_identity((size_t)n_utt));
   const std::vector<int> &dn = sized.dn;
   g->dl.size(sized);
-  HIP_CHECK(hipStreamSynchronize(st));  // the host vector above
   const float alpha = g->momentum / (1.0f + g->momentum);
   g->clear_last();
   std::lock_guard<ChipLock> chip(chip_mutex(g->device));
@@ -852,14 +661,10 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     // mel -> linear, the ragged stages, the initial phase: all from the mel, so a retry starts from an intact S / S'
     HIP_CHECK(hipEventRecord(g->ev.e[0], st));
     g->mel_to_linear(mel_dev_all, (int)in.total);
-    if (contour) {
-      if (pros.f0) g->f0_launch(g->S.p, *pros.f0, g->contour_ftab.p, g->contour_n_tab);  // (from the intact S: a retry writes the same pitches)
-      g->contour_launch();
-    } else if (staged) launch_prosody_batch(g->S.p, g->S_pros.p, g->pros_tab.p, n_utt, (int)rows.total, g->tw.p, st);
-    if (timbre) g->timbre_rows(S_staged, (int)rows.total);  // (out of place: a retry finds S and S_pros intact)
-    if (use_spsi) g->spsi_batch(all.S, spsi_tab, all.ang, all.tprev);
+    g->mg.run(g->S.p);  // (out of place: a retry writes the same S_pros and S_timbre from the intact S)
+    if (use_spsi) g->mg.spsi(all.S, all.ang, all.tprev);
     HIP_CHECK(hipEventRecord(g->ev.e[1], st));
-    if (!use_spsi) launch_gl_phase_init_batch(all, g->seed, g->frame_local.p, st);
+    if (!use_spsi) launch_gl_phase_init_batch(all, g->seed, g->mg.frame_local.p, st);
     // the plan, on the host while the device works on the above.  A handle without a usable persistent engine (demoted: the
     // retry) gets the empty one: everything runs one by one on the launch-per-iteration kernels.
     const GlBatchPlan plan = gl_batch_plan(Fu, g->hop, g->persistent_usable() ? g->n_cu : 0, g->per_cu4, g->gopts.batch_shape,
@@ -932,6 +737,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
       n_samples[u] = g->dl.out_samples((size_t)u);  // (dn[u], or n_out of the silence stage: the buffer holds dn[u] floats)
       g->dl.push_last((size_t)dp.tab_pos[(size_t)u]);
     }
+    g->mg.collect();
     return;
   }
 }

@@ -4,13 +4,12 @@
 #include "delivery.h"
 #include "engine_gate.h"
 #include "kernels.h"
+#include "magnitude.h"
 #include "prosody_contour.h"
 #include "runtime.h"
 
 namespace xdtts {
-// xdtts_prosody (include/xdtts.h): the argument rules, F' and the case that launches nothing.  Host arithmetic only.
-inline bool prosody_is_identity(const xdtts_prosody &p) { return p.rate == 1.0f && p.pitch == 1.0f; }
-size_t prosody_frames(size_t F, float rate);                   // 0 for a bad argument
+// xdtts_prosody (include/xdtts.h): the argument rules.  Host arithmetic only.
 void prosody_check(const xdtts_prosody *p, size_t n_frames);  // fails with XDTTS_ERR_BAD_ARG and a message
 // xdtts_prosody_contour (include/xdtts.h) on top of prosody_contour.h, which knows no status codes: the argument rules for a
 // request of n_frames frames (fails with XDTTS_ERR_BAD_ARG, the message names the field and the point), and the table.
@@ -18,45 +17,29 @@ void contour_check(const xdtts_prosody_contour *c, size_t n_frames);
 void contour_check_at(const xdtts_prosody_contour *c, int u, size_t n_frames);  // ... for utterance u of a batch
 void contour_check_array(const xdtts_prosody_contour *c, int n_utt);            // the fields of n_utt contours, before a handle is looked at
 void contour_table(const xdtts_prosody_contour &c, size_t n_frames, ContourTable &t);  // (checked arguments)
-// What a request path puts between mel -> linear and the loop, as ONE argument: nothing, a uniform prosody (checked by the
-// caller), or the table of a contour (built by the caller once the frame count is known).  The single-utterance path reads
-// element 0, the batch path one element per utterance.
-// With a pitch target (f0_plan.h) the tables are a TargetPlan's and `f0` is its job: the tracker and the target run on S in
-// front of the contour stage and multiply their ratios into the tables' pitches on the device.
-struct F0Job {
-  F0Opts opts;
-  int q_lo = 0, q_hi = 0;
-  const PitchTarget *targets = nullptr;  // one per utterance
-};
-struct ProsodyArg {
-  const xdtts_prosody *uniform = nullptr;
-  const ContourTable *contour = nullptr;
-  const F0Job *f0 = nullptr;  // (with `contour` only)
-  ProsodyArg() = default;
-  ProsodyArg(std::nullptr_t) {}
-  ProsodyArg(const xdtts_prosody *p) : uniform(p) {}
-  ProsodyArg(const ContourTable *t, const F0Job *j = nullptr) : contour(t), f0(j) {}
-  explicit operator bool() const { return uniform || contour; }
-  bool identity(int u) const { return contour ? contour[u].identity : (!uniform || prosody_is_identity(uniform[u])); }
-  int frames(int u, int F) const { return contour ? contour[u].Fout : (uniform ? (int)prosody_frames((size_t)F, uniform[u].rate) : F); }  // F'
-};
 // xdtts_f0_opts / xdtts_pitch_target on top of f0_plan.h, which knows no status codes: the checked options (null = the default)
 // with their quefrency range, and the targets of n_utt utterances; both fail with XDTTS_ERR_BAD_ARG and need no handle.
 F0Job f0_job_checked(const xdtts_f0_opts *o);
 void pitch_target_check_array(const xdtts_pitch_target *t, int n_utt);
-// What a target request runs on, built once the frame counts are known (checked options and targets): the contour tables --
-// the caller's, or the rate-1 table where an utterance under a target that is not the identity has no contour of its own (its
-// identity flag is off: the stage reads the pitches the device writes) -- and the job.  active = some target is not the
-// identity; without it arg() is the request of the contours alone (or nothing: the bits of the plain entry).
-struct TargetPlan {
-  F0Job job;
-  std::vector<PitchTarget> targets;
-  std::vector<ContourTable> tabs;
-  bool active = false, any_contour = false;
-  ProsodyArg arg() const { return active ? ProsodyArg(tabs.data(), &job) : (any_contour ? ProsodyArg(tabs.data()) : ProsodyArg()); }
+// What an entry asks for between mel -> linear and the loop, as the boundary received it (fields checked, frame counts not yet
+// known): nothing, one prosody per utterance, one contour per utterance, or a tracker job with one target per utterance over
+// contours that may be null (tracked: the target hook's -- the tracker runs even where every target is the identity).
+struct MagnitudeAsk {
+  const xdtts_prosody *pros = nullptr;
+  const xdtts_prosody_contour *cont = nullptr;
+  const F0Job *job = nullptr;
+  const xdtts_pitch_target *tg = nullptr;
+  const xdtts_prosody_contour *const *tc = nullptr;
+  bool tracked = false;
+  static MagnitudeAsk prosody(const xdtts_prosody *p) { return {p, nullptr, nullptr, nullptr, nullptr, false}; }
+  static MagnitudeAsk contour(const xdtts_prosody_contour *c) { return {nullptr, c, nullptr, nullptr, nullptr, false}; }
+  static MagnitudeAsk target(const F0Job *j, const xdtts_pitch_target *t, const xdtts_prosody_contour *const *c, bool tracked = false) { return {nullptr, nullptr, j, t, c, tracked}; }
+  MagnitudeAsk at(int u) const { return {pros ? pros + u : nullptr, cont ? cont + u : nullptr, job, tg ? tg + u : nullptr, tc ? tc + u : nullptr, tracked}; }  // utterance u alone
 };
-void target_plan(const F0Job &job, const xdtts_pitch_target *t, const xdtts_prosody_contour *const *c, int n_utt, const size_t *n_frames,
-                 TargetPlan &p);
+// ... and the request it becomes once the frame counts are known: each utterance checked against its count (XDTTS_ERR_BAD_ARG;
+// first >= 0: the utterances are first .. of a batch or sequence and the message names them), the contour tables built.
+// n_frames == null (the uniform form or nothing, which need no count to be built): for frames() alone.
+MagnitudeRequest magnitude_request(const MagnitudeAsk &a, int n_utt, const size_t *n_frames, int first = -1);
 // The options of a stream request (stream_plan.h, which knows no status codes), before a handle is looked at; null = the default
 inline StreamOpts stream_opts_checked(const xdtts_stream_opts *o) {
   StreamOpts s = stream_opts_default();
@@ -65,7 +48,7 @@ inline StreamOpts stream_opts_checked(const xdtts_stream_opts *o) {
   return s;
 }
 // xdtts_timbre (include/xdtts.h) on top of timbre_plan.h, which knows no status codes: the checked setting (null = the default,
-// the identity), before a handle is looked at; and the record of one utterance of the stage.
+// the identity), before a handle is looked at.
 inline Timbre timbre_checked(const xdtts_timbre *t) {
   static_assert(sizeof(xdtts_timbre) == sizeof(Timbre) && sizeof(Timbre) == 20, "Timbre is xdtts_timbre");
   Timbre s = timbre_default();
@@ -73,26 +56,22 @@ inline Timbre timbre_checked(const xdtts_timbre *t) {
   bad_arg_if(timbre_check(s));
   return s;
 }
-inline TimbreUtt timbre_utt(int src0, int dst0, int F, const Timbre &t) {
-  return TimbreUtt{src0, dst0, F, t.vtl, t.breath, t.seed, t.lifter, t.log_floor};
-}
-// Rows::add (gl_plan.h, which knows no status codes) inside a request: past the cap it fails with XDTTS_ERR_BAD_ARG and the text
-inline void rows_add(Rows &r, size_t rows, size_t cap, const char *too_large) {
+// The *_plan.h headers know no status codes: past a cap they throw std::length_error, which inside a request fails with
+// XDTTS_ERR_BAD_ARG and the text -- Rows::add (gl_plan.h), magnitude_plan (magnitude_plan.h: 2^24 rows) and delivery_plan
+// (delivery_plan.h: more than 2^31 - 1 delivered samples)
+template <class F>
+inline auto bad_arg_past_cap(F f) -> decltype(f()) {
   try {
-    r.add(rows, cap, too_large);
+    return f();
   } catch (const std::length_error &e) {
     fail(XDTTS_ERR_BAD_ARG, "%s", e.what());
   }
 }
-// ... and delivery_plan (delivery_plan.h) likewise: more than 2^31 - 1 delivered samples fail with XDTTS_ERR_BAD_ARG and the text
-inline DeliveryPlan delivery_plan_checked(const DeliveryStages &s, const std::vector<size_t> &n, const std::vector<long long> &base,
-                                          const std::vector<int> &order) {
-  try {
-    return delivery_plan(s, n, base, order);
-  } catch (const std::length_error &e) {
-    fail(XDTTS_ERR_BAD_ARG, "%s", e.what());
-  }
-}
+inline void rows_add(Rows &r, size_t rows, size_t cap, const char *too_large) { bad_arg_past_cap([&] { r.add(rows, cap, too_large); }); }
+template <class... A>
+inline MagnitudePlan magnitude_plan_checked(const A &...a) { return bad_arg_past_cap([&] { return magnitude_plan(a...); }); }
+template <class... A>
+inline DeliveryPlan delivery_plan_checked(const A &...a) { return bad_arg_past_cap([&] { return delivery_plan(a...); }); }
 }  // namespace xdtts
 
 struct xdtts_griffinlim {
@@ -119,7 +98,6 @@ struct xdtts_griffinlim {
   // persistent engine (griffinlim.hip: k_gl_persistent)
   DevBuf<unsigned long long> xch;  // neighbour-overlap granules
   DevBuf<xdtts::GlSeg> segs;              // vocoder batch: per-workgroup segment table
-  DevBuf<int> frame_local;         // vocoder batch: row -> frame index inside its utterance
   DevBuf<int> gl_err;
   int *host_err = nullptr;         // pinned
   unsigned epoch = 0;              // tag base; tags are never reused while xch lives
@@ -148,76 +126,14 @@ struct xdtts_griffinlim {
   xdtts::Events an_ev;
   float an_ms[3] = {0, 0, 0};
 
-  // prosody (prosody.hip): the modified magnitude [F'][nb]; S itself stays as mel -> linear left it
-  DevBuf<float> S_pros;
-  DevBuf<xdtts::ProsodyUtt> pros_tab;  // vocoder batch: per-utterance rows and parameters of the ragged stage (k_prosody_batch)
-  // ... and the contour form (k_prosody_contour), single call and batch alike: the per-utterance records and the concatenated
-  // frame table {c, pitch, gain}.  The host vectors are the upload's source: they stay until the next contour request of this
-  // handle, which every path starts behind a drained stream.
-  DevBuf<xdtts::ContourUtt> contour_utts;
-  DevBuf<unsigned> contour_ftab;
-  std::vector<xdtts::ContourUtt> contour_utts_host;
-  std::vector<unsigned> contour_ftab_host;
-  int contour_n_tab = 0, contour_rows = 0;  // entries per array of the frame table; sum of F'
-  // Uploads (on the stream) the records and tables of n_utt utterances lying back to back in S (rows F_u) and S_pros (rows
-  // F'_u, allocated here); returns sum F'.  contour_launch() then runs the stage, any number of times (a retry).
-  // (keep_pitch: a fourth array behind the three, the pitches once more -- what k_f0_track multiplies its ratios into `pitch` from)
-  int contour_upload(const xdtts::ContourTable *tabs, int n_utt, bool keep_pitch = false);
-  void contour_launch();
-  // pitch tracker and pitch targets (f0.hip): raw / strength / f0 / ratio of the rows of a request, the per-utterance records
-  // and stats.  f0_prepare() sizes the buffers and uploads the records (on the stream; the host vector stays until the next
-  // tracker request of this handle); f0_launch() runs k_f0_frames on S_dev [rows][nb] and k_f0_track and sends the stats to
-  // the pinned buffer, any number of times (a retry).  ftab: the contour table whose pitches take the ratios, or null.
-  DevBuf<float> f0_raw, f0_strength, f0_val, f0_ratio;
-  DevBuf<xdtts::F0Stats> f0_stats;
-  DevBuf<xdtts::F0Utt> f0_utts;
-  std::vector<xdtts::F0Utt> f0_utts_host;
-  xdtts::PinnedArray<xdtts::F0Stats> f0_host;
-  int f0_rows = 0;
-  std::vector<xdtts_f0_stats> last_f0;  // xdtts_griffinlim_last_f0
-  void f0_prepare(const std::vector<xdtts::F0Utt> &utts);
-  void f0_prepare_contour(const xdtts::F0Job &job);  // ... from the records contour_upload() has just built
-  void f0_launch(const float *S_dev, const xdtts::F0Job &job, unsigned *ftab, int n_tab, hipEvent_t between = nullptr);
-  void f0_collect();  // behind a drained stream: the pinned stats -> last_f0
-
-  // timbre (timbre.hip): the voice of this handle -- vocal-tract length and breathiness on the magnitude that would enter the
-  // loop (S, or S_pros behind a prosody stage), out of place into S_timbre [F'][nb]; S and S_pros stay as their stages left them.
-  // The identity (the default) launches and allocates nothing.  The table of the ragged form and its host vector, the upload's
-  // source, stay until the next request of this handle, which every path starts behind a drained stream.
-  xdtts::Timbre timbre = xdtts::timbre_default();
-  bool timbre_on() const { return !xdtts::timbre_is_identity(timbre); }
-  DevBuf<float> S_timbre;
-  DevBuf<xdtts::TimbreUtt> timbre_tab;
-  std::vector<xdtts::TimbreUtt> timbre_tab_host;
-  // One utterance: S_in [F][nb] -> S_timbre (allocated by the caller) under t, one launch on the stream, nothing uploaded.
-  void timbre_one(const float *S_in, int F, const xdtts::Timbre &t);
-  // Ragged: the records of timbre_tab_host (uploaded by the caller as timbre_tab), rows_all rows, one launch; any number of
-  // times (a retry).
-  void timbre_rows(const float *S_in, int rows_all);
-
-  // initial phase (phase_spsi.hip): 0 = the seeded random stream, 1 = SPSI on the magnitude that enters the loop
-  int phase_init = 0;
-  DevBuf<uint2> spsi_map, spsi_comp;
-  DevBuf<unsigned> spsi_entry, spsi_turns;  // spsi_turns: the parity hooks only
-  DevBuf<xdtts::SpsiSeg> spsi_segs;         // vocoder batch: the segments of all utterances
-  DevBuf<xdtts::SpsiUtt> spsi_utts;
-  // The SPSI stage on the stream: S [F][nb] -> ang, tprev (and turns, if wanted).  One utterance ...
-  void spsi(const float *S_dev, int F, float2 *ang_out, float2 *tprev_out, unsigned *turns = nullptr);
-  // ... and the ragged form: spsi_tables() (uploads; the caller drains the stream before the host vectors go), then any
-  // number of spsi_batch() launches on the rows the tables describe.
-  struct SpsiTables {
-    std::vector<xdtts::SpsiSeg> segs;
-    std::vector<xdtts::SpsiUtt> utts;
-    int rows = 0;
-    bool chained = false;
-  };
-  void spsi_tables(const std::vector<int> &Fu, SpsiTables &t);
-  void spsi_batch(const float *S_dev, const SpsiTables &t, float2 *ang_out, float2 *tprev_out, unsigned *turns = nullptr);
+  // The magnitude chain between mel -> linear and the loop (magnitude.h): tracker and targets, prosody or contour, timbre, the SPSI
+  // initial phase -- settings, tables, buffers, the tracker's stats of the last call, and the one runner of every request path.
+  xdtts::Magnitude mg;
 
   // The delivery chain behind the loop (delivery.h): output rate, compressor, output normalisation or loudness with or without
   // the limiter -- settings, tables, buffers, the stats of the last call, and the one runner of every request path.
   xdtts::Delivery dl;
-  void clear_last() { dl.clear_last(), last_f0.clear(); }
+  void clear_last() { dl.clear_last(), mg.last_f0.clear(); }
 
   // stream (stream.hip): the utterances of a sequence joined with their gaps, faded, levelled and encoded -- the stage behind
   // everything above (xdtts_griffinlim_join, xdtts_synthesize_document).
@@ -250,11 +166,6 @@ struct xdtts_griffinlim {
   // into its rows of S [rows.total][nb], on the stream.  bufs(>= rows.total) first.
   void upload_rows(const float *const *S_host, const xdtts::Rows &rows);
   void mel_to_linear(const float *mel_dev_ptr, int F);
-  // S [F][nb] -> S_pros [F'][nb] in one launch on the stream; returns F'.  The identity launches nothing and returns F.
-  // The caller then points GlBufs.S at prosody_S(p) with F' frames; its bufs() was sized for max(F, F').
-  // (a contour: its table goes up on the stream in front of the launch of k_prosody_contour)
-  int prosody(const xdtts::ProsodyArg &p, int F);
-  float *prosody_S(const xdtts::ProsodyArg &p) { return p.identity(0) ? S.p : S_pros.p; }
   // Once per API call (never inside a retry attempt): a demoted handle counts the call and, after PROBE_AFTER of them,
   // gives the persistent engine another try -- the cause of a timed-out exchange may have been transient.
   void probe_tick() { gate.tick(); }
@@ -279,17 +190,17 @@ void mel_filter_bank(double sr, int n_fft, int n_mels, double fmin, double fmax,
 // The loop alone on the S in place (infer_linear: a caller's phase0 and iteration count, no normalisation); takes the chip lock.
 void gl_iterate_and_fetch(xdtts_griffinlim *g, const GlBufs &b, const float *phase0_dev, int iters, float **audio, size_t *n_samples,
                           bool normalise);
-// GriffinLim::infer from a mel in HBM, the one single-utterance request path: chip lock, gl_enqueue_from_device_mel, gl_collect.
-// (p: nothing, a checked prosody or a contour's table -- the single-utterance stage behind mel -> linear, last_ms[0] covers
-// both; F stays the mel's frame count everywhere)
-void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const ProsodyArg &p, float **audio, size_t *n_samples);
-// ... and its two halves for a caller that holds the chip lock itself and works between them (the sequence entry)
-void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const ProsodyArg &p = ProsodyArg());
-void gl_collect(xdtts_griffinlim *g, int F, PinnedGuard &host, float **audio, size_t *n_samples, const ProsodyArg &p = ProsodyArg());
-// (pros: nothing, or one checked prosody / one contour table per utterance -- the ragged stage behind the one mel -> linear
-// GEMM; audios[u] then has hop * (F'_u - 1) samples)
+// GriffinLim::infer from a mel in HBM, the one single-utterance request path: chip lock, gl_enqueue_from_device_mel, gl_collect,
+// the tracker's stats.  (req: the magnitude chain behind mel -> linear, last_ms[0] covers both; F is the mel's frame count)
+void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const MagnitudeRequest &req, float **audio, size_t *n_samples);
+// ... and its two halves for a caller that holds the chip lock itself and works between them (the sequence entry); gl_collect
+// works from the magnitude plan in place, the one of the enqueue in front of it
+void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const MagnitudeRequest &req);
+void gl_collect(xdtts_griffinlim *g, PinnedGuard &host, float **audio, size_t *n_samples);
+// (req: one utterance per element of Fu -- the ragged stages behind the one mel -> linear GEMM; audios[u] then has
+// hop * (F'_u - 1) samples)
 void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples,
-                          const ProsodyArg &pros = ProsodyArg());
+                          const MagnitudeRequest &req);
 // The fields of n_utt prosodies before any handle is looked at (entries that take an array): fails with XDTTS_ERR_BAD_ARG,
 // the message names the field and the utterance.
 void prosody_check_array(const xdtts_prosody *p, int n_utt);

@@ -7,6 +7,7 @@
 #include "gl_plan.h"
 #include "limiter_plan.h"
 #include "loudness_plan.h"
+#include "magnitude_plan.h"
 #include "resample_plan.h"
 #include "stream_plan.h"
 #include "timbre_plan.h"
@@ -312,29 +313,18 @@ void launch_spec_distance(const float *X, const float *St, size_t n, double *par
 // ---- prosody (prosody.hip): speaking rate and pitch on the magnitude, between mel -> linear and the loop -------------------------
 // S [F][513] -> Sout [Fout][513]: frames resampled by `rate` (linear interpolation in time), then, unless pitch == 1, each frame's
 // log fine structure (what a cepstral lifter of `lifter` bins leaves of ln max(., log_floor)) resampled by `pitch` on the frequency
-// axis under the unchanged envelope.  Fout = prosody_frames(F, rate) (griffinlim_handle.h); F >= 2 unless rate == 1.  One launch.
+// axis under the unchanged envelope.  Fout = prosody_frames(F, rate) (magnitude_plan.h); F >= 2 unless rate == 1.  One launch.
 void launch_prosody(const float *S, float *Sout, int F, int Fout, float rate, float pitch, int lifter, float log_floor,
                     const float2 *tw, hipStream_t s);
 // The ragged form, one launch for the utterances of a batch: utterance u's F rows start at row src0 of S, its Fout =
 // prosody_frames(F, rate) rows at row dst0 of Sout (dst0 ascending, the utterances back to back: dst0[u + 1] = dst0[u] + Fout[u]);
 // Fout_all = the sum.  tab is device memory.  Every row equals what launch_prosody gives for the utterance alone, bit for bit;
-// an utterance with rate == pitch == 1 is copied.
-struct ProsodyUtt {
-  int src0, F, dst0, Fout;
-  float rate, pitch;
-  int lifter;
-  float log_floor;
-};
+// an utterance with rate == pitch == 1 is copied.  (struct ProsodyUtt, ContourUtt, TimbreUtt: magnitude_plan.h)
 void launch_prosody_batch(const float *S, float *Sout, const ProsodyUtt *tab, int n_utt, int Fout_all, const float2 *tw, hipStream_t s);
 // The contour form (xdtts_prosody_contour), single call (n_utt = 1) and ragged batch in one kernel: utterance u's F rows start at
 // row src0 of S, its Fout rows at row dst0 of Sout (ascending, back to back), its frame table at entry tab0 of ftab.  ftab
 // (device) = the cumulative slownesses c of all utterances, then their pitches, then their gains (float bits), n_tab entries
 // each: ContourTable of prosody_contour.h, concatenated.  identity != 0: the rows are copied, no table is read.
-struct ContourUtt {
-  int src0, F, dst0, Fout, tab0, lifter;
-  float log_floor;
-  int identity;
-};
 void launch_prosody_contour(const float *S, float *Sout, const ContourUtt *utt, int n_utt, const unsigned *ftab, int n_tab, int Fout_all,
                             const float2 *tw, hipStream_t s);
 
@@ -345,13 +335,6 @@ void launch_prosody_contour(const float *S, float *Sout, const ContourUtt *utt, 
 // (include/xdtts.h, timbre_plan.h).  An utterance with vtl == 1 and breath == 0 is copied.  tab (device memory, n_utt records),
 // or nullptr: n_utt = 1 and the record is `one`, a kernel argument -- nothing is uploaded.  One launch of one kernel either
 // way; a row has the same bits in both forms.
-struct TimbreUtt {
-  int src0, dst0, F;
-  float vtl, breath;
-  uint32_t seed;
-  int lifter;
-  float log_floor;
-};
 void launch_timbre(const float *S, float *Sout, const TimbreUtt *tab, int n_utt, const TimbreUtt &one, int rows_all, const float2 *tw,
                    hipStream_t s);
 
@@ -360,37 +343,19 @@ void launch_timbre(const float *S, float *Sout, const TimbreUtt *tab, int n_utt,
 // its neighbours); o, q_lo, q_hi: checked options and their quefrency range (f0_plan.h).  One launch.
 void launch_f0_frames(const float *S, int rows, const F0Opts &o, int q_lo, int q_hi, const float2 *tw, float *raw, float *strength,
                       hipStream_t s);
-// One utterance of launch_f0_track: rows row0 .. row0 + F (1 <= F <= F0_MAX_FRAMES) of raw / strength / f0 / ratio; tab0 = its entry
-// in the contour frame table whose pitch slice takes the ratios, -1 = none; the fields of its xdtts_pitch_target.
-struct F0Utt {
-  int row0, F, tab0, mode;
-  float value, range;
-};
-// One workgroup per utterance: f0, ratio (rows as raw), stats[u], and for tab0 >= 0 the table's pitches
+// One workgroup per utterance (struct F0Utt: magnitude_plan.h): f0, ratio (rows as raw), stats[u], and for tab0 >= 0 the table's pitches
 // ftab[n_tab + tab0 + t] = clamp(ftab[3 n_tab + tab0 + t] * ratio[t]) -- ftab = the table of launch_prosody_contour with a
 // FOURTH array behind the three it reads: the pitches before the target.  ftab may be null where no utterance has a table.
 void launch_f0_track(const float *raw, const float *strength, const F0Utt *utts_dev, int n_utt, float threshold, float *f0, float *ratio,
                      F0Stats *stats, unsigned *ftab, int n_tab, hipStream_t s);
 
 // ---- initial phase by Single Pass Spectrogram Inversion (phase_spsi.hip; phase_init mode 1, include/xdtts.h) -----------------
-// The recurrence over the frames runs as a scan over segments of SPSI_L consecutive frames of one utterance: the dependent
-// depth is 2 SPSI_L + F / SPSI_L LDS gathers (82 at F = 800 with 24; 20 .. 32 are within 10 % of it), against F.
-constexpr int SPSI_L = 24;
-struct SpsiSeg {
-  int row0;   // row of the segment's first frame in S / ang / tprev (the utterances of a batch lie one behind the other)
-  int n;      // its frames, 1 .. SPSI_L
-  int first;  // the utterance's first segment: it starts from phase 0
-  int last;   // the utterance's last segment: nothing enters behind it
-};
-struct SpsiUtt {
-  int seg0, nseg;  // the utterance's segments in the table
-};
+// (SPSI_L, the segments of the scan -- SpsiSeg, SpsiUtt, spsi_segments(F) of one utterance: magnitude_plan.h)
 struct SpsiBufs {
   uint2 *map;       // [F][513]     (owner, delta) of every cell
   uint2 *comp;      // [nseg][513]  the segments' composites
   unsigned *entry;  // [nseg][513]  the phase in front of each segment
 };
-size_t spsi_segments(int F);  // of one utterance
 // S [F][513] -> ang = (cos, sin) of the SPSI phase, tprev = 0, and with turns != null the phase itself (uint32, 2^-32 turn),
 // all [F][513].  segs_dev / utts_dev == null: one utterance of F frames (nseg = spsi_segments(F), n_utt = 1); else the device
 // tables of a batch, F = its rows in all.  chained: some utterance has more than one segment (else two launches instead of four).

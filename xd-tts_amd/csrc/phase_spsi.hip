@@ -246,8 +246,6 @@ __global__ void k_spsi_export(const unsigned *__restrict__ turns, const float2 *
 
 }  // namespace
 
-size_t spsi_segments(int F) { return (size_t)((F + SPSI_L - 1) / SPSI_L); }
-
 void launch_spsi(const float *S, int F, const SpsiSeg *segs_dev, const SpsiUtt *utts_dev, int nseg, int n_utt, bool chained,
                  const SpsiBufs &b, float2 *ang, float2 *tprev, unsigned *turns, hipStream_t s) {
   if (F <= 0 || nseg <= 0 || n_utt <= 0) return;
