@@ -41,8 +41,8 @@
 //     block of the decoder LSTM behind the energy gather, into the softmax -> h_dec chain of all 256 workgroups;
 //   * no s_waitcnt vmcnt(0) stands between a publish store and the block behind it (loads_settled() at the end of every
 //     gather; tests/test_kernel_isa_persistent_cpu.py counts the FMAs between each publish and the next full wait).
-//     The skewed pair loop keeps the waits it was tuned with: without them its early polls leave earlier still, and it
-//     measured 1.9 % slower (11.05 against 10.85 us per pair step);
+//     The skewed pair loop has both since its chunks run one phase slot apart (in the two-phases-apart order they cost
+//     1.9 %: its early polls then left earlier still);
 //   * one-chunk kernel: the attention role issues the first poll of the energies, and the projection role the first poll of
 //     the mel rows, from inside the block behind its own publish (EPOLL_AT / MPOLL_AT; the PRE form of gather(), which the
 //     skewed pair loop has for every edge), and the projection role does not fill the layer-1 LDS table it never reads.
@@ -138,13 +138,12 @@ __device__ __forceinline__ unsigned gather_poll(const u64 *base, unsigned idx, u
     if (all || give_up(spins, err)) return spins;
   }
 }
-// (SETTLE = false: the skewed pair loop, which keeps the waits it was tuned with -- see ph1)
-template <int N, bool PRE = false, bool SETTLE = true>
+template <int N, bool PRE = false>
 __device__ __forceinline__ unsigned gather(const u64 *base, unsigned idx, unsigned stride, unsigned want,
                                            const bool (&need)[N], float (&out)[N], unsigned (&tag)[N], const PollCtl &err,
                                            const u64 *pre = nullptr) {
   const unsigned spins = gather_poll<N, PRE>(base, idx, stride, want, need, out, tag, err, pre);
-  if (SETTLE) loads_settled();
+  loads_settled();
   return spins;
 }
 
@@ -215,8 +214,8 @@ struct PersistWeights {
   const float *att_b, *dec_b, *v_w, *loc_fused, *proj_b, *pre0T, *pre1T;
 };
 
-// SKEW (PB = 2 only): the two chunks do not run their steps in lock-step but two phases apart, a workgroup alternating
-// between them -- while one chunk's vector crosses the chip the workgroup runs the other chunk's phase instead of sleeping
+// SKEW (PB = 2 only): the two chunks do not run their steps in lock-step but one phase slot apart, a workgroup alternating
+// between them -- while chunk 0's vector crosses the chip the workgroup runs chunk 1's phase instead of sleeping
 // (see the loop at "skewed pair").
 // GATE: the stop rule decides (mod.rs:319-324; the reference's mode) -- its verdict through gate_fires, and a 1-chunk launch returns at
 // once for a chunk that has stopped.  The gate-less instantiations (fixed frame counts: parity hooks, benchmarks; d.use_gate = 0)
@@ -544,22 +543,29 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
     // arithmetic that needs it and a publish:  ph1 x -> attention-LSTM tail -> h_att;  ph2 h_att -> (attention role) query,
     // energies;  ph3 energies -> softmax, decoder-LSTM tail -> h_dec;  ph4 h_dec -> (projection role) mel rows;
     // ph5 (projection role) mel -> prenet -> x.  In lock-step both chunks wait together and compute one after the other;
-    // here chunk 1 runs two phases behind chunk 0 and a workgroup alternates between the chunks, so that one chunk's
-    // arithmetic fills the other's wait:
-    //     c0.ph1(s) c1.ph4(s-1) | c0.ph2(s) c1.ph5(s-1) | c0.ph3(s) c1.ph1(s) | c0.ph4(s) c1.ph2(s) | c0.ph5(s) c1.ph3(s)
+    // here every phase has its own gather and a workgroup alternates between the chunks, chunk 1 TRAILING chunk 0 by one
+    // phase slot, so that chunk 1's arithmetic fills chunk 0's waits:
+    //     c0.ph1(s) c1.ph1(s) | c0.ph2(s) c1.ph2(s) | c0.ph3(s) c1.ph3(s) | c0.ph4(s) c1.ph4(s) | c0.ph5(s) c1.ph5(s)
+    // Chunk 0's chain of five edges sets the step; a vector of chunk 1 was published a slot or two before its gather, so
+    // that gather rarely waits and never holds chunk 0's next phase back for long.  (Until this order the chunks ran two
+    // phases apart -- c0.ph3 beside c1.ph1 -- and every workgroup sat ~2.6 us in each chunk's wait for the energies while
+    // the other chunk's x had long arrived: 10.7 us per pair step against 9.8, profiles/pair_step.txt.)
+    // Role first: the projection workgroups of chunk 0 run their ph5 (mel -> prenet -> x, the head of chunk 0's next step)
+    // ahead of chunk 1's ph4, which for them is a deferred column block.
     // The launch ends when either chunk stops (the host continues the other with the 1-chunk kernel): chunk 0 found
-    // stopped at its ph1(s) -> chunk 1 completes step s-1, both have run s steps; chunk 1 found stopped at its ph1(s) ->
-    // chunk 0 completes step s: it has run s+1 steps, which is what ctl[0] then says (it is the survivor).
+    // stopped at its ph1(s) -> both have run s steps; chunk 1 found stopped at its ph1(s) -> chunk 0 completes step s:
+    // it has run s+1 steps, which is what ctl[0] then says (it is the survivor).
     static_assert(PB == 2, "the skewed loop is the pair kernel");
     const int tid_k = tid;
     const bool lag = g.slow && c == g.slow - 1;
     unsigned drop1 = 0u, drop2 = 0u;  // projection role: masks of step s+1, hashed in ph4, used in ph5
     // The first poll of a phase's vector is issued by the phase BEFORE it (the other chunk's), at its very end: a phase pays
     // the poll's round trip (~0.45 us) even when its vector has long arrived, and part of that now runs under the previous
-    // phase's tail.  (Issued earlier -- right behind that phase's publish -- the poll samples the slots before the slowest
-    // producer's store has landed: 10.98 us per step against 10.6-10.7; in the middle of the deferred column blocks: the
-    // same as behind them; lock-step: 11.27.)  The granules validate themselves (tag = step + 1), so a poll that was too
-    // early, or none at all at the ends of the sequence, only means the ordinary poll loop.
+    // phase's tail.  (Measured in the trailing order, profiles/pair_step.txt: without the early polls of chunk 0's vectors
+    // +0.55 us per step; issued 256 clocks later +0.4 us.)  As in the lock-step loop, no publish is followed by a wait
+    // (gather() ends in loads_settled()) and the deferred column blocks are pinned: with the waits kept this order measured
+    // 10.3 us per step and spilled, with the blocks pinned alone 10.0.  The granules validate themselves (tag = step + 1),
+    // so a poll that was too early, or none at all at the ends of the sequence, only means the ordinary poll loop.
     u64 pf[2] = {0ull, 0ull};
     auto issue_x = [&](auto B, int s) {
       constexpr int b = decltype(B)::value;
@@ -597,6 +603,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         a0 = dot4(wa[0][k], v, a0);
         a1 = dot4(wa[1][k], v, a1);
       }
+      pin(a0, a1);
       aacc[b][0] = a0;
       aacc[b][1] = a1;
     };
@@ -609,6 +616,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         a0 = dot4(wd[0][k], v, a0);
         a1 = dot4(wd[1][k], v, a1);
       }
+      pin(a0, a1);
       dacc[b][0] = a0;
       dacc[b][1] = a1;
     };
@@ -625,7 +633,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         const bool need[1] = {tid < 256};
         float v[1];
         unsigned tg[1];
-        gather<1, true, false>(g.x, (unsigned)((p * GS + b) * PRENET + i), 0u, want, need, v, tg, pc, pf);
+        gather<1, true>(g.x, (unsigned)((p * GS + b) * PRENET + i), 0u, want, need, v, tg, pc, pf);
         if (need[0]) {
           s_x[b * PRENET + i] = v[0];
           if (i == 0) s_act[b] = (tg[0] & ACT_BIT) ? 1 : 0;
@@ -678,7 +686,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         const bool need[2] = {true, true};
         float v[2];
         unsigned tg[2];
-        gather<2, true, false>(g.hatt, (unsigned)((p * GS + b) * ATT_RNN + tid), PT, want, need, v, tg, pc, pf);
+        gather<2, true>(g.hatt, (unsigned)((p * GS + b) * ATT_RNN + tid), PT, want, need, v, tg, pc, pf);
         s_hatt[b * ATT_RNN + TID] = v[0];
         s_hatt[b * ATT_RNN + TID + PT] = v[1];
       }
@@ -716,6 +724,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
           a0 = dot4(wd[0][k], v, a0);
           a1 = dot4(wd[1][k], v, a1);
         }
+        pin(a0, a1);
         dacc[b][0] = a0;
         dacc[b][1] = a1;
       }
@@ -737,7 +746,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         const bool need[2] = {t < T, t < T};
         float v[2];
         unsigned tg[2];
-        gather<2, true, false>(g.ep, (unsigned)(((p * GS + b) * ATTN_CU + j) * EP_LD + t), 4u * EP_LD, want, need, v, tg, pc, pf);
+        gather<2, true>(g.ep, (unsigned)(((p * GS + b) * ATTN_CU + j) * EP_LD + t), 4u * EP_LD, want, need, v, tg, pc, pf);
         float e = v[0] + v[1];
         e += dpp_move<0xB1, 0xf>(0.f, e);  // quad_perm:[1,0,3,2]
         e += dpp_move<0x4E, 0xf>(0.f, e);  // quad_perm:[2,3,0,1]
@@ -813,7 +822,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         const bool need[2] = {true, true};
         float v[2];
         unsigned tg[2];
-        gather<2, true, false>(g.hdec, (unsigned)((p * GS + b) * DEC_RNN + tid), PT, want, need, v, tg, pc, pf);
+        gather<2, true>(g.hdec, (unsigned)((p * GS + b) * DEC_RNN + tid), PT, want, need, v, tg, pc, pf);
         s_hdec[b * DEC_RNN + TID] = v[0];
         s_hdec[b * DEC_RNN + TID + PT] = v[1];
       }
@@ -849,7 +858,7 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
         const bool need[1] = {true};
         float v[1];
         unsigned tg[1];
-        gather<1, true, false>(g.mel, (unsigned)(((p * GS + b) * MEL_GL + tid) * MEL_ST), 0, want, need, v, tg, pc, pf);
+        gather<1, true>(g.mel, (unsigned)(((p * GS + b) * MEL_GL + tid) * MEL_ST), 0, want, need, v, tg, pc, pf);
         s_mel[tid] = v[0];
       }
       __syncthreads();
@@ -902,31 +911,31 @@ __global__ __launch_bounds__(PT) void k_decoder_persistent(DecoderBufs d, Persis
       nxt();
       PROF_MARK(5 * b + 4);
     };
-    bool tail1 = false;  // chunk 1 has run ph1..ph3 of step s-1: its ph4 / ph5 come in the first half of this round
     if (s_act[2] != 0 && s_act[3] != 0) {
       issue_x(I0, s);
       for (;; ++s) {
-        bool a0 = s < s_stop;
-        if (a0) a0 = ph1(I0, s, [&] { if (tail1) issue_h(g.hdec, I1, s - 1); else issue_h(g.hatt, I0, s); });
-        if (tail1) ph4(I1, s - 1, [&] { if (a0) issue_h(g.hatt, I0, s); });
-        if (a0) ph2(I0, s, [&] { if (tail1) issue_mel(I1, s - 1); else issue_ep(I0, s); });
-        if (tail1) {
-          ph5(I1, s - 1, [&] { if (a0) issue_ep(I0, s); });
-          tail1 = false;
+        // chunk 0 has stopped (or the limit / an exchange failure): both chunks have completed s steps
+        if (!(s < s_stop && ph1(I0, s, [&] { issue_x(I1, s); }))) break;
+        const bool a1 = ph1(I1, s, [&] { issue_h(g.hatt, I0, s); });
+        if (!a1) issue_h(g.hatt, I0, s);  // (a ph1 that found its chunk stopped issued nothing: pf still holds its x granules)
+        ph2(I0, s, [&] { if (a1) issue_h(g.hatt, I1, s); else issue_ep(I0, s); });
+        if (a1) ph2(I1, s, [&] { issue_ep(I0, s); });
+        ph3(I0, s, [&] { if (a1) issue_ep(I1, s); else issue_h(g.hdec, I0, s); });
+        if (a1) ph3(I1, s, [&] { issue_h(g.hdec, I0, s); });
+        if (a1 && pre && rb == 0) {  // (workgroup-uniform) role first: chunk 0's mel -> prenet -> x ahead of chunk 1's h_dec columns
+          ph4(I0, s, [&] { issue_mel(I0, s); });
+          ph5(I0, s, [&] { issue_h(g.hdec, I1, s); });
+          ph4(I1, s, [&] { issue_mel(I1, s); });
+        } else {
+          ph4(I0, s, [&] { if (a1) issue_h(g.hdec, I1, s); else issue_mel(I0, s); });
+          if (a1) ph4(I1, s, [&] { issue_mel(I0, s); });
+          ph5(I0, s, [&] { if (a1) issue_mel(I1, s); else issue_x(I0, s + 1); });
         }
-        if (!a0) break;  // chunk 0 has stopped (or the limit / an exchange failure): both chunks have completed s steps
-        ph3(I0, s, [&] { issue_x(I1, s); });
-        const bool a1 = ph1(I1, s, [&] { issue_h(g.hdec, I0, s); });
-        if (!a1) issue_h(g.hdec, I0, s);
-        ph4(I0, s, [&] { if (a1) issue_h(g.hatt, I1, s); else issue_mel(I0, s); });
-        if (a1) ph2(I1, s, [&] { issue_mel(I0, s); });
-        ph5(I0, s, [&] { if (a1) issue_ep(I1, s); });
         if (!a1) {  // chunk 1 has stopped: chunk 0, the survivor, has completed step s
           ++s;
           break;
         }
-        ph3(I1, s, [&] { issue_x(I0, s + 1); });
-        tail1 = true;
+        ph5(I1, s, [&] { issue_x(I0, s + 1); });
       }
     }
   } else
