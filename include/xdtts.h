@@ -679,6 +679,89 @@ xdtts_status xdtts_griffinlim_timbre_linear_batch(xdtts_griffinlim *g, const flo
 /* Host arithmetic, no handle, no device: n of cell (frame, bin) above. */
 uint32_t xdtts_timbre_noise_bits(uint32_t seed, uint32_t frame, uint32_t bin);
 
+/* Clean-up: spectral noise suppression and a tone curve.  The loop's target is pinv(mel), and Tacotron2's mel is clamped at 1e-5,
+ * so every "silent" cell carries a floor that Griffin-Lim turns into broadband hiss under the voice and in every pause (the
+ * complaint the `denoiser_strength` knob of NVIDIA's inference script answers).  The remedy is a gain on the magnitude: classical
+ * over-subtraction against a per-bin noise estimate with a spectral floor, and beside it a per-device tone profile (handset,
+ * small speaker, telephony) as a gain per bin.
+ *   strength  in [0, 16]: the over-subtraction factor; 0 = no subtraction
+ *   quantile  in [0, 1]: which order statistic over an utterance's frames is "the noise" (0.5: the median of each bin)
+ *   floor_db  in [-80, 0]: the most a cell is attenuated
+ *   tone      0 .. 8 points (hz, dB), hz strictly ascending in (0, 11025], dB in [-40, 20]; 0 points = flat
+ * The setting is the IDENTITY when strength == 0 and every tone_db that is used equals 0 (the default); only these decide it.
+ * The stage then launches nothing and allocates nothing, and every entry returns the bits it returns without it.
+ * The definition, exactly, for an utterance of F >= 1 frames of the magnitude S as mel -> linear left it (the NNLS refinement
+ * included), k = 0 .. 512:
+ *   r      = floor((double) quantile * (F - 1))
+ *   key(x) = bits(x) & 0x7fffffff       (a total order; the numeric one on the non-negative finite values mel -> linear produces)
+ *   N[k]   = without a profile: the float whose bits are the r-th smallest (0-based) of key(S[0 .. F)[k]) -- ties are equal
+ *            values and cannot matter; the frames are those of the utterance alone, never a neighbour's in a batch.
+ *            With a profile: profile[k].
+ *   aN[k]  = fl(strength * N[k])
+ *   q      = fl(aN[k] / S[t][k])        (correctly rounded)
+ *   d      = fl(1 - q)
+ *   gmin   = (float) pow(10, (double) floor_db / 20)         (the single libm call of the gain rule; it runs on the host)
+ *   G      = d > gmin ? d : gmin        (a NaN d gives gmin: S == 0 gives gmin, and 0 comes out)
+ *   E[k]   = n_tone > 0: (float) pow(10, dB(k) / 20), dB(k) piecewise linear in log2(f_k) between the points and constant
+ *            outside them, f_k = k * 22050 / 1024, bin 0 takes the first point's value; in double, on the host.  n_tone == 0: 1.
+ *   S'[t][k] = fl(fl(S[t][k] * G) * E[k])
+ * Every operation is rounded to fp32 on its own, nothing is fused.  With strength == 0 the selection and G are skipped (G = 1);
+ * where every tone_db that is used is 0 the product with E is skipped (E = 1).  Comparisons, selections and single rounded
+ * operations only: the device equals xdtts_denoise_reference bit for bit.  Subnormal magnitudes are kept by the kernels;
+ * mel -> linear produces none worth the name and nothing relies on them.
+ * `profile` is a caller's noise magnitude of n_bins floats (every one finite), or NULL: typically the order statistic of a
+ * silent utterance of the same checkpoint, taken once with xdtts_griffinlim_noise_profile.  The handle copies it to the device
+ * at set time; the setter drains the stream first, as a growth does.
+ * Place: the FIRST stage of the magnitude chain, out of place -- in front of the pitch tracker, prosody, contour, timbre and the
+ * initial phase: all of them, and the loop, see the cleaned magnitude; S stays intact for a retry.
+ * A SETTING OF THE HANDLE, off by default, honoured by every entry that runs mel -> linear itself: the list in the timbre block
+ * above.  xdtts_griffinlim_infer_linear, the _prosody_linear / _contour_linear / _timbre_linear / _f0_linear /
+ * _pitch_target_linear hooks, xdtts_griffinlim_f0 and the analysis entries do NOT honour it.  One setting and one profile hold
+ * for every utterance of a batch, sequence or document call.
+ * Stats, per utterance, all integers (order-free): cells = 513 F; floored = the cells with G == gmin (0 without subtraction);
+ * rank = r where the selection ran, else 0; profiled = 1 where the subtraction ran against a profile.  They travel back behind
+ * the stage through a pinned buffer, like the tracker's.
+ * Argument rules, checked before a handle is looked at (XDTTS_ERR_BAD_ARG; the message names the field, and for the batch hook
+ * the utterance): every field finite and in the range above, tone_hz strictly ascending, every profile bin finite; a request of
+ * the stage alone holds 1 .. 2^20 frames per utterance.  A failed set leaves the setting as it was.
+ * Out of scope: smoothing of the gain over time or frequency (the over-subtraction plus floor rule is the classical stand-alone
+ * form; a smoothing rule needs real speech to judge), adaptive minimum-statistics noise tracking, a profile per utterance in the
+ * delivering entries, the stage in the analysis direction. */
+typedef struct {
+  float   strength;    /* 0 .. 16: over-subtraction factor; 0 = no subtraction                      */
+  float   quantile;    /* 0 .. 1: which order statistic over an utterance's frames is "the noise"    */
+  float   floor_db;    /* -80 .. 0: the most a cell is attenuated (the spectral floor)               */
+  int32_t n_tone;      /* 0 .. 8 points of the tone curve; 0 = flat                                  */
+  float   tone_hz[8];  /* strictly ascending, 0 < hz <= 11025                                        */
+  float   tone_db[8];  /* -40 .. +20                                                                 */
+} xdtts_denoise;       /* 80 bytes; default {0, 0.5, -20, 0, {0}, {0}} = the identity */
+typedef struct { uint32_t cells, floored, rank, profiled; } xdtts_denoise_stats;
+void xdtts_denoise_default(xdtts_denoise *d);
+/* d == NULL turns the stage off (the default, and no profile); profile: n_bins floats or NULL. */
+xdtts_status xdtts_griffinlim_set_denoise(xdtts_griffinlim *g, const xdtts_denoise *d, const float *profile);
+/* profile_out (n_bins floats) may be NULL; *profiled = 1 where a profile is set (it may be NULL too). */
+xdtts_status xdtts_griffinlim_get_denoise(xdtts_griffinlim *g, xdtts_denoise *d, float *profile_out, int32_t *profiled);
+/* The stats of each utterance of the last delivering call that ran the stage, or of the last hook of the stage alone, in the
+ * caller's order, shaped like xdtts_griffinlim_last_f0; *n = 0 after a delivering call with the setting off. */
+xdtts_status xdtts_griffinlim_last_denoise(const xdtts_griffinlim *g, xdtts_denoise_stats *out, size_t cap, size_t *n);
+/* Parity hook, the stage alone, whatever the handle holds: S (n_bins x F, C order, as xdtts_griffinlim_mel_to_linear returns
+ * it), 1 <= F <= 2^20 -> S_out (n_bins x F).  The identity returns S's bits and touches no device.  last_timings: ms[0] = the
+ * stage alone, ms[1] = the layout change behind it. */
+xdtts_status xdtts_griffinlim_denoise_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_denoise *d,
+                                             const float *profile, float *S_out);
+/* The ragged form the batch entries run, one setting PER UTTERANCE and one shared profile or NULL: every S_outs[u] equals the
+ * single hook's for S[u] alone bit for bit, whatever the mix and the order. */
+xdtts_status xdtts_griffinlim_denoise_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
+                                                   const xdtts_denoise *d /* [n_utt] */, const float *profile, float *const *S_outs);
+/* The selection alone: out[k] = N[k] of S under `quantile`. */
+xdtts_status xdtts_griffinlim_noise_profile(xdtts_griffinlim *g, const float *S, size_t n_frames, float quantile, float *out /* [n_bins] */);
+/* Host arithmetic, no handle, no device: r; gmin; E[513]; and the definition as serial plain C++ (stats may be NULL). */
+uint32_t xdtts_denoise_rank(size_t n_frames, float quantile);
+float xdtts_denoise_floor(float floor_db);
+xdtts_status xdtts_denoise_tone(const xdtts_denoise *d, float *E /* [513] */);
+xdtts_status xdtts_denoise_reference(const float *S, size_t n_frames, const xdtts_denoise *d, const float *profile, float *S_out,
+                                     xdtts_denoise_stats *stats);
+
 /* The output rate.  The loop produces 22 050 Hz audio (XDTTS_SAMPLE_RATE, the reference's WAV_SPEC); telephony, WebRTC / Opus
  * and audio pipelines want 8 .. 48 kHz and beyond.  With the option set, a polyphase windowed-sinc resampler runs on the
  * device between the final ISTFT and the output normalisation, so the level rules (peak 1, rms target, no sample outside

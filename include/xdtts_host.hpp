@@ -537,6 +537,64 @@ class GriffinLim {
     check(xdtts_griffinlim_timbre_linear_batch(g_, in.data(), nf.data(), (int32_t)n, t.data(), op.data()));
     return out;
   }
+  // The clean-up stage of this handle (xdtts_griffinlim_set_denoise): spectral subtraction with a floor and a tone curve on the
+  // magnitude as mel -> linear left it, in front of every other stage.  The default is the identity, which launches nothing;
+  // every entry that runs mel -> linear itself honours the setting.  profile: n_bins floats (e.g. noise_profile() of a silent
+  // utterance of the checkpoint), or empty = none.
+  static xdtts_denoise default_denoise() {
+    xdtts_denoise d{};
+    xdtts_denoise_default(&d);
+    return d;
+  }
+  void set_denoise(const xdtts_denoise &d, const std::vector<float> &profile = {}) {
+    if (!profile.empty() && profile.size() != 513) throw std::runtime_error("xdtts: a noise profile has 513 bins");
+    check(xdtts_griffinlim_set_denoise(g_, &d, profile.empty() ? nullptr : profile.data()));
+  }
+  void clear_denoise() { check(xdtts_griffinlim_set_denoise(g_, nullptr, nullptr)); }
+  xdtts_denoise denoise_setting(std::vector<float> *profile = nullptr) const {
+    xdtts_denoise d{};
+    std::vector<float> p(513);
+    int32_t profiled = 0;
+    check(xdtts_griffinlim_get_denoise(g_, &d, p.data(), &profiled));
+    if (profile) *profile = profiled ? p : std::vector<float>();
+    return d;
+  }
+  std::vector<xdtts_denoise_stats> last_denoise() const {
+    size_t n = 0;
+    check(xdtts_griffinlim_last_denoise(g_, nullptr, 0, &n));
+    std::vector<xdtts_denoise_stats> out(n);
+    if (n) check(xdtts_griffinlim_last_denoise(g_, out.data(), n, &n));
+    return out;
+  }
+  // ... the stage alone on the caller's magnitude (xdtts_griffinlim_denoise_linear), whatever the setting: S (n_bins x F) -> S'
+  Array2 denoise_linear(const Array2 &S, const xdtts_denoise &d, const std::vector<float> &profile = {}) const {
+    Array2 out{S.rows, S.cols, std::vector<float>(S.data.size())};
+    check(xdtts_griffinlim_denoise_linear(g_, S.data.data(), S.cols, &d, profile.empty() ? nullptr : profile.data(), out.data.data()));
+    return out;
+  }
+  // ... for several magnitudes, one setting each and one shared profile (xdtts_griffinlim_denoise_linear_batch): the single call's bits
+  std::vector<Array2> denoise_linear_batch(const std::vector<Array2> &S, const std::vector<xdtts_denoise> &d, const std::vector<float> &profile = {}) const {
+    const size_t n = S.size();
+    if (d.size() != n) throw std::runtime_error("xdtts: one denoise setting per utterance");
+    std::vector<Array2> out(n);
+    std::vector<const float *> in(n);
+    std::vector<float *> op(n);
+    std::vector<size_t> nf(n);
+    for (size_t u = 0; u < n; ++u) {
+      out[u] = Array2{S[u].rows, S[u].cols, std::vector<float>(S[u].data.size())};
+      in[u] = S[u].data.data();
+      op[u] = out[u].data.data();
+      nf[u] = S[u].cols;
+    }
+    check(xdtts_griffinlim_denoise_linear_batch(g_, in.data(), nf.data(), (int32_t)n, d.data(), profile.empty() ? nullptr : profile.data(), op.data()));
+    return out;
+  }
+  // ... and the selection alone (xdtts_griffinlim_noise_profile): per bin the order statistic `quantile` over S's frames
+  std::vector<float> noise_profile(const Array2 &S, float quantile = 0.5f) const {
+    std::vector<float> out(513);
+    check(xdtts_griffinlim_noise_profile(g_, S.data.data(), S.cols, quantile, out.data()));
+    return out;
+  }
   // The inverse direction (xdtts_griffinlim_analyze): audio -> (S (n_bins x F), mel (n_mels x F)) under the handle's conventions,
   // F = audio.size() / 256 + 1
   std::pair<Array2, Array2> analyze(const std::vector<float> &audio, float mel_floor = 1e-5f) const {

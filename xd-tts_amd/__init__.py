@@ -75,6 +75,43 @@ class Timbre(C.Structure):
         return (self.vtl, self.breath, self.seed, self.lifter, self.log_floor)
 
 
+class Denoise(C.Structure):
+    """xdtts_denoise: the clean-up stage of a vocoder handle, the first stage on the magnitude behind mel -> linear.  strength in
+    [0, 16] (over-subtraction factor, 0 = none), quantile in [0, 1] (which order statistic over an utterance's frames is the
+    noise), floor_db in [-80, 0] (the most a cell is attenuated), tone = up to 8 (hz, dB) points, hz strictly ascending in
+    (0, 11025], dB in [-40, 20].  Denoise() holds the library's defaults (0, 0.5, -20, no tone), i.e. the identity; keywords
+    override fields: Denoise(strength=2, tone=[(300, -6), (3400, 0)])."""
+
+    _fields_ = [("strength", C.c_float), ("quantile", C.c_float), ("floor_db", C.c_float), ("n_tone", C.c_int32),
+                ("tone_hz", C.c_float * 8), ("tone_db", C.c_float * 8)]
+
+    def __init__(self, tone=None, **kw):
+        super().__init__()
+        lib.xdtts_denoise_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+        if tone is not None:
+            pts = [(float(h), float(d)) for h, d in tone]
+            if len(pts) > 8:
+                raise ValueError("a tone curve has at most 8 points, got %d" % len(pts))
+            self.n_tone = len(pts)
+            for i, (h, d) in enumerate(pts):
+                self.tone_hz[i], self.tone_db[i] = h, d
+
+    def astuple(self):
+        return (self.strength, self.quantile, self.floor_db, self.n_tone, tuple(self.tone_hz), tuple(self.tone_db))
+
+
+class DenoiseStats(C.Structure):
+    """xdtts_denoise_stats of one utterance: cells = 513 F, floored = the cells at the spectral floor, rank = r of the selection
+    (0 where none ran), profiled = 1 where the subtraction ran against a caller's profile."""
+
+    _fields_ = [("cells", C.c_uint32), ("floored", C.c_uint32), ("rank", C.c_uint32), ("profiled", C.c_uint32)]
+
+    def astuple(self):
+        return (self.cells, self.floored, self.rank, self.profiled)
+
+
 class ProsodyPoint(C.Structure):
     """xdtts_prosody_point: (pos, rate, pitch, gain), pos a fraction of the utterance's duration in [0, 1]."""
 
@@ -360,6 +397,17 @@ SYMBOLS = {
     "xdtts_griffinlim_get_timbre": (_I32, [_VP, C.POINTER(Timbre)]),
     "xdtts_griffinlim_timbre_linear": (_I32, [_VP, _VP, _SZ, C.POINTER(Timbre), _VP]),
     "xdtts_griffinlim_timbre_linear_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
+    "xdtts_denoise_default": (None, [C.POINTER(Denoise)]),
+    "xdtts_griffinlim_set_denoise": (_I32, [_VP, C.POINTER(Denoise), _VP]),
+    "xdtts_griffinlim_get_denoise": (_I32, [_VP, C.POINTER(Denoise), _VP, C.POINTER(_I32)]),
+    "xdtts_griffinlim_last_denoise": (_I32, [_VP, _VP, _SZ, C.POINTER(_SZ)]),
+    "xdtts_griffinlim_denoise_linear": (_I32, [_VP, _VP, _SZ, C.POINTER(Denoise), _VP, _VP]),
+    "xdtts_griffinlim_denoise_linear_batch": (_I32, [_VP, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "xdtts_griffinlim_noise_profile": (_I32, [_VP, _VP, _SZ, _F, _VP]),
+    "xdtts_denoise_rank": (_U32, [_SZ, _F]),
+    "xdtts_denoise_floor": (_F, [_F]),
+    "xdtts_denoise_tone": (_I32, [C.POINTER(Denoise), _VP]),
+    "xdtts_denoise_reference": (_I32, [_VP, _SZ, C.POINTER(Denoise), _VP, _VP, C.POINTER(DenoiseStats)]),
     "xdtts_griffinlim_set_output_rate": (_I32, [_VP, _I32]),
     "xdtts_griffinlim_get_output_rate": (_I32, [_VP, C.POINTER(_I32)]),
     "xdtts_resample_plan": (_I32, [_I32, _SZ, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_SZ)]),
@@ -1327,6 +1375,68 @@ class GriffinLim:
         _check(lib.xdtts_griffinlim_timbre_linear_batch(self._h, sp, nf, n, ta, op))
         return outs
 
+    # -- clean-up: spectral subtraction with a floor and a tone curve, the first stage behind mel -> linear ----
+    def set_denoise(self, denoise=None, profile=None):
+        """The handle's clean-up stage from now on: a Denoise, or None for off (the default: nothing is launched), with an
+        optional noise profile (n_bins floats, e.g. noise_profile() of a silent utterance of the checkpoint).  Honoured by every
+        entry that runs mel -> linear itself (infer*, synthesize*); infer_linear and the *_linear hooks do not."""
+        p = None if profile is None else np.ascontiguousarray(profile, dtype=np.float32).ravel()
+        if p is not None and p.size != self.n_bins:
+            raise ValueError("a noise profile has %d bins, got %d" % (self.n_bins, p.size))
+        _check(lib.xdtts_griffinlim_set_denoise(self._h, _opt_ref(denoise), None if p is None else _ptr(p)))
+
+    def get_denoise(self):
+        """(Denoise, profile or None) as set."""
+        d, flag = Denoise(), C.c_int32()
+        p = np.zeros(self.n_bins, dtype=np.float32)
+        _check(lib.xdtts_griffinlim_get_denoise(self._h, C.byref(d), _ptr(p), C.byref(flag)))
+        return d, (p if flag.value else None)
+
+    def last_denoise(self):
+        """The DenoiseStats of each utterance of the last call that ran the stage, in the caller's order ([] after a delivering
+        call with the setting off)."""
+        n = C.c_size_t()
+        _check(lib.xdtts_griffinlim_last_denoise(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return []
+        out = (DenoiseStats * n.value)()
+        _check(lib.xdtts_griffinlim_last_denoise(self._h, out, n.value, C.byref(n)))
+        return list(out)
+
+    def denoise_linear(self, S, denoise, profile=None):
+        """The clean-up stage alone (parity hook), whatever the handle's setting: S (n_bins, F) -> S' (n_bins, F)."""
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        out = np.empty_like(S)
+        p = None if profile is None else np.ascontiguousarray(profile, dtype=np.float32).ravel()
+        _check(lib.xdtts_griffinlim_denoise_linear(self._h, _ptr(S), S.shape[1], C.byref(denoise), None if p is None else _ptr(p), _ptr(out)))
+        return out
+
+    def denoise_linear_batch(self, S_list, denoise_list, profile=None):
+        """The ragged stage alone (parity hook): a list of S_u (n_bins, F_u), one Denoise each and one shared profile or None
+        -> the list of S'_u, every one the single hook's bit for bit."""
+        Ss = [np.ascontiguousarray(S, dtype=np.float32) for S in S_list]
+        n = len(Ss)
+        ds = list(denoise_list)
+        if len(ds) != n:
+            raise ValueError("denoise_linear_batch takes one Denoise per utterance: %d for %d utterances" % (len(ds), n))
+        da = (Denoise * max(n, 1))()
+        for u, d in enumerate(ds):
+            C.memmove(C.byref(da[u]), C.byref(d), C.sizeof(Denoise))
+        outs = [np.empty_like(S) for S in Ss]
+        sp = (C.c_void_p * max(n, 1))(*[S.ctypes.data for S in Ss])
+        op = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        nf = (C.c_size_t * max(n, 1))(*[S.shape[1] for S in Ss])
+        p = None if profile is None else np.ascontiguousarray(profile, dtype=np.float32).ravel()
+        _check(lib.xdtts_griffinlim_denoise_linear_batch(self._h, sp, nf, n, da, None if p is None else _ptr(p), op))
+        return outs
+
+    def noise_profile(self, S, quantile=0.5):
+        """The selection alone: per bin the order statistic `quantile` over the frames of S (n_bins, F) -> (n_bins,)."""
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        out = np.empty(S.shape[0], dtype=np.float32)
+        _check(lib.xdtts_griffinlim_noise_profile(self._h, _ptr(S), S.shape[1], float(quantile), _ptr(out)))
+        return out
+
     # -- limiter: look-ahead true-peak limiter where the loudness stage scaled ----
     def set_limiter(self, lookahead_us=0):
         """With a target and a ceiling set (set_loudness): the gain is formed without the ceiling and a look-ahead limiter of
@@ -1687,6 +1797,35 @@ def silence_reference(audio, rate, silence):
     st = SilenceStats()
     _check(lib.xdtts_silence_reference(_ptr(x) if x.size else None, x.size, int(rate), C.byref(silence), _ptr(out), C.byref(st)))
     return out[:st.n_out].copy(), st
+
+
+def denoise_rank(n_frames, quantile):
+    """r = floor(quantile * (F - 1)) of the clean-up stage's selection.  Host arithmetic."""
+    return int(lib.xdtts_denoise_rank(int(n_frames), float(quantile)))
+
+
+def denoise_floor(floor_db):
+    """gmin = (float) 10 ** (floor_db / 20) as the clean-up stage forms it.  Host arithmetic."""
+    return np.float32(lib.xdtts_denoise_floor(float(floor_db)))
+
+
+def denoise_tone(denoise):
+    """E[513] of a Denoise's tone curve (all 1 without points).  Host arithmetic."""
+    E = np.empty(513, dtype=np.float32)
+    _check(lib.xdtts_denoise_tone(C.byref(denoise), _ptr(E)))
+    return E
+
+
+def denoise_reference(S, denoise, profile=None):
+    """The clean-up stage's definition as serial plain C++ on the host: S (513, F) -> (S' (513, F), DenoiseStats)."""
+    S = np.ascontiguousarray(S, dtype=np.float32)
+    out = np.empty_like(S)
+    st = DenoiseStats()
+    p = None if profile is None else np.ascontiguousarray(profile, dtype=np.float32).ravel()
+    if p is not None and p.size != 513:
+        raise ValueError("a noise profile has 513 bins, got %d" % p.size)
+    _check(lib.xdtts_denoise_reference(_ptr(S), S.shape[1], C.byref(denoise), None if p is None else _ptr(p), _ptr(out), C.byref(st)))
+    return out, st
 
 
 def timbre_noise_bits(seed, frame, bin):

@@ -1,5 +1,5 @@
 // api_gl_magnitude.cpp -- the extern "C" boundary, vocoder half: the entries that work on the magnitude between mel -> linear and
-// the loop -- prosody, contours, the pitch tracker and pitch targets, the SPSI initial phase, timbre.
+// the loop -- prosody, contours, the pitch tracker and pitch targets, the SPSI initial phase, timbre, the clean-up stage.
 #include <algorithm>
 #include <cmath>
 
@@ -512,6 +512,149 @@ xdtts_status xdtts_griffinlim_timbre_linear_batch(xdtts_griffinlim *g, const flo
 
 xdtts_status xdtts_griffinlim_timbre_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_timbre *t, float *S_out) {
   return xdtts_griffinlim_timbre_linear_batch(g, &S, &n_frames, 1, t, &S_out);
+}
+
+// ---- clean-up: spectral subtraction with a floor and a tone curve, the first stage of the chain (denoise_plan.h, denoise.hip) ----
+
+void xdtts_denoise_default(xdtts_denoise *d) {
+  if (!d) return;
+  const Denoise s = denoise_default();
+  std::memcpy(d, &s, sizeof s);
+}
+
+uint32_t xdtts_denoise_rank(size_t n_frames, float quantile) { return denoise_rank(n_frames, quantile); }
+
+float xdtts_denoise_floor(float floor_db) { return denoise_floor(floor_db); }
+
+xdtts_status xdtts_denoise_tone(const xdtts_denoise *d, float *E) {
+  return guard([&] {
+    if (!d || !E) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    denoise_tone(denoise_checked(d, nullptr), E);
+  });
+}
+
+xdtts_status xdtts_denoise_reference(const float *S, size_t n_frames, const xdtts_denoise *d, const float *profile, float *S_out,
+                                     xdtts_denoise_stats *stats) {
+  return guard([&] {
+    if (!d) fail(XDTTS_ERR_BAD_ARG, "null denoise");
+    const Denoise s = denoise_checked(d, profile);
+    bad_arg_if(denoise_frames_check(n_frames));
+    if (!S || !S_out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    DenoiseStats st;
+    denoise_reference(S, n_frames, s, profile, S_out, &st);
+    if (stats) std::memcpy(stats, &st, sizeof st);
+  });
+}
+
+xdtts_status xdtts_griffinlim_set_denoise(xdtts_griffinlim *g, const xdtts_denoise *d, const float *profile) {
+  return guard([&] {
+    const Denoise s = denoise_checked(d, d ? profile : nullptr);  // (the fields before the handle; a failure leaves the setting as it was)
+    if (!g) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    const bool profiled = d && profile;
+    std::vector<float> E((size_t)DENOISE_NB), P(profiled ? profile : nullptr, profiled ? profile + DENOISE_NB : nullptr);
+    denoise_tone(s, E.data());
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (!denoise_is_identity(s)) {  // (the identity allocates nothing)
+      HIP_CHECK(hipSetDevice(g->device));
+      HIP_CHECK(hipStreamSynchronize(g->stream));  // as a growth: nothing in flight reads what is replaced
+      g->mg.dn_tone.upload(E.data(), E.size(), g->stream);
+      if (profiled) g->mg.dn_profile.upload(P.data(), P.size(), g->stream);
+      HIP_CHECK(hipStreamSynchronize(g->stream));
+    }
+    g->mg.denoise = s;
+    g->mg.denoise_profiled = profiled;
+    g->mg.denoise_profile = std::move(P);
+  });
+}
+
+xdtts_status xdtts_griffinlim_get_denoise(xdtts_griffinlim *g, xdtts_denoise *d, float *profile_out, int32_t *profiled) {
+  return guard([&] {
+    if (!g || !d) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    std::memcpy(d, &g->mg.denoise, sizeof g->mg.denoise);
+    if (profiled) *profiled = g->mg.denoise_profiled ? 1 : 0;
+    if (profile_out && g->mg.denoise_profiled) std::memcpy(profile_out, g->mg.denoise_profile.data(), (size_t)DENOISE_NB * sizeof(float));
+  });
+}
+
+xdtts_status xdtts_griffinlim_last_denoise(const xdtts_griffinlim *g, xdtts_denoise_stats *out, size_t cap, size_t *n) {
+  return last_stats_out(g, g ? &g->mg.last_denoise : nullptr, false, out, cap, n);
+}
+
+// Parity hook of the stage alone: the utterances' magnitudes one behind the other on the device, the selection where an
+// utterance asks for it and ONE k_denoise launch -- with the table for several utterances, with the record as a kernel argument
+// for one (the form the single-utterance entries run) -- and back.  A request of identities alone touches no device.
+// last_timings: ms[0] = the stage alone, ms[1] = the layout change.
+xdtts_status xdtts_griffinlim_denoise_linear_batch(xdtts_griffinlim *g, const float *const *S, const size_t *n_frames, int32_t n_utt,
+                                                   const xdtts_denoise *d, const float *profile, float *const *S_outs) {
+  return guard([&] {
+    if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    if (!d) fail(XDTTS_ERR_BAD_ARG, "null denoise");
+    std::vector<DenoiseJob> jobs((size_t)n_utt);
+    std::vector<float> tones;  // one row per utterance with a curve that is not flat
+    bool any = false;
+    for (int u = 0; u < n_utt; ++u) {
+      Denoise s;
+      std::memcpy(&s, &d[u], sizeof s);
+      std::string msg = denoise_check(s);
+      if (msg.empty() && n_frames) msg = denoise_frames_check(n_frames[u]);
+      if (!msg.empty()) fail(XDTTS_ERR_BAD_ARG, "utterance %d: %s", u, msg.c_str());
+      any = any || !denoise_is_identity(s);
+      int row = -1;
+      if (!denoise_tone_is_flat(s)) {
+        row = (int)(tones.size() / (size_t)DENOISE_NB);
+        tones.resize(tones.size() + (size_t)DENOISE_NB);
+        denoise_tone(s, tones.data() + (size_t)row * DENOISE_NB);
+      }
+      jobs[(size_t)u] = denoise_job(s, profile != nullptr, row);
+    }
+    bad_arg_if(denoise_profile_check(profile));
+    if (!g || !S || !n_frames || !S_outs) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    for (int u = 0; u < n_utt; ++u)
+      if (!S[u] || !S_outs[u]) fail(XDTTS_ERR_BAD_ARG, "utterance %d: null magnitude", u);
+    MagnitudePlan plan = magnitude_plan_checked(MagnitudeRequest::none(n_utt), n_frames, NO_TIMBRE, 0, false, jobs);
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (!any) {  // the identity: S's bits, nothing launched, nothing allocated
+      for (int u = 0; u < n_utt; ++u)
+        if (S_outs[u] != S[u]) std::memmove(S_outs[u], S[u], n_frames[u] * (size_t)g->nb * sizeof(float));
+      return;
+    }
+    stage_hook(g, S, std::move(plan), n_utt > 1, S_outs, [&](Magnitude &m) {
+      if (profile) m.dn_hook_profile.upload(profile, (size_t)DENOISE_NB, g->stream);  // (the sources outlive the hook's final wait)
+      if (!tones.empty()) m.dn_hook_tone.upload(tones.data(), tones.size(), g->stream);
+      return m.clean(g->S.p, m.dn_hook_profile.p, m.dn_hook_tone.p), m.S_clean.p;
+    });
+    g->clear_last();
+    g->mg.collect_clean();
+  });
+}
+
+xdtts_status xdtts_griffinlim_denoise_linear(xdtts_griffinlim *g, const float *S, size_t n_frames, const xdtts_denoise *d,
+                                             const float *profile, float *S_out) {
+  return xdtts_griffinlim_denoise_linear_batch(g, &S, &n_frames, 1, d, profile, &S_out);
+}
+
+// The selection alone: the magnitude on the device, ONE k_noise_profile launch in the single form, N back.  ms[0] = the launch.
+xdtts_status xdtts_griffinlim_noise_profile(xdtts_griffinlim *g, const float *S, size_t n_frames, float quantile, float *out) {
+  return guard([&] {
+    bad_arg_if(denoise_quantile_check(quantile));
+    bad_arg_if(denoise_frames_check(n_frames));
+    if (!g || !S || !out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    Denoise s = denoise_default();
+    s.strength = 1.0f, s.quantile = quantile;
+    MagnitudePlan plan = magnitude_plan_checked(MagnitudeRequest::none(1), &n_frames, NO_TIMBRE, 0, false, std::vector<DenoiseJob>(1, denoise_job(s, false, -1)));
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    g->bufs((int)plan.loop_rows);
+    g->upload_rows(&S, plan.in);
+    g->mg.prepare(std::move(plan), false);
+    HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
+    launch_noise_profile(g->S.p, nullptr, 1, g->mg.plan.clean[0], g->mg.dn_N.p, g->stream);
+    HIP_CHECK(hipEventRecord(g->ev.e[1], g->stream));
+    HIP_CHECK(hipEventRecord(g->ev.e[2], g->stream));
+    HIP_CHECK(hipMemcpyAsync(out, g->mg.dn_N.p, (size_t)DENOISE_NB * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    g->finish_timings();  // (drains the stream)
+  });
 }
 
 }  // extern "C"

@@ -497,7 +497,7 @@ static GlBufs request_bufs(xdtts_griffinlim *g) {
 // (req: checked against F -- the loop runs on what the magnitude chain returns, with F' frames.  gl_collect works from the plan
 // this leaves in place: S, S' and the timbre's output are intact, a demoted engine's retry runs on them again.)
 void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, PinnedGuard &host, const MagnitudeRequest &req) {
-  MagnitudePlan plan = magnitude_plan_checked(req, &F, g->mg.timbres(), g->mg.phase_init);
+  MagnitudePlan plan = magnitude_plan_checked(req, &F, g->mg.timbres(), g->mg.phase_init, false, g->mg.denoises());
   g->bufs((int)plan.loop_rows);
   HIP_CHECK(hipEventRecord(g->ev.e[0], g->stream));
   g->mg.prepare(std::move(plan), false);  // (a contour's table goes up on the stream; nothing is waited for)
@@ -509,6 +509,7 @@ void gl_enqueue_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, i
 }
 void gl_collect(xdtts_griffinlim *g, PinnedGuard &host, float **audio, size_t *n_samples) {
   collect_run(g, request_bufs(g), nullptr, g->iters, true, host, audio, n_samples);
+  g->mg.collect_clean();  // (the stream is drained: the stage's stats have landed)
 }
 
 void gl_run_from_device_mel(xdtts_griffinlim *g, const float *mel_dev_ptr, int F, const MagnitudeRequest &req, float **audio, size_t *n_samples) {
@@ -631,7 +632,7 @@ void prosody_check_array(const xdtts_prosody *p, int n_utt) {
 void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fin, float **audios, size_t *n_samples,
                           const MagnitudeRequest &req) {
   const int n_utt = (int)Fin.size();
-  MagnitudePlan mplan = magnitude_plan_checked(req, Fin.data(), g->mg.timbres(), g->mg.phase_init);
+  MagnitudePlan mplan = magnitude_plan_checked(req, Fin.data(), g->mg.timbres(), g->mg.phase_init, false, g->mg.denoises());
   HIP_CHECK(hipSetDevice(g->device));
   hipStream_t st = g->stream;
   GlBufs all = g->bufs((int)mplan.loop_rows);
@@ -738,6 +739,7 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
       g->dl.push_last((size_t)dp.tab_pos[(size_t)u]);
     }
     g->mg.collect();
+    g->mg.collect_clean();
     return;
   }
 }

@@ -56,6 +56,15 @@ inline Timbre timbre_checked(const xdtts_timbre *t) {
   bad_arg_if(timbre_check(s));
   return s;
 }
+// xdtts_denoise (include/xdtts.h) on top of denoise_plan.h: the checked setting (null = the default, the identity) and the
+// caller's profile (null = none), before a handle is looked at.
+inline Denoise denoise_checked(const xdtts_denoise *d, const float *profile) {
+  Denoise s = denoise_default();
+  if (d) std::memcpy(&s, d, sizeof s);
+  bad_arg_if(denoise_check(s));
+  bad_arg_if(denoise_profile_check(profile));
+  return s;
+}
 // The *_plan.h headers know no status codes: past a cap they throw std::length_error, which inside a request fails with
 // XDTTS_ERR_BAD_ARG and the text -- Rows::add (gl_plan.h), magnitude_plan (magnitude_plan.h: 2^24 rows) and delivery_plan
 // (delivery_plan.h: more than 2^31 - 1 delivered samples)
@@ -133,7 +142,7 @@ struct xdtts_griffinlim {
   // The delivery chain behind the loop (delivery.h): output rate, compressor, output normalisation or loudness with or without
   // the limiter -- settings, tables, buffers, the stats of the last call, and the one runner of every request path.
   xdtts::Delivery dl;
-  void clear_last() { dl.clear_last(), mg.last_f0.clear(); }
+  void clear_last() { dl.clear_last(), mg.last_f0.clear(), mg.last_denoise.clear(); }
 
   // stream (stream.hip): the utterances of a sequence joined with their gaps, faded, levelled and encoded -- the stage behind
   // everything above (xdtts_griffinlim_join, xdtts_synthesize_document).

@@ -338,6 +338,17 @@ void launch_prosody_contour(const float *S, float *Sout, const ContourUtt *utt, 
 void launch_timbre(const float *S, float *Sout, const TimbreUtt *tab, int n_utt, const TimbreUtt &one, int rows_all, const float2 *tw,
                    hipStream_t s);
 
+// ---- clean-up stage (denoise.hip): spectral subtraction with a floor, and a tone curve, in front of everything else ----------
+// (include/xdtts.h, denoise_plan.h).  tab (device memory, n_utt records: struct DenoiseUtt), or nullptr: n_utt = 1 and the
+// record is `one`, a kernel argument -- nothing is uploaded.  A cell has the same bits in both forms.
+// k_noise_profile: N [n_utt][513] = per bin the rank-th smallest key of the utterance's rows of S; an utterance that selects
+// nothing (no subtraction, or a profile) leaves its row of N untouched.
+void launch_noise_profile(const float *S, const DenoiseUtt *tab, int n_utt, const DenoiseUtt &one, float *N, hipStream_t s);
+// k_denoise: rows_all rows of S -> Sout; Nsel = the table above, profile [513] and tone [.][513] where a record asks for them.
+// stats [n_utt]: `floored` is ADDED to (zero it in front of the launch), the other fields are written.
+void launch_denoise(const float *S, float *Sout, const DenoiseUtt *tab, int n_utt, const DenoiseUtt &one, int rows_all, const float *Nsel,
+                    const float *profile, const float *tone, DenoiseStats *stats, hipStream_t s);
+
 // ---- pitch tracker (f0.hip): F0 per frame from the magnitude's cepstrum, the utterance's median, pitch targets (include/xdtts.h) ----
 // raw[t], strength[t] for every row t < rows of S [rows][513] (the utterances of a batch back to back: a frame needs nothing of
 // its neighbours); o, q_lo, q_hi: checked options and their quefrency range (f0_plan.h).  One launch.

@@ -1,5 +1,5 @@
 // magnitude.cpp -- the magnitude chain's state and its one runner (magnitude.h): buffers, the record tables' uploads and the
-// launches of tracker + target -> contour | uniform prosody -> timbre, and of the SPSI initial phase, for a single request and a batch.
+// launches of clean-up -> tracker + target -> contour | uniform prosody -> timbre, and of the SPSI initial phase, for a single request and a batch.
 #include "magnitude.h"
 
 #include "env.h"
@@ -7,11 +7,19 @@
 namespace xdtts {
 
 static_assert(sizeof(xdtts_f0_stats) == sizeof(F0Stats), "F0Stats is xdtts_f0_stats");
+static_assert(sizeof(xdtts_denoise_stats) == sizeof(DenoiseStats) && sizeof(xdtts_denoise) == sizeof(Denoise) && sizeof(Denoise) == 80,
+              "the layouts of denoise_plan.h");
 
 void Magnitude::prepare(MagnitudePlan p, bool with_tables) {
   plan = std::move(p);
   tables = with_tables;
   const size_t cells = std::max<size_t>(plan.rows.total, 1) * (size_t)nb, n_utt = std::max<size_t>((size_t)plan.rows.n(), 1);
+  if (!plan.clean.empty()) {
+    S_clean.alloc(std::max<size_t>(plan.in.total, 1) * (size_t)nb);
+    dn_N.alloc(plan.clean.size() * (size_t)nb);
+    dn_stats.alloc(plan.clean.size());
+    dn_host.reserve(plan.clean.size());
+  }
   if (plan.staged()) S_pros.alloc(cells);
   if (!plan.timbre.empty()) S_timbre.alloc(cells);
   if (plan.prosody == MagnitudeRequest::CONTOUR) {
@@ -34,11 +42,26 @@ void Magnitude::prepare(MagnitudePlan p, bool with_tables) {
   frame_local.upload(plan.frame_local.data(), plan.frame_local.size(), stream);
   if (plan.prosody == MagnitudeRequest::UNIFORM) pros_tab.upload(plan.pros.data(), plan.pros.size(), stream);
   if (!plan.timbre.empty()) timbre_tab.upload(plan.timbre.data(), plan.timbre.size(), stream);
+  if (!plan.clean.empty()) clean_tab.upload(plan.clean.data(), plan.clean.size(), stream);
   if (plan.spsi) {
     spsi_segs.upload(plan.spsi_segs.data(), plan.spsi_segs.size(), stream);
     spsi_utts.upload(plan.spsi_utts.data(), plan.spsi_utts.size(), stream);
   }
   HIP_CHECK(hipStreamSynchronize(stream));  // the tables are up
+}
+
+// The selection where some utterance asks for it, then the pointwise kernel over all rows; the stats' `floored` is zeroed on the
+// stream in front of them, so a retry counts afresh.
+void Magnitude::clean(const float *S, const float *profile, const float *tone, hipEvent_t between) {
+  const int n_utt = (int)plan.clean.size();
+  bool selects = false;
+  for (const DenoiseUtt &t : plan.clean) selects = selects || denoise_utt_selects(t);
+  HIP_CHECK(hipMemsetAsync(dn_stats.p, 0, (size_t)n_utt * sizeof(DenoiseStats), stream));
+  if (selects) launch_noise_profile(S, tables ? clean_tab.p : nullptr, n_utt, tables ? DenoiseUtt{} : plan.clean[0], dn_N.p, stream);
+  if (between) HIP_CHECK(hipEventRecord(between, stream));
+  launch_denoise(S, S_clean.p, tables ? clean_tab.p : nullptr, n_utt, tables ? DenoiseUtt{} : plan.clean[0], (int)plan.in.total, dn_N.p, profile,
+                 tone, dn_stats.p, stream);
+  HIP_CHECK(hipMemcpyAsync(dn_host.p, dn_stats.p, (size_t)n_utt * sizeof(DenoiseStats), hipMemcpyDeviceToHost, stream));
 }
 
 void Magnitude::track(const float *S, hipEvent_t between) {
@@ -74,12 +97,15 @@ void Magnitude::spsi(const float *S_in, float2 *ang, float2 *tprev, unsigned *tu
               (int)plan.spsi_utts.size(), plan.chained, SpsiBufs{spsi_map.p, spsi_comp.p, spsi_entry.p}, ang, tprev, turns, stream);
 }
 
-// THE magnitude order: the tracker and the targets write the contour table's pitches, then the contour or the uniform prosody,
-// then the handle's timbre on what that left (the tracker saw the unmodified voice).
+// THE magnitude order: the clean-up stage on what mel -> linear left, then on its output (or on S) the tracker and the targets,
+// which write the contour table's pitches, then the contour or the uniform prosody, then the handle's timbre on what that left
+// (the tracker saw the voice before prosody and timbre).
 float *Magnitude::run(float *S) {
-  if (plan.track) track(S);
-  if (plan.staged()) prosody(S);
-  if (!plan.timbre.empty()) voice(plan.staged() ? S_pros.p : S);
+  if (!plan.clean.empty()) clean(S, dn_profile.p, dn_tone.p);
+  float *B = base_S(S);
+  if (plan.track) track(B);
+  if (plan.staged()) prosody(B);
+  if (!plan.timbre.empty()) voice(plan.staged() ? S_pros.p : B);
   return loop_S(S);
 }
 
@@ -87,6 +113,13 @@ void Magnitude::collect() {
   if (!plan.track) return;
   last_f0.resize(plan.f0.size());
   if (!last_f0.empty()) std::memcpy(last_f0.data(), f0_host.p, last_f0.size() * sizeof(F0Stats));
+}
+
+void Magnitude::collect_clean() {
+  const size_t n = plan.clean.size(), at = last_denoise.size();
+  if (!n) return;
+  last_denoise.resize(at + n);
+  std::memcpy(last_denoise.data() + at, dn_host.p, n * sizeof(DenoiseStats));
 }
 
 }  // namespace xdtts

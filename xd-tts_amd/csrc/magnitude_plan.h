@@ -1,6 +1,6 @@
 // magnitude_plan.h -- the host arithmetic of the magnitude chain between mel -> linear and the Griffin-Lim loop: what a request
-// asks for (nothing, a uniform prosody, a contour, a pitch target over a contour), which stages run (tracker and target, then the
-// contour or the uniform prosody, then timbre, then the SPSI initial phase), the frames F'_u behind them, the per-utterance
+// asks for (nothing, a uniform prosody, a contour, a pitch target over a contour), which stages run (the clean-up stage, tracker
+// and target, then the contour or the uniform prosody, then timbre, then the SPSI initial phase), the frames F'_u behind them, the per-utterance
 // records of the stages' launches, the totals every buffer is sized from, and the buffer the loop reads.  Plain host C++, no
 // HIP: tests/magnitude_plan_test.cpp drives it on a machine without a GPU.
 #pragma once
@@ -14,6 +14,7 @@
 #include <utility>
 #include <vector>
 
+#include "denoise_plan.h"
 #include "f0_plan.h"
 #include "gl_plan.h"
 #include "prosody_contour.h"
@@ -172,6 +173,8 @@ inline std::string target_tables(const PitchTarget *t, const Contour *const *c, 
 // ---- everything the host decides before a launch
 struct MagnitudePlan {
   Rows in, rows;  // the mel's frames F_u, and the frames behind the prosody stage, F'_u: the rows of everything from there on
+  std::vector<DenoiseUtt> clean;    // the clean-up stage, on the F_u rows of `in`, in front of everything: where it runs, its
+                                    // output takes S's place for every stage below and for the loop (`loop` keeps its meaning)
   MagnitudeRequest::Form prosody = MagnitudeRequest::NONE;  // the form that runs; NONE: nothing is launched, S' is S
   bool track = false;  // the tracker and the targets run in front of it
   F0Job job;
@@ -192,10 +195,11 @@ struct MagnitudePlan {
 
 // Fin[u]: the frames of utterance u's mel.  timbre: empty = the stage is off, one setting = every utterance's, else one each (the
 // stage's hook).  phase_init 1 = SPSI.  always: a hook of a stage alone runs the request's form even where every utterance is the
-// identity (a request path then launches nothing).  Throws std::length_error past 2^24 rows.
+// identity (a request path then launches nothing).  denoise: as timbre -- empty = the clean-up stage is off, one job = every
+// utterance's, else one each (the stage's hook).  Throws std::length_error past 2^24 rows.
 template <class Int>
 inline MagnitudePlan magnitude_plan(const MagnitudeRequest &req, const Int *Fin, const std::vector<Timbre> &timbre, int phase_init,
-                                    bool always = false) {
+                                    bool always = false, const std::vector<DenoiseJob> &denoise = std::vector<DenoiseJob>()) {
   MagnitudePlan p;
   const int n_utt = req.n();
   bool staged = always && req.form() != MagnitudeRequest::NONE;
@@ -211,6 +215,7 @@ inline MagnitudePlan magnitude_plan(const MagnitudeRequest &req, const Int *Fin,
     p.in.add(F, (size_t)1 << 24, "batch too large");
     p.rows.add(Fp, (size_t)1 << 24, "batch too large");
     const int src0 = p.in.row0[(size_t)u], dst0 = p.rows.row0[(size_t)u];
+    if (!denoise.empty()) p.clean.push_back(denoise_utt(denoise[denoise.size() == 1 ? 0 : (size_t)u], src0, (int)F));
     if (p.prosody == MagnitudeRequest::UNIFORM) {
       const Prosody &q = req.prosody(u);
       p.pros.push_back({src0, (int)F, dst0, (int)Fp, q.rate, q.pitch, q.lifter, q.log_floor});
