@@ -313,6 +313,16 @@ xdtts_status xdtts_griffinlim_infer(xdtts_griffinlim *g, const float *mel, size_
 xdtts_status xdtts_griffinlim_infer_batch(xdtts_griffinlim *g, const float *const *mels, size_t n_mels,
                                           const size_t *n_frames, int32_t n_utt, float **audios,
                                           size_t *n_samples);
+/* How a batch of these frame counts would be packed into persistent launches by a call made now (host arithmetic, nothing is
+ * launched, no setting changes; the first call on a handle reads the device's attributes).  n_frames[u] >= 2 is what enters the
+ * loop (behind a rate change: F').  It reads what the batch entries read at the call: the handle's probed CU count and
+ * co-resident 4-frame workgroups per CU, opts.batch_shape, and the developer switches XDTTS_GL (launch: no persistent engine)
+ * and XDTTS_GL_BATCH_FORCE.  TF, WG: frames per workgroup (4 or 8) and workgroups per CU (1 or 2) of every launch;
+ * launch_of[u]: the launch utterance u rides in, 0 .. n_launches - 1, or -1 where it runs alone on the single call's engine
+ * (fewer than 16 frames, or more workgroups than CUs); n_cu: 0 for a handle without a usable persistent engine (every
+ * utterance alone).  Any out pointer may be NULL; a NULL handle or n_utt <= 0 is XDTTS_ERR_BAD_ARG. */
+xdtts_status xdtts_griffinlim_batch_plan(xdtts_griffinlim *g, const size_t *n_frames, int32_t n_utt, int32_t *TF, int32_t *WG,
+                                         int32_t *n_launches, int32_t *launch_of, int32_t *n_cu, int32_t *per_cu4);
 
 /* The loop alone (G2..G5 and the final ISTFT): no mel->linear inversion before it and no output normalisation
  * after it -- the bench / parity entry of SURVEY.md section 8(b).  S is n_bins x F linear magnitude; phase0 is

@@ -1,12 +1,14 @@
 // delivery_plan_test.cpp -- the delivery chain's host arithmetic (xd-tts_amd/csrc/delivery_plan.h) on the host alone (no HIP, no
 // GPU): delivered counts and places against values worked out by hand, the running workgroup numbers of every record table
-// under a permuted layout order, the launch extents of runs of rows, and the 2^31 - 1 failure.
+// under a permuted layout order, the launch extents of runs of rows, the row orders of two multi-launch batches with the runs of
+// rows the request path takes launch by launch, and the 2^31 - 1 failure.
 // Built and run by tests/test_delivery_plan_cpu.py (plain, and with the address and undefined-behaviour sanitizers); prints "ok".
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 
 #include "delivery_plan.h"
+#include "gl_plan.h"
 
 using namespace xdtts;
 
@@ -139,8 +141,62 @@ static bool too_large(size_t last) {
   }
 }
 
+// The row orders of real multi-launch batches (gl_plan.h: GlBatchPlan::order at 256 CUs; the batches A and C of
+// tests/vocoder_batches.py): the request path runs every stage once per launch over the rows of that launch's riders, then once
+// per alone utterance.  Those runs of rows are consecutive, start where the previous one ended, and their extents tile every
+// stage's workgroup range exactly once.
+static void check_batch_orders() {
+  std::vector<int> A = {1000, 1001, 999, 5, 17}, C;
+  for (int i = 0; i < 70; ++i) C.push_back(16 + (7 * i) % 23);
+  const int forces[3] = {41, 42, 8};
+  const int rates[3] = {22050, 8000, 48000};
+  for (const std::vector<int> *Fu : {&A, &C})
+    for (int force : forces)
+      for (int rate : rates) {
+        g_case = "batch of " + std::to_string(Fu->size()) + " force " + std::to_string(force) + " rate " + std::to_string(rate);
+        const GlBatchPlan gp = gl_batch_plan(*Fu, 256, 256, 2, 0, force);
+        const int n_utt = (int)Fu->size();
+        CHECK((int)gp.order.size() == n_utt);
+        if (Fu == &A) CHECK(gp.launches.size() == (force == 41 ? 3u : 2u) && gp.order != delivery_identity(5));
+        else CHECK(gp.launches.size() == (force == 42 ? 1u : 2u) && gp.order != delivery_identity(70));
+        std::vector<size_t> n;
+        for (int F : *Fu) n.push_back((size_t)256 * (size_t)(F - 1));
+        DeliveryStages s = all_on(rate);
+        s.sil = true;
+        s.sil_plan = silence_plan(silence_default(), rate);
+        const DeliveryPlan p = delivery_plan(s, n, delivery_bases(n), gp.order);
+        std::vector<std::vector<int>> fetches;
+        for (const GlBatchPlan::Launch &L : gp.launches) fetches.push_back(L.utts);
+        for (int u = 0; u < n_utt; ++u)
+          if (!gp.batched[(size_t)u]) fetches.push_back(std::vector<int>(1, u));
+        int row = 0, blk = 0, grp = 0, tile = 0, ctile = 0, stile = 0;
+        std::vector<int> seen((size_t)n_utt, 0);
+        for (const std::vector<int> &utts : fetches) {
+          const int r0 = p.tab_pos[(size_t)utts[0]], count = (int)utts.size();
+          CHECK(r0 == row);
+          int n_max = 0;
+          for (int i = 0; i < count; ++i) {
+            CHECK(p.tab_pos[(size_t)utts[(size_t)i]] == r0 + i && gp.order[(size_t)(r0 + i)] == utts[(size_t)i]);
+            CHECK(p.norm[(size_t)(r0 + i)].first == (int)p.dbase[(size_t)utts[(size_t)i]] && p.norm[(size_t)(r0 + i)].n == p.dn[(size_t)utts[(size_t)i]]);
+            n_max = std::max(n_max, p.dn[(size_t)utts[(size_t)i]]);
+            ++seen[(size_t)utts[(size_t)i]];
+          }
+          const DeliveryExtents e = delivery_extents(p, r0, count);
+          CHECK(e.grp0 == grp && e.tile0 == tile && e.ctile0 == ctile && e.stile0 == stile && e.n_max == n_max);
+          CHECK(e.groups > 0 && e.tiles > 0 && e.ctiles > 0 && e.stiles > 0);
+          if (s.resampled) CHECK(e.blk0 == blk && e.blocks > 0);
+          else CHECK(e.blk0 == 0 && e.blocks == 0);
+          row += count, blk += e.blocks, grp += e.groups, tile += e.tiles, ctile += e.ctiles, stile += e.stiles;
+        }
+        for (int u = 0; u < n_utt; ++u) CHECK(seen[(size_t)u] == 1);
+        CHECK(row == n_utt && (size_t)grp == p.groups && (size_t)tile == p.lim_tiles && (size_t)ctile == p.comp_tiles && (size_t)stile == p.sil_tiles);
+        if (s.resampled) CHECK(blk == p.rs.back().blk0 + (p.rs.back().n_out + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK);
+      }
+}
+
 int main() {
   check_stages();
+  check_batch_orders();
   const std::vector<std::vector<int>> orders[3] = {{{0}}, {{0, 1}, {1, 0}}, {{0, 1, 2, 3, 4}, {3, 0, 4, 1, 2}, {4, 3, 2, 1, 0}}};
   const int counts[3] = {1, 2, 5};
   for (int k = 0; k < 3; ++k)

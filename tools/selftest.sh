@@ -21,6 +21,8 @@ run document_check.py         python tools/document_check.py 2
 run delivery_hash.py          python tools/delivery_hash.py
 run magnitude_hash.py         python tools/magnitude_hash.py
 run magnitude_plan_test.cpp   bash -c "g++ -std=c++17 -O1 -Wall -Werror -I xd-tts_amd/csrc tests/magnitude_plan_test.cpp -o /tmp/magnitude_plan_test && /tmp/magnitude_plan_test"
+run delivery_plan_test.cpp    bash -c "g++ -std=c++17 -O1 -Wall -Werror -I xd-tts_amd/csrc tests/delivery_plan_test.cpp -o /tmp/delivery_plan_test && /tmp/delivery_plan_test"
+run gl_plan_test.cpp          bash -c "g++ -std=c++17 -O1 -Wall -Werror -I xd-tts_amd/csrc tests/gl_plan_test.cpp -o /tmp/gl_plan_test && /tmp/gl_plan_test"
 run gl_hash.py                python tools/gl_hash.py
 run gl_tf_sweep.py            python tools/gl_tf_sweep.py
 run headline_call.py          python tools/headline_call.py 3

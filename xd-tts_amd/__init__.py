@@ -352,6 +352,7 @@ SYMBOLS = {
     "xdtts_griffinlim_set_seed": (_I32, [_VP, _U32]),
     "xdtts_griffinlim_infer": (_I32, [_VP, _VP, _SZ, _SZ, C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_griffinlim_infer_batch": (_I32, [_VP, _VP, _SZ, _VP, _I32, _VP, _VP]),
+    "xdtts_griffinlim_batch_plan": (_I32, [_VP, _VP, _I32] + [_VP] * 6),
     "xdtts_griffinlim_infer_linear": (_I32, [_VP, _VP, _VP, _SZ, _SZ, C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_griffinlim_mel_to_linear": (_I32, [_VP, _VP, _SZ, _SZ, _VP]),
     "xdtts_griffinlim_step": (_I32, [_VP, _VP, _VP, _VP, _SZ, _SZ]),
@@ -1039,6 +1040,18 @@ class GriffinLim:
         else:
             _check(lib.xdtts_griffinlim_infer_batch_prosody(self._h, ptrs, ms[0].shape[0], nf, n, _prosody_array(prosody, n), audios, ns))
         return [_take(audios[u], ns[u], (ns[u],)) for u in range(n)]
+
+    def batch_plan(self, n_frames):
+        """xdtts_griffinlim_batch_plan (host arithmetic, nothing is launched): how infer_batch would pack utterances of these
+        frame counts into persistent launches if called now -- {"TF", "WG", "n_launches", "launch_of" (per utterance, -1 =
+        alone), "n_cu" (0: no usable persistent engine), "per_cu4"}; reads batch_shape, XDTTS_GL and XDTTS_GL_BATCH_FORCE."""
+        n = len(n_frames)
+        nf = (C.c_size_t * max(n, 1))(*[int(F) for F in n_frames])
+        of = (C.c_int32 * max(n, 1))()
+        v = [C.c_int32() for _ in range(5)]
+        _check(lib.xdtts_griffinlim_batch_plan(self._h, nf, n, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), of, C.byref(v[3]), C.byref(v[4])))
+        return {"TF": v[0].value, "WG": v[1].value, "n_launches": v[2].value, "launch_of": [of[u] for u in range(n)],
+                "n_cu": v[3].value, "per_cu4": v[4].value}
 
     def infer_linear(self, S, phase0=None, iters=0):
         S = np.ascontiguousarray(S, dtype=np.float32)

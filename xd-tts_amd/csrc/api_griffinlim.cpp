@@ -163,6 +163,33 @@ xdtts_status xdtts_griffinlim_infer_batch(xdtts_griffinlim *g, const float *cons
   return gl_infer_batch(g, mels, n_mels, n_frames, n_utt, MagnitudeAsk(), audios, n_samples);
 }
 
+// Host arithmetic: gl_batch_plan on the arguments gl_batch_from_device would hand it now (gl_batch_args), nothing launched
+xdtts_status xdtts_griffinlim_batch_plan(xdtts_griffinlim *g, const size_t *n_frames, int32_t n_utt, int32_t *TF, int32_t *WG,
+                                         int32_t *n_launches, int32_t *launch_of, int32_t *n_cu, int32_t *per_cu4) {
+  return guard([&] {
+    if (!g || !n_frames || n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "bad argument");
+    Rows rows;
+    for (int u = 0; u < n_utt; ++u) {
+      if (n_frames[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d: need at least 2 frames", u);
+      rows_add(rows, n_frames[u], (size_t)1 << 24, "batch too large");
+    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_CHECK(hipSetDevice(g->device));
+    const GlBatchArgs a = gl_batch_args(g);
+    const GlBatchPlan plan = gl_batch_plan(rows.F, g->hop, a.n_cu, a.per_cu4, a.batch_shape, a.force);
+    if (TF) *TF = plan.TF;
+    if (WG) *WG = plan.WG;
+    if (n_launches) *n_launches = (int32_t)plan.launches.size();
+    if (n_cu) *n_cu = a.n_cu;
+    if (per_cu4) *per_cu4 = a.per_cu4;
+    if (launch_of) {
+      for (int u = 0; u < n_utt; ++u) launch_of[u] = -1;
+      for (size_t k = 0; k < plan.launches.size(); ++k)
+        for (int u : plan.launches[k].utts) launch_of[u] = (int32_t)k;
+    }
+  });
+}
+
 xdtts_status xdtts_griffinlim_mel_to_linear(xdtts_griffinlim *g, const float *mel, size_t n_mels, size_t n_frames,
                                             float *S_out) {
   return guard([&] {

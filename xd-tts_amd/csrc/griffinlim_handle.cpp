@@ -621,6 +621,11 @@ void prosody_check_array(const xdtts_prosody *p, int n_utt) {
   for (int u = 0; u < n_utt; ++u) prosody_check_at(&p[u], u, 2);
 }
 
+GlBatchArgs gl_batch_args(xdtts_griffinlim *g) {
+  const int n_cu = g->persistent_usable() ? g->n_cu : 0;  // (first: the probe fills n_cu and per_cu4)
+  return {n_cu, g->per_cu4, g->gopts.batch_shape, env::int_or(env::GL_BATCH_FORCE, 0)};
+}
+
 // The vocoder half of a batch from a mel that is already in HBM (on g's device): [n_mels][sum Fu], utterance u at columns
 // fbase[u] .. fbase[u] + Fu[u].  mel -> linear is one GEMM over all frames, and the persistent kernel takes as many
 // utterances per launch as fit one workgroup per CU (gl_plan.h: gl_batch_plan).  Caller holds g->mu.  The reads of the mel
@@ -668,8 +673,8 @@ void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const s
     if (!use_spsi) launch_gl_phase_init_batch(all, g->seed, g->mg.frame_local.p, st);
     // the plan, on the host while the device works on the above.  A handle without a usable persistent engine (demoted: the
     // retry) gets the empty one: everything runs one by one on the launch-per-iteration kernels.
-    const GlBatchPlan plan = gl_batch_plan(Fu, g->hop, g->persistent_usable() ? g->n_cu : 0, g->per_cu4, g->gopts.batch_shape,
-                                           env::int_or(env::GL_BATCH_FORCE, 0));
+    const GlBatchArgs pa = gl_batch_args(g);
+    const GlBatchPlan plan = gl_batch_plan(Fu, g->hop, pa.n_cu, pa.per_cu4, pa.batch_shape, pa.force);
     std::vector<PinnedGuard> out;  // each utterance straight into the buffer the caller receives
     out.reserve((size_t)n_utt);
     for (int u = 0; u < n_utt; ++u) out.emplace_back((size_t)dn[(size_t)u]);

@@ -210,6 +210,14 @@ void gl_collect(xdtts_griffinlim *g, PinnedGuard &host, float **audio, size_t *n
 // hop * (F'_u - 1) samples)
 void gl_batch_from_device(xdtts_griffinlim *g, const float *mel_dev_all, const std::vector<int> &Fu, float **audios, size_t *n_samples,
                           const MagnitudeRequest &req);
+// What gl_batch_plan (gl_plan.h) takes from the handle and the environment, read at the call: the probed CU count (0 without a
+// usable persistent engine or under XDTTS_GL=launch: the empty plan), the co-resident 4-frame workgroups per CU, the batch_shape
+// option and XDTTS_GL_BATCH_FORCE.  The one source for gl_batch_from_device and xdtts_griffinlim_batch_plan.  Caller holds g->mu;
+// the first use probes the engine (device attributes only, nothing is launched).
+struct GlBatchArgs {
+  int n_cu, per_cu4, batch_shape, force;
+};
+GlBatchArgs gl_batch_args(xdtts_griffinlim *g);
 // The fields of n_utt prosodies before any handle is looked at (entries that take an array): fails with XDTTS_ERR_BAD_ARG,
 // the message names the field and the utterance.
 void prosody_check_array(const xdtts_prosody *p, int n_utt);
