@@ -238,6 +238,76 @@ xdtts_status xdtts_tacotron2_postnet_batch(xdtts_tacotron2 *h, const float *fram
  * steps = decoder steps executed. */
 xdtts_status xdtts_tacotron2_last_timings(const xdtts_tacotron2 *h, float ms[4], int32_t *steps);
 
+/* ---- Per-id durations and timing marks from the cumulative attention ----------------------
+ * Every decoder engine keeps attention_weights_cum ([B][T]) in HBM and leaves it final when it ends: the sum of the chunk's
+ * softmax rows over the frames it ran (a stopped chunk is frozen).  Entry t of a chunk's row is therefore the number of frames
+ * the decoder spent on id t, and the row sums to the chunk's frame count.  With the setting ON, two small launches behind the
+ * decode (never inside it: no per-step capture, no decoder kernel differs) turn these rows into, per utterance and in the
+ * caller's order, the chunks' valid ids back to back:
+ *   dur[i]        the fp32 cumulative weight of id i as read -- a SOFT duration: the expected number of frames on the id
+ *   dur_q16[i]    round-to-nearest-even of dur[i] * 65536 as an unsigned integer (negative or NaN: 0; saturates at 2^32 - 1)
+ *   start_q16[i]  65536 * (frames of the utterance's earlier chunks) + the sum of dur_q16 of the chunk's earlier ids; 64-bit
+ *                 integer arithmetic only, so the value does not depend on the order of the device's scan.  start is when
+ *                 id i is heard for an attention that moves monotonically; it is not a hard (Viterbi) alignment path.
+ * and per utterance xdtts_alignment_stats (integer compares and adds on the Q16 values): a cheap check that the attention read
+ * the whole sentence -- no id skipped (n_below), none stuck (n_above), the last id reached (last_q16).
+ * The setting covers xdtts_tacotron2_infer_ids (one utterance: its chunks) and _infer_batch (every chunk an utterance), and
+ * xdtts_synthesize_ids* / xdtts_synthesize_batch* (utterances as utt_chunks says).  The sequence and document entries ignore it
+ * and launch nothing; after them, as after any call with the setting off, xdtts_tacotron2_last_durations_count is 0.  With the
+ * setting off (the default) nothing is launched, allocated or copied and every entry returns the bits it returned before; with
+ * it on the mel and audio bits are unchanged too.
+ * Argument rules of the setting: on in {0, 1}; min_frames and max_frames finite, 0 <= min_frames <= max_frames <= 65535. */
+typedef struct {
+  int32_t on;          /* default 0 */
+  float   min_frames;  /* default 0.5: an id under it counts as skipped (n_below) */
+  float   max_frames;  /* default 40:  an id over it counts as stuck (n_above) */
+} xdtts_durations_opts;
+typedef struct {
+  uint64_t sum_q16;              /* sum of dur_q16 */
+  uint64_t n_frames;             /* frames of the utterance's chunks; sum_q16 / 65536 is close to it */
+  uint32_t n_ids;
+  uint32_t min_q16, min_index;   /* the shortest id (the first of equals), index in the utterance */
+  uint32_t max_q16, max_index;   /* the longest id (the first of equals) */
+  uint32_t n_below, n_above;     /* ids with dur_q16 < q16(min_frames) / > q16(max_frames) */
+  uint32_t last_q16;             /* the final id's duration */
+} xdtts_alignment_stats;         /* 48 bytes */
+void xdtts_durations_default(xdtts_durations_opts *o); /* off, 0.5, 40 */
+/* o == NULL: the default.  The fields are checked before the handle. */
+xdtts_status xdtts_tacotron2_set_durations(xdtts_tacotron2 *h, const xdtts_durations_opts *o);
+xdtts_status xdtts_tacotron2_get_durations(const xdtts_tacotron2 *h, xdtts_durations_opts *o);
+/* What the last call on the handle captured, shaped like xdtts_griffinlim_last_loudness: the number of utterances (0: none), and
+ * per utterance its ids -- *n_ids receives the count, at most cap entries are written to each output, any output may be NULL. */
+xdtts_status xdtts_tacotron2_last_durations_count(const xdtts_tacotron2 *h, size_t *n_utterances);
+xdtts_status xdtts_tacotron2_last_durations(const xdtts_tacotron2 *h, size_t utterance, float *dur, uint32_t *dur_q16,
+                                            uint64_t *start_q16, size_t cap, size_t *n_ids);
+xdtts_status xdtts_tacotron2_last_alignment(const xdtts_tacotron2 *h, size_t utterance, xdtts_alignment_stats *out);
+/* Parity hook, the stage alone on caller arrays.  cum_a / cum_b: [B][T] cumulative weights by decode SLOT; slot j is the
+ * caller's chunk order[j] (NULL: j); nframes[j] in [0, 100000], n_valid[j] in [1, T]; 1 <= B <= 4096, 1 <= T <= 512.
+ * batched != 0: the row of slot j is read from cum_b where nframes[j] is odd (the batched kernels ping-pong by step parity),
+ * else from cum_a; batched == 0: always cum_a (cum_b may be NULL).  utt_of_chunk[c], c the caller's chunk index, starts at 0
+ * and goes up by 0 or 1 (NULL: every chunk an utterance).  opts NULL: the default thresholds.  The outputs hold cap_ids ids /
+ * cap_utt utterances; *n_ids / *n_utt receive the counts (sum of n_valid / utterances); too little room, like every other
+ * argument error, is XDTTS_ERR_BAD_ARG before a device is touched.  xdtts_durations_reference is the same call on the host,
+ * serially; the two agree bit for bit.  The hook leaves xdtts_tacotron2_last_durations_count at 0. */
+xdtts_status xdtts_tacotron2_durations_gather(xdtts_tacotron2 *h, const float *cum_a, const float *cum_b, int32_t B, int32_t T,
+                                              const int32_t *nframes, const int32_t *n_valid, const int32_t *order,
+                                              int32_t batched, const int32_t *utt_of_chunk, const xdtts_durations_opts *opts,
+                                              float *dur, uint32_t *dur_q16, uint64_t *start_q16, size_t cap_ids,
+                                              xdtts_alignment_stats *stats, size_t cap_utt, size_t *n_ids, size_t *n_utt);
+xdtts_status xdtts_durations_reference(const float *cum_a, const float *cum_b, int32_t B, int32_t T, const int32_t *nframes,
+                                       const int32_t *n_valid, const int32_t *order, int32_t batched,
+                                       const int32_t *utt_of_chunk, const xdtts_durations_opts *opts, float *dur,
+                                       uint32_t *dur_q16, uint64_t *start_q16, size_t cap_ids, xdtts_alignment_stats *stats,
+                                       size_t cap_utt, size_t *n_ids, size_t *n_utt);
+/* A position x in ids, 0 <= x <= n, of an utterance of n ids and n_frames frames -> with k = floor(x) (x == n: k = n - 1) the
+ * frame position (start_q16[k] + (x - k) * dur_q16[k]) / 65536 as a fraction of n_frames - 1, clamped to [0, 1]: the pos of an
+ * xdtts_prosody_point.  Double arithmetic in this order; NaN for arguments outside the rule; n_frames == 1 gives 0. */
+double xdtts_durations_position(const uint64_t *start_q16, const uint32_t *dur_q16, size_t n, size_t n_frames, double x);
+/* The delivered sample offset of a Q16 frame position on the PLAIN path: floor(start_q16 * hop * L / (65536 * M)) with L / M
+ * the resampler's ratio for rate_out (22050: 1 / 1); -1 for a rate the resampler does not take.  NOT valid behind a rate or a
+ * contour (the frames move) or the silence stage (samples are dropped). */
+int64_t xdtts_durations_samples(uint64_t start_q16, int32_t hop, int64_t rate_out);
+
 void xdtts_tacotron2_free(xdtts_tacotron2 *h);
 
 /* ---- Griffin-Lim ------------------------------------------------------------------------ */
@@ -465,8 +535,8 @@ xdtts_status xdtts_griffinlim_prosody_linear_batch(xdtts_griffinlim *g, const fl
  * rate-1 contour maps frame j to frame j exactly: c[m] = 65536 m.  The identity contour launches nothing and returns the bits
  * of the plain entries; an identity utterance inside a mixed batch is copied.  Batch == single, bit for bit: one kernel serves both.
  * Out of scope: the sequence entries (a caller loops over xdtts_synthesize_ids_contour); semitone targets (the host converts
- * them to factors; absolute-Hz targets and the pitch range are xdtts_pitch_target, below); positions in seconds or phonemes
- * (these need alignments). */
+ * them to factors; absolute-Hz targets and the pitch range are xdtts_pitch_target, below).  Positions in ids (phonemes) are
+ * xdtts_synthesize_ids_contour_at_ids / xdtts_synthesize_batch_contour_at_ids, below. */
 typedef struct { float pos, rate, pitch, gain; } xdtts_prosody_point;   /* 16 bytes */
 typedef struct {
   const xdtts_prosody_point *points;   /* host memory, read during the call only */
@@ -1165,6 +1235,19 @@ xdtts_status xdtts_synthesize_ids_contour(xdtts_tacotron2 *h, xdtts_griffinlim *
                                           size_t n, const size_t *splits, size_t n_splits,
                                           const xdtts_infer_opts *opts, const xdtts_prosody_contour *c, float **mel,
                                           size_t *n_frames, float **audio, size_t *n_samples);
+/* ... and with a contour whose points are anchored at IDS: the arguments of xdtts_synthesize_ids_contour, but a point's pos is
+ * a position in the utterance's ids, in [0, n] and non-decreasing (k: in front of id k; n: the end; fractions fall inside an
+ * id).  The call captures the durations of its own decode whatever the durations setting says (they come down right behind the
+ * frame counts, before anything of the vocoder is enqueued; xdtts_tacotron2_last_durations holds them afterwards), maps every
+ * point on the host with xdtts_durations_position(start_q16, dur_q16, n, F, pos), keeps the mapped positions non-decreasing
+ * (the running maximum: at a chunk boundary a chunk's Q16 durations can pass the next chunk's base by a rounding), rounds them
+ * to float, and runs xdtts_synthesize_ids_contour's machinery on the result: mel and audio equal, bit for bit, those of
+ * xdtts_synthesize_ids_contour given the same mapped positions, and an all-identity contour returns the plain call's bits.
+ * A bad pos (not finite, outside [0, n], decreasing) is XDTTS_ERR_BAD_ARG naming the point, before a device is touched. */
+xdtts_status xdtts_synthesize_ids_contour_at_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids,
+                                                 size_t n, const size_t *splits, size_t n_splits,
+                                                 const xdtts_infer_opts *opts, const xdtts_prosody_contour *c, float **mel,
+                                                 size_t *n_frames, float **audio, size_t *n_samples);
 
 /* XdTts::infer (src/lib.rs:110-159) for n_utt utterances in one call -- the "batched / parallel
  * sentences" the author notes at src/phonemes.rs:677-680, BASELINE.json configs[3].  The chunks of
@@ -1199,6 +1282,14 @@ xdtts_status xdtts_synthesize_batch_contour(xdtts_tacotron2 *h, xdtts_griffinlim
                                             const xdtts_infer_opts *opts, const int32_t *fixed_steps_per_item,
                                             const xdtts_prosody_contour *c /* [n_utt] */, float **mels, size_t *n_frames,
                                             float **audios, size_t *n_samples);
+/* ... and with one id-anchored contour per utterance (xdtts_synthesize_ids_contour_at_ids above): pos of utterance u's points
+ * in [0, the id count of utterance u's chunks]; a bad field names the utterance and the point. */
+xdtts_status xdtts_synthesize_batch_contour_at_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids,
+                                                   const int32_t *lens, int32_t B, int32_t t_stride,
+                                                   const int32_t *utt_chunks, int32_t n_utt,
+                                                   const xdtts_infer_opts *opts, const int32_t *fixed_steps_per_item,
+                                                   const xdtts_prosody_contour *c /* [n_utt] */, float **mels, size_t *n_frames,
+                                                   float **audios, size_t *n_samples);
 /* xdtts_synthesize_ids and xdtts_synthesize_batch with a pitch target (xdtts_pitch_target, above; o == NULL: the default
  * options; c, or an element of it, may be NULL: no contour): the mel is the plain entry's, bit for bit, the audio goes through
  * the tracker, the target and the contour stage.  The frame count is known only behind the decoder, so the rule on it (2 ..

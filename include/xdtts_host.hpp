@@ -92,6 +92,35 @@ class Tacotron2 {
   }
   xdtts_tacotron2 *raw() const { return h_; }
 
+  // Per-id durations and timing marks (xdtts_durations_opts): the setting, and what the last call captured per utterance
+  struct Durations {
+    std::vector<float> dur;
+    std::vector<uint32_t> dur_q16;
+    std::vector<uint64_t> start_q16;
+    xdtts_alignment_stats stats;
+  };
+  void set_durations(const xdtts_durations_opts &o) { check(xdtts_tacotron2_set_durations(h_, &o)); }
+  xdtts_durations_opts get_durations() const {
+    xdtts_durations_opts o;
+    check(xdtts_tacotron2_get_durations(h_, &o));
+    return o;
+  }
+  std::vector<Durations> last_durations() const {
+    size_t n_utt = 0;
+    check(xdtts_tacotron2_last_durations_count(h_, &n_utt));
+    std::vector<Durations> out(n_utt);
+    for (size_t u = 0; u < n_utt; ++u) {
+      size_t n = 0;
+      check(xdtts_tacotron2_last_durations(h_, u, nullptr, nullptr, nullptr, 0, &n));
+      out[u].dur.resize(n);
+      out[u].dur_q16.resize(n);
+      out[u].start_q16.resize(n);
+      check(xdtts_tacotron2_last_durations(h_, u, out[u].dur.data(), out[u].dur_q16.data(), out[u].start_q16.data(), n, &n));
+      check(xdtts_tacotron2_last_alignment(h_, u, &out[u].stats));
+    }
+    return out;
+  }
+
  private:
   explicit Tacotron2(xdtts_tacotron2 *h) : h_(h) {}
   xdtts_tacotron2 *h_ = nullptr;
@@ -730,7 +759,8 @@ inline std::pair<Array2, std::vector<float>> infer_prosody(const Tacotron2 &mode
 
 // ... and with a contour (xdtts_synthesize_ids_contour): one sentence synthesised whole, its <prosody> spans applied inside it.
 inline std::pair<Array2, std::vector<float>> infer_contour(const Tacotron2 &model, const GriffinLim &vocoder, const std::vector<Unit> &units,
-                                                            const ProsodyContour &contour, const xdtts_infer_opts *opts = nullptr) {
+                                                            const ProsodyContour &contour, const xdtts_infer_opts *opts = nullptr,
+                                                            bool at_ids = false) {  // at_ids: pos in ids (xdtts_synthesize_ids_contour_at_ids)
   xdtts_infer_opts o;
   xdtts_infer_opts_default(&o);
   if (opts) o = *opts;
@@ -745,7 +775,8 @@ inline std::pair<Array2, std::vector<float>> infer_contour(const Tacotron2 &mode
   float *mel = nullptr, *audio = nullptr;
   size_t nf = 0, ns = 0;
   const xdtts_prosody_contour c = contour.c();
-  check(xdtts_synthesize_ids_contour(model.raw(), vocoder.raw(), ids.data(), ids.size(), splits.data(), n_splits, &o, &c, &mel, &nf, &audio, &ns));
+  check((at_ids ? xdtts_synthesize_ids_contour_at_ids : xdtts_synthesize_ids_contour)(model.raw(), vocoder.raw(), ids.data(), ids.size(), splits.data(),
+                                                                                     n_splits, &o, &c, &mel, &nf, &audio, &ns));
   std::pair<Array2, std::vector<float>> out;
   out.first.rows = 80;
   out.first.cols = nf;
@@ -824,7 +855,9 @@ inline std::vector<std::pair<Array2, std::vector<float>>> infer_many(const Tacot
                                                                        const std::vector<xdtts_prosody> *prosody = nullptr,
                                                                        const std::vector<ProsodyContour> *contour = nullptr,
                                                                        const std::vector<xdtts_pitch_target> *target = nullptr,
-                                                                       const xdtts_f0_opts *f0 = nullptr) {
+                                                                       const xdtts_f0_opts *f0 = nullptr,
+                                                                       bool contour_at_ids = false) {  // the contours' pos in ids: xdtts_synthesize_batch_contour_at_ids
+  if (contour_at_ids && (!contour || target)) throw std::runtime_error("xdtts: contour_at_ids goes with a contour per text and no pitch target");
   if (target && (target->size() != texts.size() || prosody)) throw std::runtime_error("xdtts: one pitch target per text, and no uniform prosody beside it");
   if (prosody && prosody->size() != texts.size()) throw std::runtime_error("xdtts: one prosody per text");
   if (contour && contour->size() != texts.size()) throw std::runtime_error("xdtts: one contour per text");
@@ -875,8 +908,9 @@ inline std::vector<std::pair<Array2, std::vector<float>>> infer_many(const Tacot
   } else if (contour) {
     std::vector<xdtts_prosody_contour> cs;
     for (const ProsodyContour &c : *contour) cs.push_back(c.c());
-    check(xdtts_synthesize_batch_contour(model.raw(), vocoder.raw(), ids.data(), lens.data(), (int32_t)lens.size(), (int32_t)T, utt_chunks.data(),
-                                         (int32_t)n_utt, &o, nullptr, cs.data(), mels.data(), nf.data(), audios.data(), ns.data()));
+    check((contour_at_ids ? xdtts_synthesize_batch_contour_at_ids : xdtts_synthesize_batch_contour)(
+        model.raw(), vocoder.raw(), ids.data(), lens.data(), (int32_t)lens.size(), (int32_t)T, utt_chunks.data(), (int32_t)n_utt, &o, nullptr, cs.data(),
+        mels.data(), nf.data(), audios.data(), ns.data()));
   } else if (prosody)
     check(xdtts_synthesize_batch_prosody(model.raw(), vocoder.raw(), ids.data(), lens.data(), (int32_t)lens.size(), (int32_t)T, utt_chunks.data(),
                                          (int32_t)n_utt, &o, nullptr, prosody->data(), mels.data(), nf.data(), audios.data(), ns.data()));

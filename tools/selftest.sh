@@ -17,6 +17,7 @@ run compressor_check.py       python tools/compressor_check.py
 run silence_check.py          python tools/silence_check.py
 run timbre_check.py           python tools/timbre_check.py
 run denoise_check.py          python tools/denoise_check.py
+run durations_check.py        python tools/durations_check.py
 run document_check.py         python tools/document_check.py 2
 run delivery_hash.py          python tools/delivery_hash.py
 run magnitude_hash.py         python tools/magnitude_hash.py

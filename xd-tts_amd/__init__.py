@@ -75,6 +75,30 @@ class Timbre(C.Structure):
         return (self.vtl, self.breath, self.seed, self.lifter, self.log_floor)
 
 
+class DurationsOpts(C.Structure):
+    """xdtts_durations_opts: the durations setting of a mel-generator handle.  on in {0, 1}; an id under min_frames counts as
+    skipped, one over max_frames as stuck (0 <= min_frames <= max_frames <= 65535).  DurationsOpts() holds the library's defaults
+    (off, 0.5, 40); keywords override fields."""
+
+    _fields_ = [("on", C.c_int32), ("min_frames", C.c_float), ("max_frames", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib.xdtts_durations_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class AlignmentStats(C.Structure):
+    """xdtts_alignment_stats: per utterance, from the Q16 durations."""
+
+    _fields_ = [("sum_q16", C.c_uint64), ("n_frames", C.c_uint64), ("n_ids", C.c_uint32), ("min_q16", C.c_uint32), ("min_index", C.c_uint32),
+                ("max_q16", C.c_uint32), ("max_index", C.c_uint32), ("n_below", C.c_uint32), ("n_above", C.c_uint32), ("last_q16", C.c_uint32)]
+
+    def astuple(self):
+        return tuple(getattr(self, f[0]) for f in self._fields_)
+
+
 class Denoise(C.Structure):
     """xdtts_denoise: the clean-up stage of a vocoder handle, the first stage on the magnitude behind mel -> linear.  strength in
     [0, 16] (over-subtraction factor, 0 = none), quantile in [0, 1] (which order statistic over an utterance's frames is the
@@ -342,6 +366,16 @@ SYMBOLS = {
     "xdtts_tacotron2_postnet": (_I32, [_VP, _VP, _I32, _VP]),
     "xdtts_tacotron2_postnet_batch": (_I32, [_VP, _VP, _SZ, _VP, _I32, _I32, _VP]),
     "xdtts_tacotron2_last_timings": (_I32, [_VP, C.POINTER(C.c_float * 4), C.POINTER(_I32)]),
+    "xdtts_durations_default": (None, [_VP]),
+    "xdtts_tacotron2_set_durations": (_I32, [_VP, _VP]),
+    "xdtts_tacotron2_get_durations": (_I32, [_VP, _VP]),
+    "xdtts_tacotron2_last_durations_count": (_I32, [_VP, C.POINTER(_SZ)]),
+    "xdtts_tacotron2_last_durations": (_I32, [_VP, _SZ, _VP, _VP, _VP, _SZ, C.POINTER(_SZ)]),
+    "xdtts_tacotron2_last_alignment": (_I32, [_VP, _SZ, _VP]),
+    "xdtts_tacotron2_durations_gather": (_I32, [_VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "xdtts_durations_reference": (_I32, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "xdtts_durations_position": (C.c_double, [_VP, _VP, _SZ, _SZ, C.c_double]),
+    "xdtts_durations_samples": (C.c_int64, [C.c_uint64, _I32, C.c_int64]),
     "xdtts_tacotron2_free": (None, [_VP]),
     "xdtts_tacotron2_sync": (_I32, [_VP]),
     "xdtts_mel_filter_bank": (_I32, [_F, _SZ, _SZ, _F, _F, _VP]),
@@ -464,7 +498,9 @@ SYMBOLS = {
     "xdtts_synthesize_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_prosody": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(Prosody), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_ids_contour": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(ProsodyContour), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
+    "xdtts_synthesize_ids_contour_at_ids": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(ProsodyContour), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_batch_contour": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "xdtts_synthesize_batch_contour_at_ids": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP, _VP]),
     "xdtts_synthesize_ids_pitch_target": (_I32, [_VP, _VP, _VP, _SZ, _VP, _SZ, C.POINTER(InferOpts), C.POINTER(F0Opts), C.POINTER(PitchTarget), C.POINTER(ProsodyContour), C.POINTER(_PF), C.POINTER(_SZ), C.POINTER(_PF), C.POINTER(_SZ)]),
     "xdtts_synthesize_batch_pitch_target": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, C.POINTER(F0Opts), _VP, _VP, _VP, _VP, _VP, _VP]),
     "xdtts_synthesize_batch": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, C.POINTER(InferOpts), _VP, _VP, _VP, _VP, _VP]),
@@ -967,6 +1003,70 @@ class Tacotron2:
         steps = C.c_int32()
         _check(lib.xdtts_tacotron2_last_timings(self._h, C.byref(ms), C.byref(steps)))
         return {"encoder_ms": ms[0], "decoder_ms": ms[1], "postnet_ms": ms[2], "total_ms": ms[3], "steps": steps.value}
+
+    # -- durations (include/xdtts.h: per-id durations and timing marks from the cumulative attention) ------------
+    def set_durations(self, opts=None, **kw):
+        """The durations setting: a DurationsOpts, or its fields as keywords (set_durations(on=1)); nothing = the default (off)."""
+        o = opts if opts is not None else DurationsOpts(**kw)
+        _check(lib.xdtts_tacotron2_set_durations(self._h, C.byref(o)))
+
+    def get_durations(self):
+        o = DurationsOpts()
+        _check(lib.xdtts_tacotron2_get_durations(self._h, C.byref(o)))
+        return o
+
+    def last_durations_count(self):
+        n = C.c_size_t()
+        _check(lib.xdtts_tacotron2_last_durations_count(self._h, C.byref(n)))
+        return n.value
+
+    def last_durations(self, utterance=0):
+        """(dur fp32, dur_q16 uint32, start_q16 uint64) of one utterance of the last call, one entry per id."""
+        n = C.c_size_t()
+        _check(lib.xdtts_tacotron2_last_durations(self._h, utterance, None, None, None, 0, C.byref(n)))
+        dur, q, st = np.empty(n.value, dtype=np.float32), np.empty(n.value, dtype=np.uint32), np.empty(n.value, dtype=np.uint64)
+        _check(lib.xdtts_tacotron2_last_durations(self._h, utterance, _ptr(dur), _ptr(q), _ptr(st), n.value, C.byref(n)))
+        return dur, q, st
+
+    def last_alignment(self, utterance=0):
+        s = AlignmentStats()
+        _check(lib.xdtts_tacotron2_last_alignment(self._h, utterance, C.byref(s)))
+        return s
+
+    def durations_gather(self, cum_a, cum_b, nframes, n_valid, order=None, batched=False, utt_of_chunk=None, opts=None):
+        """Parity hook: the stage alone on caller arrays (cum_a / cum_b: (B, T) by slot).  (dur, dur_q16, start_q16, [stats])."""
+        return _durations_call(lib.xdtts_tacotron2_durations_gather, (self._h,), cum_a, cum_b, nframes, n_valid, order, batched, utt_of_chunk, opts)
+
+
+def _durations_call(fn, head, cum_a, cum_b, nframes, n_valid, order, batched, utt_of_chunk, opts):
+    cum_a = np.ascontiguousarray(cum_a, dtype=np.float32)
+    B, T = cum_a.shape
+    cum_b = None if cum_b is None else np.ascontiguousarray(cum_b, dtype=np.float32)
+    i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+    nframes, n_valid, order, utt_of_chunk = i32(nframes), i32(n_valid), i32(order), i32(utt_of_chunk)
+    p = lambda a: None if a is None else _ptr(a)
+    N, U = int(np.clip(n_valid, 0, T).sum()), B
+    dur, q, st = np.empty(N, dtype=np.float32), np.empty(N, dtype=np.uint32), np.empty(N, dtype=np.uint64)
+    stats = (AlignmentStats * max(U, 1))()
+    n_ids, n_utt = C.c_size_t(), C.c_size_t()
+    _check(fn(*head, p(cum_a), p(cum_b), B, T, p(nframes), p(n_valid), p(order), 1 if batched else 0, p(utt_of_chunk),
+              C.byref(opts) if opts is not None else None, p(dur), p(q), p(st), N, stats, U, C.byref(n_ids), C.byref(n_utt)))
+    return dur[:n_ids.value], q[:n_ids.value], st[:n_ids.value], [stats[u] for u in range(n_utt.value)]
+
+
+def durations_reference(cum_a, cum_b, nframes, n_valid, order=None, batched=False, utt_of_chunk=None, opts=None):
+    """xdtts_durations_reference: the durations stage on the host, serially (no device)."""
+    return _durations_call(lib.xdtts_durations_reference, (), cum_a, cum_b, nframes, n_valid, order, batched, utt_of_chunk, opts)
+
+
+def durations_position(start_q16, dur_q16, n_frames, x):
+    """xdtts_durations_position: a position in ids -> a contour point's pos."""
+    st, q = np.ascontiguousarray(start_q16, dtype=np.uint64), np.ascontiguousarray(dur_q16, dtype=np.uint32)
+    return lib.xdtts_durations_position(_ptr(st), _ptr(q), st.size, n_frames, float(x))
+
+
+def durations_samples(start_q16, hop=256, rate_out=22050):
+    return lib.xdtts_durations_samples(int(start_q16), hop, rate_out)
 
 
 def create_mel_filter_bank(sample_rate, n_fft, n_mels, fmin, fmax=None):
@@ -1900,13 +2000,17 @@ def synthesize_document(tacotron2, vocoder, ids_list, gaps=None, stream_opts=Non
     return out_m, out, [int(offs[u]) for u in range(n)]
 
 
-def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, contour=None, target=None, f0_opts=None):
+def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, contour=None, target=None, f0_opts=None, contour_at_ids=None):
     """XdTts::infer (src/lib.rs:110-159): mel-gen then vocoder, mel kept in HBM in between.  prosody= (a Prosody) changes rate
     and pitch in the vocoder (xdtts_synthesize_ids_prosody): the mel returned is Tacotron2's own, the audio the modified one.
     contour= (a ProsodyContour) does so with values that vary inside the utterance (xdtts_synthesize_ids_contour).  target= (a
     PitchTarget, with contour= or alone; f0_opts= an F0Opts) tracks the utterance's F0 on the device and moves its median to an
-    absolute pitch and / or scales its range (xdtts_synthesize_ids_pitch_target); vocoder.last_f0() then holds the stats."""
+    absolute pitch and / or scales its range (xdtts_synthesize_ids_pitch_target); vocoder.last_f0() then holds the stats.
+    contour_at_ids= (a ProsodyContour whose pos are positions in ids, 0 .. len(ids); alone) anchors the contour at ids through
+    the durations of this decode (xdtts_synthesize_ids_contour_at_ids)."""
     _one_of(prosody, contour)
+    if contour_at_ids is not None and (prosody is not None or contour is not None or target is not None):
+        raise ValueError("contour_at_ids= goes alone")
     if target is not None and prosody is not None:
         raise ValueError("target= goes with contour=, not with prosody=")
     ids = np.ascontiguousarray(ids, dtype=np.int64)
@@ -1914,7 +2018,9 @@ def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, co
     mel, nf, audio, ns = _PF(), C.c_size_t(), _PF(), C.c_size_t()
     head = (tacotron2._h, vocoder._h, _ptr(ids), ids.size, None if sp is None else _ptr(sp), 0 if sp is None else sp.size, C.byref(opts) if opts else None)
     tail = (C.byref(mel), C.byref(nf), C.byref(audio), C.byref(ns))
-    if target is not None:
+    if contour_at_ids is not None:
+        _check(lib.xdtts_synthesize_ids_contour_at_ids(*head, C.byref(contour_at_ids), *tail))
+    elif target is not None:
         _check(lib.xdtts_synthesize_ids_pitch_target(*head, _opt_ref(f0_opts), C.byref(target), _opt_ref(contour), *tail))
     elif contour is not None:
         _check(lib.xdtts_synthesize_ids_contour(*head, C.byref(contour), *tail))
@@ -1926,7 +2032,7 @@ def synthesize(tacotron2, vocoder, ids, splits=None, opts=None, prosody=None, co
 
 
 def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_steps=None, want_mels=True, prosody=None, contour=None,
-                     target=None, f0_opts=None):
+                     target=None, f0_opts=None, contour_at_ids=None):
     """XdTts::infer (src/lib.rs:110-159) for several utterances in one call: `utterance_chunks[u]` is the
     list of <=window-id chunks of utterance u (find_splits + the trailing split, mod.rs:399,412-414);
     `fixed_steps`, if given, holds one frame count per chunk in the same nested shape.  All chunks decode
@@ -1934,8 +2040,12 @@ def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_step
     (mels or None, audios), one entry per utterance.  prosody= (a list of one Prosody per utterance): the mels stay Tacotron2's
     own, the audios go through the rate / pitch stage (xdtts_synthesize_batch_prosody); contour= (a list of one ProsodyContour per
     utterance) likewise with the contour stage (xdtts_synthesize_batch_contour).  target= (a list of one PitchTarget per
-    utterance; contour= may then hold None entries) runs the pitch tracker and the targets (xdtts_synthesize_batch_pitch_target)."""
+    utterance; contour= may then hold None entries) runs the pitch tracker and the targets (xdtts_synthesize_batch_pitch_target).
+    contour_at_ids= (a list of one ProsodyContour per utterance, pos in ids of that utterance; alone):
+    xdtts_synthesize_batch_contour_at_ids."""
     _one_of(prosody, contour)
+    if contour_at_ids is not None and (prosody is not None or contour is not None or target is not None):
+        raise ValueError("contour_at_ids= goes alone")
     if target is not None and prosody is not None:
         raise ValueError("target= goes with contour=, not with prosody=")
     chunks = [c for u in utterance_chunks for c in u]
@@ -1951,7 +2061,9 @@ def synthesize_batch(tacotron2, vocoder, utterance_chunks, opts=None, fixed_step
     audios = (_PF * n_utt)()
     nf, ns = (C.c_size_t * n_utt)(), (C.c_size_t * n_utt)()
     head = (tacotron2._h, vocoder._h, _ptr(ids), _ptr(lens), B, stride, _ptr(uc), n_utt, C.byref(opts) if opts else None, None if fs is None else _ptr(fs))
-    if target is not None:
+    if contour_at_ids is not None:
+        _check(lib.xdtts_synthesize_batch_contour_at_ids(*head, _contour_array(contour_at_ids, n_utt), mels, nf, audios, ns))
+    elif target is not None:
         ta, ca, _keep = _target_arrays(target, contour, n_utt)
         _check(lib.xdtts_synthesize_batch_pitch_target(*head, _opt_ref(f0_opts), ta, ca, mels, nf, audios, ns))
     elif contour is not None:

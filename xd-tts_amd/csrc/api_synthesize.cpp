@@ -17,10 +17,52 @@ static void pair_check(const xdtts_tacotron2 *h, const xdtts_griffinlim *g) {
   if (g->n_mels != N_MEL) fail(XDTTS_ERR_BAD_ARG, "the vocoder's basis has %d mel bands, the model's mel has %d", g->n_mels, N_MEL);
 }
 
-// (ask: nothing -- xdtts_synthesize_ids -- or the magnitude chain between mel -> linear and the loop, fields checked by the caller)
+// ---- id-anchored contours (xdtts_synthesize_ids_contour_at_ids / _batch_contour_at_ids): a point's pos is in ids, 0 .. n ----
+// The fields before a device is touched: a copy with pos / n is a contour in fractions, and the contour's own rules name the
+// field and the point (dividing by n keeps the order of the points and maps [0, n] onto [0, 1]; NaN stays NaN).
+static void contour_at_ids_check(const xdtts_prosody_contour *c, size_t n_ids, int u) {
+  if (!c) fail(XDTTS_ERR_BAD_ARG, "null contour");
+  if (n_ids == 0) fail(XDTTS_ERR_BAD_ARG, "empty id sequence");
+  if (!c->points || c->n_points < 1 || c->n_points > 64) {  // (the contour's own message)
+    if (u < 0) contour_check(c, 2); else contour_check_at(c, u, 2);
+  }
+  std::vector<xdtts_prosody_point> pts(c->points, c->points + c->n_points);
+  const char *in_utt = u < 0 ? "" : "utterance ";
+  char where[32] = "";
+  if (u >= 0) std::snprintf(where, sizeof where, "%d: ", u);
+  for (int k = 0; k < c->n_points; ++k) {  // pos in the words of this entry: ids
+    const float pos = pts[(size_t)k].pos;
+    if (!std::isfinite(pos) || pos < 0.0f || (double)pos > (double)n_ids)
+      fail(XDTTS_ERR_BAD_ARG, "%s%scontour point %d: pos %g is not in [0, %zu] (ids)", in_utt, where, k, (double)pos, n_ids);
+    if (k > 0 && pos < pts[(size_t)k - 1].pos)
+      fail(XDTTS_ERR_BAD_ARG, "%s%scontour point %d: pos %g is below the point before it", in_utt, where, k, (double)pos);
+  }
+  for (xdtts_prosody_point &p : pts) p.pos = (float)((double)p.pos / (double)n_ids);
+  xdtts_prosody_contour t = *c;
+  t.points = pts.data();
+  if (u < 0) contour_check(&t, 2); else contour_check_at(&t, u, 2);
+}
+// Behind the decode: the points of utterance u of the handle's capture mapped from ids to fractions of the utterance's F frames
+// with durations_position, kept non-decreasing (at a chunk boundary the sum of a chunk's Q16 durations can pass the next chunk's
+// base by a rounding: the running maximum), rounded to the fp32 pos of a point.
+static void contour_at_ids_map(const xdtts_tacotron2 *h, size_t u, size_t F, const xdtts_prosody_contour &c, std::vector<xdtts_prosody_point> &out) {
+  const DurUtt &U = h->dur_plan.utt[u];
+  out.assign(c.points, c.points + c.n_points);
+  double last = 0.0;
+  for (xdtts_prosody_point &p : out) {
+    const double pos = durations_position(h->dur_start() + U.id_off, h->dur_q16() + U.id_off, (size_t)U.n_ids, F, (double)p.pos);
+    if (!(pos >= 0.0)) fail(XDTTS_ERR_BAD_ARG, "contour point at id position %g: outside the utterance's %d ids", (double)p.pos, (int)U.n_ids);
+    last = pos > last ? pos : last;
+    p.pos = (float)last;
+  }
+}
+
+// (ask: nothing -- xdtts_synthesize_ids -- or the magnitude chain between mel -> linear and the loop, fields checked by the caller;
+// at_ids: a contour whose pos are in ids -- the durations are captured whatever the setting says, the points mapped on the host
+// once the capture has landed, and the contour machinery runs on the mapped contour)
 static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n, const size_t *splits,
                                    size_t n_splits, const xdtts_infer_opts *opts, const MagnitudeAsk &ask, float **mel, size_t *n_frames,
-                                   float **audio, size_t *n_samples) {
+                                   float **audio, size_t *n_samples, const xdtts_prosody_contour *at_ids = nullptr) {
   return guard([&] {
     if (!h || !g || !mel || !n_frames || !audio || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     pair_check(h, g);
@@ -34,8 +76,19 @@ static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, cons
     std::vector<int> lens;
     chunks_from_splits(ids, n, splits, n_splits, o.max_chunk, padded, lens);
     int total = 0;
-    h->infer_batch_device(padded.data(), lens.data(), (int)lens.size(), o.max_chunk, o, nullptr, &total);
+    const std::vector<int> one_utt(lens.size(), 0);  // (durations: the chunks are one utterance)
+    h->infer_batch_device(padded.data(), lens.data(), (int)lens.size(), o.max_chunk, o, nullptr, &total, false,
+                          DurAsk{true, at_ids != nullptr, one_utt.data()});
     if (total < 2) fail(XDTTS_ERR_BAD_ARG, "mel has %d frame(s); the vocoder needs at least 2", total);
+    std::vector<xdtts_prosody_point> mapped;
+    xdtts_prosody_contour mapped_c{};
+    if (at_ids) {
+      h->wait_durations();  // (the capture's copy alone: the post-net may still be running)
+      contour_at_ids_map(h, 0, (size_t)total, *at_ids, mapped);
+      mapped_c = *at_ids;
+      mapped_c.points = mapped.data();
+    }
+    const MagnitudeAsk ask_now = at_ids ? MagnitudeAsk::contour(&mapped_c) : ask;
     PinnedGuard mel_host((size_t)N_MEL * total);
     // the vocoder stream reads the mel behind the post-net (event 3 of infer_batch_device); the mel's copy to the host
     // follows on the mel-gen stream and overlaps the vocoder
@@ -43,8 +96,9 @@ static xdtts_status synthesize_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, cons
     HIP_CHECK(hipMemcpyAsync(mel_host.p, h->mel_dev.p, (size_t)N_MEL * total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     Drain drain(h->stream);  // the pinned buffer does not go back to the pool with the copy in flight
     const size_t total_frames = (size_t)total;  // (the frame count is known only now; nothing of the vocoder has been enqueued)
-    gl_run_from_device_mel(g, h->mel_dev.p, total, magnitude_request(ask, 1, &total_frames), audio, n_samples);
+    gl_run_from_device_mel(g, h->mel_dev.p, total, magnitude_request(ask_now, 1, &total_frames), audio, n_samples);
     h->finish_timings();  // (stream sync: the mel has landed)
+    h->publish_durations();
     *mel = mel_host.release();
     *n_frames = (size_t)total;
   });
@@ -265,7 +319,7 @@ static xdtts_status synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g,
 static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
                                      int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
                                      const int32_t *fixed_steps_per_item, const MagnitudeAsk &ask, float **mels, size_t *n_frames, float **audios,
-                                     size_t *n_samples) {
+                                     size_t *n_samples, const xdtts_prosody_contour *at_ids = nullptr) {
   return guard([&] {
     if (!h || !g || !ids || !lens || !utt_chunks || !n_frames || !audios || !n_samples) fail(XDTTS_ERR_BAD_ARG, "null argument");
     pair_check(h, g);
@@ -285,7 +339,10 @@ static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, co
     const int T = o.max_chunk;
     const std::vector<int64_t> padded = pad_batch_ids(ids, lens, B, t_stride, T);
     int total = 0;
-    const std::vector<int> F = h->infer_batch_device(padded.data(), lens, B, T, o, fixed_steps_per_item, &total);
+    std::vector<int> utt_of_chunk;  // (durations: utterance of every chunk)
+    for (int u = 0; u < n_utt; ++u) utt_of_chunk.insert(utt_of_chunk.end(), (size_t)utt_chunks[u], u);
+    const std::vector<int> F = h->infer_batch_device(padded.data(), lens, B, T, o, fixed_steps_per_item, &total, false,
+                                                      DurAsk{true, at_ids != nullptr, utt_of_chunk.data()});
     std::vector<int> Fu(n_utt, 0), col0(n_utt, 0);
     for (int u = 0, b = 0, off = 0; u < n_utt; ++u) {
       col0[u] = off;
@@ -294,7 +351,18 @@ static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, co
       if (Fu[u] < 2) fail(XDTTS_ERR_BAD_ARG, "utterance %d has %d mel frame(s); the vocoder needs at least 2", u, Fu[u]);
     }
     const std::vector<size_t> Fz(Fu.begin(), Fu.end());
-    const MagnitudeRequest req = magnitude_request(ask, n_utt, Fz.data(), 0);  // (nothing of the vocoder has been enqueued)
+    std::vector<std::vector<xdtts_prosody_point>> mapped;
+    std::vector<xdtts_prosody_contour> mapped_c;
+    if (at_ids) {
+      h->wait_durations();  // (the capture's copy alone: the post-net may still be running)
+      mapped.resize((size_t)n_utt);
+      mapped_c.assign(at_ids, at_ids + n_utt);
+      for (int u = 0; u < n_utt; ++u) {
+        contour_at_ids_map(h, (size_t)u, Fz[(size_t)u], at_ids[u], mapped[(size_t)u]);
+        mapped_c[(size_t)u].points = mapped[(size_t)u].data();
+      }
+    }
+    const MagnitudeRequest req = magnitude_request(at_ids ? MagnitudeAsk::contour(mapped_c.data()) : ask, n_utt, Fz.data(), 0);  // (nothing of the vocoder has been enqueued)
     // the vocoder stream reads the mel behind the post-net (event 3 of infer_batch_device); the host copies of the
     // mel follow on the mel-gen stream and overlap the vocoder
     HIP_CHECK(hipStreamWaitEvent(g->stream, h->ev.e[3], 0));
@@ -319,6 +387,7 @@ static xdtts_status synthesize_batch(xdtts_tacotron2 *h, xdtts_griffinlim *g, co
       }
       throw;
     }
+    h->publish_durations();
     for (int u = 0; u < n_utt; ++u) {
       n_frames[u] = (size_t)Fu[u];
       if (mels) mels[u] = mel_out[(size_t)u].release();
@@ -356,6 +425,16 @@ xdtts_status xdtts_synthesize_ids_contour(xdtts_tacotron2 *h, xdtts_griffinlim *
   xdtts_status st = guard([&] { contour_check(c, 2); });  // the fields, before a device is touched
   if (st != XDTTS_OK) return st;
   return synthesize_ids(h, g, ids, n, splits, n_splits, opts, MagnitudeAsk::contour(c), mel, n_frames, audio, n_samples);
+}
+
+// ... with a contour whose points are anchored at ids: pos in [0, n], mapped through the durations of this very decode
+xdtts_status xdtts_synthesize_ids_contour_at_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, size_t n,
+                                                 const size_t *splits, size_t n_splits, const xdtts_infer_opts *opts,
+                                                 const xdtts_prosody_contour *c, float **mel, size_t *n_frames, float **audio,
+                                                 size_t *n_samples) {
+  xdtts_status st = guard([&] { contour_at_ids_check(c, ids ? n : 0, -1); });  // the fields, before a device is touched
+  if (st != XDTTS_OK) return st;
+  return synthesize_ids(h, g, ids, n, splits, n_splits, opts, MagnitudeAsk(), mel, n_frames, audio, n_samples, c);
 }
 
 xdtts_status xdtts_synthesize_sequence(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *const *ids, const size_t *n_ids,
@@ -443,6 +522,30 @@ xdtts_status xdtts_synthesize_batch_contour(xdtts_tacotron2 *h, xdtts_griffinlim
   });
   if (st != XDTTS_OK) return st;
   return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, MagnitudeAsk::contour(c), mels, n_frames, audios, n_samples);
+}
+
+// ... one id-anchored contour per utterance: pos in [0, the utterance's id count]
+xdtts_status xdtts_synthesize_batch_contour_at_ids(xdtts_tacotron2 *h, xdtts_griffinlim *g, const int64_t *ids, const int32_t *lens, int32_t B,
+                                                   int32_t t_stride, const int32_t *utt_chunks, int32_t n_utt, const xdtts_infer_opts *opts,
+                                                   const int32_t *fixed_steps_per_item, const xdtts_prosody_contour *c, float **mels, size_t *n_frames,
+                                                   float **audios, size_t *n_samples) {
+  xdtts_status st = guard([&] {
+    null_outputs(n_utt, mels, n_frames, audios, n_samples);
+    if (n_utt <= 0) fail(XDTTS_ERR_BAD_ARG, "need at least one utterance, got %d", n_utt);
+    if (!c) fail(XDTTS_ERR_BAD_ARG, "null contour array");
+    if (!lens || !utt_chunks) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    // the fields against each utterance's id count, before a handle is looked at
+    for (int u = 0, b = 0; u < n_utt; ++u) {
+      size_t n_ids = 0;
+      for (int k = 0; k < utt_chunks[u]; ++k, ++b) {
+        if (b >= B) fail(XDTTS_ERR_BAD_ARG, "utt_chunks name more than the batch's %d chunks", B);
+        n_ids += lens[b] > 0 ? (size_t)lens[b] : 0;
+      }
+      contour_at_ids_check(&c[u], n_ids, u);
+    }
+  });
+  if (st != XDTTS_OK) return st;
+  return synthesize_batch(h, g, ids, lens, B, t_stride, utt_chunks, n_utt, opts, fixed_steps_per_item, MagnitudeAsk(), mels, n_frames, audios, n_samples, c);
 }
 
 // ... with a pitch target (xdtts_pitch_target): tracker, target and contour stage behind mel -> linear; the table is built once

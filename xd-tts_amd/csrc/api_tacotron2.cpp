@@ -166,10 +166,12 @@ xdtts_status xdtts_tacotron2_infer_ids(xdtts_tacotron2 *h, const int64_t *ids, s
     std::vector<int> lens;
     chunks_from_splits(ids, n, splits, n_splits, o.max_chunk, padded, lens);
     int total = 0;
-    h->infer_batch_device(padded.data(), lens.data(), (int)lens.size(), o.max_chunk, o, nullptr, &total);
+    const std::vector<int> one_utt(lens.size(), 0);  // (durations: the chunks are one utterance)
+    h->infer_batch_device(padded.data(), lens.data(), (int)lens.size(), o.max_chunk, o, nullptr, &total, false, DurAsk{true, false, one_utt.data()});
     PinnedGuard host((size_t)N_MEL * total);
     HIP_CHECK(hipMemcpyAsync(host.p, h->mel_dev.p, (size_t)N_MEL * total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     h->finish_timings();
+    h->publish_durations();
     *mel = host.release();
     *n_frames = (size_t)total;
   });
@@ -191,11 +193,12 @@ xdtts_status xdtts_tacotron2_infer_batch(xdtts_tacotron2 *h, const int64_t *ids,
     // the post-net leaves one dense (80 x F_b) matrix per chunk, back to back: ONE copy into a pinned slab whose pieces
     // are the buffers the caller receives (the (80 x F_total) layout took 4 160 strided row copies on the host for the
     // 52-chunk batch -- as long as the post-net on one thread, 0.3 ms on four; 52 pitched copies from the device 0.9 ms)
-    std::vector<int> F = h->infer_batch_device(padded.data(), lens, B, T, o, fixed_steps_per_item, &total, true);
+    std::vector<int> F = h->infer_batch_device(padded.data(), lens, B, T, o, fixed_steps_per_item, &total, true, DurAsk{true, false, nullptr});
     PinnedSlab slab((size_t)N_MEL * total);
     Drain drain(h->stream);  // the slab does not go back to the pool with the copy in flight
     HIP_CHECK(hipMemcpyAsync(slab.base, h->mel_dev.p, (size_t)N_MEL * total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     h->finish_timings();
+    h->publish_durations();
     size_t off = 0;
     for (int b = 0; b < B; ++b) {
       mels[b] = slab.piece(off);
@@ -532,6 +535,146 @@ xdtts_status xdtts_tacotron2_postnet_batch(xdtts_tacotron2 *h, const float *fram
     HIP_CHECK(hipStreamSynchronize(h->stream));
   });
 }
+
+// ---- durations (durations_plan.h, durations.hip) --------------------------------------------------------------------------
+
+static DurationsOpts dur_opts_of(const xdtts_durations_opts *o) {
+  static_assert(sizeof(xdtts_durations_opts) == sizeof(DurationsOpts) && sizeof(xdtts_alignment_stats) == sizeof(AlignmentStats),
+                "durations_plan.h mirrors the structs of include/xdtts.h");
+  if (!o) return durations_default();
+  const DurationsOpts d{o->on, o->min_frames, o->max_frames};
+  const std::string bad = durations_check(d);
+  if (!bad.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", bad.c_str());
+  return d;
+}
+
+void xdtts_durations_default(xdtts_durations_opts *o) {
+  if (!o) return;
+  const DurationsOpts d = durations_default();
+  o->on = d.on;
+  o->min_frames = d.min_frames;
+  o->max_frames = d.max_frames;
+}
+
+xdtts_status xdtts_tacotron2_set_durations(xdtts_tacotron2 *h, const xdtts_durations_opts *o) {
+  return guard([&] {
+    const DurationsOpts d = dur_opts_of(o);  // the fields, before the handle
+    if (!h) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->dur_opts = d;
+  });
+}
+
+xdtts_status xdtts_tacotron2_get_durations(const xdtts_tacotron2 *h, xdtts_durations_opts *o) {
+  return guard([&] {
+    if (!h || !o) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    o->on = h->dur_opts.on;
+    o->min_frames = h->dur_opts.min_frames;
+    o->max_frames = h->dur_opts.max_frames;
+  });
+}
+
+xdtts_status xdtts_tacotron2_last_durations_count(const xdtts_tacotron2 *h, size_t *n_utterances) {
+  return guard([&] {
+    if (!h || !n_utterances) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *n_utterances = h->dur_n_utt;
+  });
+}
+
+xdtts_status xdtts_tacotron2_last_durations(const xdtts_tacotron2 *h, size_t utterance, float *dur, uint32_t *dur_q16, uint64_t *start_q16,
+                                            size_t cap, size_t *n_ids) {
+  return guard([&] {
+    if (!h || !n_ids) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (utterance >= h->dur_n_utt) fail(XDTTS_ERR_BAD_ARG, "utterance %zu: the last call captured durations of %zu", utterance, h->dur_n_utt);
+    const DurUtt &U = h->dur_plan.utt[utterance];
+    *n_ids = (size_t)U.n_ids;
+    const size_t n = std::min(cap, (size_t)U.n_ids);
+    if (dur) std::memcpy(dur, h->dur_f32() + U.id_off, n * sizeof(float));
+    if (dur_q16) std::memcpy(dur_q16, h->dur_q16() + U.id_off, n * sizeof(uint32_t));
+    if (start_q16) std::memcpy(start_q16, h->dur_start() + U.id_off, n * sizeof(uint64_t));
+  });
+}
+
+xdtts_status xdtts_tacotron2_last_alignment(const xdtts_tacotron2 *h, size_t utterance, xdtts_alignment_stats *out) {
+  return guard([&] {
+    if (!h || !out) fail(XDTTS_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (utterance >= h->dur_n_utt) fail(XDTTS_ERR_BAD_ARG, "utterance %zu: the last call captured durations of %zu", utterance, h->dur_n_utt);
+    std::memcpy(out, h->dur_stats() + utterance, sizeof(*out));
+  });
+}
+
+// the outputs of the stage alone / of its host reference, cleared and checked alike
+static void dur_gather_args(const float *cum_a, const float *cum_b, int32_t B, int32_t T, const int32_t *nframes, const int32_t *n_valid,
+                            const int32_t *order, int32_t batched, const int32_t *utt_of_chunk, size_t *n_ids, size_t *n_utt, DurPlan *plan) {
+  if (n_ids) *n_ids = 0;
+  if (n_utt) *n_utt = 0;
+  if (!cum_a || !nframes || !n_valid) fail(XDTTS_ERR_BAD_ARG, "null argument");
+  const std::string bad = durations_plan(B, T, nframes, n_valid, order, batched, cum_b != nullptr, utt_of_chunk, plan);
+  if (!bad.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", bad.c_str());
+}
+static void dur_gather_room(const DurPlan &plan, size_t cap_ids, size_t cap_utt, size_t *n_ids, size_t *n_utt) {
+  if (n_ids) *n_ids = plan.n_ids;
+  if (n_utt) *n_utt = plan.utt.size();
+  if (cap_ids < plan.n_ids || cap_utt < plan.utt.size())
+    fail(XDTTS_ERR_BAD_ARG, "durations: room for %zu ids and %zu utterances, the request has %zu and %zu", cap_ids, cap_utt, plan.n_ids, plan.utt.size());
+}
+
+xdtts_status xdtts_durations_reference(const float *cum_a, const float *cum_b, int32_t B, int32_t T, const int32_t *nframes, const int32_t *n_valid,
+                                       const int32_t *order, int32_t batched, const int32_t *utt_of_chunk, const xdtts_durations_opts *opts,
+                                       float *dur, uint32_t *dur_q16, uint64_t *start_q16, size_t cap_ids, xdtts_alignment_stats *stats,
+                                       size_t cap_utt, size_t *n_ids, size_t *n_utt) {
+  return guard([&] {
+    const DurationsOpts o = dur_opts_of(opts);
+    DurPlan plan;
+    dur_gather_args(cum_a, cum_b, B, T, nframes, n_valid, order, batched, utt_of_chunk, n_ids, n_utt, &plan);
+    dur_gather_room(plan, cap_ids, cap_utt, n_ids, n_utt);
+    durations_reference(plan, cum_a, cum_b, T, nframes, batched, o, dur, dur_q16, start_q16, reinterpret_cast<AlignmentStats *>(stats));
+  });
+}
+
+// Parity hook: the stage alone on caller arrays, through launch_durations -- the launches behind every decode.
+xdtts_status xdtts_tacotron2_durations_gather(xdtts_tacotron2 *h, const float *cum_a, const float *cum_b, int32_t B, int32_t T,
+                                              const int32_t *nframes, const int32_t *n_valid, const int32_t *order, int32_t batched,
+                                              const int32_t *utt_of_chunk, const xdtts_durations_opts *opts, float *dur, uint32_t *dur_q16,
+                                              uint64_t *start_q16, size_t cap_ids, xdtts_alignment_stats *stats, size_t cap_utt, size_t *n_ids,
+                                              size_t *n_utt) {
+  return guard([&] {
+    const DurationsOpts o = dur_opts_of(opts);
+    DurPlan plan;
+    dur_gather_args(cum_a, cum_b, B, T, nframes, n_valid, order, batched, utt_of_chunk, n_ids, n_utt, &plan);
+    dur_gather_room(plan, cap_ids, cap_utt, n_ids, n_utt);
+    if (!h) fail(XDTTS_ERR_BAD_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIP_CHECK(hipSetDevice(h->device));
+    const size_t nt = (size_t)B * T;
+    h->state_stage.alloc(2 * nt);
+    DevBuf<int> counts;
+    counts.alloc((size_t)2 * B);
+    HIP_CHECK(hipMemcpyAsync(h->state_stage.p, cum_a, nt * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (batched) HIP_CHECK(hipMemcpyAsync(h->state_stage.p + nt, cum_b, nt * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(counts.p, nframes, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(counts.p + B, n_valid, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));  // the sources above are caller memory
+    h->enqueue_durations(h->state_stage.p, h->state_stage.p + nt, counts.p, counts.p + B, B, T, n_valid, order, batched != 0, utt_of_chunk, o);
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    const size_t N = plan.n_ids, U = plan.utt.size();
+    if (dur) std::memcpy(dur, h->dur_f32(), N * sizeof(float));
+    if (dur_q16) std::memcpy(dur_q16, h->dur_q16(), N * sizeof(uint32_t));
+    if (start_q16) std::memcpy(start_q16, h->dur_start(), N * sizeof(uint64_t));
+    if (stats) std::memcpy(stats, h->dur_stats(), U * sizeof(*stats));
+    h->dur_n_utt = h->dur_pending = 0;  // (a hook is no request: last_durations reports nothing of it)
+  });
+}
+
+double xdtts_durations_position(const uint64_t *start_q16, const uint32_t *dur_q16, size_t n, size_t n_frames, double x) {
+  return durations_position(start_q16, dur_q16, n, n_frames, x);
+}
+
+int64_t xdtts_durations_samples(uint64_t start_q16, int32_t hop, int64_t rate_out) { return durations_samples(start_q16, hop, rate_out); }
 
 xdtts_status xdtts_tacotron2_last_timings(const xdtts_tacotron2 *h, float ms[4], int32_t *steps) {
   return guard([&] {

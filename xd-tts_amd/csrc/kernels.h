@@ -3,6 +3,7 @@
 #include "common.h"
 #include "compressor_plan.h"
 #include "delivery_plan.h"
+#include "durations_plan.h"
 #include "f0_plan.h"
 #include "gl_plan.h"
 #include "limiter_plan.h"
@@ -464,5 +465,24 @@ void launch_silence(const float *x, float *out, const SilUtt *tab_dev, int count
 // samples at job.src + src0; out = total * sample_bytes bytes, 16-byte aligned -- nothing at or behind that is written.
 // job.gain (device memory) is read by the kernel: the measurement that writes it is ordered in front on the stream.
 void launch_stream_join(const StreamJob &job, void *out, hipStream_t s);
+
+// ---- durations (durations.hip): per-id durations and start marks from attention_weights_cum behind a decode (durations_plan.h) ----
+// Everything on the device.  cum_a / cum_b: [B][T] by slot (cum_b is read only where batched != 0); nframes / n_valid: [B] by
+// slot, read by the kernel -- nothing waits for the host; tab [B], utt [n_utt], list [B]: DurPlan's tables; dur / dur_q16 /
+// start_q16: DurPlan::n_ids entries; stats [n_utt].  Two launches: one wave per slot, then one wave per utterance.
+struct DurationsJob {
+  const float *cum_a, *cum_b;
+  int B, T, batched, n_utt;
+  const int *nframes, *n_valid;
+  const DurChunk *tab;
+  const DurUtt *utt;
+  const int *list;
+  uint32_t lo_q16, hi_q16;  // durations_q16 of min_frames / max_frames
+  float *dur;
+  uint32_t *dur_q16;
+  uint64_t *start_q16;
+  AlignmentStats *stats;
+};
+void launch_durations(const DurationsJob &job, hipStream_t s);
 
 }  // namespace xdtts

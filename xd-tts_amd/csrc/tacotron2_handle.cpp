@@ -11,6 +11,9 @@ xdtts_tacotron2::~xdtts_tacotron2() {
   if (fetched) (void)hipEventDestroy(fetched);
   if (host_ctl) (void)hipHostFree(host_ctl);
   if (in_host) (void)hipHostFree(in_host);
+  if (dur_tab_host) (void)hipHostFree(dur_tab_host);
+  if (dur_out_host) (void)hipHostFree(dur_out_host);
+  if (dur_ev) (void)hipEventDestroy(dur_ev);
   if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -369,7 +372,8 @@ int xdtts_tacotron2::postnet_groups(const float *frames_dev, size_t frame_stride
 // of chunk b at mel_dev + col_off[b] with row stride F_total; returns per-chunk frame counts.
 // per_chunk: mel_dev receives one dense (80 x F_b) matrix per chunk instead, back to back in the caller's order.
 std::vector<int> xdtts_tacotron2::infer_batch_device(const int64_t *ids_host, const int *lens, int B, int T, const xdtts_infer_opts &o,
-                                                     const int *fixed_per_item, int *F_total, bool per_chunk) {
+                                                     const int *fixed_per_item, int *F_total, bool per_chunk, const DurAsk &dur) {
+  dur_n_utt = dur_pending = 0;  // (what last_durations reports of a call that captures nothing, or fails: zero utterances)
   if (B <= 0 || B > 4096) fail(XDTTS_ERR_BAD_ARG, "batch %d out of range", B);
   if (T <= 0 || T > T_MAX) fail(XDTTS_ERR_BAD_ARG, "window %d out of range (1..%d)", T, T_MAX);
   if (o.max_steps <= 0 || o.max_steps > 100000) fail(XDTTS_ERR_BAD_ARG, "max_steps %d out of range", o.max_steps);
@@ -477,9 +481,70 @@ std::vector<int> xdtts_tacotron2::infer_batch_device(const int64_t *ids_host, co
     if (d.pmem_t) launch_dimgroup_transpose(pmem.p, pmem_t.p, B, T, stream);
     last_steps = run_decoder(d, lim);
   }
+  // the durations stage, behind the decode that stands: the final attention_weights_cum of every slot is in HBM, the frame
+  // counts and id counts too -- two small launches and one copy, brought down by the entry's final synchronisation
+  if (dur.entry && (dur.force || dur_opts.on))
+    enqueue_durations(d.awc, d.awc2, d.nframes, d.n_valid, B, T, lens, order.data(), batched_mode, dur.utt_of_chunk, dur_opts);
   if (!postnet_done) postnet_all(host_ctl + HOST_NF);
   *F_total = total;
   return F;
+}
+
+static void grow_pinned(unsigned char *&p, size_t &have, size_t need) {
+  if (need <= have) return;
+  if (p) (void)hipHostFree(p);
+  p = nullptr;
+  have = 0;
+  HIP_CHECK(hipHostMalloc((void **)&p, need, hipHostMallocDefault));
+  have = need;
+}
+
+void xdtts_tacotron2::enqueue_durations(const float *cum_a, const float *cum_b, const int *nframes_dev, const int *n_valid_dev, int B, int T,
+                                        const int *n_valid_host, const int *order, bool batched, const int *utt_of_chunk,
+                                        const xdtts::DurationsOpts &o) {
+  DurPlan plan;
+  const std::string bad = durations_plan(B, T, nullptr, n_valid_host, order, batched ? 1 : 0, cum_b != nullptr, utt_of_chunk, &plan);
+  if (!bad.empty()) fail(XDTTS_ERR_BAD_ARG, "%s", bad.c_str());
+  const size_t U = plan.utt.size(), N = plan.n_ids;
+  const size_t b_chunk = sizeof(DurChunk) * (size_t)B, b_utt = sizeof(DurUtt) * U, b_list = sizeof(int32_t) * (size_t)B;
+  grow_pinned(dur_tab_host, dur_tab_host_bytes, b_chunk + b_utt + b_list);
+  std::memcpy(dur_tab_host, plan.chunk.data(), b_chunk);
+  std::memcpy(dur_tab_host + b_chunk, plan.utt.data(), b_utt);
+  std::memcpy(dur_tab_host + b_chunk + b_utt, plan.list.data(), b_list);
+  dur_tab_dev.alloc(b_chunk + b_utt + b_list);
+  HIP_CHECK(hipMemcpyAsync(dur_tab_dev.p, dur_tab_host, b_chunk + b_utt + b_list, hipMemcpyHostToDevice, stream));
+  const size_t b_out = 8 * N + sizeof(AlignmentStats) * U + 8 * N;
+  grow_pinned(dur_out_host, dur_out_host_bytes, b_out);
+  dur_out_dev.alloc(b_out);
+  DurationsJob job{};
+  job.cum_a = cum_a;
+  job.cum_b = batched ? cum_b : cum_a;
+  job.B = B;
+  job.T = T;
+  job.batched = batched ? 1 : 0;
+  job.n_utt = (int)U;
+  job.nframes = nframes_dev;
+  job.n_valid = n_valid_dev;
+  job.tab = reinterpret_cast<const DurChunk *>(dur_tab_dev.p);
+  job.utt = reinterpret_cast<const DurUtt *>(dur_tab_dev.p + b_chunk);
+  job.list = reinterpret_cast<const int *>(dur_tab_dev.p + b_chunk + b_utt);
+  job.lo_q16 = durations_q16(o.min_frames);
+  job.hi_q16 = durations_q16(o.max_frames);
+  job.start_q16 = reinterpret_cast<uint64_t *>(dur_out_dev.p);
+  job.stats = reinterpret_cast<AlignmentStats *>(dur_out_dev.p + 8 * N);
+  job.dur = reinterpret_cast<float *>(dur_out_dev.p + 8 * N + sizeof(AlignmentStats) * U);
+  job.dur_q16 = reinterpret_cast<uint32_t *>(job.dur + N);
+  launch_durations(job, stream);
+  HIP_CHECK(hipMemcpyAsync(dur_out_host, dur_out_dev.p, b_out, hipMemcpyDeviceToHost, stream));
+  if (!dur_ev) HIP_CHECK(hipEventCreateWithFlags(&dur_ev, hipEventDisableTiming));
+  HIP_CHECK(hipEventRecord(dur_ev, stream));
+  dur_plan = std::move(plan);
+  dur_pending = U;  // (published by the entry, behind its final synchronisation: publish_durations)
+}
+
+void xdtts_tacotron2::wait_durations() {
+  if (!dur_pending || !dur_ev) fail(XDTTS_ERR_HIP, "durations: nothing was captured");
+  HIP_CHECK(hipEventSynchronize(dur_ev));
 }
 
 // the cooperative BiLSTM bounds its spins; a timeout there must not pass silently

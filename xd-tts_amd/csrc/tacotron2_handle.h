@@ -7,6 +7,17 @@
 #include "kernels.h"
 #include "runtime.h"
 
+namespace xdtts {
+// What an entry asks of infer_batch_device about the durations stage: entry = one of the entries the setting covers (the sequence
+// and document entries are not: they pass nothing, capture nothing, and the last result is cleared), force = capture whatever the
+// setting says (the id-anchored contour entries), utt_of_chunk [B] in the caller's order (nullptr: every chunk an utterance of
+// its own).
+struct DurAsk {
+  bool entry = false, force = false;
+  const int *utt_of_chunk = nullptr;
+};
+}  // namespace xdtts
+
 struct xdtts_tacotron2 {
   using DecoderBufs = xdtts::DecoderBufs;
   using EngineGate = xdtts::EngineGate;
@@ -97,6 +108,27 @@ struct xdtts_tacotron2 {
   static constexpr int GRAPH_STEPS = 20;
   xdtts::GraphCache graph;
 
+  // ---- durations (durations.hip, durations_plan.h): per-id timings from attention_weights_cum behind a decode ----
+  using DurAsk = xdtts::DurAsk;
+  xdtts::DurationsOpts dur_opts = xdtts::durations_default();
+  xdtts::DurPlan dur_plan;            // layout of the last capture
+  size_t dur_n_utt = 0;               // utterances the last call captured (0: none -- setting off, or an entry outside it)
+  size_t dur_pending = 0;             // ... of a capture whose copy is enqueued: published by the entry behind its final synchronisation
+  hipEvent_t dur_ev = nullptr;        // behind that copy (the id-anchored contour entries wait for it: they map on the host)
+  void publish_durations() { dur_n_utt = dur_pending; dur_pending = 0; }
+  void wait_durations();              // until the enqueued capture has landed in the pinned mirror
+  DevBuf<unsigned char> dur_tab_dev;  // DurChunk[B] | DurUtt[U] | list[B]
+  DevBuf<unsigned char> dur_out_dev;  // start_q16[N] | AlignmentStats[U] | dur[N] | dur_q16[N]
+  unsigned char *dur_tab_host = nullptr, *dur_out_host = nullptr;  // pinned: staging of the tables, mirror of the outputs
+  size_t dur_tab_host_bytes = 0, dur_out_host_bytes = 0;
+  // enqueues the stage and the copy of its outputs on the handle's stream; the entry's final synchronisation brings them down
+  void enqueue_durations(const float *cum_a, const float *cum_b, const int *nframes_dev, const int *n_valid_dev, int B, int T,
+                         const int *n_valid_host, const int *order, bool batched, const int *utt_of_chunk, const xdtts::DurationsOpts &o);
+  const uint64_t *dur_start() const { return reinterpret_cast<const uint64_t *>(dur_out_host); }
+  const xdtts::AlignmentStats *dur_stats() const { return reinterpret_cast<const xdtts::AlignmentStats *>(dur_out_host + 8 * dur_plan.n_ids); }
+  const float *dur_f32() const { return reinterpret_cast<const float *>(dur_out_host + 8 * dur_plan.n_ids + sizeof(xdtts::AlignmentStats) * dur_plan.utt.size()); }
+  const uint32_t *dur_q16() const { return reinterpret_cast<const uint32_t *>(dur_f32() + dur_plan.n_ids); }
+
   hipEvent_t fetched = nullptr;  // behind the copies that bring error word and frame counts back (run_decoder)
   // every dense contraction of the handle goes through run_gemm: split-K where it pays (gemm.hip: gemm_splitk_plan), the slices'
   // meeting place and the tiles' arrival counters owned by the handle (one stream: launches never overlap)
@@ -120,7 +152,7 @@ struct xdtts_tacotron2 {
   // (80 x F_b) matrix per chunk back to back.  Returns F_total.
   int postnet_groups(const float *frames_dev, size_t frame_stride, const int *Fs, const int *order, int B, bool per_chunk);
   std::vector<int> infer_batch_device(const int64_t *ids_host, const int *lens, int B, int T, const xdtts_infer_opts &o,
-                                      const int *fixed_per_item, int *F_total, bool per_chunk = false);
+                                      const int *fixed_per_item, int *F_total, bool per_chunk = false, const DurAsk &dur = DurAsk());
   void check_encoder_exchange();
   void finish_timings();
 
